@@ -1,19 +1,26 @@
 """Headline benchmark: HiFi-GAN-light generator inference on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config light|large512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config light|large512] [--dump-outputs DIR] [--full]
 
 Default workload (BASELINE.json configs[1]): conf/hifigan/light.yaml, batch = 1 utterance per GPU,
 mel 80 x 1000 frames of synthetic U[0,1) data already resident in HBM, seeded gain-calibrated
 random-init weights (no checkpoint exists offline), weight norm folded.  One "step" = one
 ``Generator.forward`` over the per-GPU batch -> 240 000 samples per utterance.  Utterance 0 is the
-mel the committed reference golden was made from, and the LAST timed output is checked against that
+mel the committed reference golden was made from; with ``--full`` the LAST timed output is checked against that
 golden (<= 1e-4, the north star's bound) before anything is printed: the timed forward is the
 parity-checked forward.
 
-N > 1: one rank per GPU.  `python bench.py --gpus N` started as ONE process replaces itself with
+A plain run does only what the headline needs: set-up, the prewarm and W warm-up steps, the K timed steps, the range-guard
+check of those steps, ``--dump-outputs`` and the line.  Everything else -- the cold-start and no-gather legs, the parity
+check, exact fp32, the roofline and host figures, the CPU baseline, the other configs and the appended strong-scaling
+job -- runs only with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step returned to its caller as
+DIR/<name>.npy (float32; a seeded sample of rows where the whole would exceed DUMP_BYTES); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+N > 1: one rank per GPU.  `python bench.py --gpus N` started as ONE process runs
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
-(refused when the node shows fewer than N devices); started by that launcher (WORLD_SIZE in the environment) it is
-a rank.  Weights are built on rank 0 and broadcast over RCCL once; every rank runs its own utterances (weak scaling: the path has no exchange step) and
+as a child and exits with its status (refused when the node shows fewer than N devices); started by that launcher
+(WORLD_SIZE in the environment) it is a rank.  Weights are built on rank 0 and broadcast over RCCL once; every rank runs its own utterances (weak scaling: the path has no exchange step) and
 every step's waveforms are gathered to rank 0 INSIDE the timed region (asynchronously, overlapping the
 next step's forward); the same steps without the gather are timed too and reported beside it.
 
@@ -23,15 +30,15 @@ to int16 on the GPU (fv_encode_16bits), rank 0 gathers the int16 waveforms; the 
 gather of sub-batch i - 1 are in flight under sub-batch i's forward (parallel.synthesize_pipelined); scatter, forward,
 encode and gather are all inside the timed step (the same step without scatter / gather is timed beside it), and rank 0
 checks gathered rows against its own single-utterance runs bit for bit.  ``--config large512`` makes it the
-headline of the line; the default run appends it as ``strong_scaling_job`` (one timed step; ``--no-job``
-skips it), so that one invocation per GPU count gives both scaling curves.
+headline of the line; a ``--full`` run of the default config appends it as ``strong_scaling_job`` (one timed step;
+``--no-job`` skips it), so that one invocation per GPU count gives both scaling curves.
 
 Sustained rate: every leg runs PREWARM_S (0.75) seconds of untimed forwards in front of its W warm-up steps -- an idle MI355X
 ramps for ~30 ms, boosts for ~0.5 s and then settles (profiles/r06_clock_ramp.txt); the default W = 5 is 3 ms -- then W warm-up
-and EXACTLY K timed steps; the same K steps without it are timed first and reported as ``cold_start``
+and EXACTLY K timed steps; with ``--full`` the same K steps without it are timed first and reported as ``cold_start``
 (FV_BENCH_PREWARM_S=0 switches the prewarm off).
 
-Prints ONE JSON line: value = whole-job audio samples / second, plus RTF at 22.05 kHz and 24 kHz, the
+Prints ONE JSON line: value = whole-job audio samples / second, plus RTF at 22.05 kHz and 24 kHz; with ``--full`` also the
 roofline of the dominant kernel family (fp32-MFMA convs, per-launch HIP events on the launch stream),
 the C = 16 stage against the memory roofline, and the reference's CPU path (its ATen op sequence,
 oracle/torch_port.py) timed on this host's cores.
@@ -98,6 +105,23 @@ def check_against_golden(wav_row):
     err = float(np.abs(y[g["T1000_idx"]] - g["T1000_samples"]).max())
     assert err <= TOL, f"timed output differs from the reference golden by {err:.3e} > {TOL}"
     return err
+
+
+DUMP_BYTES = 48 << 20     # --dump-outputs: float32 bytes of rows written at most (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, name, rows):
+    """``--dump-outputs``: the last timed step's output [rows, samples] as <path>/<name>.npy in float32.  Where all rows
+    would exceed DUMP_BYTES, a fixed seeded choice of rows is written, and their indices as <path>/<name>_rows.npy."""
+    rows = rows.detach().cpu()
+    n = rows.shape[0]
+    keep = max(1, min(n, DUMP_BYTES // max(4 * rows[0].numel(), 1)))
+    os.makedirs(path, exist_ok=True)
+    if keep < n:
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        rows = rows[torch.from_numpy(idx)]
+        np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, name + ".npy"), rows.to(torch.float32).numpy())
 
 
 def host_cpu():
@@ -536,7 +560,8 @@ def build_model(config, dev, dist, rank, precision="split"):
 
 def run_job(args, dev, dist, world, rank, steps, warmup):
     """BASELINE.json configs[4]: HiFi-GAN large, JOB_UTTERANCES utterances of 80 x 1000 per step, sharded over the
-    ranks (strong scaling).  Returns (elapsed seconds, steps, samples per utterance, utterances, extras)."""
+    ranks (strong scaling).  Returns (elapsed seconds, samples per utterance, utterances, workload, extras, the last
+    step's int16 waveforms [utterances, samples] on rank 0)."""
     from fastvocoder_amd import audio, parallel
     model, _, _ = build_model("large512", dev, dist, rank)
     total_utt = JOB_UTTERANCES
@@ -564,7 +589,7 @@ def run_job(args, dev, dist, world, rank, steps, warmup):
     torch.cuda.synchronize()
     elapsed, pcm = timed_steps(step, steps, warmup, dist, dev, warm=False)    # (0.1-0.8 s per step: its own warm-up)
     extra = {}
-    if dist is not None:
+    if dist is not None and args.full:
         # the same job with every rank's block already on its GPU and left there: no scatter, no gather
         lo, hi = parallel.shard_range(total_utt, world, rank)
         own = torch.from_numpy(utterance_mels(lo, hi - lo)).to(dev) if hi > lo else None
@@ -574,11 +599,12 @@ def run_job(args, dev, dist, world, rank, steps, warmup):
                                            "on the rank: forward + wav sink only, no scatter, no gather"}
     if rank == 0:
         assert pcm.dtype == torch.int16 and pcm.shape[0] == total_utt
-        # gathered rows == this rank's own single-utterance runs of the same mels, bit for bit
-        per = (total_utt + world - 1) // world
-        for idx in sorted({0, 1, per - 1, per % total_utt, total_utt - 1}):
-            one = rank_block(mels[idx:idx + 1])
-            assert torch.equal(one[0], pcm[idx]), f"utterance {idx} differs between the sharded job and a solo run"
+        if args.full:
+            # gathered rows == this rank's own single-utterance runs of the same mels, bit for bit
+            per = (total_utt + world - 1) // world
+            for idx in sorted({0, 1, per - 1, per % total_utt, total_utt - 1}):
+                one = rank_block(mels[idx:idx + 1])
+                assert torch.equal(one[0], pcm[idx]), f"utterance {idx} differs between the sharded job and a solo run"
         assert not model.check_range()
     samples_per_utt = int(pcm.shape[-1]) if rank == 0 else 240 * T_FRAMES
     workload = (f"HiFi-GAN large (conf/hifigan/large.yaml), {total_utt} utterances of mel 80x{T_FRAMES} per step "
@@ -589,7 +615,7 @@ def run_job(args, dev, dist, world, rank, steps, warmup):
                 + "; BASELINE.json configs[4]")
     del model
     torch.cuda.empty_cache()
-    return elapsed, samples_per_utt, total_utt, workload, extra
+    return elapsed, samples_per_utt, total_utt, workload, extra, pcm
 
 
 def free_port():
@@ -669,13 +695,20 @@ def main():
     ap.add_argument("--no-others", action="store_true", help="light: skip BASELINE configs 1, 3, 4 (other_configs)")
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU: start the N ranks, run a stand-in job over gloo on the host, print one line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline: cold start, parity, exact fp32, roofline, host figures, "
+                         "CPU baseline, other configs, strong-scaling job")
     args = ap.parse_args()
     steps = args.steps if args.steps is not None else (50 if args.config == "light" else 2)
     warmup = args.warmup if args.warmup is not None else (5 if args.config == "light" else 1)
+    if steps < 1 or warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     one_gpu = os.environ.get("FV_BENCH_ONE_GPU", "0") == "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started as one process (`python bench.py --gpus N`): become the N ranks -- exec the same launch line the
+        # started as one process (`python bench.py --gpus N`): run the N ranks as a child -- the same launch line the
         # driver uses for N > 1.  A node that cannot give every rank its own GPU is refused here, before anything starts.
         visible = torch.cuda.device_count()
         if not (args.launch_check or one_gpu) and visible < args.gpus:
@@ -683,7 +716,8 @@ def main():
                      "(HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES?): refusing to run ranks on shared devices")
         sys.stdout.flush()
         sys.stderr.flush()
-        os.execv(sys.executable, self_launch_argv(args.gpus, sys.argv[1:], free_port()))
+        import subprocess
+        sys.exit(subprocess.call(self_launch_argv(args.gpus, sys.argv[1:], free_port())))
     if args.launch_check:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29599")
@@ -745,40 +779,48 @@ def main():
         torch.cuda.synchronize()
         use_gather = gather is not None and not args.no_gather
         step, done = make_step(model, use_gather)
-        # the contract's protocol on the device as the process start left it (W warm-up steps, K timed), reported beside
-        # the headline; then the same W + K behind PREWARM_S seconds of untimed forwards: the headline
-        cold_elapsed, _ = timed_steps(step, steps, warmup, dist, dev, after=done, warm=False)
+        # --full: the contract's protocol on the device as the process start left it (W warm-up steps, K timed), reported
+        # beside the headline; then the same W + K behind PREWARM_S seconds of untimed forwards: the headline
+        if args.full:
+            cold_elapsed, _ = timed_steps(step, steps, warmup, dist, dev, after=done, warm=False)
         elapsed, wav = timed_steps(step, steps, warmup, dist, dev, after=done)
-        extra["cold_start"] = {"ms_per_step": 1e3 * cold_elapsed / steps,
-                               "what": f"the same {steps} steps after {warmup} warm-up steps WITHOUT the prewarm, first thing after "
-                                       "the plan build: the device's clock governor is still ramping (bench.py PREWARM_S)"}
+        if args.full:
+            extra["cold_start"] = {"ms_per_step": 1e3 * cold_elapsed / steps,
+                                   "what": f"the same {steps} steps after {warmup} warm-up steps WITHOUT the prewarm, first thing "
+                                           "after the plan build: the device's clock governor is still ramping (bench.py PREWARM_S)"}
         extra["prewarm"] = {"seconds": PREWARM_S, "forwards": PREWARM_LOG[-1] if PREWARM_LOG else 0,
                             "what": "untimed forwards of the same workload in front of the W warm-up steps of every leg, so "
                                     "that the K timed steps run at the device's steady-state clock (FV_BENCH_PREWARM_S=0: off)"}
         # the timed forwards ran stream-ordered (range_guard "lazy", set explicitly: the check is deferred): the check, now
         guard_clean = not model.check_range()
         assert guard_clean, "a timed forward left the split-f16 range: its output is not the reference's"
+        result = wav              # what the caller of the timed path holds after the last step (rank 0: every rank's rows)
         if use_gather:
             bufs = gather.flush()
             if rank == 0:          # rank 0 holds every rank's last waveforms, its own block bit for bit
                 assert len(bufs) == world and all(tuple(b.shape) == tuple(wav.shape) for b in bufs)
                 assert torch.equal(bufs[0].to(wav.device), wav)
-            step2, done2 = make_step(model, False)
-            e2, _ = timed_steps(step2, steps, warmup, dist, dev, after=done2)
-            extra["without_gather"] = {"ms_per_step": 1e3 * e2 / steps,
-                                       "what": "the same steps with the waveforms left on the ranks that made them"}
+                result = torch.cat([b.to(wav.device) for b in bufs])
+            if args.full:
+                step2, done2 = make_step(model, False)
+                e2, _ = timed_steps(step2, steps, warmup, dist, dev, after=done2)
+                extra["without_gather"] = {"ms_per_step": 1e3 * e2 / steps,
+                                           "what": "the same steps with the waveforms left on the ranks that made them"}
         samples_per_utt = int(wav.shape[-1])
         utt_per_step = B * world
-        golden_err = check_against_golden(wav[0]) if rank == 0 else None
+        golden_err = check_against_golden(wav[0]) if rank == 0 and args.full else None
         workload = (f"HiFi-GAN light (conf/hifigan/light.yaml) generator forward, mel 80x{T_FRAMES}, batch {B} "
                     f"utterance(s) per GPU, {samples_per_utt} samples each; BASELINE.json configs[1]"
                     + ("; waveforms gathered to rank 0 inside the timed steps" if use_gather else ""))
         scaling = "weak"
     else:
-        elapsed, samples_per_utt, utt_per_step, workload, extra = run_job(args, dev, dist, world, rank, steps, warmup)
+        elapsed, samples_per_utt, utt_per_step, workload, extra, result = run_job(args, dev, dist, world, rank, steps,
+                                                                                   warmup)
         golden_err = None
         scaling = "strong"
         mel = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "wav" if args.config == "light" else "pcm", result)
 
     total_samples = samples_per_utt * utt_per_step * steps
     value = total_samples / elapsed
@@ -801,7 +843,9 @@ def main():
                              "what": "last timed output, utterance 0, vs tests/golden/full_hifigan_light.npz "
                                      "(the reference's own output for this mel and these weights)"}
         out.update(extra)
-    if args.config == "light":
+        if args.config == "light":
+            out["config"]["plan_ops_per_forward"] = model._trunk_plan(T_FRAMES).num_ops()
+    if args.config == "light" and args.full:
         # ---- exact fp32: the same forward with every product on the fp32 matrix cores (precision = "f32") ----------
         if not args.no_exact:
             exact, _, _ = build_model("light", dev, dist, rank, precision="f32")
@@ -822,9 +866,8 @@ def main():
                             "everywhere (exact fp32 products, bit for bit an fmaf chain); without gather"}
             del exact
             torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         if args.config == "light":
-            out["config"]["plan_ops_per_forward"] = model._trunk_plan(T_FRAMES).num_ops()
             roofline, hbm = roofline_report(model, mel, ms_per_step)
             out["roofline"] = roofline
             out["roofline_hbm_stage"] = hbm
@@ -869,20 +912,20 @@ def main():
             if not args.no_cpu_baseline and world == 1:
                 out["cpu_baseline"] = cpu_baseline(cfg, sd, seeded_mel(T_FRAMES, seed=1))
                 out["cpu_baseline"]["rtf_22k05"] = out["cpu_baseline"]["seconds"] / (samples_per_utt / 22050.0)
-    if args.config == "light" and not args.no_others and world == 1 and rank == 0:
+    if args.config == "light" and args.full and not args.no_others and world == 1 and rank == 0:
         # ---- BASELINE configs 1, 3, 4: parity cases, driver-timed beside the headline (~1 s of GPU time) -------------
         out["other_configs"] = other_configs(dev)
-    if args.config == "light" and not args.no_job:
+    if args.config == "light" and args.full and not args.no_job:
         # ---- the strong-scaling job, appended: one timed step (all ranks take part) --------------------------------
         del model
         torch.cuda.empty_cache()
-        ej, spu, utt, wl, xj = run_job(args, dev, dist, world, rank, 1, 1)
+        ej, spu, utt, wl, xj, _ = run_job(args, dev, dist, world, rank, 1, 1)
         if rank == 0:
             tot = spu * utt
             out["strong_scaling_job"] = dict({"value": tot / ej, "unit": "samples/s", "ms_per_step": 1e3 * ej, "steps": 1,
                                               "warmup": 1, "scaling": "strong", "n_gpus": world,
                                               "rtf_22k05": ej / (tot / 22050.0), "workload": wl}, **xj)
-    if rank == 0:
+    if rank == 0 and args.full:
         # the figures a reader wants first, LAST in the line (a log tail keeps the end of it)
         oc = out.get("other_configs", {})
         out["summary"] = {
@@ -900,6 +943,7 @@ def main():
             "parity_max_abs": out.get("parity", {}).get("max_abs_vs_reference_golden"),
             "cpu_baseline_samples_per_s": out.get("cpu_baseline", {}).get("value"),
         }
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -30,7 +30,7 @@ def _bench(*args, **env):
 def test_bench_light_through_the_distributed_path():
     """Default workload through RCCL init, weight broadcast, per-step gather inside the timed region,
     barrier bracket and MAX all-reduce; the timed output is checked against the reference golden."""
-    out = _bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-job", "--no-exact")
+    out = _bench("--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-job", "--no-exact")
     assert out["n_gpus"] == 1 and out["scaling"] == "weak" and out["unit"] == "samples/s"
     assert "gathered to rank 0 inside the timed steps" in out["config"]["workload"]
     assert out["parity"]["max_abs_vs_reference_golden"] <= 1e-4
@@ -48,7 +48,7 @@ def test_bench_light_through_the_distributed_path():
 def test_bench_large512_job_shape_on_one_rank():
     """BASELINE configs[4] harness (scatter of mels, sub-batched forward, int16 sink, gather), shrunk to
     6 utterances: rows equal solo runs bit for bit (asserted inside bench.py)."""
-    out = _bench("--config", "large512", "--steps", "1", "--warmup", "0", "--sub", "4", FV_BENCH_JOB="6")
+    out = _bench("--full", "--config", "large512", "--steps", "1", "--warmup", "0", "--sub", "4", FV_BENCH_JOB="6")
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 6
     assert "int16 wav sink" in out["config"]["workload"]
     assert abs(out["value"] - 6 * 240000 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-6
@@ -69,14 +69,14 @@ def _torchrun2(*args, **env):
 
 
 def test_bench_gpus_2_started_directly_launches_its_ranks():
-    """`python bench.py --gpus 2` started as ONE process, the way the driver starts the bench: it re-executes itself
-    under torch.distributed.run (two ranks, here both on cuda:0 over gloo) and prints ONE line with both curves -- the
+    """`python bench.py --gpus 2` started as ONE process, the way the driver starts the bench: it runs itself
+    under torch.distributed.run as a child (two ranks, here both on cuda:0 over gloo) and prints ONE line with both curves -- the
     weak-scaling headline, golden-checked, and the appended strong-scaling job through parallel.synthesize_pipelined
     (rows bit-identical to solo runs, asserted inside bench.py)."""
     e = dict(os.environ, FV_BENCH_ONE_GPU="1", FV_BENCH_BACKEND="gloo", FV_BENCH_JOB="10")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "FV_BENCH_FORCE_DIST", "MASTER_PORT"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--no-exact", "--sub", "2"], env=e, cwd=cases.ROOT, capture_output=True,
                        text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
@@ -94,7 +94,7 @@ def test_two_ranks_share_the_gpu_strong_scaling_job():
     """BASELINE configs[4] with world_size 2 and the real generator: root scatter of 8 mels, two HIP forwards (one
     per rank, sub-batches of 2), int16 sink, root gather -- rows bit-identical to the root's own solo runs (asserted
     inside bench.py), and the job without scatter / gather timed beside it."""
-    out = _torchrun2("--config", "large512", "--steps", "1", "--warmup", "0", "--sub", "2", FV_BENCH_JOB="8")
+    out = _torchrun2("--full", "--config", "large512", "--steps", "1", "--warmup", "0", "--sub", "2", FV_BENCH_JOB="8")
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["global_batch"] == 8
     assert out["without_gather"]["ms_per_step"] > 0
     assert abs(out["value"] - 8 * 240000 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-6
@@ -103,7 +103,7 @@ def test_two_ranks_share_the_gpu_strong_scaling_job():
 def test_two_ranks_share_the_gpu_default_line_has_both_curves():
     """The default invocation at N = 2: the weak-scaling headline (each rank its own utterance, gathered inside the
     steps, golden-checked on rank 0) AND the appended strong-scaling job, each with its no-gather figure."""
-    out = _torchrun2("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-exact", FV_BENCH_JOB="6")
+    out = _torchrun2("--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-exact", FV_BENCH_JOB="6")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["global_batch"] == 2
     assert out["parity"]["max_abs_vs_reference_golden"] <= 1e-4
     assert out["without_gather"]["ms_per_step"] > 0

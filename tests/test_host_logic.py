@@ -397,6 +397,26 @@ def test_bench_refuses_worlds_it_cannot_place():
     assert bench.world_error(2, 2, 1, 1, one_gpu=True) is None
 
 
+def test_bench_dump_outputs_writes_float32_and_a_seeded_sample_of_rows(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: rows as float32; above the byte cap the same seeded choice of rows on every run, with
+    their indices beside them."""
+    import bench
+    pcm = torch.arange(10 * 8, dtype=torch.int16).reshape(10, 8) - 40
+    bench.dump_outputs(str(tmp_path / "all"), "pcm", pcm)
+    assert sorted(os.listdir(tmp_path / "all")) == ["pcm.npy"]
+    got = np.load(tmp_path / "all" / "pcm.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pcm.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 8 * 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "pcm", pcm)
+    rows = np.load(tmp_path / "a" / "pcm_rows.npy")
+    got = np.load(tmp_path / "a" / "pcm.npy")
+    assert rows.dtype == np.float64 and rows.shape == (3,) and np.all(np.diff(rows) > 0) and rows.max() < 10
+    assert got.dtype == np.float32 and np.array_equal(got, pcm.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "pcm_rows.npy"))
+    assert np.array_equal(got, np.load(tmp_path / "b" / "pcm.npy"))
+
+
 def test_stage32_policy_follows_the_window_arithmetic():
     """hifigan.stage32_windows_fit: the 32-channel one-launch stage kernel is used where its fixed 384-column windows are at
     least 65 % full -- the shapes measured in DESIGN.md section 4.3 fall on the sides they were measured on."""

@@ -12,6 +12,6 @@ for r in csv.DictReader(open("gpurun_out/ks/bench_kernel_stats.csv")):
             tot+=float(r["TotalDurationNs"]); n+=int(r["Calls"])
 print("rocprofv3: convh + convp average", round(tot/n/1e3,2), "us over", n, "dispatches")
 PY
-python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']
 print('bench.py: ms_per_step', d['ms_per_step'], 'frac', r['frac'], 'avg_launch_us', r['avg_launch_us'], r['measured'][-90:], 'kernel_ms', r['whole_step']['kernel_ms'], 'gaps', r['whole_step']['launch_gaps_ms']); print(r['by_family_ms_per_step']); print(d['roofline_hbm_stage']['frac'])"

@@ -1,4 +1,4 @@
-"""Turn gpurun_out/<tag>/ (tools/collect_profiles.sh) into the committed profiles/<tag>_* summaries."""
+"""Turn profile_out/<tag>/ (tools/collect_profiles.sh) into the committed profiles/<tag>_* summaries."""
 import csv
 import os
 import shutil
@@ -7,7 +7,7 @@ import sys
 from collections import defaultdict
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-src, dst = f"gpurun_out/{tag}", "profiles"
+src, dst = f"profile_out/{tag}", "profiles"
 os.makedirs(dst, exist_ok=True)
 shutil.copy(f"{src}/stats/bench_kernel_stats.csv", f"{dst}/{tag}_bench_kernel_stats.csv")
 shutil.copy(f"{src}/bench.json", f"{dst}/{tag}_bench.json")
