@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -31,7 +31,7 @@ PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outp
 POST_NONE, POST_TANH, POST_RELU = 0, 1, 2
 SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0, MAX_SLOTS = -1, 0, 1, 2, 32
 SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = 28, 29, 30    # caller-provided tensors of Plan.run(aux=..., out2=...)
-ABI_VERSION = 13
+ABI_VERSION = 14
 PAIR_F32, PAIR_SPLIT_F16 = 0, 1   # arithmetic of the fused ResBlock-pair kernels (fastvocoder_hip.h)
 
 
@@ -224,6 +224,7 @@ def lib():
                                           i, ctypes.POINTER(i), f, i, f]
     L.fv_encode_16bits.argtypes = [vp, vp, vp, i, i64, f, i, vp]
     L.fv_pqmf_analysis.argtypes = [vp, vp, vp, i, i, i, i64, vp]
+    L.fv_melspectrogram.argtypes = [vp, vp, vp, i, i64, i, i, i, i, i, f, vp]
     L.fv_fold_batchnorm_conv.argtypes = [vp, vp, vp, vp, vp, vp, f, vp, vp, i, i, i, vp]
     L.fv_packed_upsample_conv1d_floats.argtypes = [i, i, i, i, i]
     L.fv_packed_upsample_conv1d_floats.restype = i64
@@ -847,6 +848,26 @@ def pqmf_analysis(x, analysis_filter):
     with _on(x, h, y) as stream:
         check(lib().fv_pqmf_analysis(_ptr(x, "x"), _ptr(h, "analysis_filter"), _ptr(y), B, S, ntaps, T, stream))
     return y
+
+
+def mel_table_floats():
+    """Length of the fp32 table fv_melspectrogram reads (FV_MEL_TABLE_FLOATS)."""
+    return lib().fv_mel_table_floats()
+
+
+def melspectrogram(x, tables, sample_rate=24000, n_fft=2048, hop=240, win_length=1200, n_mels=80, fmin=40.0):
+    """x [B,n] fp32 device waveforms -> [B,n_mels,1+n//hop] normalised mel (fv_melspectrogram, one launch on the
+    current stream); tables: the fp32 device table of audio.mel_tables (include/fastvocoder_hip.h layout)."""
+    if x.dim() != 2:
+        raise NativeError(f"melspectrogram: x must be [B, n], got {tuple(x.shape)}")
+    B, n = x.shape
+    mel = torch.empty((B, n_mels, 1 + n // hop if hop > 0 else 0), dtype=torch.float32, device=x.device)
+    if tables.numel() != mel_table_floats():
+        raise NativeError(f"melspectrogram: tables hold {tables.numel()} floats, the library reads {mel_table_floats()}")
+    with _on(x, tables, mel) as stream:
+        check(lib().fv_melspectrogram(_ptr(x, "x"), _ptr(mel), _ptr(tables, "tables"), B, n, int(sample_rate),
+                                      int(n_fft), int(hop), int(win_length), int(n_mels), float(fmin), stream))
+    return mel
 
 
 def pqmf_synthesis(x, synthesis_filter, y):

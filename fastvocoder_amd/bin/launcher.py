@@ -1,6 +1,6 @@
-"""``MODE=<synthesize|test|publish> python -m fastvocoder_amd.bin.launcher --flags``
+"""``MODE=<synthesize|test|publish|preprocess> python -m fastvocoder_amd.bin.launcher --flags``
 -- the reference's $MODE dispatch (bin/launcher.py:7-19) for the inference-side
-modes.  ``train`` / ``preprocess`` are training-side and out of scope."""
+modes and the dataset preparation.  ``train`` is out of scope."""
 import os
 import sys
 
@@ -16,11 +16,14 @@ def main():
     elif mode == "publish":
         from .publish import run_publisher
         run_publisher()
-    elif mode in ("train", "preprocess"):
+    elif mode == "preprocess":
+        from .preprocess import run_preprocess
+        run_preprocess()
+    elif mode == "train":
         sys.exit(f"MODE={mode} is a training-side mode of the reference and is not part of "
                  "fastvocoder_amd (generator inference only)")
     else:
-        sys.exit("set MODE=synthesize | test | publish")
+        sys.exit("set MODE=synthesize | test | publish | preprocess")
 
 
 if __name__ == "__main__":

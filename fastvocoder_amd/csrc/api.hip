@@ -508,6 +508,23 @@ int fv_encode_16bits(float* x, int16_t* out, float* peak, int B, int64_t n, floa
                            reinterpret_cast<unsigned*>(peak), scale_in_place, (hipStream_t)stream);
 }
 
+int fv_mel_table_floats(void) { return FV_MEL_TABLE_FLOATS; }
+
+int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, int64_t n, int sample_rate, int n_fft,
+                      int hop, int win_length, int n_mels, float fmin, void* stream) {
+    if (sample_rate != 24000 || n_fft != 2048 || hop != 240 || win_length != 1200 || n_mels != 80 || fmin != 40.f)
+        return fail(FV_ERR_UNSUPPORTED,
+                    "melspectrogram: only sr=24000 n_fft=2048 hop=240 win_length=1200 n_mels=80 fmin=40 "
+                    "(got sr=%d n_fft=%d hop=%d win_length=%d n_mels=%d fmin=%g)",
+                    sample_rate, n_fft, hop, win_length, n_mels, (double)fmin);
+    if (!x || !mel || !tables || B <= 0 || B > 65535)
+        return fail(FV_ERR_INVALID_ARG, "melspectrogram: null tensor or B=%d", B);
+    if (n < n_fft / 2 + 1 || n / hop >= (int64_t)1 << 32)
+        return fail(FV_ERR_INVALID_ARG, "melspectrogram: n=%lld samples (reflect padding by %d needs n >= %d)",
+                    (long long)n, n_fft / 2, n_fft / 2 + 1);
+    return launch_melspectrogram(x, mel, tables, B, n, (hipStream_t)stream);
+}
+
 int fv_conv1d_2src_fused(const float* x, const float* x2, const float* packed, const float* bias,
                          const float* res, float* y, float* y_act, int B, int Cin1, int Cin2, int Cout,
                          int T, int post, float act_slope, void* stream) {

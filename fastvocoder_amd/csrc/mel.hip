@@ -1,0 +1,170 @@
+// Mel-spectrogram front end (reference: data/audio.py:58-61 melspectrogram with hparams.py:4-15,
+// librosa < 0.10 semantics; include/fastvocoder_hip.h fv_melspectrogram) in one launch:
+// wav -> preemphasis -> reflect-padded, Hann-windowed frames -> |rFFT| -> Slaney mel filters -> dB, clip.
+//
+// One wave per frame, kMelFrames frames per block.  The 2048-point real FFT is a 1024-point complex FFT of
+// the even/odd sample pairs (z[m] = f[2m] + i f[2m+1]) plus the usual split step into bins 0..1024:
+//   X[k] = E[k] + W^k O[k],  E = (Z[k] + conj Z[N-k]) / 2,  O = (Z[k] - conj Z[N-k]) / 2i,  W = exp(-2 pi i / 2048).
+// The complex FFT is Stockham radix-4 (1024 = 4^5, five passes, natural order out): each lane holds four
+// radix-4 butterflies in registers, so the frame is exchanged through its own 8 KB of LDS in place between the
+// passes.  The first pass reads its inputs straight from x (frame gather, preemphasis and the reflect index
+// mapping on the fly; only the 600 pairs under the window are non-zero).  The magnitudes then overwrite the
+// frame's LDS, and the block's 80 x kMelFrames (filter, frame) dot products run over the sparse filters; lanes
+// that share a filter write kMelFrames consecutive frames of one [B, 80, T] row.
+// Every table (window, twiddles, filters) comes from the host in float64 rounded once to fp32.
+#include "fv_internal.h"
+
+namespace fv {
+
+constexpr int kMelNc = 1024;               // complex FFT size = n_fft / 2
+constexpr int kMelHop = 240, kMelWin = 1200, kMelLpad = 424, kMelHalf = 1024, kMelMels = 80;
+constexpr int kMelFrames = 4;              // frames (= waves) per block
+constexpr int kMelThreads = 64 * kMelFrames;
+
+// preemphasised sample at padded position P (p = lfilter([1, -0.97], [1], x), then numpy 'reflect' by 1024);
+// n >= 1025 keeps one reflection in range on either side
+__device__ __forceinline__ float mel_padded_sample(const float* __restrict__ xr, int64_t n, int64_t P) {
+    int64_t q = P - kMelHalf;
+    if (q < 0) q = -q;
+    if (q >= n) q = 2 * (n - 1) - q;
+    const float v = xr[q];
+    return q > 0 ? fmaf(-0.97f, xr[q - 1], v) : v;
+}
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
+    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+// forward radix-4 DFT of v[0..3] (exp(-2 pi i rk / 4)), Stockham output order
+__device__ __forceinline__ void radix4(float2* v) {
+    const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y);
+    const float2 a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
+    const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y);
+    const float2 a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);   // -i (v1 - v3)
+    v[0] = make_float2(a0.x + a2.x, a0.y + a2.y);
+    v[1] = make_float2(a1.x + a3.x, a1.y + a3.y);
+    v[2] = make_float2(a0.x - a2.x, a0.y - a2.y);
+    v[3] = make_float2(a1.x - a3.x, a1.y - a3.y);
+}
+
+// Stockham pass with sub-transform size Ns: butterfly j reads z[j + 256 r], writes z[(j/Ns)*4Ns + j%Ns + Ns r]
+template <int Ns>
+__device__ __forceinline__ void mel_fft_pass(float2* __restrict__ z, const float2* __restrict__ tw, int lane) {
+    float2 v[4][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[q][r] = z[j + 256 * r];
+    }
+    __syncthreads();   // every read of the pass before any write (in place)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        if (Ns > 1) {
+            const int ti = (j % Ns) * (kMelNc / (4 * Ns));   // r * ti < 1024
+#pragma unroll
+            for (int r = 1; r < 4; ++r) v[q][r] = cmul(v[q][r], tw[r * ti]);
+        }
+        radix4(v[q]);
+        const int d = (j / Ns) * Ns * 4 + (j % Ns);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[d + Ns * r] = v[q][r];
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restrict__ x, float* __restrict__ mel,
+                                                          const float* __restrict__ tab, int64_t n, int64_t T) {
+    __shared__ float2 zs[kMelFrames][kMelNc];   // one frame per wave: complex FFT, then its magnitudes
+    __shared__ float2 tw[kMelNc];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int64_t t0 = (int64_t)blockIdx.x * kMelFrames;
+    const int64_t t = t0 + wv;
+    const float* __restrict__ xr = x + (size_t)b * n;
+    const float* __restrict__ win = tab + FV_MEL_TAB_WINDOW;
+    const float2* __restrict__ twg = reinterpret_cast<const float2*>(tab + FV_MEL_TAB_TWIDDLE);
+    for (int i = threadIdx.x; i < kMelNc; i += kMelThreads) tw[i] = twg[i];
+    float2* z = zs[wv];
+
+    // pass 1 (Ns = 1, no twiddles) on the gathered frame: z[m] = (w f)[2m] + i (w f)[2m+1]
+    {
+        float2 v[4][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = lane + 64 * q + 256 * r;
+                const int i0 = 2 * m - kMelLpad;   // window tap of sample 2m (even; the window length is even)
+                float2 s = make_float2(0.f, 0.f);
+                if (t < T && i0 >= 0 && i0 < kMelWin) {
+                    const int64_t P = t * kMelHop + 2 * m;
+                    s.x = win[i0] * mel_padded_sample(xr, n, P);
+                    s.y = win[i0 + 1] * mel_padded_sample(xr, n, P + 1);
+                }
+                v[q][r] = s;
+            }
+            const int j = lane + 64 * q;
+            radix4(v[q]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) z[4 * j + r] = v[q][r];
+        }
+        __syncthreads();
+    }
+    mel_fft_pass<4>(z, tw, lane);
+    mel_fft_pass<16>(z, tw, lane);
+    mel_fft_pass<64>(z, tw, lane);
+    mel_fft_pass<256>(z, tw, lane);
+
+    // split step: |X[k]| for k = lane + 64 i; X[1024] = Re Z[0] - Im Z[0]
+    {
+        const float2* __restrict__ sp = reinterpret_cast<const float2*>(tab + FV_MEL_TAB_SPLIT);
+        float mag[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int k = lane + 64 * i;
+            const float2 a = z[k], c = z[(kMelNc - k) & (kMelNc - 1)];
+            const float2 e = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));   // (Z[k] + conj Z[N-k]) / 2
+            const float2 o = make_float2(0.5f * (a.y + c.y), -0.5f * (a.x - c.x));  // (Z[k] - conj Z[N-k]) / 2i
+            const float2 wo = cmul(sp[k], o);
+            const float re = e.x + wo.x, im = e.y + wo.y;
+            mag[i] = sqrtf(fmaf(re, re, im * im));
+        }
+        const float nyq = fabsf(z[0].x - z[0].y);
+        __syncthreads();
+        float* mz = reinterpret_cast<float*>(z);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mz[lane + 64 * i] = mag[i];
+        if (lane == 0) mz[kMelNc] = nyq;
+        __syncthreads();
+    }
+
+    // mel filters, dB, normalise: task = (filter m, frame f), frames fastest so that a filter's lanes store
+    // kMelFrames consecutive outputs of its row
+    const float* __restrict__ heads = tab + FV_MEL_TAB_FILTERS;
+    const float* __restrict__ wts = tab + FV_MEL_TAB_WEIGHTS;
+    for (int task = threadIdx.x; task < kMelMels * kMelFrames; task += kMelThreads) {
+        const int m = task / kMelFrames, f = task % kMelFrames;
+        const int64_t tf = t0 + f;
+        if (tf >= T) continue;
+        const int start = (int)heads[3 * m], len = (int)heads[3 * m + 1], off = (int)heads[3 * m + 2];
+        const float* mz = reinterpret_cast<const float*>(zs[f]) + start;
+        const float* w = wts + off;
+        float acc = 0.f;
+        for (int i = 0; i < len; ++i) acc = fmaf(w[i], mz[i], acc);
+        const float db = 20.f * log10f(fmaxf(1e-5f, acc)) - 20.f;           // _amp_to_db - ref_level_db
+        const float v = fminf(fmaxf((db + 100.f) * 0.01f, 0.f), 1.f);        // _normalize
+        mel[((size_t)b * kMelMels + m) * (size_t)T + tf] = v;
+    }
+}
+
+int launch_melspectrogram(const float* x, float* mel, const float* tab, int B, int64_t n, hipStream_t s) {
+    const int64_t T = 1 + n / kMelHop;
+    const int64_t blocks = (T + kMelFrames - 1) / kMelFrames;
+    hipLaunchKernelGGL(mel_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(kMelThreads), 0, s, x, mel, tab, n, T);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace fv

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 13
+#define FV_ABI_VERSION 14
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -429,6 +429,37 @@ int fv_pqmf_analysis(const float* x, const float* h, float* y, int B, int S, int
  */
 int fv_encode_16bits(float* x, int16_t* out, float* peak, int B, int64_t n, float rescale_out,
                      int scale_in_place, void* stream);
+
+/*
+ * The reference's mel-spectrogram front end (data/audio.py:58-61 melspectrogram, hparams.py:4-15) in ONE launch,
+ * per waveform (row) of x [B, n]:
+ *   1. preemphasis p[0] = x[0], p[i] = x[i] - 0.97 x[i-1]                 (scipy lfilter, zero initial state)
+ *   2. |STFT|: center=True with numpy 'reflect' padding by n_fft/2, periodic Hann of win_length centred in
+ *      n_fft, hop; T = 1 + n / hop frames, bins 0..n_fft/2                  (librosa < 0.10 stft)
+ *   3. mel = filters @ |STFT|, the Slaney-normalised mel filters of librosa.filters.mel(sr, n_fft, n_mels, fmin)
+ *   4. out = clip((20 log10(max(1e-5, mel)) - ref_level_db(20) - min_level_db(-100)) / 100, 0, 1)
+ * x: fp32 device [B, n]; mel: fp32 device [B, n_mels, T] (the generators' forward layout).
+ * tables: fp32 device, FV_MEL_TABLE_FLOATS floats in the layout below, built in float64 on the host and rounded
+ * once (fastvocoder_amd/audio.py mel_tables):
+ *   [FV_MEL_TAB_WINDOW]   win_length window taps (the non-zero part of the padded window)
+ *   [FV_MEL_TAB_TWIDDLE]  n_fft/2 complex (re, im) exp(-2 pi i t / (n_fft/2)), the packed complex FFT's twiddles
+ *   [FV_MEL_TAB_SPLIT]    n_fft/2 complex exp(-2 pi i k / n_fft), the real-FFT split step's twiddles
+ *   [FV_MEL_TAB_FILTERS]  n_mels x (first bin, bin count, offset into the weights), integers held as floats
+ *   [FV_MEL_TAB_WEIGHTS]  each filter's non-zero weights, consecutive, at most FV_MEL_MAX_WEIGHTS in all
+ * The kernel is specialised to the reference's parameters: sample_rate 24000, n_fft 2048, hop 240, win_length 1200,
+ * n_mels 80, fmin 40; anything else returns FV_ERR_UNSUPPORTED.  n < n_fft/2 + 1 (too short to reflect-pad) or
+ * B outside 1..65535 returns FV_ERR_INVALID_ARG.
+ */
+#define FV_MEL_TAB_WINDOW 0
+#define FV_MEL_TAB_TWIDDLE 1200
+#define FV_MEL_TAB_SPLIT 3248
+#define FV_MEL_TAB_FILTERS 5296
+#define FV_MEL_TAB_WEIGHTS 5536
+#define FV_MEL_MAX_WEIGHTS 2050
+#define FV_MEL_TABLE_FLOATS (FV_MEL_TAB_WEIGHTS + FV_MEL_MAX_WEIGHTS)
+int fv_mel_table_floats(void);
+int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, int64_t n, int sample_rate, int n_fft,
+                      int hop, int win_length, int n_mels, float fmin, void* stream);
 
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
