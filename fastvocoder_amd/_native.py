@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "stft_loss.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -31,7 +31,7 @@ PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outp
 POST_NONE, POST_TANH, POST_RELU = 0, 1, 2
 SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0, MAX_SLOTS = -1, 0, 1, 2, 32
 SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = 28, 29, 30    # caller-provided tensors of Plan.run(aux=..., out2=...)
-ABI_VERSION = 14
+ABI_VERSION = 15
 PAIR_F32, PAIR_SPLIT_F16 = 0, 1   # arithmetic of the fused ResBlock-pair kernels (fastvocoder_hip.h)
 
 
@@ -225,6 +225,12 @@ def lib():
     L.fv_encode_16bits.argtypes = [vp, vp, vp, i, i64, f, i, vp]
     L.fv_pqmf_analysis.argtypes = [vp, vp, vp, i, i, i, i64, vp]
     L.fv_melspectrogram.argtypes = [vp, vp, vp, i, i64, i, i, i, i, i, f, vp]
+    L.fv_stft_table_floats.argtypes = [i, i]
+    L.fv_stft_magnitude.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
+    L.fv_stft_distance_workspace_bytes.argtypes = [i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i)]
+    L.fv_stft_distance_workspace_bytes.restype = i64
+    L.fv_stft_distance.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
+                                   ctypes.POINTER(i), vp, vp, ctypes.c_size_t, vp]
     L.fv_fold_batchnorm_conv.argtypes = [vp, vp, vp, vp, vp, vp, f, vp, vp, i, i, i, vp]
     L.fv_packed_upsample_conv1d_floats.argtypes = [i, i, i, i, i]
     L.fv_packed_upsample_conv1d_floats.restype = i64
@@ -868,6 +874,57 @@ def melspectrogram(x, tables, sample_rate=24000, n_fft=2048, hop=240, win_length
         check(lib().fv_melspectrogram(_ptr(x, "x"), _ptr(mel), _ptr(tables, "tables"), B, n, int(sample_rate),
                                       int(n_fft), int(hop), int(win_length), int(n_mels), float(fmin), stream))
     return mel
+
+
+def stft_table_floats(n_fft, win_length):
+    """Length of the fp32 table fv_stft_magnitude / fv_stft_distance read for one resolution."""
+    rc = lib().fv_stft_table_floats(int(n_fft), int(win_length))
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def stft_magnitude(x, table, n_fft, hop, win_length):
+    """x [B,n] fp32 device -> |STFT| [B, 1+n//hop, n_fft//2+1] (fv_stft_magnitude, one launch on the current
+    stream); table: the fp32 device table of loss.stft_tables (include/fastvocoder_hip.h layout)."""
+    if x.dim() != 2:
+        raise NativeError(f"stft_magnitude: x must be [B, n], got {tuple(x.shape)}")
+    B, n = x.shape
+    if table.numel() != stft_table_floats(n_fft, win_length):
+        raise NativeError(f"stft_magnitude: table holds {table.numel()} floats, the library reads "
+                          f"{stft_table_floats(n_fft, win_length)}")
+    mag = torch.empty((B, 1 + n // hop if hop > 0 else 0, n_fft // 2 + 1), dtype=torch.float32, device=x.device)
+    with _on(x, table, mag) as stream:
+        check(lib().fv_stft_magnitude(_ptr(x, "x"), _ptr(mag), _ptr(table, "table"), B, n, int(n_fft), int(hop),
+                                      int(win_length), stream))
+    return mag
+
+
+def stft_distance(x, y, tables, n_ffts, hops, win_lengths):
+    """x, y [B,n] fp32 device -> float64 [R,B,3] partial sums (S_diff, S_ref, S_log) per resolution and row
+    (fv_stft_distance: two launches on the current stream, the workspace from torch's allocator)."""
+    if x.dim() != 2 or x.shape != y.shape:
+        raise NativeError(f"stft_distance: x and y must both be [B, n], got {tuple(x.shape)} and {tuple(y.shape)}")
+    B, n = x.shape
+    R = len(tables)
+    if not (len(n_ffts) == len(hops) == len(win_lengths) == R):
+        raise NativeError("stft_distance: one table, n_fft, hop and win_length per resolution")
+    for t, nf, wl in zip(tables, n_ffts, win_lengths):
+        if t.numel() != stft_table_floats(nf, wl):
+            raise NativeError(f"stft_distance: a table holds {t.numel()} floats, the library reads "
+                              f"{stft_table_floats(nf, wl)}")
+    ia = ctypes.c_int * R
+    nf_a, hop_a, wl_a = ia(*map(int, n_ffts)), ia(*map(int, hops)), ia(*map(int, win_lengths))
+    need = lib().fv_stft_distance_workspace_bytes(B, n, R, nf_a, hop_a)
+    if need < 0:
+        check(int(need))
+    out = torch.empty((R, B, 3), dtype=torch.float64, device=x.device)
+    ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    with _on(x, y, out, ws, *tables) as stream:
+        tab_a = (ctypes.c_void_p * R)(*[_ptr(t, "table") for t in tables])
+        check(lib().fv_stft_distance(_ptr(x, "x"), _ptr(y, "y"), tab_a, B, n, R, nf_a, hop_a, wl_a, out.data_ptr(),
+                                     ws.data_ptr(), ws.numel() * 8, stream))
+    return out
 
 
 def pqmf_synthesis(x, synthesis_filter, y):

@@ -1,6 +1,6 @@
-"""``MODE=<synthesize|test|publish|preprocess> python -m fastvocoder_amd.bin.launcher --flags``
+"""``MODE=<synthesize|test|publish|preprocess|evaluation> python -m fastvocoder_amd.bin.launcher --flags``
 -- the reference's $MODE dispatch (bin/launcher.py:7-19) for the inference-side
-modes and the dataset preparation.  ``train`` is out of scope."""
+modes, the dataset preparation and the evaluation.  ``train`` is out of scope."""
 import os
 import sys
 
@@ -19,11 +19,14 @@ def main():
     elif mode == "preprocess":
         from .preprocess import run_preprocess
         run_preprocess()
+    elif mode == "evaluation":
+        from .evaluation import run_evaluation
+        run_evaluation()
     elif mode == "train":
         sys.exit(f"MODE={mode} is a training-side mode of the reference and is not part of "
                  "fastvocoder_amd (generator inference only)")
     else:
-        sys.exit("set MODE=synthesize | test | publish | preprocess")
+        sys.exit("set MODE=synthesize | test | publish | preprocess | evaluation")
 
 
 if __name__ == "__main__":

@@ -525,6 +525,65 @@ int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, in
     return launch_melspectrogram(x, mel, tables, B, n, (hipStream_t)stream);
 }
 
+static int stft_check_res(const char* who, int64_t n, int n_fft, int hop, int win_length) {
+    if ((n_fft != 512 && n_fft != 1024 && n_fft != 2048) || hop < 1 || win_length < 1 || win_length > n_fft)
+        return fail(FV_ERR_UNSUPPORTED,
+                    "%s: n_fft must be 512, 1024 or 2048, hop >= 1 and 1 <= win_length <= n_fft "
+                    "(got n_fft=%d hop=%d win_length=%d)", who, n_fft, hop, win_length);
+    if (n < n_fft / 2 + 1 || n / hop >= (int64_t)1 << 31)
+        return fail(FV_ERR_INVALID_ARG, "%s: n=%lld samples (reflect padding by %d needs n >= %d)", who,
+                    (long long)n, n_fft / 2, n_fft / 2 + 1);
+    return 0;
+}
+
+int fv_stft_table_floats(int n_fft, int win_length) {
+    if ((n_fft != 512 && n_fft != 1024 && n_fft != 2048) || win_length < 1 || win_length > n_fft)
+        return fail(FV_ERR_UNSUPPORTED, "stft table: n_fft=%d win_length=%d", n_fft, win_length);
+    return FV_STFT_TAB_WINDOW(n_fft) + win_length;
+}
+
+int fv_stft_magnitude(const float* x, float* mag, const float* table, int B, int64_t n, int n_fft, int hop,
+                      int win_length, void* stream) {
+    if (int rc = stft_check_res("stft_magnitude", n, n_fft, hop, win_length)) return rc;
+    if (!x || !mag || !table || B <= 0 || B > 65535)
+        return fail(FV_ERR_INVALID_ARG, "stft_magnitude: null tensor or B=%d", B);
+    return launch_stft_magnitude(x, mag, table, B, n, n_fft, hop, win_length, (hipStream_t)stream);
+}
+
+static int64_t stft_distance_check(int B, int64_t n, int R, const int* n_fft, const int* hop, const int* win) {
+    if (R < 1 || R > FV_STFT_MAX_RES || !n_fft || !hop)
+        return fail(FV_ERR_INVALID_ARG, "stft_distance: R=%d resolutions (1..%d)", R, FV_STFT_MAX_RES);
+    if (B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "stft_distance: B=%d", B);
+    int64_t chunks = 0;
+    for (int r = 0; r < R; ++r) {
+        if (int rc = stft_check_res("stft_distance", n, n_fft[r], hop[r], win ? win[r] : n_fft[r])) return rc;
+        chunks += stft_chunks(n, hop[r]);
+    }
+    if (chunks >= (int64_t)1 << 31) return fail(FV_ERR_INVALID_ARG, "stft_distance: n=%lld too long", (long long)n);
+    return (int64_t)B * chunks * 3 * (int64_t)sizeof(double);
+}
+
+int64_t fv_stft_distance_workspace_bytes(int B, int64_t n, int R, const int* n_fft, const int* hop) {
+    return stft_distance_check(B, n, R, n_fft, hop, nullptr);
+}
+
+int fv_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
+                     const int* n_fft, const int* hop, const int* win_length, double* out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (!win_length) return fail(FV_ERR_INVALID_ARG, "stft_distance: win_length is null");
+    const int64_t need = stft_distance_check(B, n, R, n_fft, hop, win_length);
+    if (need < 0) return (int)need;
+    if (!x || !y || !tables || !out || !workspace)
+        return fail(FV_ERR_INVALID_ARG, "stft_distance: null pointer");
+    for (int r = 0; r < R; ++r)
+        if (!tables[r]) return fail(FV_ERR_INVALID_ARG, "stft_distance: table %d is null", r);
+    if ((uint64_t)workspace_bytes < (uint64_t)need || ((uintptr_t)workspace & 7))
+        return fail(FV_ERR_INVALID_ARG, "stft_distance: workspace of %zu bytes, needs %lld (8-byte aligned)",
+                    workspace_bytes, (long long)need);
+    return launch_stft_distance(x, y, tables, B, n, R, n_fft, hop, win_length, out,
+                                static_cast<double*>(workspace), (hipStream_t)stream);
+}
+
 int fv_conv1d_2src_fused(const float* x, const float* x2, const float* packed, const float* bias,
                          const float* res, float* y, float* y_act, int B, int Cin1, int Cin2, int Cout,
                          int T, int post, float act_slope, void* stream) {

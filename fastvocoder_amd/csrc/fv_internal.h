@@ -433,6 +433,11 @@ int launch_encode16(float* x, int B, int64_t n, float rescale, short* out, unsig
 int launch_pqmf_analysis(const float* xin, const float* ha, float* x, int B, int S, int ntaps,
                          int64_t T, hipStream_t s);
 int launch_melspectrogram(const float* x, float* mel, const float* tab, int B, int64_t n, hipStream_t s);
+int64_t stft_chunks(int64_t n, int hop);   // distance-kernel blocks per utterance and resolution (stft_loss.hip)
+int launch_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
+                         const int* nfft, const int* hop, const int* win, double* out, double* ws, hipStream_t s);
+int launch_stft_magnitude(const float* x, float* mag, const float* tab, int B, int64_t n, int nfft, int hop, int win,
+                          hipStream_t s);
 
 // self-check of pair_kernels.hpp div_exact against the device's division (fv_div_probe; pair_inst_c16.hip)
 int launch_div_probe(unsigned first, long long n, float d, unsigned long long* mismatches, hipStream_t s);

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 14
+#define FV_ABI_VERSION 15
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -460,6 +460,55 @@ int fv_encode_16bits(float* x, int16_t* out, float* peak, int B, int64_t n, floa
 int fv_mel_table_floats(void);
 int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, int64_t n, int sample_rate, int n_fft,
                       int hop, int win_length, int n_mels, float fmin, void* stream);
+
+/*
+ * The reference's STFT magnitude (model/loss/stft_loss.py:16-39 stft: torch.stft with its defaults, then
+ * sqrt(clamp(re^2 + im^2, min=1e-7))), per row of x [B, n]:
+ *   center=True with numpy 'reflect' padding by n_fft/2 on each side (no edge repeat); the win_length window centred
+ *   in n_fft (left offset (n_fft - win_length) / 2, zeros around it); T = 1 + n / hop frames; bins 0..n_fft/2;
+ *   mag[b, t, k] = sqrt(max(re^2 + im^2, 1e-7)).
+ * x: fp32 device [B, n]; mag: fp32 device [B, T, n_fft/2 + 1] (the reference's (B, #frames, #bins)).
+ * table: fp32 device, fv_stft_table_floats(n_fft, win_length) floats, built in float64 on the host and rounded once
+ * (fastvocoder_amd/loss/stft_loss.py stft_tables):
+ *   [FV_STFT_TAB_TWIDDLE(n_fft)]  n_fft/2 complex (re, im) exp(-2 pi i t / (n_fft/2)), the packed complex FFT's twiddles
+ *   [FV_STFT_TAB_SPLIT(n_fft)]    n_fft/2 complex exp(-2 pi i k / n_fft), the real-FFT split step's twiddles
+ *   [FV_STFT_TAB_WINDOW(n_fft)]   the win_length window taps (torch.hann_window(win_length) by default)
+ * n_fft must be 512, 1024 or 2048, hop >= 1 and 1 <= win_length <= n_fft, otherwise FV_ERR_UNSUPPORTED (and
+ * fv_stft_table_floats returns FV_ERR_UNSUPPORTED).  n < n_fft/2 + 1 (too short to reflect-pad), a null pointer or
+ * B outside 1..65535 returns FV_ERR_INVALID_ARG.  One launch.
+ */
+#define FV_STFT_MAX_RES 8
+#define FV_STFT_TAB_TWIDDLE(n_fft) 0
+#define FV_STFT_TAB_SPLIT(n_fft) (n_fft)
+#define FV_STFT_TAB_WINDOW(n_fft) (2 * (n_fft))
+int fv_stft_table_floats(int n_fft, int win_length);
+int fv_stft_magnitude(const float* x, float* mag, const float* table, int B, int64_t n, int n_fft, int hop,
+                      int win_length, void* stream);
+
+/*
+ * The per-utterance partial sums of the reference's multi-resolution STFT loss (model/loss/stft_loss.py:42-80
+ * SpectralConvergenceLoss / LogSTFTMagnitudeLoss, :124-155 MultiResolutionSTFTLoss) for an estimate x and a target
+ * y, both fp32 device [B, n].  With X, Y the fv_stft_magnitude magnitudes of x and y at resolution r
+ * (n_fft[r], hop[r], win_length[r], tables[r]), summed over all T_r frames and n_fft[r]/2 + 1 bins:
+ *   out[r, b, 0] = S_diff = sum (|Y| - |X|)^2
+ *   out[r, b, 1] = S_ref  = sum |Y|^2
+ *   out[r, b, 2] = S_log  = sum |ln|Y| - ln|X||
+ * out: float64 device [R, B, 3].  The reference's batch-level terms are
+ *   SC_r = sqrt(sum_b S_diff) / sqrt(sum_b S_ref),  mag_r = sum_b S_log / (B T_r (n_fft[r]/2 + 1)),
+ * each averaged over the R resolutions (fastvocoder_amd/loss/stft_loss.py).  tables: a HOST array of R device
+ * pointers, each table laid out as for fv_stft_magnitude; n_fft, hop, win_length: HOST arrays of R ints.
+ * Two launches on `stream`: all resolutions' frames in one (the magnitudes never leave the chip; each block writes
+ * three float64 partials to `workspace`), then a fixed-order float64 sum per (r, b).  No atomics: identical calls
+ * return identical bits.  workspace: device memory of at least fv_stft_distance_workspace_bytes(B, n, R, n_fft, hop)
+ * bytes (8-byte aligned).  Per-resolution parameters are checked as for fv_stft_magnitude (FV_ERR_UNSUPPORTED,
+ * FV_ERR_INVALID_ARG for a short n); R outside 1..FV_STFT_MAX_RES, a small workspace, a null pointer or B outside
+ * 1..65535 returns FV_ERR_INVALID_ARG.  fv_stft_distance_workspace_bytes returns a negative FV_ERR_* code for
+ * arguments fv_stft_distance would refuse.
+ */
+int64_t fv_stft_distance_workspace_bytes(int B, int64_t n, int R, const int* n_fft, const int* hop);
+int fv_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
+                     const int* n_fft, const int* hop, const int* win_length, double* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
