@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "stft_loss.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "stft_loss.hip", "disc.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -31,7 +31,7 @@ PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outp
 POST_NONE, POST_TANH, POST_RELU = 0, 1, 2
 SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0, MAX_SLOTS = -1, 0, 1, 2, 32
 SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = 28, 29, 30    # caller-provided tensors of Plan.run(aux=..., out2=...)
-ABI_VERSION = 15
+ABI_VERSION = 16
 PAIR_F32, PAIR_SPLIT_F16 = 0, 1   # arithmetic of the fused ResBlock-pair kernels (fastvocoder_hip.h)
 
 
@@ -231,6 +231,13 @@ def lib():
     L.fv_stft_distance_workspace_bytes.restype = i64
     L.fv_stft_distance.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
                                    ctypes.POINTER(i), vp, vp, ctypes.c_size_t, vp]
+    L.fv_stft_magnitude_bins.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
+    L.fv_grouped_conv1d.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
+    L.fv_avg_pool1d.argtypes = [vp, vp, i, i64, i, i, i, vp]
+    L.fv_disc_score_workspace_bytes.argtypes = [i, i, ctypes.POINTER(i64)]
+    L.fv_disc_score_workspace_bytes.restype = i64
+    L.fv_disc_score_sums.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i, i, vp, vp,
+                                     ctypes.c_size_t, vp]
     L.fv_fold_batchnorm_conv.argtypes = [vp, vp, vp, vp, vp, vp, f, vp, vp, i, i, i, vp]
     L.fv_packed_upsample_conv1d_floats.argtypes = [i, i, i, i, i]
     L.fv_packed_upsample_conv1d_floats.restype = i64
@@ -924,6 +931,75 @@ def stft_distance(x, y, tables, n_ffts, hops, win_lengths):
         tab_a = (ctypes.c_void_p * R)(*[_ptr(t, "table") for t in tables])
         check(lib().fv_stft_distance(_ptr(x, "x"), _ptr(y, "y"), tab_a, B, n, R, nf_a, hop_a, wl_a, out.data_ptr(),
                                      ws.data_ptr(), ws.numel() * 8, stream))
+    return out
+
+
+def stft_magnitude_bins(x, table, n_fft, hop, win_length):
+    """x [B,n] fp32 device -> |STFT| [B, n_fft//2+1, 1+n//hop], bins-major (fv_stft_magnitude_bins, one launch): the
+    transpose of stft_magnitude's result, bit for bit."""
+    if x.dim() != 2:
+        raise NativeError(f"stft_magnitude_bins: x must be [B, n], got {tuple(x.shape)}")
+    B, n = x.shape
+    if table.numel() != stft_table_floats(n_fft, win_length):
+        raise NativeError(f"stft_magnitude_bins: table holds {table.numel()} floats, the library reads "
+                          f"{stft_table_floats(n_fft, win_length)}")
+    mag = torch.empty((B, n_fft // 2 + 1, 1 + n // hop if hop > 0 else 0), dtype=torch.float32, device=x.device)
+    with _on(x, table, mag) as stream:
+        check(lib().fv_stft_magnitude_bins(_ptr(x, "x"), _ptr(mag), _ptr(table, "table"), B, n, int(n_fft), int(hop),
+                                           int(win_length), stream))
+    return mag
+
+
+def grouped_conv1d(x, w, bias, k, stride, pad, slope=1.0, out=None):
+    """x [B,Cin,Tin], w [Cout,4,k] folded weight (groups = Cin/4), bias [Cout] or None -> lrelu(conv, slope)
+    [B,Cout,(Tin+2pad-k)//stride+1] (fv_grouped_conv1d, one launch)."""
+    if x.dim() != 3 or w.dim() != 3:
+        raise NativeError(f"grouped_conv1d: x [B,Cin,T] and w [Cout,4,k], got {tuple(x.shape)} and {tuple(w.shape)}")
+    B, cin, T = x.shape
+    cout = w.shape[0]
+    if w.shape[1:] != (4, k):
+        raise NativeError(f"grouped_conv1d: w must be [Cout, 4, {k}], got {tuple(w.shape)}")
+    tout = (T + 2 * pad - k) // stride + 1 if stride > 0 else 0
+    if out is None:
+        out = torch.empty((B, cout, max(tout, 0)), dtype=torch.float32, device=x.device)
+    with _on(x, w, bias, out) as stream:
+        check(lib().fv_grouped_conv1d(_ptr(x, "x"), _ptr(w, "w"), _ptr(bias, "bias", True), _ptr(out, "out"), B, cin,
+                                      cout, T, int(k), int(stride), int(pad), float(slope), stream))
+    return out
+
+
+def avg_pool1d(x, k, stride, pad):
+    """x [..., Tin] fp32 device -> AvgPool1d(k, stride, pad, count_include_pad=False) [..., Tout] (fv_avg_pool1d)."""
+    tin = x.shape[-1]
+    rows = x.numel() // tin if tin else 0
+    tout = (tin + 2 * pad - k) // stride + 1 if stride > 0 else 0
+    out = torch.empty(tuple(x.shape[:-1]) + (max(tout, 0),), dtype=torch.float32, device=x.device)
+    with _on(x, out) as stream:
+        check(lib().fv_avg_pool1d(_ptr(x, "x"), _ptr(out), rows, tin, int(k), int(stride), int(pad), stream))
+    return out
+
+
+def disc_score_sums(es, rs):
+    """Lists of M map pairs, each e_m and r_m fp32 device [B, ...] of one shape -> float64 [M, B, 4]:
+    sum|e-r|, sum(e-1)^2, sum e^2, sum(r-1)^2 per map and row (fv_disc_score_sums: two launches)."""
+    M = len(es)
+    if M != len(rs) or M == 0:
+        raise NativeError(f"disc_score_sums: {len(es)} estimate maps and {len(rs)} real maps")
+    B = es[0].shape[0]
+    for e, r in zip(es, rs):
+        if e.shape != r.shape or e.shape[0] != B:
+            raise NativeError(f"disc_score_sums: map shapes {tuple(e.shape)} and {tuple(r.shape)} (batch {B})")
+    n = (ctypes.c_int64 * M)(*[e[0].numel() for e in es])
+    need = lib().fv_disc_score_workspace_bytes(B, M, n)
+    if need < 0:
+        check(int(need))
+    dev = es[0].device
+    out = torch.empty((M, B, 4), dtype=torch.float64, device=dev)
+    ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.float64, device=dev)
+    with _on(out, ws, *es, *rs) as stream:
+        e_a = (ctypes.c_void_p * M)(*[_ptr(e, "e") for e in es])
+        r_a = (ctypes.c_void_p * M)(*[_ptr(r, "r") for r in rs])
+        check(lib().fv_disc_score_sums(e_a, r_a, n, M, B, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream))
     return out
 
 

@@ -8,6 +8,16 @@ resolutions), one utterance at a time, on the GPU.  Output, one line per utteran
     eval mean utterances=<count> sc=<mean sc> mag=<mean mag>
 
 (numbers printed with ``%.8e``; sc and mag are each averaged over the three resolutions).
+
+With ``--discriminator`` the checkpoint's ``'discriminator'`` entry (a training checkpoint of the reference holds it
+beside ``'model'``, bin/train.py:235-247) is loaded into fastvocoder_amd.discriminator.Discriminator, and every
+utterance is also scored with the adversarial / feature-map / discriminator terms of the reference's training loop
+(loss.discriminator_terms), estimate against target:
+
+    eval-d <i> adv=<adversarial> fm=<feature map> real=<real> fake=<fake> d=<real + fake>
+    eval-d mean utterances=<count> adv=<mean adv> fm=<mean fm> d=<mean d>
+
+each after the corresponding ``eval`` line.  Without the flag the output is unchanged.
 """
 import argparse
 import os
@@ -15,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from ..loss import MultiResolutionSTFTLoss
+from ..loss import MultiResolutionSTFTLoss, discriminator_terms
 from .synthesize import Synthesizer
 
 
@@ -37,14 +47,36 @@ def load_data(audio_index_path, mel_index_path, index_list):
     return audio_list, mel_list, [audio_index[i] for i in index_list]
 
 
-def score(synthesizer, loss, wav, mel):
-    """(samples, sc, mag) of one utterance: synthesize mel [80, T], crop both to the common length."""
+def score(synthesizer, loss, wav, mel, discriminator=None):
+    """(samples, sc, mag) of one utterance: synthesize mel [80, T], crop both to the common length; with a
+    discriminator also its five terms (a dict) as a fourth item."""
     est = synthesizer.synthesize(np.asarray(mel).T)[0]
     target = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).to(est.device)
     n = min(est.shape[0], target.shape[0])
     with torch.no_grad():
         sc, mag = loss.per_utterance(est[None, :n], target[None, :n])[0].tolist()
-    return n, sc, mag
+    if discriminator is None:
+        return n, sc, mag
+    return n, sc, mag, score_discriminator(discriminator, est[:n].contiguous(), target[:n].contiguous())
+
+
+def load_discriminator(synthesizer):
+    """The checkpoint's discriminator on the synthesizer's device, or a clear exit when the checkpoint has none."""
+    from ..discriminator import Discriminator
+    sd = synthesizer.checkpoint.get("discriminator") if isinstance(synthesizer.checkpoint, dict) else None
+    if sd is None:
+        raise SystemExit("evaluation: --discriminator needs a checkpoint with a 'discriminator' entry (a training "
+                         "checkpoint of the reference); this one has none")
+    d = Discriminator().to(synthesizer.device)
+    d.load_state_dict(sd)
+    return d.eval()
+
+
+def score_discriminator(discriminator, est, target):
+    """The five discriminator terms of one (estimate, target) pair of [n] device waveforms, as floats."""
+    with torch.no_grad():
+        terms = discriminator_terms(discriminator(est[None, None]), discriminator(target[None, None]))
+    return {k: float(v) for k, v in terms.items()}
 
 
 def run_evaluation(argv=None):
@@ -55,6 +87,9 @@ def run_evaluation(argv=None):
     parser.add_argument('--config', type=str, help="path to model configuration file")
     parser.add_argument('--model_name', type=str, help="melgan, hifigan, multiband-hifigan and basis-melgan.")
     parser.add_argument('--num', type=int, default=6, help="score utterances 0..num-1 of the index (default 6)")
+    parser.add_argument('--discriminator', action='store_true',
+                        help="also print the adversarial / feature-map / discriminator scores of the checkpoint's "
+                             "'discriminator'")
     args = parser.parse_args(argv)
     if args.num < 1:
         raise SystemExit("evaluation: --num must be at least 1")
@@ -62,13 +97,22 @@ def run_evaluation(argv=None):
     synthesizer = Synthesizer(args.checkpoint_path, args.config, args.model_name)
     audio_list, mel_list, names = load_data(args.audio_index_path, args.mel_index_path, list(range(args.num)))
     loss = MultiResolutionSTFTLoss().to(synthesizer.device)
-    rows = []
+    disc = load_discriminator(synthesizer) if args.discriminator else None
+    rows, drows = [], []
     for i, (wav, mel, name) in enumerate(zip(audio_list, mel_list, names)):
-        n, sc, mag = score(synthesizer, loss, wav, mel)
+        n, sc, mag, *d = score(synthesizer, loss, wav, mel, disc)
         rows.append((sc, mag))
         print(f"eval {i} {name} samples={n} sc={sc:.8e} mag={mag:.8e}")
+        if d:
+            t = d[0]
+            drows.append((t["adversarial"], t["feature_map"], t["discriminator"]))
+            print(f"eval-d {i} adv={t['adversarial']:.8e} fm={t['feature_map']:.8e} real={t['real']:.8e} "
+                  f"fake={t['fake']:.8e} d={t['discriminator']:.8e}")
     sc_mean, mag_mean = (float(np.mean(c)) for c in zip(*rows))
     print(f"eval mean utterances={len(rows)} sc={sc_mean:.8e} mag={mag_mean:.8e}")
+    if drows:
+        adv, fm, d = (float(np.mean(c)) for c in zip(*drows))
+        print(f"eval-d mean utterances={len(drows)} adv={adv:.8e} fm={fm:.8e} d={d:.8e}")
     return rows
 
 

@@ -584,6 +584,64 @@ int fv_stft_distance(const float* x, const float* y, const float* const* tables,
                                 static_cast<double*>(workspace), (hipStream_t)stream);
 }
 
+int fv_stft_magnitude_bins(const float* x, float* mag, const float* table, int B, int64_t n, int n_fft, int hop,
+                           int win_length, void* stream) {
+    if (int rc = stft_check_res("stft_magnitude_bins", n, n_fft, hop, win_length)) return rc;
+    if (!x || !mag || !table || B <= 0 || B > 65535)
+        return fail(FV_ERR_INVALID_ARG, "stft_magnitude_bins: null tensor or B=%d", B);
+    return launch_stft_magnitude(x, mag, table, B, n, n_fft, hop, win_length, (hipStream_t)stream, true);
+}
+
+int fv_grouped_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Tin,
+                      int k, int stride, int pad, float slope, void* stream) {
+    if (Cin < 4 || Cin % 4 || Cout < 1 || Cout % (Cin / 4) || k < 1 || stride < 1)
+        return fail(FV_ERR_UNSUPPORTED, "grouped_conv1d: Cin=%d Cout=%d k=%d stride=%d (Cin %% 4 == 0, groups = Cin/4 "
+                    "dividing Cout, k >= 1, stride >= 1)", Cin, Cout, k, stride);
+    const int opg = Cout / (Cin / 4);
+    if (grouped_conv_lds_bytes(k, stride, opg % 16 == 0 ? 16 : 4) > 65536)
+        return fail(FV_ERR_UNSUPPORTED, "grouped_conv1d: k=%d stride=%d exceed a block's shared memory", k, stride);
+    if (!x || !w || !y || B <= 0 || B > 65535 || Tin < 1 || pad < 0)
+        return fail(FV_ERR_INVALID_ARG, "grouped_conv1d: null tensor, B=%d, Tin=%d or pad=%d", B, Tin, pad);
+    if (y == x || y == w) return fail(FV_ERR_INVALID_ARG, "grouped_conv1d: y must not alias x or w");
+    const int64_t span = (int64_t)Tin + 2 * (int64_t)pad - k;
+    if (span < 0) return fail(FV_ERR_INVALID_ARG, "grouped_conv1d: empty output (Tin=%d pad=%d k=%d)", Tin, pad, k);
+    return launch_grouped_conv1d(x, w, bias, y, B, Cin, Cout, Tin, (int)(span / stride + 1), k, stride, pad, slope,
+                                 (hipStream_t)stream);
+}
+
+int fv_avg_pool1d(const float* x, float* y, int rows, int64_t Tin, int k, int stride, int pad, void* stream) {
+    if (!x || !y || x == y || rows < 1 || rows > 65535 || k < 1 || stride < 1 || pad < 0 || 2 * pad > k)
+        return fail(FV_ERR_INVALID_ARG, "avg_pool1d: rows=%d k=%d stride=%d pad=%d", rows, k, stride, pad);
+    const int64_t span = Tin + 2 * (int64_t)pad - k;
+    if (Tin < 1 || span < 0)
+        return fail(FV_ERR_INVALID_ARG, "avg_pool1d: empty output (Tin=%lld k=%d pad=%d)", (long long)Tin, k, pad);
+    return launch_avg_pool1d(x, y, rows, Tin, span / stride + 1, k, stride, pad, (hipStream_t)stream);
+}
+
+int64_t fv_disc_score_workspace_bytes(int B, int M, const int64_t* n) {
+    if (M < 1 || M > FV_DISC_MAX_MAPS || !n)
+        return fail(FV_ERR_INVALID_ARG, "disc_score_sums: M=%d maps (1..%d)", M, FV_DISC_MAX_MAPS);
+    if (B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "disc_score_sums: B=%d", B);
+    for (int m = 0; m < M; ++m)
+        if (n[m] < 1) return fail(FV_ERR_INVALID_ARG, "disc_score_sums: map %d has %lld elements", m, (long long)n[m]);
+    const int64_t chunks = score_chunks(M, n);
+    if (chunks >= (int64_t)1 << 31) return fail(FV_ERR_INVALID_ARG, "disc_score_sums: maps too large");
+    return (int64_t)B * chunks * 4 * (int64_t)sizeof(double);
+}
+
+int fv_disc_score_sums(const float* const* e, const float* const* r, const int64_t* n, int M, int B, double* out,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    const int64_t need = fv_disc_score_workspace_bytes(B, M, n);
+    if (need < 0) return (int)need;
+    if (!e || !r || !out || !workspace) return fail(FV_ERR_INVALID_ARG, "disc_score_sums: null pointer");
+    for (int m = 0; m < M; ++m)
+        if (!e[m] || !r[m]) return fail(FV_ERR_INVALID_ARG, "disc_score_sums: map %d is null", m);
+    if ((uint64_t)workspace_bytes < (uint64_t)need || ((uintptr_t)workspace & 7))
+        return fail(FV_ERR_INVALID_ARG, "disc_score_sums: workspace of %zu bytes, needs %lld (8-byte aligned)",
+                    workspace_bytes, (long long)need);
+    return launch_disc_score_sums(e, r, n, M, B, out, static_cast<double*>(workspace), (hipStream_t)stream);
+}
+
 int fv_conv1d_2src_fused(const float* x, const float* x2, const float* packed, const float* bias,
                          const float* res, float* y, float* y_act, int B, int Cin1, int Cin2, int Cout,
                          int T, int post, float act_slope, void* stream) {

@@ -437,7 +437,16 @@ int64_t stft_chunks(int64_t n, int hop);   // distance-kernel blocks per utteran
 int launch_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
                          const int* nfft, const int* hop, const int* win, double* out, double* ws, hipStream_t s);
 int launch_stft_magnitude(const float* x, float* mag, const float* tab, int B, int64_t n, int nfft, int hop, int win,
-                          hipStream_t s);
+                          hipStream_t s, bool bins_major = false);   // bins_major: [B, bins, T] (fv_stft_magnitude_bins)
+// discriminator kernels (disc.hip)
+size_t grouped_conv_lds_bytes(int k, int s, int ocb);
+int launch_grouped_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout,
+                          int Tin, int Tout, int k, int s, int pad, float slope, hipStream_t st);
+int launch_avg_pool1d(const float* x, float* y, int rows, int64_t Tin, int64_t Tout, int k, int s, int p,
+                      hipStream_t st);
+int64_t score_chunks(int M, const int64_t* n);   // score-sum blocks per row over all maps
+int launch_disc_score_sums(const float* const* e, const float* const* r, const int64_t* n, int M, int B, double* out,
+                           double* ws, hipStream_t st);
 
 // self-check of pair_kernels.hpp div_exact against the device's division (fv_div_probe; pair_inst_c16.hip)
 int launch_div_probe(unsigned first, long long n, float d, unsigned long long* mismatches, hipStream_t s);

@@ -279,8 +279,9 @@ __global__ __launch_bounds__(64) void stft_sum_kernel(const double* __restrict__
 }
 
 // magnitude mode: the two buffers of a wave hold frames t0 + 2 wv and t0 + 2 wv + 1 of one row;
-// grid (ceil(T / 2 kStftWaves), B) -> mag [B, T, Nc + 1]
-template <int Nc>
+// grid (ceil(T / 2 kStftWaves), B) -> mag [B, T, Nc + 1], or [B, Nc + 1, T] with BinsMajor (the discriminator's
+// layout, mfd.py: the same arithmetic, only the store address differs)
+template <int Nc, bool BinsMajor>
 __device__ void stft_magnitude_block(const float* __restrict__ xr, float* __restrict__ mag, const float* tab,
                                      int64_t n, int hop, int wlen, int64_t T, float2* zs, float2* tw) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -299,16 +300,19 @@ __device__ void stft_magnitude_block(const float* __restrict__ xr, float* __rest
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         if (t[s] < 0) continue;
-        float* row = mag + (size_t)t[s] * (Nc + 1);
+        // element of bin k: row[k * kstride]
+        float* row = BinsMajor ? mag + t[s] : mag + (size_t)t[s] * (Nc + 1);
+        const size_t kstride = BinsMajor ? (size_t)T : 1;
 #pragma unroll
         for (int i = 0; i < Nc / 64; ++i) {
             const int k = lane + 64 * i;
-            row[k] = stft_bin_mag(z + s * Nc, k, Nc, spg[k]);
+            row[k * kstride] = stft_bin_mag(z + s * Nc, k, Nc, spg[k]);
         }
-        if (lane == 0) row[Nc] = stft_nyq_mag(z + s * Nc);
+        if (lane == 0) row[Nc * kstride] = stft_nyq_mag(z + s * Nc);
     }
 }
 
+template <bool BinsMajor>
 __global__ __launch_bounds__(kStftThreads) void stft_magnitude_kernel(const float* __restrict__ x,
                                                                       float* __restrict__ mag,
                                                                       const float* __restrict__ tab, int64_t n,
@@ -319,9 +323,9 @@ __global__ __launch_bounds__(kStftThreads) void stft_magnitude_kernel(const floa
     const float* xr = x + (size_t)b * n;
     float* mr = mag + (size_t)b * T * (nfft / 2 + 1);
     switch (nfft) {
-        case 512: stft_magnitude_block<256>(xr, mr, tab, n, hop, wlen, T, zs, tw); break;
-        case 1024: stft_magnitude_block<512>(xr, mr, tab, n, hop, wlen, T, zs, tw); break;
-        default: stft_magnitude_block<1024>(xr, mr, tab, n, hop, wlen, T, zs, tw); break;
+        case 512: stft_magnitude_block<256, BinsMajor>(xr, mr, tab, n, hop, wlen, T, zs, tw); break;
+        case 1024: stft_magnitude_block<512, BinsMajor>(xr, mr, tab, n, hop, wlen, T, zs, tw); break;
+        default: stft_magnitude_block<1024, BinsMajor>(xr, mr, tab, n, hop, wlen, T, zs, tw); break;
     }
 }
 
@@ -350,11 +354,15 @@ int launch_stft_distance(const float* x, const float* y, const float* const* tab
 }
 
 int launch_stft_magnitude(const float* x, float* mag, const float* tab, int B, int64_t n, int nfft, int hop, int win,
-                          hipStream_t s) {
+                          hipStream_t s, bool bins_major) {
     const int64_t T = 1 + n / hop;
     const int64_t blocks = (T + 2 * kStftWaves - 1) / (2 * kStftWaves);
-    hipLaunchKernelGGL(stft_magnitude_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s, x, mag,
-                       tab, n, nfft, hop, win, T);
+    if (bins_major)
+        hipLaunchKernelGGL(stft_magnitude_kernel<true>, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s,
+                           x, mag, tab, n, nfft, hop, win, T);
+    else
+        hipLaunchKernelGGL(stft_magnitude_kernel<false>, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s,
+                           x, mag, tab, n, nfft, hop, win, T);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,144 @@
+"""What the discriminators share: the argument checks and the native run of one conv stack.
+
+A sub-discriminator keeps its convs in the reference's containers (``layers.<i>`` Sequentials of pad / Conv1d /
+LeakyReLU) so that ``state_dict`` keys match; their ``forward`` is never called.  ``ConvStack`` folds weight norm and
+packs the dense convs once (engine.effective_weight on the GPU, _native.pack_conv1d), caches the result against the
+module state (engine.NativeModule._fv_state: identity and version of every parameter and buffer), and runs the stack
+as one launch per layer."""
+import numpy as np
+import torch
+
+from .. import _native
+from ..generator.engine import PAD_REFLECT, PAD_ZERO, NativeModule, effective_weight
+
+
+def check_activation(nonlinear_activation, nonlinear_activation_params):
+    if nonlinear_activation != "LeakyReLU":
+        raise NotImplementedError(f"activation {nonlinear_activation}: the discriminator kernels fuse LeakyReLU only")
+    return float(nonlinear_activation_params.get("negative_slope", 0.01))
+
+
+def check_pad(pad, pad_params):
+    if pad != "ReflectionPad1d" or pad_params:
+        raise NotImplementedError(f"padding {pad}{pad_params}: the discriminator kernels fuse ReflectionPad1d only")
+
+
+def check_grouped(in_chs):
+    if in_chs < 4 or in_chs % 4:
+        raise NotImplementedError(f"a downsample layer with {in_chs} input channels: groups = in_chs // 4 must give "
+                                  "4 input channels per group (in_chs a multiple of 4)")
+
+
+def device_input(x, name, dims):
+    """x as a contiguous fp32 device tensor of rank ``dims``, or a clear error (the checks of fastvocoder_amd.loss)."""
+    if not torch.is_tensor(x):
+        raise TypeError(f"{name} must be a tensor, got {type(x).__name__}")
+    if not x.is_cuda:
+        raise _native.NativeError(f"{name} lives on {x.device}; the discriminators run on the ROCm device "
+                                  "(there is no CPU path in fastvocoder_amd)")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"{name} requires grad: the fastvocoder_amd discriminators are inference-only (forward, no "
+                           "autograd); call them under torch.no_grad() or pass a detached tensor")
+    if x.dim() != dims:
+        raise ValueError(f"{name} must have {dims} dimensions, got shape {tuple(x.shape)}")
+    if not x.is_floating_point():
+        raise TypeError(f"{name} must be a floating-point signal, got {x.dtype}")
+    return x.to(torch.float32).contiguous()
+
+
+def check_length(module, n):
+    need = module.min_length()
+    if n < need:
+        raise ValueError(f"{type(module).__name__}: an input of {n} samples is too short; its reflection pads need at "
+                         f"least {need} samples")
+
+
+def first_length(ok, start=1):
+    """Smallest n >= start with ok(n), for ok monotone in n."""
+    hi = max(start, 1)
+    while not ok(hi):
+        hi *= 2
+    lo = max(start, hi // 2)
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if ok(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+class ConvStack(NativeModule):
+    """Base of the two sub-discriminators: ``layers`` as in the reference, ``_spec`` one entry per layer."""
+
+    def _build_stack(self, in_channels, out_channels, kernel_sizes, channels, max_downsample_channels, bias,
+                     downsample_scales, slope, tap, pad_name, pad_params):
+        """The reference's layer list (msd.py:54-103, mfd.py:76-121); ``tap(s)`` = the downsample kernel of scale s."""
+        assert len(kernel_sizes) == 2
+        assert kernel_sizes[0] % 2 == 1
+        assert kernel_sizes[1] % 2 == 1
+        act = lambda: torch.nn.LeakyReLU(slope)  # noqa: E731
+        k0 = int(np.prod(kernel_sizes))
+        self.layers = torch.nn.ModuleList()
+        self.layers += [torch.nn.Sequential(getattr(torch.nn, pad_name)((k0 - 1) // 2, **pad_params),
+                                            torch.nn.Conv1d(in_channels, channels, k0, bias=bias), act())]
+        spec = [("dense", k0, (k0 - 1) // 2, PAD_REFLECT, slope)]
+        in_chs = channels
+        for s in downsample_scales:
+            check_grouped(in_chs)
+            out_chs = min(in_chs * s, max_downsample_channels)
+            k = tap(s)
+            self.layers += [torch.nn.Sequential(
+                torch.nn.Conv1d(in_chs, out_chs, kernel_size=k, stride=s, padding=(k - 1) // 2, groups=in_chs // 4,
+                                bias=bias), act())]
+            spec.append(("grouped", k, (k - 1) // 2, s, slope))
+            in_chs = out_chs
+        out_chs = min(in_chs * 2, max_downsample_channels)
+        self.layers += [torch.nn.Sequential(
+            torch.nn.Conv1d(in_chs, out_chs, kernel_sizes[0], padding=(kernel_sizes[0] - 1) // 2, bias=bias), act())]
+        spec.append(("dense", kernel_sizes[0], (kernel_sizes[0] - 1) // 2, PAD_ZERO, slope))
+        self.layers += [torch.nn.Conv1d(out_chs, out_channels, kernel_sizes[1], padding=(kernel_sizes[1] - 1) // 2,
+                                        bias=bias)]
+        spec.append(("dense", kernel_sizes[1], (kernel_sizes[1] - 1) // 2, PAD_ZERO, 1.0))
+        self._spec = spec
+        self._first_pad = (k0 - 1) // 2
+
+    def _convs(self):
+        out = []
+        for layer in self.layers:
+            if isinstance(layer, torch.nn.Conv1d):
+                out.append(layer)
+            else:
+                out.append(next(m for m in layer if isinstance(m, torch.nn.Conv1d)))
+        return out
+
+    def _native_layers(self):
+        """[(spec, weight, bias)] with weight norm folded (grouped: [Cout, 4, k]; dense: packed), cached against the
+        module state."""
+        state = self._fv_state()
+        hit = self._fv_plans.get("layers")
+        if hit is not None and hit[0] == state:
+            return hit[1]
+        self._device()
+        with torch.no_grad():
+            layers = []
+            for spec, conv in zip(self._spec, self._convs()):
+                w = effective_weight(conv)
+                b = None if conv.bias is None else conv.bias.detach().contiguous().float()
+                layers.append((spec, w.contiguous() if spec[0] == "grouped" else _native.pack_conv1d(w), b,
+                               conv.out_channels))
+        self._fv_plans["layers"] = (self._fv_state(), layers)
+        return layers
+
+    def _run_stack(self, x):
+        """x [B, C, T] fp32 device -> the list of every layer's output (the reference's ``outs``)."""
+        outs = []
+        for (spec, w, b, cout) in self._native_layers():
+            if spec[0] == "grouped":
+                _, k, pad, stride, slope = spec
+                x = _native.grouped_conv1d(x, w, b, k, stride, pad, slope)
+            else:
+                _, k, pad, mode, slope = spec
+                x = _native.conv1d_fused(x, w, b, cout, k, pad=pad, pad_mode=mode, act_slope=slope)
+            outs.append(x)
+        return outs

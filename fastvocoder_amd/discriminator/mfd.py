@@ -1,0 +1,80 @@
+"""Multi-resolution STFT discriminators (reference: model/discriminator/mfd.py) on the MI355X."""
+import torch
+
+from .. import _native
+from ..generator.engine import NativeModule
+from ..loss.stft_loss import _stft_table_host, _window_fn
+from .common import ConvStack, check_activation, check_length, check_pad, device_input
+
+
+class STFTDiscriminator(ConvStack):
+    """mfd.py:44-136: the clamped STFT magnitude (B, bins, frames) -- bins as channels, no transpose -- then a conv
+    stack: reflect-padded Conv1d(bins -> channels, prod(kernel_sizes)), grouped strided downsamples (k = 6 s + 1),
+    Conv1d(k0), Conv1d(k1 -> 1).  Weight norm is applied at construction, as in the reference.  The window is the
+    registered buffer ``window`` (its loaded values are used)."""
+
+    def __init__(self, fft_size=1024, shift_size=120, win_length=600, window="hann_window", out_channels=1,
+                 kernel_sizes=[5, 3], channels=64, max_downsample_channels=1024, bias=True, downsample_scales=[4, 4],
+                 nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2},
+                 pad="ReflectionPad1d", pad_params={}):
+        super().__init__()
+        if out_channels != 1:
+            raise NotImplementedError(f"STFTDiscriminator: out_channels={out_channels} (the discriminator path "
+                                      "supports 1)")
+        if fft_size not in (512, 1024, 2048) or int(shift_size) < 1 or not 1 <= win_length <= fft_size:
+            raise NotImplementedError(f"STFTDiscriminator: fft_size={fft_size} shift_size={shift_size} "
+                                      f"win_length={win_length} (the FFT kernel takes n_fft 512, 1024 or 2048)")
+        slope = check_activation(nonlinear_activation, nonlinear_activation_params)
+        check_pad(pad, pad_params)
+        self.fft_size = fft_size
+        self.shift_size = shift_size
+        self.win_length = win_length
+        self.register_buffer("window", _window_fn(window)(win_length))
+        self._build_stack(fft_size // 2 + 1, out_channels, kernel_sizes, channels, max_downsample_channels, bias,
+                          downsample_scales, slope, lambda s: s * 6 + 1, pad, pad_params)
+        self.apply_weight_norm()
+
+    def min_length(self):
+        """Shortest input: the STFT's reflect pad needs n > fft_size / 2, the first conv's more frames than its pad."""
+        return max(self.fft_size // 2 + 1, self._first_pad * self.shift_size)
+
+    def _table(self):
+        state = self._fv_state()
+        hit = self._fv_plans.get("table")
+        if hit is not None and hit[0] == state:
+            return hit[1]
+        tab = torch.from_numpy(_stft_table_host(self.fft_size, self.win_length, self.window)).to(self._device())
+        self._fv_plans["table"] = (state, tab)
+        return tab
+
+    def forward(self, x):
+        """x (B, T) -> list of every layer's output (the reference's STFTDiscriminator takes the squeezed signal)."""
+        x = device_input(x, "x", 2)
+        check_length(self, x.shape[-1])
+        mag = _native.stft_magnitude_bins(x, self._table(), self.fft_size, self.shift_size, self.win_length)
+        return self._run_stack(mag)
+
+
+class MultiResolutionSTFTDiscriminator(NativeModule):
+    """mfd.py:139-178: one STFTDiscriminator per (fft_size, hop_size, win_length)."""
+
+    def __init__(self, fft_sizes=[2048, 1024, 512], hop_sizes=[240, 120, 50], win_lengths=[1200, 600, 240],
+                 window="hann_window", downsample_pooling="AvgPool1d",
+                 downsample_pooling_params={"kernel_size": 4, "stride": 2, "padding": 1, "count_include_pad": False}):
+        super().__init__()
+        assert len(fft_sizes) == len(hop_sizes) == len(win_lengths)
+        self.stft_discriminator = torch.nn.ModuleList()
+        for fs, ss, wl in zip(fft_sizes, hop_sizes, win_lengths):
+            self.stft_discriminator += [STFTDiscriminator(fft_size=fs, shift_size=ss, win_length=wl, window=window)]
+
+    def min_length(self):
+        return max(d.min_length() for d in self.stft_discriminator)
+
+    def forward(self, x):
+        """x (B, 1, T) -> list over the resolutions of each one's list of layer outputs."""
+        x = device_input(x, "x", 3)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        x = x.squeeze(1)
+        return [f(x) for f in self.stft_discriminator]

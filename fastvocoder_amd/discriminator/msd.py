@@ -1,0 +1,96 @@
+"""MelGAN discriminators (reference: model/discriminator/msd.py) on the MI355X."""
+import torch
+
+from .. import _native
+from ..generator.engine import NativeModule
+from .common import ConvStack, check_activation, check_length, check_pad, device_input, first_length
+
+
+class MelGANDiscriminator(ConvStack):
+    """msd.py:13-118: reflect-padded Conv1d(1 -> channels, prod(kernel_sizes)), grouped strided downsamples
+    (k = 10 s + 1, groups = in_chs // 4), Conv1d(k0) and Conv1d(k1 -> 1); LeakyReLU after all but the last."""
+
+    def __init__(self, in_channels=1, out_channels=1, kernel_sizes=[5, 3], channels=16, max_downsample_channels=1024,
+                 bias=True, downsample_scales=[4, 4, 4, 4], nonlinear_activation="LeakyReLU",
+                 nonlinear_activation_params={"negative_slope": 0.2}, pad="ReflectionPad1d", pad_params={}):
+        super().__init__()
+        if in_channels != 1 or out_channels != 1:
+            raise NotImplementedError(f"MelGANDiscriminator: in_channels={in_channels} out_channels={out_channels} "
+                                      "(the discriminator path supports 1 and 1)")
+        slope = check_activation(nonlinear_activation, nonlinear_activation_params)
+        check_pad(pad, pad_params)
+        self._build_stack(in_channels, out_channels, kernel_sizes, channels, max_downsample_channels, bias,
+                          downsample_scales, slope, lambda s: s * 10 + 1, pad, pad_params)
+
+    def min_length(self):
+        """Shortest input the reflection pad accepts (more samples than the pad)."""
+        return self._first_pad + 1
+
+    def forward(self, x):
+        """x (B, 1, T) -> list of every layer's output."""
+        x = device_input(x, "x", 3)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        return self._run_stack(x)
+
+
+class MelGANMultiScaleDiscriminator(NativeModule):
+    """msd.py:121-241: ``scales`` MelGANDiscriminators, the input average-pooled between scales; weight norm applied
+    and the weights re-drawn from N(0, 0.02) at construction, as in the reference."""
+
+    _RESET_STD = 0.02   # msd.py:240
+
+    def __init__(self, in_channels=1, out_channels=1, scales=3, downsample_pooling="AvgPool1d",
+                 downsample_pooling_params={"kernel_size": 4, "stride": 2, "padding": 1, "count_include_pad": False},
+                 kernel_sizes=[5, 3], channels=16, max_downsample_channels=1024, bias=True,
+                 downsample_scales=[4, 4, 4, 4], nonlinear_activation="LeakyReLU",
+                 nonlinear_activation_params={"negative_slope": 0.2}, pad="ReflectionPad1d", pad_params={},
+                 use_weight_norm=True):
+        super().__init__()
+        pp = dict(downsample_pooling_params)
+        if downsample_pooling != "AvgPool1d" or pp.get("count_include_pad", True) or pp.get("ceil_mode", False) \
+                or pp.get("divisor_override") is not None:
+            raise NotImplementedError(f"pooling {downsample_pooling}{downsample_pooling_params}: the pool kernel is "
+                                      "AvgPool1d with count_include_pad=False and ceil_mode=False")
+        self.discriminators = torch.nn.ModuleList()
+        for _ in range(scales):
+            self.discriminators += [MelGANDiscriminator(
+                in_channels=in_channels, out_channels=out_channels, kernel_sizes=kernel_sizes, channels=channels,
+                max_downsample_channels=max_downsample_channels, bias=bias, downsample_scales=downsample_scales,
+                nonlinear_activation=nonlinear_activation, nonlinear_activation_params=nonlinear_activation_params,
+                pad=pad, pad_params=pad_params)]
+        self.pooling = getattr(torch.nn, downsample_pooling)(**downsample_pooling_params)
+        k = pp["kernel_size"]
+        self._pool = (k, pp.get("stride") or k, pp.get("padding", 0))
+        if use_weight_norm:
+            self.apply_weight_norm()
+        self.reset_parameters()
+
+    def _pooled_length(self, n):
+        k, s, p = self._pool
+        return (n + 2 * p - k) // s + 1
+
+    def min_length(self):
+        """Shortest input for which every scale's input is longer than its reflection pad."""
+        def ok(n):
+            for i, d in enumerate(self.discriminators):
+                if n < d.min_length():
+                    return False
+                if i + 1 < len(self.discriminators):
+                    n = self._pooled_length(n)
+            return True
+        return first_length(ok)
+
+    def forward(self, x):
+        """x (B, 1, T) -> list over the scales of each scale's list of layer outputs."""
+        x = device_input(x, "x", 3)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        outs = []
+        for i, f in enumerate(self.discriminators):
+            outs += [f(x)]
+            if i + 1 < len(self.discriminators):
+                x = _native.avg_pool1d(x, *self._pool)
+        return outs

@@ -129,9 +129,12 @@ def state_dict_spec(model_name, cfg, weight_norm=True):
 def seeded_state_dict(model_name, cfg, seed=0, gain=None, weight_norm=True):
     """{key: float32 ndarray}; bit-identical for a given (model, cfg, seed, gain)."""
     gain = DEFAULT_GAIN[model_name] if gain is None else gain
-    rng = np.random.RandomState(seed)
+    return _fill(state_dict_spec(model_name, cfg, weight_norm), np.random.RandomState(seed), gain)
+
+
+def _fill(spec, rng, gain):
+    """Draw the values of a [(key, shape, kind)] spec from rng, in the fixed order of seeded_state_dict."""
     sd, vs = {}, {}
-    spec = state_dict_spec(model_name, cfg, weight_norm)
     # v / plain weights / biases first, in key order, then g from ||v||
     for key, shape, kind in sorted(spec, key=lambda e: e[0]):
         tag = kind[0]
@@ -166,7 +169,76 @@ def seeded_state_dict(model_name, cfg, seed=0, gain=None, weight_norm=True):
                 for k in range(4):
                     u[k, k, 0] = 1.0
                 sd[key] = u
+        elif kind[0] == "window":
+            n = kind[1]
+            sd[key] = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(n) / n)).astype(np.float32)   # torch.hann_window(n)
     return {k: sd[k] for k, _, _ in spec}
+
+
+# Discriminators (model/discriminator/).  The reference draws conv weights from N(0, 0.02) (msd.py:240), which leaves
+# the late feature maps of a random network near-constant -- a parity check on them would be vacuous (the same lesson
+# as SURVEY.md section 8c).  The uniform fan-in gain below keeps every map input-dependent (std of the last map's
+# response to the input ~0.1-1 at the default configuration; tests/golden/make_discriminator_golden.py prints it).
+DISCRIMINATOR_GAIN = 2.4
+MSD_KW = dict(scales=3, kernel_sizes=[5, 3], channels=16, max_downsample_channels=1024, bias=True,
+              downsample_scales=[4, 4, 4, 4])
+STFT_KW = dict(fft_size=1024, shift_size=120, win_length=600, kernel_sizes=[5, 3], channels=64,
+               max_downsample_channels=1024, bias=True, downsample_scales=[4, 4])
+MFD_RESOLUTIONS = ([2048, 1024, 512], [240, 120, 50], [1200, 600, 240])
+
+
+def _conv_stack_spec(spec, prefix, cin, kernel_sizes, channels, max_downsample_channels, bias, downsample_scales,
+                     tap, wn):
+    k0 = int(np.prod(kernel_sizes))
+    _conv(spec, f"{prefix}layers.0.1", channels, cin, k0, bias, wn)
+    in_chs = channels
+    for i, s in enumerate(downsample_scales):
+        out_chs = min(in_chs * s, max_downsample_channels)
+        _conv(spec, f"{prefix}layers.{i + 1}.0", out_chs, 4, tap(s), bias, wn)
+        in_chs = out_chs
+    n = len(downsample_scales) + 1
+    out_chs = min(in_chs * 2, max_downsample_channels)
+    _conv(spec, f"{prefix}layers.{n}.0", out_chs, in_chs, kernel_sizes[0], bias, wn)
+    _conv(spec, f"{prefix}layers.{n + 1}", 1, out_chs, kernel_sizes[1], bias, wn)
+
+
+def discriminator_spec(kind="discriminator", weight_norm=True, prefix="", **kw):
+    """[(key, shape, kind)] of fastvocoder_amd.discriminator's (and the reference's) modules: kind "melgan"
+    (MelGANDiscriminator), "msd" (MelGANMultiScaleDiscriminator), "stft" (STFTDiscriminator), "mfd"
+    (MultiResolutionSTFTDiscriminator) or "discriminator" (Discriminator(), no kwargs), with the shape kwargs of
+    the constructor.  ``weight_norm``: g / v pairs (every module but a bare MelGANDiscriminator has them)."""
+    spec = []
+    if kind == "melgan":
+        c = dict(MSD_KW, **kw)
+        _conv_stack_spec(spec, prefix, 1, c["kernel_sizes"], c["channels"], c["max_downsample_channels"], c["bias"],
+                         c["downsample_scales"], lambda s: 10 * s + 1, weight_norm)
+    elif kind == "msd":
+        c = dict(MSD_KW, **kw)
+        for i in range(c.pop("scales")):
+            spec += discriminator_spec("melgan", weight_norm, f"{prefix}discriminators.{i}.", **c)
+    elif kind == "stft":
+        c = dict(STFT_KW, **kw)
+        spec.append((f"{prefix}window", (c["win_length"],), ("window", c["win_length"])))
+        _conv_stack_spec(spec, prefix, c["fft_size"] // 2 + 1, c["kernel_sizes"], c["channels"],
+                         c["max_downsample_channels"], c["bias"], c["downsample_scales"], lambda s: 6 * s + 1,
+                         weight_norm)
+    elif kind == "mfd":
+        ffts, hops, wins = kw.get("fft_sizes", MFD_RESOLUTIONS[0]), kw.get("hop_sizes", MFD_RESOLUTIONS[1]), \
+            kw.get("win_lengths", MFD_RESOLUTIONS[2])
+        for i, (nf, hop, wl) in enumerate(zip(ffts, hops, wins)):
+            spec += discriminator_spec("stft", weight_norm, f"{prefix}stft_discriminator.{i}.", fft_size=nf,
+                                       shift_size=hop, win_length=wl)
+    elif kind == "discriminator":
+        spec += discriminator_spec("msd", weight_norm, f"{prefix}msd.")
+        spec += discriminator_spec("mfd", weight_norm, f"{prefix}mfd.")
+    else:
+        raise ValueError(f"unknown discriminator kind {kind!r}")
+    return spec
+
+
+def seeded_discriminator_state_dict(kind="discriminator", seed=0, gain=DISCRIMINATOR_GAIN, weight_norm=True, **kw):
+    """{key: float32 ndarray} for discriminator_spec(kind, weight_norm, **kw); bit-identical for given arguments."""
+    return _fill(discriminator_spec(kind, weight_norm, **kw), np.random.RandomState(seed), gain)
 
 
 def seeded_mel(T, seed=0, batch=None):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 15
+#define FV_ABI_VERSION 16
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -509,6 +509,61 @@ int64_t fv_stft_distance_workspace_bytes(int B, int64_t n, int R, const int* n_f
 int fv_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
                      const int* n_fft, const int* hop, const int* win_length, double* out, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/*
+ * fv_stft_magnitude in the discriminator's layout (model/discriminator/mfd.py:19-41 stft, which does not transpose):
+ * mag: fp32 device [B, n_fft/2 + 1, T], mag[b, k, t].  The same FFT code and arithmetic as fv_stft_magnitude -- the
+ * result is the transpose of its output bit for bit.  Arguments, checks and error codes as fv_stft_magnitude.
+ * One launch.
+ */
+int fv_stft_magnitude_bins(const float* x, float* mag, const float* table, int B, int64_t n, int n_fft, int hop,
+                           int win_length, void* stream);
+
+/*
+ * The discriminators' strided grouped conv (model/discriminator/msd.py:67-80, mfd.py:85-98: torch.nn.Conv1d with
+ * groups = Cin / 4, zero padding, then LeakyReLU):
+ *     y[b, c, t] = lrelu( bias[c] + sum_{ci<4, j<k} w[c, ci, j] * x[b, 4 (c / (Cout/G)) + ci, t*stride + j - pad], slope )
+ * with G = Cin / 4 groups and x read as 0 outside [0, Tin).  x [B,Cin,Tin]; w [Cout, 4, k] (the folded weight, as
+ * fv_fold_weight_norm writes it; no packing); bias [Cout] or NULL; y [B,Cout,Tout],
+ * Tout = (Tin + 2 pad - k) / stride + 1.  slope = 1 gives the raw conv.  y must not alias x or w.
+ * Exact fp32 on the VALU, each output summed in the fixed order ci = 0..3, j = 0..k-1, then + bias: a row's values do
+ * not depend on B or on the other rows.  Supported: Cin % 4 == 0 (4 input channels per group), Cout % (Cin / 4) == 0,
+ * stride >= 1 and kernels up to the shared-memory budget of a block (every k = 10 stride + 1 or 6 stride + 1 with
+ * stride <= 5); anything else returns FV_ERR_UNSUPPORTED.  Tout < 1, pad < 0, a null pointer or B outside 1..65535
+ * returns FV_ERR_INVALID_ARG.  One launch.
+ */
+int fv_grouped_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Tin,
+                      int k, int stride, int pad, float slope, void* stream);
+
+/*
+ * torch.nn.AvgPool1d(k, stride, padding, count_include_pad=False, ceil_mode=False) on `rows` rows of x
+ * (model/discriminator/msd.py:150, 207: the input of every MelGAN scale after the first):
+ *     y[r, t] = (sum of x[r, i] for i in [t*stride - pad, t*stride - pad + k) and 0 <= i < Tin) / (number of such i)
+ * x [rows, Tin]; y [rows, Tout], Tout = (Tin + 2 pad - k) / stride + 1; fp32 sum in order of i, one division.
+ * k >= 1, stride >= 1, 0 <= pad <= k / 2 (torch's own limit) and Tout >= 1, else FV_ERR_INVALID_ARG (likewise for a
+ * null pointer, aliasing or rows < 1).  One launch.
+ */
+int fv_avg_pool1d(const float* x, float* y, int rows, int64_t Tin, int k, int stride, int pad, void* stream);
+
+/*
+ * Per-utterance sums behind the discriminator scores of the reference's training loop (bin/train.py:97-117
+ * adversarial and feature-map loss, :157-169 discriminator loss) for M pairs of feature maps (e_m the estimate's,
+ * r_m the real signal's), each pair fp32 device [B, n_m] rows (a map [B, C, T] has n_m = C T); per map and row b:
+ *   out[m, b, 0] = sum |e - r|
+ *   out[m, b, 1] = sum (e - 1)^2
+ *   out[m, b, 2] = sum e^2
+ *   out[m, b, 3] = sum (r - 1)^2
+ * out: float64 device [M, B, 4].  e, r: HOST arrays of M device pointers; n: HOST array of M element counts.
+ * Two launches on `stream`: every map's elements in one (each block writes four float64 partials to `workspace`),
+ * then a fixed-order float64 sum per (m, b).  No atomics: identical calls return identical bits.  workspace: device
+ * memory of at least fv_disc_score_workspace_bytes(B, M, n) bytes (8-byte aligned).  M outside
+ * 1..FV_DISC_MAX_MAPS, n_m < 1, a small workspace, a null pointer or B outside 1..65535 returns FV_ERR_INVALID_ARG;
+ * fv_disc_score_workspace_bytes returns a negative FV_ERR_* code for arguments fv_disc_score_sums would refuse.
+ */
+#define FV_DISC_MAX_MAPS 48
+int64_t fv_disc_score_workspace_bytes(int B, int M, const int64_t* n);
+int fv_disc_score_sums(const float* const* e, const float* const* r, const int64_t* n, int M, int B, double* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
