@@ -19,11 +19,15 @@ from fastvocoder_amd.synthetic import seeded_mel, seeded_state_dict
 from oracle import generators as og
 from oracle import ops as oo
 from oracle import torch_port
+from tests import accuracy_budget as ab
 from tests import cases
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4  # north_star: outputs match the reference generator within 1e-4 fp32 max-abs
+# Beside it, where a whole generator's output is compared with the fp32 ATen port: the float64 budget of
+# tests/accuracy_budget.py (the GPU's distance from the float64 port against the fp32 port's).
+F64 = torch.float64
 
 
 def _dev():
@@ -613,6 +617,7 @@ def test_shipped_configs_vs_aten_port_full_length(tag, name, path):
         y = m.inference(mel)
     ref = torch_port.inference(name, mel, sd, cfg).numpy()
     assert _err(y, ref) <= TOL
+    ab.check(y, ref, torch_port.inference(name, mel, sd, cfg, dtype=F64), f"{tag} T=250")
 
 
 @pytest.mark.parametrize("name,path,T", [("hifigan", "conf/hifigan/light.yaml", 100), ("hifigan", "conf/hifigan/large.yaml", 40),
@@ -739,6 +744,7 @@ def test_headline_workload_full_tensor_at_T1000():
         y = m.inference(mel)
     ref = torch_port.inference("hifigan", mel, sd, cfg).numpy()
     assert y.numel() == 240000 and _err(y, ref) <= TOL
+    ab.check(y, ref, torch_port.inference("hifigan", mel, sd, cfg, dtype=F64), "hifigan light T=1000")
     g = np.load(os.path.join(cases.ROOT, "tests", "golden", "full_hifigan_light.npz"))
     assert np.abs(y.cpu().numpy()[g["T1000_idx"]] - g["T1000_samples"]).max() <= TOL
 
@@ -760,17 +766,33 @@ def test_other_baseline_workloads_full_tensor_at_T1000(name, path, golden):
     ref = torch_port.inference(name, mel, sd, cfg).numpy()
     g = np.load(os.path.join(cases.ROOT, "tests", "golden", golden + ".npz"))
     assert y.numel() == ref.size == int(g["T1000_n"]) and _err(y, ref) <= TOL
+    ab.check(y, ref, torch_port.inference(name, mel, sd, cfg, dtype=F64), f"{golden} T=1000")
     assert np.abs(y.cpu().numpy().reshape(-1)[g["T1000_idx"]] - g["T1000_samples"]).max() <= TOL
 
 
 _PORT_CACHE = {}      # (model, conf, what, T) -> the ATen port's output: the two fuse_stage variants share the reference
+_PORT64_CACHE = {}    # the same for the float64 port
 
 
-def _port(name, path, what, T, make):
+def _port(name, path, what, T, make, cache=_PORT_CACHE):
     key = (name, path, what, T)
-    if key not in _PORT_CACHE:
-        _PORT_CACHE[key] = make()
-    return _PORT_CACHE[key]
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
+
+
+def _port64(name, path, what, T, make):
+    return _port(name, path, what, T, make, _PORT64_CACHE)
+
+
+def _budgeted(corners, randoms):
+    """The lengths of a sweep that also meet the float64 budget: every corner length and every second random one (the
+    float64 port costs ~3x the fp32 port on the host; the 1e-4 bound still covers every length)."""
+    return set(corners) | set(sorted(set(randoms) - set(corners))[::2])
+
+
+def _sweep_randoms(n_random, t_max):
+    return [int(v) for v in np.random.RandomState(606).randint(1, t_max + 1, size=n_random)]
 
 
 def _sweep_lengths(n_random, t_max, batch_for_policy=(1, 3)):
@@ -786,8 +808,7 @@ def _sweep_lengths(n_random, t_max, batch_for_policy=(1, 3)):
         flips = [t for t in range(2, t_max + 1) if stage32_windows_fit(120 * t * B, 256) != stage32_windows_fit(120 * (t - 1) * B, 256)]
         for t in flips[:: max(1, len(flips) // 4)][:4]:
             ts.update((t - 1, t))
-    rng = np.random.RandomState(606)
-    ts.update(int(v) for v in rng.randint(1, t_max + 1, size=n_random))
+    ts.update(_sweep_randoms(n_random, t_max))
     return sorted(t for t in ts if t <= t_max)
 
 
@@ -808,26 +829,37 @@ def test_random_lengths_vs_aten_port(name, path, t_max, n_random, fuse):
     m, sd = _model(name, cfg, seed=0)
     m.fuse_stage = fuse
     folded = torch_port.fold_state_dict(sd)
+    folded64 = torch_port.fold_state_dict(sd, F64)
     lengths = _sweep_lengths(n_random, t_max)
     assert len(lengths) >= 25, lengths
     worst = 0.0
     batched = set(lengths[:3] + lengths[len(lengths) // 3::4][:3])
+    budgeted = _budgeted(set(lengths) - set(_sweep_randoms(n_random, t_max)), _sweep_randoms(n_random, t_max)) | batched
+    ratios = []
     threads = torch.get_num_threads()
     torch.set_num_threads(min(threads, 32))          # (the port's small convs do not scale past a few dozen threads)
     with torch.no_grad():
         for T in lengths:
             mel = seeded_mel(T, seed=3000 + T)
-            err = _err(m.inference(mel), _port(name, path, "inference", T, lambda: torch_port.inference(name, mel, folded, cfg).numpy()))
+            got, ref = m.inference(mel), _port(name, path, "inference", T, lambda: torch_port.inference(name, mel, folded, cfg).numpy())
+            err = _err(got, ref)
             assert err <= TOL, (T, err)
             worst = max(worst, err)
+            if T in budgeted:
+                r64 = _port64(name, path, "inference", T, lambda: torch_port.inference(name, mel, folded64, cfg, dtype=F64))
+                ratios.append(ab.check(got, ref, r64, f"T={T}"))
             if T in batched:
                 x = seeded_mel(T, seed=5000 + T, batch=3)
-                err = _err(m(torch.from_numpy(x)), _port(name, path, "forward", T, lambda: torch_port.forward(name, x, folded, cfg).numpy()))
+                got, ref = m(torch.from_numpy(x)), _port(name, path, "forward", T, lambda: torch_port.forward(name, x, folded, cfg).numpy())
+                err = _err(got, ref)
                 assert err <= TOL, (T, "batch 3", err)
                 worst = max(worst, err)
+                r64 = _port64(name, path, "forward", T, lambda: torch_port.forward(name, x, folded64, cfg, dtype=F64))
+                ratios.append(ab.check(got, ref, r64, f"T={T} batch 3"))
     torch.set_num_threads(threads)
     assert not m.check_range()
-    print(f"{name} {path} fuse_stage={fuse}: {len(lengths)} lengths, worst {worst:.2e}")
+    print(f"{name} {path} fuse_stage={fuse}: {len(lengths)} lengths, worst {worst:.2e}; budget at {len(ratios)} outputs: "
+          f"max ratio {max(r['max_ratio'] for r in ratios):.2f}, rms ratio {max(r['rms_ratio'] for r in ratios):.2f}")
 
 
 @pytest.mark.parametrize("name,path,t_max,n_random", [
@@ -845,34 +877,43 @@ def test_random_lengths_vs_aten_port_other_generators(name, path, t_max, n_rando
     cfg = cases.load_conf(path)
     m, sd = _model(name, cfg, seed=0)
     folded = torch_port.fold_state_dict(sd)
+    folded64 = torch_port.fold_state_dict(sd, F64)
     rng = np.random.RandomState(707)
     lo = 4 if "melgan" in name else 1
     ts = {lo, lo + 1, lo + 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 255, 256, 257, t_max}
-    ts.update(int(v) for v in rng.randint(lo, t_max + 1, size=n_random))
+    randoms = [int(v) for v in rng.randint(lo, t_max + 1, size=n_random)]
+    ts.update(randoms)
     lengths = sorted(t for t in ts if lo <= t <= t_max)
     assert len(lengths) >= 25, lengths
     batched = set(lengths[:3] + lengths[len(lengths) // 3::4][:3])
-    worst = 0.0
+    budgeted = _budgeted(set(lengths) - set(randoms), randoms) | batched
+    worst, ratios = 0.0, []
     threads = torch.get_num_threads()
     torch.set_num_threads(min(threads, 32))
     with torch.no_grad():
         for T in lengths:
             mel = seeded_mel(T, seed=7000 + T)
-            err = _err(m.inference(mel), torch_port.inference(name, mel, folded, cfg).numpy())
+            got, ref = m.inference(mel), torch_port.inference(name, mel, folded, cfg).numpy()
+            err = _err(got, ref)
             assert err <= TOL, (T, err)
             worst = max(worst, err)
+            if T in budgeted:
+                ratios.append(ab.check(got, ref, torch_port.inference(name, mel, folded64, cfg, dtype=F64), f"T={T}"))
             if T in batched:
                 x = seeded_mel(T, seed=9000 + T, batch=3)
                 got, ref = m(torch.from_numpy(x)), torch_port.forward(name, x, folded, cfg)
-                pairs = list(zip(got, ref)) if isinstance(ref, tuple) else [(got, ref)]
+                r64 = torch_port.forward(name, x, folded64, cfg, dtype=F64)
+                pairs = list(zip(got, ref, r64)) if isinstance(ref, tuple) else [(got, ref, r64)]
                 assert not isinstance(ref, tuple) or len(got) == len(ref)
-                for g, r in pairs:
+                for i, (g, r, r2) in enumerate(pairs):
                     err = _err(g, r.numpy())
                     assert err <= TOL, (T, "batch 3", err)
                     worst = max(worst, err)
+                    ratios.append(ab.check(g, r, r2, f"T={T} batch 3 output {i}"))
     torch.set_num_threads(threads)
     assert not m.check_range()
-    print(f"{name} {path}: {len(lengths)} lengths, worst {worst:.2e}")
+    print(f"{name} {path}: {len(lengths)} lengths, worst {worst:.2e}; budget at {len(ratios)} outputs: "
+          f"max ratio {max(r['max_ratio'] for r in ratios):.2f}, rms ratio {max(r['rms_ratio'] for r in ratios):.2f}")
 
 
 @pytest.mark.parametrize("name,path,t_max", [
@@ -887,29 +928,38 @@ def test_random_lengths_on_the_exact_fp32_kernels(name, path, t_max):
     m, sd = _model(name, cfg, seed=0)
     m.precision = "f32"
     folded = torch_port.fold_state_dict(sd)
+    folded64 = torch_port.fold_state_dict(sd, F64)
     rng = np.random.RandomState(909)
     lo = 4 if "melgan" in name else 1
     ts = {lo, lo + 1, 9, 16, 17, 43, 63, 64, 65, 127, 129, 256, 1000 if t_max >= 1000 else t_max, t_max}
-    ts.update(int(v) for v in rng.randint(lo, t_max + 1, size=8))
+    randoms = [int(v) for v in rng.randint(lo, t_max + 1, size=8)]
+    ts.update(randoms)
     lengths = sorted(t for t in ts if lo <= t <= t_max)
-    worst = 0.0
+    budgeted = _budgeted(set(lengths) - set(randoms), randoms)
+    worst, ratios = 0.0, []
     threads = torch.get_num_threads()
     torch.set_num_threads(min(threads, 32))
     with torch.no_grad():
         for i, T in enumerate(lengths):
             mel = seeded_mel(T, seed=15000 + T)
-            err = _err(m.inference(mel), torch_port.inference(name, mel, folded, cfg).numpy())
+            got, ref = m.inference(mel), torch_port.inference(name, mel, folded, cfg).numpy()
+            err = _err(got, ref)
             assert err <= TOL, (T, err)
             worst = max(worst, err)
+            if T in budgeted:
+                ratios.append(ab.check(got, ref, torch_port.inference(name, mel, folded64, cfg, dtype=F64), f"f32 T={T}"))
             if i % 5 == 0:
                 x = seeded_mel(T, seed=16000 + T, batch=2)
                 got, ref = m(torch.from_numpy(x)), torch_port.forward(name, x, folded, cfg)
-                for g, r in (list(zip(got, ref)) if isinstance(ref, tuple) else [(got, ref)]):
+                r64 = torch_port.forward(name, x, folded64, cfg, dtype=F64)
+                for g, r, r2 in (list(zip(got, ref, r64)) if isinstance(ref, tuple) else [(got, ref, r64)]):
                     err = _err(g, r.numpy())
                     assert err <= TOL, (T, "batch 2", err)
                     worst = max(worst, err)
+                    ratios.append(ab.check(g, r, r2, f"f32 T={T} batch 2"))
     torch.set_num_threads(threads)
-    print(f"{name} precision=f32: {len(lengths)} lengths, worst {worst:.2e}")
+    print(f"{name} precision=f32: {len(lengths)} lengths, worst {worst:.2e}; budget at {len(ratios)} outputs: "
+          f"max ratio {max(r['max_ratio'] for r in ratios):.2f}, rms ratio {max(r['rms_ratio'] for r in ratios):.2f}")
 
 
 @pytest.mark.parametrize("name,path,B,T", [
@@ -944,14 +994,58 @@ def test_saturated_kernel_forms_vs_aten_port(name, path, B, T):
     threads = torch.get_num_threads()
     torch.set_num_threads(min(threads, 64))
     ref = torch_port.forward(name, x, folded, cfg)
+    r64 = torch_port.forward(name, x, torch_port.fold_state_dict(sd, F64), cfg, dtype=F64)
     torch.set_num_threads(threads)
     worst = 0.0
-    for g, r in (list(zip(got, ref)) if isinstance(ref, tuple) else [(got, ref)]):
+    for i, (g, r, r2) in enumerate(list(zip(got, ref, r64)) if isinstance(ref, tuple) else [(got, ref, r64)]):
         err = _err(g, r.numpy())
         assert err <= TOL, (name, B, T, err)
         worst = max(worst, err)
+        ab.check(g, r, r2, f"{name} saturated B={B} T={T} output {i}")
     assert not m.check_range()
     print(f"{name} {path} B={B} T={T}: worst {worst:.2e}, {n_launches} launches")
+
+
+def test_policy_flips_between_same_shape_calls_on_one_module():
+    """The per-call plan route (engine.NativeModule._exec) is keyed on (getter, batch, frames) plus the module state:
+    flipping a policy between two calls of the SAME shape on ONE module must reach a plan built under the new policy,
+    and flipping it back must reach the old one again.  HiFi-GAN light, one policy at a time and back; the launch count
+    changes wherever the policy changes the graph (range_guard only drops the guard word: same launches), the first
+    call's bits come back after every flip, and every output meets the float64 budget."""
+    cfg = cases.load_conf("conf/hifigan/light.yaml")
+    m, sd = _model("hifigan", cfg, seed=0)
+    x = seeded_mel(120, seed=61, batch=2)
+    xd = torch.from_numpy(x).to(_dev())
+    p32 = torch_port.forward("hifigan", x, sd, cfg).numpy()
+    r64 = torch_port.forward("hifigan", x, sd, cfg, dtype=F64)
+
+    def call(what):
+        torch.cuda.synchronize()
+        _native.profile_collect(-1)
+        _native.profile_enable(True)
+        with torch.no_grad():
+            out = m(xd)
+        torch.cuda.synchronize()
+        _native.profile_enable(False)
+        n = int(_native.profile_collect(-1)["launches"])
+        assert _err(out, p32) <= TOL
+        ab.check(out, p32, r64, f"{what}: {n} launches")
+        return out, n
+
+    base, n0 = call("default")
+    assert n0 > 0
+    for attr, value, changes_graph in [("precision", "f32", True), ("fuse_pairs", False, True), ("fuse_stage", False, True),
+                                       ("fold_post", False, True), ("range_guard", "off", False)]:
+        old = getattr(m, attr)
+        setattr(m, attr, value)
+        out, n = call(f"{attr} = {value!r}")
+        assert (n != n0) == changes_graph, (attr, n, n0)
+        if attr == "precision":
+            assert not torch.equal(out, base)           # other arithmetic: not the split plan served again
+        setattr(m, attr, old)
+        back, n = call(f"{attr} back to {old!r}")
+        assert n == n0 and torch.equal(back, base), (attr, n, n0)
+    assert not m.check_range()
 
 
 def test_batch_rows_are_independent_and_bit_identical():
@@ -1112,6 +1206,7 @@ def test_random_chunking_of_shipped_generators(name, path, t_hi):
     cfg = cases.load_conf(path)
     m, sd = _model(name, cfg, seed=0)
     folded = torch_port.fold_state_dict(sd)
+    folded64 = torch_port.fold_state_dict(sd, F64)
     rng = np.random.RandomState(808)
     pairs = [(int(rng.randint(40, t_hi + 1)), None) for _ in range(5)]
     pairs = [(T, int(rng.randint(3, T))) for T, _ in pairs] + [(129, 128), (130, 5), (257, 64)]
@@ -1127,9 +1222,11 @@ def test_random_chunking_of_shipped_generators(name, path, t_hi):
             got = m.inference(mel).cpu().numpy()
             assert got.shape == whole.shape, (T, chunk)
             assert np.abs(got - whole).max() <= 1e-5, (T, chunk, float(np.abs(got - whole).max()))
-            err = _err(torch.from_numpy(got), torch_port.inference(name, mel, folded, cfg).numpy())
+            ref = torch_port.inference(name, mel, folded, cfg).numpy()
+            err = _err(torch.from_numpy(got), ref)
             assert err <= TOL, (T, chunk, err)
             worst = max(worst, err)
+            ab.check(got, ref, torch_port.inference(name, mel, folded64, cfg, dtype=F64), f"{name} T={T} chunks of {chunk}")
     torch.set_num_threads(threads)
     m.max_frames_per_run = 16384
     assert not m.check_range()
@@ -1252,6 +1349,8 @@ def test_generator_beyond_the_f16_range_repeats_on_fp32():
     sd = {k: v.detach().cpu().numpy() for k, v in exact.state_dict().items()}
     ref = torch_port.inference("hifigan", mel, sd, cases.load_conf("conf/hifigan/light.yaml")).numpy()
     assert _err(want, ref) <= TOL
+    ab.check(got, ref, torch_port.inference("hifigan", mel, sd, cases.load_conf("conf/hifigan/light.yaml"), dtype=F64),
+             "repeated on fp32 after an overflow")
     # forward under the DEFAULT policy: checked before it returns, with or without torch.no_grad()
     x = torch.from_numpy(np.ascontiguousarray(mel.T[None])).to(_dev())      # the same mel, forward layout [1, 80, T]
     dflt = _scaled_hifigan(1e6)
@@ -1381,6 +1480,7 @@ def test_channel_scales_of_a_trained_model_stay_inside_the_tolerance(path, T, sp
     ref = torch_port.inference("hifigan", mel, sd, cfg).numpy()
     assert float(np.abs(ref).max()) > 0.05
     assert _err(got, ref) <= TOL and _err(got, want.cpu().numpy()) <= TOL
+    ab.check(got, ref, torch_port.inference("hifigan", mel, sd, cfg, dtype=F64), f"{path} gains 2^{2 * spread}")
     print(f"{path} spread 2^{2 * spread}: {_err(got, ref):.2e} from the port, {_err(got, want.cpu().numpy()):.2e} from the unscaled model")
 
 
@@ -1406,6 +1506,7 @@ def test_silence_and_transients_in_the_mel(name, path):
         got = m.inference(mel)
     ref = torch_port.inference(name, mel, folded, cfg).numpy()
     assert bool(torch.isfinite(got).all()) and _err(got, ref) <= TOL
+    ab.check(got, ref, torch_port.inference(name, mel, sd, cfg, dtype=F64), f"{name} silence and transients")
     print(f"{name}: {_err(got, ref):.2e}, policy after the call: {m._fv_policy()[0]}")
 
 
@@ -1426,6 +1527,12 @@ def test_generator_below_the_low_side_repeats_on_fp32():
     with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad():
         got = m.inference(mel)
     assert torch.equal(got, want) and m._fv_policy()[0] == "f32"
+    # the repeated call's output against the float64 port of the scaled model
+    cfg = cases.load_conf("conf/hifigan/light.yaml")
+    sd = {k: v.detach().cpu().numpy() for k, v in exact.state_dict().items()}
+    ref = torch_port.inference("hifigan", mel, sd, cfg).numpy()
+    assert _err(got, ref) <= TOL
+    ab.check(got, ref, torch_port.inference("hifigan", mel, sd, cfg, dtype=F64), "repeated on fp32 below the low side")
     ok = _scaled_hifigan(2.0 ** -6)
     with torch.no_grad():
         y = ok.inference(mel)

@@ -153,3 +153,37 @@ def test_weight_norm_fold_matches_torch():
         w = oo.weight_norm_fold(v, gg)
         ref = torch._weight_norm(torch.from_numpy(v), torch.from_numpy(gg), 0).numpy()
         assert np.abs(w - ref).max() <= 1e-6
+
+
+def test_port_default_dtype_is_bit_identical_to_explicit_float32():
+    """bench.py's cpu_baseline times the port's default: the dtype keyword must not change a bit of it."""
+    for tag, name, cfg in cases.SMALL:
+        if tag not in ("hifigan_s", "mb_s", "melgan_nown", "basis_causal_ll"):
+            continue
+        sd = seeded_state_dict(name, cfg, seed=7)
+        mel = seeded_mel(cases.SMALL_T, seed=5)
+        assert torch.equal(torch_port.inference(name, mel, sd, cfg),
+                           torch_port.inference(name, mel, sd, cfg, dtype=torch.float32))
+        x = seeded_mel(cases.SMALL_T, seed=6, batch=2)
+        a, b = torch_port.forward(name, x, sd, cfg), torch_port.forward(name, x, sd, cfg, dtype=torch.float32)
+        for u, v in (zip(a, b) if isinstance(a, tuple) else [(a, b)]):
+            assert u.dtype == torch.float32 and torch.equal(u, v)
+        f32 = torch_port.fold_state_dict(sd)
+        assert all(torch.equal(v, torch_port.fold_state_dict(sd, torch.float32)[k]) for k, v in f32.items())
+
+
+@pytest.mark.parametrize("tag,name,path", cases.SHIPPED, ids=[c[0] for c in cases.SHIPPED])
+def test_float64_port_meets_the_reference_float64_run(golden_dir, tag, name, path):
+    """The yardstick of tests/accuracy_budget.py: the port in float64 at the benchmark length (seed-0 weights, the golden's
+    mel) against strided samples of the reference's own float64 run (make_golden.py `T1000_samples64`), and the fp32 port's
+    distance from it against the reference's fp32-vs-fp64 noise stored beside them."""
+    g = _load(golden_dir, f"full_{tag}.npz")
+    cfg = cases.load_conf(path)
+    sd = seeded_state_dict(name, cfg, seed=0)
+    mel = seeded_mel(cases.STATS_T, seed=1)
+    r64 = torch_port.inference(name, mel, sd, cfg, dtype=torch.float64).numpy().reshape(-1)
+    assert r64.dtype == np.float64 and r64.size == int(g["T1000_n"])
+    assert np.abs(r64[g["T1000_idx"]] - g["T1000_samples64"]).max() <= 1e-9
+    p32 = torch_port.inference(name, mel, sd, cfg).numpy().reshape(-1)
+    noise = float(np.abs(p32.astype(np.float64) - r64).max())
+    assert 0 < noise <= 2 * float(g["T1000_ref_fp32_noise"]), (noise, float(g["T1000_ref_fp32_noise"]))
