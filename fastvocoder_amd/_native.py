@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "stft_loss.hip", "disc.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "griffin_lim.hip", "stft_loss.hip", "disc.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -24,14 +24,14 @@ SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_
           [f"conv_inst_s{i}.hip" for i in range(6)]
 HEADERS = ["fv_internal.h", "conv_kernels.hpp", "pair_kernels.hpp", "pair_inst.hpp", "pairh_kernels.hpp",
            "pairh_inst.hpp", "convh_kernels.hpp", "convh_inst.hpp", "convr_kernels.hpp",
-           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h"]
+           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "fft1024.hpp"]
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)
 POST_NONE, POST_TANH, POST_RELU = 0, 1, 2
 SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0, MAX_SLOTS = -1, 0, 1, 2, 32
 SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = 28, 29, 30    # caller-provided tensors of Plan.run(aux=..., out2=...)
-ABI_VERSION = 16
+ABI_VERSION = 17
 PAIR_F32, PAIR_SPLIT_F16 = 0, 1   # arithmetic of the fused ResBlock-pair kernels (fastvocoder_hip.h)
 
 
@@ -225,6 +225,15 @@ def lib():
     L.fv_encode_16bits.argtypes = [vp, vp, vp, i, i64, f, i, vp]
     L.fv_pqmf_analysis.argtypes = [vp, vp, vp, i, i, i, i64, vp]
     L.fv_melspectrogram.argtypes = [vp, vp, vp, i, i64, i, i, i, i, i, f, vp]
+    L.fv_istft_workspace_bytes.argtypes = [i, i]
+    L.fv_istft_workspace_bytes.restype = i64
+    L.fv_griffin_lim_workspace_bytes.argtypes = [i, i]
+    L.fv_griffin_lim_workspace_bytes.restype = i64
+    L.fv_stft.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
+    L.fv_istft.argtypes = [vp, vp, vp, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_griffin_lim.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_mel_to_linear.argtypes = [vp, vp, vp, i, i, i, i, f, vp]
+    L.fv_inv_preemphasis.argtypes = [vp, vp, i, i64, f, vp]
     L.fv_stft_table_floats.argtypes = [i, i]
     L.fv_stft_magnitude.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
     L.fv_stft_distance_workspace_bytes.argtypes = [i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i)]
@@ -881,6 +890,109 @@ def melspectrogram(x, tables, sample_rate=24000, n_fft=2048, hop=240, win_length
         check(lib().fv_melspectrogram(_ptr(x, "x"), _ptr(mel), _ptr(tables, "tables"), B, n, int(sample_rate),
                                       int(n_fft), int(hop), int(win_length), int(n_mels), float(fmin), stream))
     return mel
+
+
+def gl_table_floats():
+    """Length of the fp32 table the Griffin-Lim entry points read (FV_GL_TABLE_FLOATS)."""
+    return lib().fv_gl_table_floats()
+
+
+def _gl_tables(tables, who):
+    if tables.numel() != gl_table_floats():
+        raise NativeError(f"{who}: tables hold {tables.numel()} floats, the library reads {gl_table_floats()}")
+
+
+def _gl_workspace(B, T, device):
+    need = lib().fv_griffin_lim_workspace_bytes(B, T)
+    if need < 0:
+        check(int(need))
+    return torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+
+
+def stft_complex(y, tables, n_fft=2048, hop=240, win_length=1200):
+    """y [B,n] fp32 device -> complex64 [B, 1+n//hop, n_fft//2+1] (fv_stft, one launch; frames-major)."""
+    if y.dim() != 2:
+        raise NativeError(f"stft: y must be [B, n], got {tuple(y.shape)}")
+    _gl_tables(tables, "stft")
+    B, n = y.shape
+    spec = torch.empty((B, 1 + n // hop if hop > 0 else 0, n_fft // 2 + 1, 2), dtype=torch.float32, device=y.device)
+    with _on(y, tables, spec) as stream:
+        check(lib().fv_stft(_ptr(y, "y"), _ptr(spec), _ptr(tables, "tables"), B, n, int(n_fft), int(hop),
+                            int(win_length), stream))
+    return torch.view_as_complex(spec)
+
+
+def _complex_floats(z, shape_tail, who):
+    """A complex64 (or [..., 2] float32) device tensor as contiguous float32 [..., 2]."""
+    if z.is_complex():
+        if z.dtype != torch.complex64:
+            raise NativeError(f"{who}: expected complex64, got {z.dtype}")
+        z = torch.view_as_real(z.contiguous())
+    if z.dim() != 4 or z.shape[-1] != 2 or z.shape[2] != shape_tail:
+        raise NativeError(f"{who}: expected [B, T, {shape_tail}] complex, got {tuple(z.shape)}")
+    return z.contiguous()
+
+
+def istft(spec, tables, n_fft=2048, hop=240, win_length=1200):
+    """spec complex64 [B, T, n_fft//2+1] device (frames-major) -> y [B, hop (T-1)] (fv_istft, two launches)."""
+    _gl_tables(tables, "istft")
+    spec = _complex_floats(spec, n_fft // 2 + 1, "istft")
+    B, T = spec.shape[:2]
+    y = torch.empty((B, max(hop * (T - 1), 0)), dtype=torch.float32, device=spec.device)
+    ws = _gl_workspace(B, T, spec.device)
+    with _on(spec, tables, y, ws) as stream:
+        check(lib().fv_istft(_ptr(spec, "spec"), _ptr(y), _ptr(tables, "tables"), B, T, int(n_fft), int(hop),
+                             int(win_length), ws.data_ptr(), ws.numel() * 4, stream))
+    return y
+
+
+def griffin_lim(S, phase0, tables, iters, y=None, n_fft=2048, hop=240, win_length=1200):
+    """S [B, T, n_fft//2+1] fp32 device magnitudes (frames-major), phase0 complex64 [B, T, n_fft//2+1] initial phases
+    -> y [B, hop (T-1)] after ``iters`` projections (fv_griffin_lim: two launches per iteration on the current stream,
+    no host synchronisation).  phase0=None: the iterations start from ``y`` (which is not modified)."""
+    _gl_tables(tables, "griffin_lim")
+    if S.dim() != 3 or S.shape[2] != n_fft // 2 + 1:
+        raise NativeError(f"griffin_lim: S must be [B, T, {n_fft // 2 + 1}], got {tuple(S.shape)}")
+    B, T = S.shape[:2]
+    if phase0 is not None:
+        phase0 = _complex_floats(phase0, n_fft // 2 + 1, "griffin_lim")
+        if tuple(phase0.shape[:2]) != (B, T):
+            raise NativeError(f"griffin_lim: phase0 is {tuple(phase0.shape[:3])}, S is {tuple(S.shape)}")
+        y = torch.empty((B, max(hop * (T - 1), 0)), dtype=torch.float32, device=S.device)
+    else:
+        if y is None or tuple(y.shape) != (B, hop * (T - 1)):
+            raise NativeError(f"griffin_lim: without phase0 a starting y [B, {hop * (T - 1)}] is needed")
+        y = y.clone().contiguous()
+    ws = _gl_workspace(B, T, S.device)
+    with _on(S, tables, y, ws, *([] if phase0 is None else [phase0])) as stream:
+        check(lib().fv_griffin_lim(_ptr(S, "S"), _ptr(phase0, "phase0", True), _ptr(y, "y"), _ptr(tables, "tables"),
+                                   B, T, int(iters), int(n_fft), int(hop), int(win_length), ws.data_ptr(),
+                                   ws.numel() * 4, stream))
+    return y
+
+
+def mel_to_linear(mel, inv_basis, power):
+    """mel [B,80,T] fp32 device (normalised), inv_basis [80,1025] fp32 device -> S [B,T,1025] (fv_mel_to_linear)."""
+    if mel.dim() != 3 or inv_basis.dim() != 2 or mel.shape[1] != inv_basis.shape[0]:
+        raise NativeError(f"mel_to_linear: mel [B, n_mels, T] and inv_basis [n_mels, n_freq], got {tuple(mel.shape)} "
+                          f"and {tuple(inv_basis.shape)}")
+    B, n_mels, T = mel.shape
+    n_freq = inv_basis.shape[1]
+    S = torch.empty((B, T, n_freq), dtype=torch.float32, device=mel.device)
+    with _on(mel, inv_basis, S) as stream:
+        check(lib().fv_mel_to_linear(_ptr(mel, "mel"), _ptr(inv_basis, "inv_basis"), _ptr(S), B, T, n_mels, n_freq,
+                                     float(power), stream))
+    return S
+
+
+def inv_preemphasis(y, coef):
+    """y [B,n] fp32 device -> out[b,i] = y[b,i] + coef out[b,i-1] (fv_inv_preemphasis, one launch)."""
+    if y.dim() != 2:
+        raise NativeError(f"inv_preemphasis: y must be [B, n], got {tuple(y.shape)}")
+    out = torch.empty_like(y)
+    with _on(y, out) as stream:
+        check(lib().fv_inv_preemphasis(_ptr(y, "y"), _ptr(out), y.shape[0], y.shape[1], float(coef), stream))
+    return out
 
 
 def stft_table_floats(n_fft, win_length):

@@ -1,8 +1,9 @@
 """The audio side of the reference (data/audio.py): the wav sink of the synthesize flow
 (encode_16bits / save_wav, data/audio.py:12-26), and the mel front end that makes a generator's
 input from a wav (load_wav / melspectrogram, data/audio.py:17-21,58-61) for copy-synthesis and
-MODE=preprocess.  Griffin-Lim, the linear ``spectrogram`` and the TensorFlow helpers of the
-reference stay out of scope.
+MODE=preprocess, and the inverse direction: Griffin-Lim (inv_mel_spectrogram / inv_spectrogram,
+data/audio.py:37-47,66-95,179-190), the baseline the synthesize flow writes beside the vocoder's wav.
+The TensorFlow helpers of the reference and the resampling in ``load_wav`` stay out of scope.
 
 ``encode_16bits`` / ``save_wav`` take what the reference's take (a float numpy array, scaled IN
 PLACE) and, additionally, a float32 tensor on the ROCm device: then the peak reduction, scaling and
@@ -15,6 +16,14 @@ padded STFT with a periodic Hann window, magnitude, Slaney mel filters, dB, norm
 launch (csrc/mel.hip, fv_melspectrogram); there is no CPU arithmetic path.  The small numpy helpers
 below carry the reference's names; ``_build_mel_basis`` is the float64 restatement of
 ``librosa.filters.mel`` the kernel's filter table is built from.
+
+``inv_mel_spectrogram`` is the reference's chain mel -> linear magnitude (pseudo-inverse of the mel
+filters, ** power) -> Griffin-Lim (griffin_lim_iters projections) -> inverse preemphasis, all on the
+GPU (csrc/griffin_lim.hip: fv_mel_to_linear, fv_griffin_lim, fv_inv_preemphasis).  The reference draws
+the initial phase from the global NumPy state; here the draw is an argument (``angles`` / ``seed``), so a
+run can be repeated.  Device tensors hold spectra FRAMES-MAJOR ([B, T, 1025], as the kernels read them);
+the numpy-facing helpers (``_stft``, ``_istft``, ``_mel_to_linear``, ``_griffin_lim``) take and return
+librosa's [1025, T].
 """
 import numpy as np
 import scipy.io.wavfile
@@ -183,3 +192,208 @@ def melspectrogram(y):
         raise _native.NativeError("melspectrogram runs on the ROCm device (there is no CPU path in fastvocoder_amd)")
     x = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to("cuda")
     return melspectrogram(x)[0].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
+# the inverse direction: Griffin-Lim (csrc/griffin_lim.hip)
+# ---------------------------------------------------------------------------
+
+def inv_preemphasis(x):
+    """lfilter([1], [1, -preemphasis], x) on the GPU (fv_inv_preemphasis): numpy 1-D -> numpy float32; fp32 device
+    tensor [n] or [B, n] -> device tensor of the same shape."""
+    if torch.is_tensor(x):
+        _need_device_f32(x, "inv_preemphasis", (1, 2))
+        return _native.inv_preemphasis(x.reshape(1, -1) if x.dim() == 1 else x.contiguous(),
+                                       hparams.preemphasis).reshape(x.shape)
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError(f"inv_preemphasis: expected a 1-D waveform, got shape {x.shape}")
+    return inv_preemphasis(_to_device(x, "inv_preemphasis")).cpu().numpy()
+
+
+def _denormalize(S):
+    return (np.clip(S, 0, 1) * -hparams.min_level_db) + hparams.min_level_db
+
+
+def _db_to_amp(x):
+    return np.power(10.0, x * 0.05)
+
+
+def _need_device_f32(t, who, dims):
+    if not t.is_cuda:
+        raise _native.NativeError(f"{who}: a tensor argument must live on the ROCm device; pass a numpy array for "
+                                  "the host route")
+    if t.dtype != torch.float32 or t.dim() not in dims:
+        raise _native.NativeError(f"{who}: expected a float32 tensor of {' or '.join(map(str, dims))} dimensions, got "
+                                  f"{t.dtype} {tuple(t.shape)}")
+
+
+def _to_device(a, who, dtype=np.float32):
+    if not torch.cuda.is_available():
+        raise _native.NativeError(f"{who} runs on the ROCm device (there is no CPU path in fastvocoder_amd)")
+    _native.lib()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
+
+
+def _gl_table_host():
+    """The fp32 table the Griffin-Lim kernels read (include/fastvocoder_hip.h, FV_GL_TAB_*), built in float64: the
+    window, twiddle and split parts of the mel table, then the squared window."""
+    n_fft, _, win_length = _stft_parameters()
+    nc = n_fft // 2
+    tab = np.zeros(_GL_TAB_WIN2 + win_length, dtype=np.float64)
+    w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)   # periodic Hann
+    tw = np.exp(-2j * np.pi * np.arange(nc) / nc)
+    sp = np.exp(-2j * np.pi * np.arange(nc) / n_fft)
+    tab[0:win_length] = w
+    tab[_MEL_TAB_TWIDDLE:_MEL_TAB_TWIDDLE + 2 * nc] = np.stack([tw.real, tw.imag], 1).ravel()
+    tab[_MEL_TAB_SPLIT:_MEL_TAB_SPLIT + 2 * nc] = np.stack([sp.real, sp.imag], 1).ravel()
+    tab[_GL_TAB_WIN2:] = w * w
+    return tab.astype(np.float32)
+
+
+def _inv_mel_basis_host():
+    """pinv(_build_mel_basis()) in float64, transposed to [num_mels, num_freq] (a wave reads consecutive bins) and
+    rounded once to fp32."""
+    return np.ascontiguousarray(np.linalg.pinv(_build_mel_basis()).T).astype(np.float32)
+
+
+_GL_TAB_WIN2 = 5296            # include/fastvocoder_hip.h FV_GL_TAB_WIN2
+_gl_tables, _inv_bases = {}, {}
+
+
+def _per_device(cache, device, make):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _native.NativeError(f"Griffin-Lim tables live on the ROCm device, not {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device not in cache:
+        cache[device] = torch.from_numpy(make()).to(device)
+    return cache[device]
+
+
+def griffin_lim_tables(device):
+    """The device copy of the Griffin-Lim table, built once per device."""
+    return _per_device(_gl_tables, device, _gl_table_host)
+
+
+def inv_mel_basis(device):
+    """The device copy of the transposed pseudo-inverse of the mel filters, built once per device."""
+    return _per_device(_inv_bases, device, _inv_mel_basis_host)
+
+
+def _stft(y):
+    """librosa.stft(y, n_fft, hop, win) on the GPU (fv_stft): numpy 1-D -> complex64 numpy [num_freq, T]; fp32 device
+    tensor [n] / [B, n] -> complex64 device tensor [B, T, num_freq] (frames-major)."""
+    n_fft, hop, win_length = _stft_parameters()
+    if torch.is_tensor(y):
+        _need_device_f32(y, "_stft", (1, 2))
+        return _native.stft_complex((y.reshape(1, -1) if y.dim() == 1 else y).contiguous(),
+                                    griffin_lim_tables(y.device), n_fft, hop, win_length)
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError(f"_stft: expected a 1-D waveform, got shape {y.shape}")
+    return np.ascontiguousarray(_stft(_to_device(y, "_stft"))[0].cpu().numpy().T)
+
+
+def _istft(D):
+    """librosa.istft(D, hop, win) on the GPU (fv_istft): complex numpy [num_freq, T] -> float32 numpy
+    [hop (T - 1)]; complex64 device tensor [B, T, num_freq] (frames-major) -> device tensor [B, hop (T - 1)]."""
+    n_fft, hop, win_length = _stft_parameters()
+    if torch.is_tensor(D):
+        if not D.is_cuda:
+            raise _native.NativeError("_istft: a tensor argument must live on the ROCm device")
+        return _native.istft(D, griffin_lim_tables(D.device), n_fft, hop, win_length)
+    D = np.asarray(D)
+    if D.ndim != 2 or D.shape[0] != hparams.num_freq:
+        raise ValueError(f"_istft: expected [{hparams.num_freq}, T], got shape {D.shape}")
+    d = _to_device(D.T[None], "_istft", np.complex64)
+    return _istft(d)[0].cpu().numpy()
+
+
+def _initial_phase(angles, seed, B, T, device):
+    """exp(2j pi u) for the reference's uniform draw u [num_freq, T] (given, or drawn on the host from
+    RandomState(seed) / the global NumPy state), computed in float64, rounded once: complex64 device [B, T, num_freq]."""
+    F = hparams.num_freq
+    if angles is None:
+        rng = np.random if seed is None else np.random.RandomState(seed)
+        angles = rng.rand(F, T) if B == 1 else np.stack([rng.rand(F, T) for _ in range(B)])
+    angles = np.asarray(angles, dtype=np.float64)
+    if angles.shape == (F, T):
+        angles = np.broadcast_to(angles, (B, F, T))
+    if angles.shape != (B, F, T):
+        raise ValueError(f"angles: expected [{F}, {T}] or [{B}, {F}, {T}], got {angles.shape}")
+    ph = np.exp(2j * np.pi * angles.transpose(0, 2, 1)).astype(np.complex64)
+    return torch.from_numpy(np.ascontiguousarray(ph)).to(device)
+
+
+def _griffin_lim_device(S, angles, seed, iters):
+    """S: fp32 device [B, T, num_freq] -> y [B, hop (T - 1)]."""
+    n_fft, hop, win_length = _stft_parameters()
+    B, T = S.shape[:2]
+    if hop * (T - 1) < n_fft // 2 + 1:
+        raise ValueError(f"Griffin-Lim needs at least {(n_fft // 2 + 1 + hop - 1) // hop + 1} frames (its iterate of "
+                         f"{hop} (T - 1) samples is reflect-padded by {n_fft // 2}), got T={T}")
+    ph = _initial_phase(angles, seed, B, T, S.device)
+    return _native.griffin_lim(S, ph, griffin_lim_tables(S.device), int(iters), None, n_fft, hop, win_length)
+
+
+def _griffin_lim(S, angles=None, seed=None, iters=None):
+    """The reference's ``_griffin_lim`` on the GPU (fv_griffin_lim): S numpy [num_freq, T] magnitudes -> float32 numpy
+    [hop (T - 1)]; fp32 device tensor [B, T, num_freq] (frames-major) -> device tensor [B, hop (T - 1)].
+    ``angles``: the uniform [0, 1) draw the reference takes from np.random.rand(num_freq, T) ([B, num_freq, T] for a
+    batch); absent, it is drawn from np.random.RandomState(seed), or the global NumPy state for seed=None."""
+    iters = hparams.griffin_lim_iters if iters is None else iters
+    if torch.is_tensor(S):
+        _need_device_f32(S, "_griffin_lim", (3,))
+        return _griffin_lim_device(S.contiguous(), angles, seed, iters)
+    S = np.abs(np.asarray(S))
+    if S.ndim != 2 or S.shape[0] != hparams.num_freq:
+        raise ValueError(f"_griffin_lim: expected [{hparams.num_freq}, T], got shape {S.shape}")
+    return _griffin_lim_device(_to_device(S.T[None], "_griffin_lim"), angles, seed, iters)[0].cpu().numpy()
+
+
+def _mel_to_linear(mel_spectrogram, power=1.0):
+    """max(1e-10, pinv(mel_basis) @ mel_spectrogram) ** power on the GPU (fv_mel_to_linear).  NOTE the argument: as in
+    the reference's chain this is the AMPLITUDE mel (``_db_to_amp(_denormalize(mel) + ref_level_db)``) for numpy
+    [num_mels, T] -> float32 numpy [num_freq, T]; the kernel takes the normalised mel, so the amplitudes are mapped back
+    (exactly invertible above the 1e-5 floor of ``_amp_to_db``)."""
+    A = np.asarray(mel_spectrogram, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != hparams.num_mels:
+        raise ValueError(f"_mel_to_linear: expected [{hparams.num_mels}, T], got shape {A.shape}")
+    mel = (20 * np.log10(np.maximum(1e-300, A)) - hparams.ref_level_db - hparams.min_level_db) / -hparams.min_level_db
+    if mel.min() < 0 or mel.max() > 1:
+        raise ValueError("_mel_to_linear: amplitudes outside the range of a normalised mel "
+                         f"([{_db_to_amp(hparams.min_level_db + hparams.ref_level_db):g}, "
+                         f"{_db_to_amp(hparams.ref_level_db):g}])")
+    S = _mel_to_linear_device(_to_device(mel[None], "_mel_to_linear"), power)
+    return np.ascontiguousarray(S[0].cpu().numpy().T)
+
+
+def _mel_to_linear_device(mel, power):
+    """Normalised mel, fp32 device [B, num_mels, T] -> S [B, T, num_freq] = _mel_to_linear(...) ** power."""
+    return _native.mel_to_linear(mel.contiguous(), inv_mel_basis(mel.device), power)
+
+
+def inv_mel_spectrogram(mel_spectrogram, angles=None, seed=None, iters=None):
+    """The reference's ``inv_mel_spectrogram`` on the GPU: normalised mel -> waveform by Griffin-Lim.
+
+    - numpy [num_mels, T] -> 1-D float32 numpy array of hop_size (T - 1) samples;
+    - fp32 device tensor [num_mels, T] or [B, num_mels, T] -> device tensor [hop_size (T - 1)] / [B, hop_size (T - 1)]
+      (chains after ``melspectrogram`` with no host round trip).
+    ``angles`` / ``seed``: the initial phase draw, see ``_griffin_lim``.  ``iters``: hparams.griffin_lim_iters.
+    T must be at least 6 frames.  Values outside [0, 1] are clipped, as the reference's ``_denormalize`` does."""
+    iters = hparams.griffin_lim_iters if iters is None else iters
+    if torch.is_tensor(mel_spectrogram):
+        mel = mel_spectrogram
+        _need_device_f32(mel, "inv_mel_spectrogram", (2, 3))
+        m3 = mel.unsqueeze(0) if mel.dim() == 2 else mel
+        if m3.shape[1] != hparams.num_mels:
+            raise ValueError(f"inv_mel_spectrogram: expected {hparams.num_mels} mel channels, got {tuple(mel.shape)}")
+        S = _mel_to_linear_device(m3, hparams.power)
+        y = _native.inv_preemphasis(_griffin_lim_device(S, angles, seed, iters), hparams.preemphasis)
+        return y[0] if mel.dim() == 2 else y
+    mel = np.asarray(mel_spectrogram)
+    if mel.ndim != 2 or mel.shape[0] != hparams.num_mels:
+        raise ValueError(f"inv_mel_spectrogram: expected [{hparams.num_mels}, T], got shape {mel.shape}")
+    return inv_mel_spectrogram(_to_device(mel, "inv_mel_spectrogram"), angles, seed, iters).cpu().numpy()

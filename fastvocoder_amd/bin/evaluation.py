@@ -18,6 +18,15 @@ utterance is also scored with the adversarial / feature-map / discriminator term
     eval-d mean utterances=<count> adv=<mean adv> fm=<mean fm> d=<mean d>
 
 each after the corresponding ``eval`` line.  Without the flag the output is unchanged.
+
+With ``--griffin_lim`` every utterance's mel is also inverted by Griffin-Lim (audio.inv_mel_spectrogram, the initial
+phase seeded with ``--gl_seed``, default 0) and scored against the same target with the same distance -- the floor to
+read the vocoder's distances against:
+
+    eval-gl <i> samples=<n> sc=<spectral convergence> mag=<log-STFT-magnitude L1>
+    eval-gl mean utterances=<count> sc=<mean sc> mag=<mean mag>
+
+each after the utterance's ``eval`` (and ``eval-d``) line.  Without the flag the output is unchanged.
 """
 import argparse
 import os
@@ -25,6 +34,7 @@ import os
 import numpy as np
 import torch
 
+from ..audio import inv_mel_spectrogram
 from ..loss import MultiResolutionSTFTLoss, discriminator_terms
 from .synthesize import Synthesizer
 
@@ -60,6 +70,16 @@ def score(synthesizer, loss, wav, mel, discriminator=None):
     return n, sc, mag, score_discriminator(discriminator, est[:n].contiguous(), target[:n].contiguous())
 
 
+def score_griffin_lim(loss, wav, mel, device, seed):
+    """(samples, sc, mag) of Griffin-Lim of mel [80, T] against the target, cropped to the common length."""
+    est = inv_mel_spectrogram(torch.as_tensor(np.asarray(mel), dtype=torch.float32).to(device), seed=seed)
+    target = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).to(device)
+    n = min(est.shape[0], target.shape[0])
+    with torch.no_grad():
+        sc, mag = loss.per_utterance(est[None, :n].contiguous(), target[None, :n].contiguous())[0].tolist()
+    return n, sc, mag
+
+
 def load_discriminator(synthesizer):
     """The checkpoint's discriminator on the synthesizer's device, or a clear exit when the checkpoint has none."""
     from ..discriminator import Discriminator
@@ -90,6 +110,9 @@ def run_evaluation(argv=None):
     parser.add_argument('--discriminator', action='store_true',
                         help="also print the adversarial / feature-map / discriminator scores of the checkpoint's "
                              "'discriminator'")
+    parser.add_argument('--griffin_lim', action='store_true',
+                        help="also score Griffin-Lim of each mel against the same target (eval-gl lines)")
+    parser.add_argument('--gl_seed', type=int, default=0, help="seed of the Griffin-Lim initial phase (default 0)")
     args = parser.parse_args(argv)
     if args.num < 1:
         raise SystemExit("evaluation: --num must be at least 1")
@@ -98,7 +121,7 @@ def run_evaluation(argv=None):
     audio_list, mel_list, names = load_data(args.audio_index_path, args.mel_index_path, list(range(args.num)))
     loss = MultiResolutionSTFTLoss().to(synthesizer.device)
     disc = load_discriminator(synthesizer) if args.discriminator else None
-    rows, drows = [], []
+    rows, drows, grows = [], [], []
     for i, (wav, mel, name) in enumerate(zip(audio_list, mel_list, names)):
         n, sc, mag, *d = score(synthesizer, loss, wav, mel, disc)
         rows.append((sc, mag))
@@ -108,11 +131,18 @@ def run_evaluation(argv=None):
             drows.append((t["adversarial"], t["feature_map"], t["discriminator"]))
             print(f"eval-d {i} adv={t['adversarial']:.8e} fm={t['feature_map']:.8e} real={t['real']:.8e} "
                   f"fake={t['fake']:.8e} d={t['discriminator']:.8e}")
+        if args.griffin_lim:
+            gn, gsc, gmag = score_griffin_lim(loss, wav, mel, synthesizer.device, args.gl_seed)
+            grows.append((gsc, gmag))
+            print(f"eval-gl {i} samples={gn} sc={gsc:.8e} mag={gmag:.8e}")
     sc_mean, mag_mean = (float(np.mean(c)) for c in zip(*rows))
     print(f"eval mean utterances={len(rows)} sc={sc_mean:.8e} mag={mag_mean:.8e}")
     if drows:
         adv, fm, d = (float(np.mean(c)) for c in zip(*drows))
         print(f"eval-d mean utterances={len(drows)} adv={adv:.8e} fm={fm:.8e} d={d:.8e}")
+    if grows:
+        gsc, gmag = (float(np.mean(c)) for c in zip(*grows))
+        print(f"eval-gl mean utterances={len(grows)} sc={gsc:.8e} mag={gmag:.8e}")
     return rows
 
 

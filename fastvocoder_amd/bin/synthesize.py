@@ -3,9 +3,10 @@
 Same surface as the reference's bin/synthesize.py: ``Synthesizer(checkpoint_path,
 config_path, model_name)`` with ``.synthesize(mel[T,80]) -> (est, est - bias,
 bias)`` and ``.test_rtf(mel)``; ``run_synthesizer()`` parses the same flags and
-writes ``<wav>``, ``<wav[:-3]>remove.wav`` and ``<wav[:-3]>bias.wav``.  The
-reference's fourth output (Griffin-Lim ``gl.wav``) needs librosa and is skipped
-with a notice.
+writes ``<wav>``, ``<wav[:-3]>remove.wav``, ``<wav[:-3]>bias.wav`` and
+``<wav[:-3]>gl.wav``, the Griffin-Lim reconstruction of the same mel
+(audio.inv_mel_spectrogram, on the GPU; ``--gl_seed`` makes its initial phase, which
+the reference draws unseeded, repeatable).
 """
 import argparse
 import os
@@ -15,7 +16,7 @@ import torch
 import yaml
 
 from .. import hparams as hp
-from ..audio import save_wav
+from ..audio import inv_mel_spectrogram, save_wav
 from ..generator import (BasisMelGANGenerator, HiFiGANGenerator, MelGANGenerator,
                          MultiBandHiFiGANGenerator)
 
@@ -138,14 +139,19 @@ def run_synthesizer():
     parser.add_argument("--model_name", type=str,
                         help="melgan, hifigan, multiband-hifigan and basis-melgan.")
     parser.add_argument("--config", type=str, help="path to model configuration file")
+    parser.add_argument("--gl_seed", type=int, default=None,
+                        help="seed of the Griffin-Lim initial phase of <stem>gl.wav (default: unseeded, the global "
+                             "NumPy state, as the reference draws it)")
     args = parser.parse_args()
 
     synthesizer = Synthesizer(args.checkpoint_path, args.config, args.model_name)
     mel = np.load(args.mel_path)
+    gl_wav = inv_mel_spectrogram(torch.from_numpy(np.ascontiguousarray(mel, dtype=np.float32)).to(synthesizer.device),
+                                 seed=args.gl_seed)
     outs = synthesizer.synthesize(mel.T)
     est_source, est_source_remove_bias, bias = (o.cpu().numpy() for o in outs)
     stem = args.wav_path[:-3]
     save_wav(est_source, args.wav_path, hp.sample_rate, rescale_out=hp.rescale_out)
     save_wav(est_source_remove_bias, stem + "remove.wav", hp.sample_rate, rescale_out=hp.rescale_out)
     save_wav(bias, stem + "bias.wav", hp.sample_rate, rescale_out=hp.rescale_out)
-    print(f"[fastvocoder_amd] skipped {stem}gl.wav: Griffin-Lim needs librosa (out of scope)")
+    save_wav(gl_wav, stem + "gl.wav", hp.sample_rate, rescale_out=hp.rescale_out)

@@ -525,6 +525,91 @@ int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, in
     return launch_melspectrogram(x, mel, tables, B, n, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// Griffin-Lim (griffin_lim.hip)
+// ---------------------------------------------------------------------------
+static int gl_check_geometry(const char* who, int n_fft, int hop, int win_length) {
+    if (n_fft != 2048 || hop != 240 || win_length != 1200)
+        return fail(FV_ERR_UNSUPPORTED, "%s: only n_fft=2048 hop=240 win_length=1200 (got n_fft=%d hop=%d win_length=%d)",
+                    who, n_fft, hop, win_length);
+    return 0;
+}
+
+static int gl_check_frames(const char* who, int B, int T, int min_T) {
+    if (B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "%s: B=%d (1..65535)", who, B);
+    if (T < min_T || T > FV_GL_MAX_FRAMES)
+        return fail(FV_ERR_INVALID_ARG, "%s: T=%d frames (%d..%d)", who, T, min_T, FV_GL_MAX_FRAMES);
+    return 0;
+}
+
+static int gl_check_workspace(const char* who, int B, int T, const void* workspace, size_t workspace_bytes) {
+    const int64_t need = fv_istft_workspace_bytes(B, T);
+    if (!workspace || (uint64_t)workspace_bytes < (uint64_t)need || ((uintptr_t)workspace & 15))
+        return fail(FV_ERR_WORKSPACE, "%s: workspace of %zu bytes, needs %lld (16-byte aligned)", who, workspace_bytes,
+                    (long long)need);
+    return 0;
+}
+
+int fv_gl_table_floats(void) { return FV_GL_TABLE_FLOATS; }
+
+int64_t fv_istft_workspace_bytes(int B, int T) {
+    if (B <= 0 || B > 65535 || T < 1 || T > FV_GL_MAX_FRAMES) return fail(FV_ERR_INVALID_ARG, "istft workspace: B=%d T=%d", B, T);
+    return (int64_t)B * T * 1200 * (int64_t)sizeof(float);
+}
+
+int64_t fv_griffin_lim_workspace_bytes(int B, int T) { return fv_istft_workspace_bytes(B, T); }
+
+int fv_stft(const float* y, float* spec, const float* tables, int B, int64_t n, int n_fft, int hop, int win_length,
+            void* stream) {
+    if (int rc = gl_check_geometry("stft", n_fft, hop, win_length)) return rc;
+    if (!y || !spec || !tables || ((uintptr_t)spec & 7) || ((uintptr_t)tables & 15))
+        return fail(FV_ERR_INVALID_ARG, "stft: null or misaligned pointer");
+    if (n < n_fft / 2 + 1 || n / hop >= FV_GL_MAX_FRAMES)
+        return fail(FV_ERR_INVALID_ARG, "stft: n=%lld samples (reflect padding by %d needs n >= %d)", (long long)n,
+                    n_fft / 2, n_fft / 2 + 1);
+    if (int rc = gl_check_frames("stft", B, (int)(1 + n / hop), 1)) return rc;
+    return launch_stft_complex(y, spec, tables, B, n, (hipStream_t)stream);
+}
+
+int fv_istft(const float* spec, float* y, const float* tables, int B, int T, int n_fft, int hop, int win_length,
+             void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = gl_check_geometry("istft", n_fft, hop, win_length)) return rc;
+    if (int rc = gl_check_frames("istft", B, T, 2)) return rc;
+    if (!spec || !y || !tables || ((uintptr_t)spec & 7) || ((uintptr_t)y & 15) || ((uintptr_t)tables & 15))
+        return fail(FV_ERR_INVALID_ARG, "istft: null or misaligned pointer");
+    if (int rc = gl_check_workspace("istft", B, T, workspace, workspace_bytes)) return rc;
+    return launch_istft(spec, y, tables, B, T, static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
+int fv_griffin_lim(const float* S, const float* phase0, float* y, const float* tables, int B, int T, int iters,
+                   int n_fft, int hop, int win_length, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = gl_check_geometry("griffin_lim", n_fft, hop, win_length)) return rc;
+    // the iterate of 240 (T - 1) samples is reflect-padded by 1024: T >= 6
+    if (int rc = gl_check_frames("griffin_lim", B, T, 6)) return rc;
+    if (iters < 0) return fail(FV_ERR_INVALID_ARG, "griffin_lim: iters=%d", iters);
+    if (!S || !y || !tables || ((uintptr_t)phase0 & 7) || ((uintptr_t)y & 15) || ((uintptr_t)tables & 15))
+        return fail(FV_ERR_INVALID_ARG, "griffin_lim: null or misaligned pointer");
+    if (int rc = gl_check_workspace("griffin_lim", B, T, workspace, workspace_bytes)) return rc;
+    return launch_griffin_lim(S, phase0, y, tables, B, T, iters, static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
+int fv_mel_to_linear(const float* mel, const float* inv_basis, float* S, int B, int T, int n_mels, int n_freq,
+                     float power, void* stream) {
+    if (n_mels != 80 || n_freq != 1025)
+        return fail(FV_ERR_UNSUPPORTED, "mel_to_linear: only n_mels=80 n_freq=1025 (got %d, %d)", n_mels, n_freq);
+    if (int rc = gl_check_frames("mel_to_linear", B, T, 1)) return rc;
+    if (!mel || !inv_basis || !S || !(power > 0.f))
+        return fail(FV_ERR_INVALID_ARG, "mel_to_linear: null tensor or power=%g", (double)power);
+    return launch_mel_to_linear(mel, inv_basis, S, B, T, power, (hipStream_t)stream);
+}
+
+int fv_inv_preemphasis(const float* y, float* out, int B, int64_t n, float coef, void* stream) {
+    if (!y || !out || B <= 0 || B > 65535 || n < 1 || !(fabsf(coef) < 1.f))
+        return fail(FV_ERR_INVALID_ARG, "inv_preemphasis: null tensor, B=%d, n=%lld or |coef|=%g >= 1", B, (long long)n,
+                    (double)fabsf(coef));
+    return launch_inv_preemphasis(y, out, B, n, coef, (hipStream_t)stream);
+}
+
 static int stft_check_res(const char* who, int64_t n, int n_fft, int hop, int win_length) {
     if ((n_fft != 512 && n_fft != 1024 && n_fft != 2048) || hop < 1 || win_length < 1 || win_length > n_fft)
         return fail(FV_ERR_UNSUPPORTED,

@@ -433,6 +433,13 @@ int launch_encode16(float* x, int B, int64_t n, float rescale, short* out, unsig
 int launch_pqmf_analysis(const float* xin, const float* ha, float* x, int B, int S, int ntaps,
                          int64_t T, hipStream_t s);
 int launch_melspectrogram(const float* x, float* mel, const float* tab, int B, int64_t n, hipStream_t s);
+// Griffin-Lim (griffin_lim.hip); frames: the [B, T, 1200] frame buffer of the overlap-add
+int launch_stft_complex(const float* y, float* spec, const float* tab, int B, int64_t n, hipStream_t s);
+int launch_istft(const float* spec, float* y, const float* tab, int B, int T, float* frames, hipStream_t s);
+int launch_griffin_lim(const float* S, const float* phase0, float* y, const float* tab, int B, int T, int iters,
+                       float* frames, hipStream_t s);
+int launch_mel_to_linear(const float* mel, const float* invb, float* S, int B, int T, float power, hipStream_t s);
+int launch_inv_preemphasis(const float* y, float* out, int B, int64_t n, float coef, hipStream_t s);
 int64_t stft_chunks(int64_t n, int hop);   // distance-kernel blocks per utterance and resolution (stft_loss.hip)
 int launch_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
                          const int* nfft, const int* hop, const int* win, double* out, double* ws, hipStream_t s);

@@ -12,11 +12,10 @@
 // frame's LDS, and the block's 80 x kMelFrames (filter, frame) dot products run over the sparse filters; lanes
 // that share a filter write kMelFrames consecutive frames of one [B, 80, T] row.
 // Every table (window, twiddles, filters) comes from the host in float64 rounded once to fp32.
-#include "fv_internal.h"
+#include "fft1024.hpp"
 
 namespace fv {
 
-constexpr int kMelNc = 1024;               // complex FFT size = n_fft / 2
 constexpr int kMelHop = 240, kMelWin = 1200, kMelLpad = 424, kMelHalf = 1024, kMelMels = 80;
 constexpr int kMelFrames = 4;              // frames (= waves) per block
 constexpr int kMelThreads = 64 * kMelFrames;
@@ -29,49 +28,6 @@ __device__ __forceinline__ float mel_padded_sample(const float* __restrict__ xr,
     if (q >= n) q = 2 * (n - 1) - q;
     const float v = xr[q];
     return q > 0 ? fmaf(-0.97f, xr[q - 1], v) : v;
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// forward radix-4 DFT of v[0..3] (exp(-2 pi i rk / 4)), Stockham output order
-__device__ __forceinline__ void radix4(float2* v) {
-    const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y);
-    const float2 a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
-    const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y);
-    const float2 a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);   // -i (v1 - v3)
-    v[0] = make_float2(a0.x + a2.x, a0.y + a2.y);
-    v[1] = make_float2(a1.x + a3.x, a1.y + a3.y);
-    v[2] = make_float2(a0.x - a2.x, a0.y - a2.y);
-    v[3] = make_float2(a1.x - a3.x, a1.y - a3.y);
-}
-
-// Stockham pass with sub-transform size Ns: butterfly j reads z[j + 256 r], writes z[(j/Ns)*4Ns + j%Ns + Ns r]
-template <int Ns>
-__device__ __forceinline__ void mel_fft_pass(float2* __restrict__ z, const float2* __restrict__ tw, int lane) {
-    float2 v[4][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int j = lane + 64 * q;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[q][r] = z[j + 256 * r];
-    }
-    __syncthreads();   // every read of the pass before any write (in place)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int j = lane + 64 * q;
-        if (Ns > 1) {
-            const int ti = (j % Ns) * (kMelNc / (4 * Ns));   // r * ti < 1024
-#pragma unroll
-            for (int r = 1; r < 4; ++r) v[q][r] = cmul(v[q][r], tw[r * ti]);
-        }
-        radix4(v[q]);
-        const int d = (j / Ns) * Ns * 4 + (j % Ns);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z[d + Ns * r] = v[q][r];
-    }
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restrict__ x, float* __restrict__ mel,
@@ -112,10 +68,10 @@ __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restric
         }
         __syncthreads();
     }
-    mel_fft_pass<4>(z, tw, lane);
-    mel_fft_pass<16>(z, tw, lane);
-    mel_fft_pass<64>(z, tw, lane);
-    mel_fft_pass<256>(z, tw, lane);
+    fft1024_pass<4>(z, tw, lane);
+    fft1024_pass<16>(z, tw, lane);
+    fft1024_pass<64>(z, tw, lane);
+    fft1024_pass<256>(z, tw, lane);
 
     // split step: |X[k]| for k = lane + 64 i; X[1024] = Re Z[0] - Im Z[0]
     {

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 16
+#define FV_ABI_VERSION 17   /* 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, fv_mel_to_linear, fv_inv_preemphasis) */
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -460,6 +460,56 @@ int fv_encode_16bits(float* x, int16_t* out, float* peak, int B, int64_t n, floa
 int fv_mel_table_floats(void);
 int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, int64_t n, int sample_rate, int n_fft,
                       int hop, int win_length, int n_mels, float fmin, void* stream);
+
+/*
+ * Griffin-Lim: the reference's inv_mel_spectrogram (data/audio.py:66-95,179-190 with hparams.py as shipped, librosa < 0.10
+ * semantics), the inverse direction of fv_melspectrogram.  Geometry n_fft 2048 / hop 240 / win_length 1200 (a periodic
+ * Hann window centred in the frame) only; anything else returns FV_ERR_UNSUPPORTED.  Spectra and magnitudes are
+ * FRAMES-MAJOR here, [B, T, 1025] (a frame's bins consecutive: a wave owns a frame), the transpose of librosa's
+ * [1025, T]; complex values are (re, im) float pairs.
+ *
+ * tables: fp32 device, FV_GL_TABLE_FLOATS floats, 16-byte aligned, built in float64 on the host and rounded once
+ * (fastvocoder_amd/audio.py griffin_lim_tables); the first three parts are fv_melspectrogram's:
+ *   [FV_GL_TAB_WINDOW]   1200 window taps        [FV_GL_TAB_TWIDDLE]  1024 complex exp(-2 pi i t / 1024)
+ *   [FV_GL_TAB_SPLIT]    1024 complex exp(-2 pi i k / 2048)           [FV_GL_TAB_WIN2]  the 1200 squared window taps
+ *
+ * fv_stft: y [B, n] -> spec [B, T, 1025] complex, T = 1 + n / 240: librosa.stft(y, 2048, 240, 1200), centred, numpy
+ *   'reflect' padding by 1024 (n >= 1025).  One launch.
+ * fv_istft: spec [B, T, 1025] complex -> y [B, 240 (T - 1)]: librosa.istft(D, hop_length=240, win_length=1200): inverse
+ *   real FFT of each frame (Im of bins 0 and 1024 ignored), times the window, overlap-added, divided by the overlap-added
+ *   squared window where that exceeds FLT_MIN, 1024 samples trimmed from each end.  T >= 2.  Two launches: the frames
+ *   into the workspace ([B, T, 1200] floats, fv_istft_workspace_bytes), then a gather that sums each sample's (at most
+ *   five) frames in increasing frame order -- no atomics: identical calls give identical bits.
+ * fv_griffin_lim: S [B, T, 1025] magnitudes, phase0 [B, T, 1025] complex initial phases (exp(2 pi i u), u the
+ *   reference's uniform draw), y [B, 240 (T - 1)]:  y = istft(S * phase0), then `iters` times
+ *   y = istft(S * exp(i angle(stft(y)))), angle(0) = 0.  phase0 = NULL: the iterations start from the caller's y.
+ *   T >= 6 (the iterate is reflect-padded).  Two launches per iteration (the projection with the frame resident in LDS,
+ *   the overlap-add gather), all enqueued on `stream` without a host synchronisation; same workspace as fv_istft.
+ *   Rows are independent: row b of a batched call has the bits of its single call.
+ * fv_mel_to_linear: mel [B, 80, T] normalised mel (values clipped to [0, 1]), inv_basis [80, 1025] = pinv(mel filters)^T
+ *   in fp32 -> S [B, T, 1025] = max(1e-10, pinv @ 10^((mel 100 - 100 + 20) / 20))^power (the dot products in float64).
+ * fv_inv_preemphasis: out[b, i] = y[b, i] + coef out[b, i-1] (scipy lfilter([1], [1, -coef]), zero initial state) over
+ *   rows of n samples, |coef| < 1, as a blocked scan whose carries are exact; out may be y.
+ * y, workspace and tables must be 16-byte aligned, spec / phase0 8-byte aligned.
+ */
+#define FV_GL_TAB_WINDOW 0
+#define FV_GL_TAB_TWIDDLE 1200
+#define FV_GL_TAB_SPLIT 3248
+#define FV_GL_TAB_WIN2 5296
+#define FV_GL_TABLE_FLOATS (FV_GL_TAB_WIN2 + 1200)
+#define FV_GL_MAX_FRAMES (1 << 20)
+int fv_gl_table_floats(void);
+int64_t fv_istft_workspace_bytes(int B, int T);
+int64_t fv_griffin_lim_workspace_bytes(int B, int T);
+int fv_stft(const float* y, float* spec, const float* tables, int B, int64_t n, int n_fft, int hop, int win_length,
+            void* stream);
+int fv_istft(const float* spec, float* y, const float* tables, int B, int T, int n_fft, int hop, int win_length,
+             void* workspace, size_t workspace_bytes, void* stream);
+int fv_griffin_lim(const float* S, const float* phase0, float* y, const float* tables, int B, int T, int iters,
+                   int n_fft, int hop, int win_length, void* workspace, size_t workspace_bytes, void* stream);
+int fv_mel_to_linear(const float* mel, const float* inv_basis, float* S, int B, int T, int n_mels, int n_freq,
+                     float power, void* stream);
+int fv_inv_preemphasis(const float* y, float* out, int B, int64_t n, float coef, void* stream);
 
 /*
  * The reference's STFT magnitude (model/loss/stft_loss.py:16-39 stft: torch.stft with its defaults, then
