@@ -24,7 +24,7 @@ SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_
           [f"conv_inst_s{i}.hip" for i in range(6)]
 HEADERS = ["fv_internal.h", "conv_kernels.hpp", "pair_kernels.hpp", "pair_inst.hpp", "pairh_kernels.hpp",
            "pairh_inst.hpp", "convh_kernels.hpp", "convh_inst.hpp", "convr_kernels.hpp",
-           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "fft1024.hpp"]
+           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp"]
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)

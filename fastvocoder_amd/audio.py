@@ -32,6 +32,7 @@ import torch
 
 from . import _native
 from . import hparams
+from ._stft_tables import device_cached, periodic_hann, rfft_twiddles
 
 
 def encode_16bits(x, rescale_out=1.0):
@@ -129,13 +130,9 @@ def _normalize(S):
 def _mel_table_host():
     """The fp32 table fv_melspectrogram reads (include/fastvocoder_hip.h, FV_MEL_TAB_*), built in float64."""
     n_fft, _, win_length = _stft_parameters()
-    nc = n_fft // 2
     tab = np.zeros(_MEL_TAB_WEIGHTS + _MEL_MAX_WEIGHTS, dtype=np.float64)
-    tab[0:win_length] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)   # periodic Hann
-    tw = np.exp(-2j * np.pi * np.arange(nc) / nc)
-    sp = np.exp(-2j * np.pi * np.arange(nc) / n_fft)
-    tab[_MEL_TAB_TWIDDLE:_MEL_TAB_TWIDDLE + 2 * nc] = np.stack([tw.real, tw.imag], 1).ravel()
-    tab[_MEL_TAB_SPLIT:_MEL_TAB_SPLIT + 2 * nc] = np.stack([sp.real, sp.imag], 1).ravel()
+    tab[0:win_length] = periodic_hann(win_length)
+    tab[_MEL_TAB_TWIDDLE:_MEL_TAB_SPLIT], tab[_MEL_TAB_SPLIT:_MEL_TAB_FILTERS] = rfft_twiddles(n_fft)
     basis = _build_mel_basis()
     off = 0
     for m, row in enumerate(basis):
@@ -156,14 +153,7 @@ _mel_tables = {}
 
 def mel_tables(device):
     """The device copy of the mel table, built once per device."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _native.NativeError(f"mel tables live on the ROCm device, not {device}")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _mel_tables:
-        _mel_tables[device] = torch.from_numpy(_mel_table_host()).to(device)
-    return _mel_tables[device]
+    return device_cached(_mel_tables, device, (), _mel_table_host, "mel tables")
 
 
 def melspectrogram(y):
@@ -239,14 +229,10 @@ def _gl_table_host():
     """The fp32 table the Griffin-Lim kernels read (include/fastvocoder_hip.h, FV_GL_TAB_*), built in float64: the
     window, twiddle and split parts of the mel table, then the squared window."""
     n_fft, _, win_length = _stft_parameters()
-    nc = n_fft // 2
     tab = np.zeros(_GL_TAB_WIN2 + win_length, dtype=np.float64)
-    w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)   # periodic Hann
-    tw = np.exp(-2j * np.pi * np.arange(nc) / nc)
-    sp = np.exp(-2j * np.pi * np.arange(nc) / n_fft)
+    w = periodic_hann(win_length)
     tab[0:win_length] = w
-    tab[_MEL_TAB_TWIDDLE:_MEL_TAB_TWIDDLE + 2 * nc] = np.stack([tw.real, tw.imag], 1).ravel()
-    tab[_MEL_TAB_SPLIT:_MEL_TAB_SPLIT + 2 * nc] = np.stack([sp.real, sp.imag], 1).ravel()
+    tab[_MEL_TAB_TWIDDLE:_MEL_TAB_SPLIT], tab[_MEL_TAB_SPLIT:_GL_TAB_WIN2] = rfft_twiddles(n_fft)
     tab[_GL_TAB_WIN2:] = w * w
     return tab.astype(np.float32)
 
@@ -261,25 +247,14 @@ _GL_TAB_WIN2 = 5296            # include/fastvocoder_hip.h FV_GL_TAB_WIN2
 _gl_tables, _inv_bases = {}, {}
 
 
-def _per_device(cache, device, make):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _native.NativeError(f"Griffin-Lim tables live on the ROCm device, not {device}")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in cache:
-        cache[device] = torch.from_numpy(make()).to(device)
-    return cache[device]
-
-
 def griffin_lim_tables(device):
     """The device copy of the Griffin-Lim table, built once per device."""
-    return _per_device(_gl_tables, device, _gl_table_host)
+    return device_cached(_gl_tables, device, (), _gl_table_host, "Griffin-Lim tables")
 
 
 def inv_mel_basis(device):
     """The device copy of the transposed pseudo-inverse of the mel filters, built once per device."""
-    return _per_device(_inv_bases, device, _inv_mel_basis_host)
+    return device_cached(_inv_bases, device, (), _inv_mel_basis_host, "Griffin-Lim tables")
 
 
 def _stft(y):

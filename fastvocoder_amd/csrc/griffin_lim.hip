@@ -5,7 +5,7 @@
 // gl_frame_kernel: one wave per frame, kGlFrames frames per block, the frame resident in its own 8 KB of LDS from the
 // gather to the windowed output.  A projection is ONE launch of it:
 //   gather 1200 samples of y under the window (numpy 'reflect' index mapping) -> window -> 1024-point complex FFT of
-//   the sample pairs (fft1024.hpp) -> split step to bins 0..1024 -> phase normalisation, times S[t, k] -> merge step
+//   the sample pairs (stft_core.hpp) -> split step to bins 0..1024 -> phase normalisation, times S[t, k] -> merge step
 //   (the split step's inverse) -> inverse complex FFT -> window -> the frame's 1200 samples to frames[B, T, 1200].
 // Split and merge work on the bin pair (k, 1024 - k), which depends on Z[k] and Z[1024 - k] alone, so the spectrum
 // never leaves the lane's registers.  The inverse FFT is the forward one between two conjugations
@@ -21,7 +21,7 @@
 // float64.  inv_preemph_kernel: o[n] = y[n] + a o[n-1] as a blocked scan, the carry exact (never truncated).
 #include <float.h>
 
-#include "fft1024.hpp"
+#include "stft_core.hpp"
 
 namespace fv {
 
@@ -30,14 +30,6 @@ constexpr int kGlFrames = 4;               // frames (= waves) per block
 constexpr int kGlThreads = 64 * kGlFrames;
 
 enum { GL_ISTFT = 0, GL_INIT = 1, GL_ITER = 2, GL_STFT = 3 };
-
-// sample of y at padded position P (numpy 'reflect' by 1024; n >= 1025 keeps one reflection in range)
-__device__ __forceinline__ float gl_padded_sample(const float* __restrict__ yr, int64_t n, int64_t P) {
-    int64_t q = P - kGlHalf;
-    if (q < 0) q = -q;
-    if (q >= n) q = 2 * (n - 1) - q;
-    return yr[q];
-}
 
 // exp(i angle(v)), angle(0) = 0.  The components are scaled by a power of two first, so that neither the squares
 // nor their sum leave the fp32 range.
@@ -73,24 +65,10 @@ __global__ __launch_bounds__(kGlThreads) void gl_frame_kernel(const float* __res
     if (MODE == GL_ITER || MODE == GL_STFT) {
         // z[m] = (w f)[2m] + i (w f)[2m+1]; only the 600 pairs under the window are non-zero
         const float* __restrict__ yr = y + (size_t)b * n;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int m = lane + 64 * i;
-            const int i0 = 2 * m - kGlLpad;
-            float2 s = make_float2(0.f, 0.f);
-            if (live && i0 >= 0 && i0 < kGlWin) {
-                const int64_t P = (int64_t)t * kGlHop + 2 * m;
-                s.x = win[i0] * gl_padded_sample(yr, n, P);
-                s.y = win[i0 + 1] * gl_padded_sample(yr, n, P + 1);
-            }
-            z[m] = s;
-        }
-        __syncthreads();
-        fft1024_pass<1>(z, tw, lane);
-        fft1024_pass<4>(z, tw, lane);
-        fft1024_pass<16>(z, tw, lane);
-        fft1024_pass<64>(z, tw, lane);
-        fft1024_pass<256>(z, tw, lane);
+        const int64_t tt[1] = {live ? t : -1};
+        gather_pass<kMelNc, 1>(z, [&](int, int64_t P) { return yr[reflect_index(n, kGlHalf, P)]; }, tt, win, kGlHop,
+                               kGlWin, kGlLpad, lane);
+        fft_rest<kMelNc, 1>(z, tw, lane);
     }
 
     // bin pairs (k, 1024 - k), k = 0..512: k = lane + 64 i, and k = 512 on lane 0.  In place: the pair reads and
@@ -106,13 +84,9 @@ __global__ __launch_bounds__(kGlThreads) void gl_frame_kernel(const float* __res
         const float2 w = sp[k];
         float2 xk, xm;                             // X[k], X[1024 - k]
         if (MODE == GL_ITER || MODE == GL_STFT) {
-            // X[k] = E + W^k O,  X[1024-k] = conj(E - W^k O),  E = (Z[k] + conj Z[N-k]) / 2,  O = (Z[k] - conj Z[N-k]) / 2i
-            const float2 a = z[k], c = z[kz];
-            const float2 e = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));
-            const float2 o = make_float2(0.5f * (a.y + c.y), -0.5f * (a.x - c.x));
-            const float2 wo = cmul(w, o);
-            xk = make_float2(e.x + wo.x, e.y + wo.y);
-            xm = make_float2(e.x - wo.x, -(e.y - wo.y));
+            const BinPair X = split_bin(z, k, kMelNc, w);
+            xk = X.k;
+            xm = X.m;
         }
         if (MODE == GL_STFT) {
             if (live) {
@@ -142,11 +116,8 @@ __global__ __launch_bounds__(kGlThreads) void gl_frame_kernel(const float* __res
     }
     if (MODE == GL_STFT) return;
     __syncthreads();
-    fft1024_pass<1>(z, tw, lane);
-    fft1024_pass<4>(z, tw, lane);
-    fft1024_pass<16>(z, tw, lane);
-    fft1024_pass<64>(z, tw, lane);
-    fft1024_pass<256>(z, tw, lane);
+    fft_pass4<kMelNc, 1, 1>(z, tw, lane);
+    fft_rest<kMelNc, 1>(z, tw, lane);
 
     // f[2m] = Re conj(z[m]) / 1024, f[2m+1] = Im conj(z[m]) / 1024; the 600 pairs under the window
     if (!live) return;

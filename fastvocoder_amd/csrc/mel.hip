@@ -2,17 +2,14 @@
 // librosa < 0.10 semantics; include/fastvocoder_hip.h fv_melspectrogram) in one launch:
 // wav -> preemphasis -> reflect-padded, Hann-windowed frames -> |rFFT| -> Slaney mel filters -> dB, clip.
 //
-// One wave per frame, kMelFrames frames per block.  The 2048-point real FFT is a 1024-point complex FFT of
-// the even/odd sample pairs (z[m] = f[2m] + i f[2m+1]) plus the usual split step into bins 0..1024:
-//   X[k] = E[k] + W^k O[k],  E = (Z[k] + conj Z[N-k]) / 2,  O = (Z[k] - conj Z[N-k]) / 2i,  W = exp(-2 pi i / 2048).
-// The complex FFT is Stockham radix-4 (1024 = 4^5, five passes, natural order out): each lane holds four
-// radix-4 butterflies in registers, so the frame is exchanged through its own 8 KB of LDS in place between the
-// passes.  The first pass reads its inputs straight from x (frame gather, preemphasis and the reflect index
-// mapping on the fly; only the 600 pairs under the window are non-zero).  The magnitudes then overwrite the
-// frame's LDS, and the block's 80 x kMelFrames (filter, frame) dot products run over the sparse filters; lanes
-// that share a filter write kMelFrames consecutive frames of one [B, 80, T] row.
+// One wave per frame, kMelFrames frames per block.  The 2048-point real FFT is stft_core.hpp's: a 1024-point complex
+// FFT of the sample pairs in the frame's own 8 KB of LDS, whose first pass reads its inputs straight from x (frame
+// gather, preemphasis and the reflect index mapping on the fly; only the 600 pairs under the window are non-zero), and
+// the split step into bins 0..1024.  The magnitudes then overwrite the frame's LDS, and the block's 80 x kMelFrames
+// (filter, frame) dot products run over the sparse filters; lanes that share a filter write kMelFrames consecutive
+// frames of one [B, 80, T] row.
 // Every table (window, twiddles, filters) comes from the host in float64 rounded once to fp32.
-#include "fft1024.hpp"
+#include "stft_core.hpp"
 
 namespace fv {
 
@@ -20,12 +17,9 @@ constexpr int kMelHop = 240, kMelWin = 1200, kMelLpad = 424, kMelHalf = 1024, kM
 constexpr int kMelFrames = 4;              // frames (= waves) per block
 constexpr int kMelThreads = 64 * kMelFrames;
 
-// preemphasised sample at padded position P (p = lfilter([1, -0.97], [1], x), then numpy 'reflect' by 1024);
-// n >= 1025 keeps one reflection in range on either side
-__device__ __forceinline__ float mel_padded_sample(const float* __restrict__ xr, int64_t n, int64_t P) {
-    int64_t q = P - kMelHalf;
-    if (q < 0) q = -q;
-    if (q >= n) q = 2 * (n - 1) - q;
+// preemphasised sample at padded position P (p = lfilter([1, -0.97], [1], x), then numpy 'reflect' by 1024)
+__device__ __forceinline__ float mel_sample(const float* __restrict__ xr, int64_t n, int64_t P) {
+    const int64_t q = reflect_index(n, kMelHalf, P);
     const float v = xr[q];
     return q > 0 ? fmaf(-0.97f, xr[q - 1], v) : v;
 }
@@ -44,7 +38,9 @@ __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restric
     for (int i = threadIdx.x; i < kMelNc; i += kMelThreads) tw[i] = twg[i];
     float2* z = zs[wv];
 
-    // pass 1 (Ns = 1, no twiddles) on the gathered frame: z[m] = (w f)[2m] + i (w f)[2m+1]
+    // pass 1 (Ns = 1, no twiddles) on the gathered frame: z[m] = (w f)[2m] + i (w f)[2m+1].  stft_core.hpp's
+    // gather_pass<kMelNc, 1> with this geometry fixed at compile time: window and left pad are even, so one range test
+    // covers a pair (the same values; the general per-tap form measured 0.8 % slower at B = 64, DESIGN.md "STFT core")
     {
         float2 v[4][4];
 #pragma unroll
@@ -56,8 +52,8 @@ __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restric
                 float2 s = make_float2(0.f, 0.f);
                 if (t < T && i0 >= 0 && i0 < kMelWin) {
                     const int64_t P = t * kMelHop + 2 * m;
-                    s.x = win[i0] * mel_padded_sample(xr, n, P);
-                    s.y = win[i0 + 1] * mel_padded_sample(xr, n, P + 1);
+                    s.x = win[i0] * mel_sample(xr, n, P);
+                    s.y = win[i0 + 1] * mel_sample(xr, n, P + 1);
                 }
                 v[q][r] = s;
             }
@@ -68,10 +64,7 @@ __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restric
         }
         __syncthreads();
     }
-    fft1024_pass<4>(z, tw, lane);
-    fft1024_pass<16>(z, tw, lane);
-    fft1024_pass<64>(z, tw, lane);
-    fft1024_pass<256>(z, tw, lane);
+    fft_rest<kMelNc, 1>(z, tw, lane);
 
     // split step: |X[k]| for k = lane + 64 i; X[1024] = Re Z[0] - Im Z[0]
     {
@@ -80,11 +73,8 @@ __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restric
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int k = lane + 64 * i;
-            const float2 a = z[k], c = z[(kMelNc - k) & (kMelNc - 1)];
-            const float2 e = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));   // (Z[k] + conj Z[N-k]) / 2
-            const float2 o = make_float2(0.5f * (a.y + c.y), -0.5f * (a.x - c.x));  // (Z[k] - conj Z[N-k]) / 2i
-            const float2 wo = cmul(sp[k], o);
-            const float re = e.x + wo.x, im = e.y + wo.y;
+            const float2 X = split_bin(z, k, kMelNc, sp[k]).k;
+            const float re = X.x, im = X.y;
             mag[i] = sqrtf(fmaf(re, re, im * im));
         }
         const float nyq = fabsf(z[0].x - z[0].y);

@@ -5,10 +5,7 @@
 // torch.stft defaults: center=True with numpy 'reflect' padding by n_fft/2, the win_length window centred in n_fft,
 // 1 + n / hop frames, bins 0..n_fft/2; mag = sqrt(max(re^2 + im^2, 1e-7)).
 //
-// One wave per frame.  Each n_fft-point real FFT is an Nc = n_fft/2-point complex FFT of the even/odd sample pairs
-// (z[m] = f[2m] + i f[2m+1]) plus the split step, as in mel.hip:
-//   F[k] = E[k] + W^k O[k],  E = (Z[k] + conj Z[Nc-k]) / 2,  O = (Z[k] - conj Z[Nc-k]) / 2i,  W = exp(-2 pi i / n_fft).
-// The complex FFT is Stockham radix-4 (256 = 4^4, 1024 = 4^5) with one radix-2 pass last for 512, in place in LDS.
+// One wave per frame, the windowed real FFT of stft_core.hpp with Nc = n_fft/2 = 256, 512 or 1024.
 // In the distance kernel a wave transforms the same frame of x and of y side by side (two Nc-point buffers, the same
 // instructions for both), so x == y gives |X| == |Y| bit for bit and both terms exactly 0.  The magnitudes stay in
 // registers: each block reduces (|Y| - |X|)^2, |Y|^2 and |ln|Y| - ln|X|| over its frames and bins and writes the three
@@ -16,7 +13,7 @@
 // No atomics: two identical calls give identical bits.  All resolutions of a call run in the one launch: blockIdx.x
 // walks the resolutions' frame chunks one after another.
 // Every table (FFT twiddles, split twiddles, window) comes from the host in float64 rounded once to fp32.
-#include "fv_internal.h"
+#include "stft_core.hpp"
 
 namespace fv {
 
@@ -37,129 +34,10 @@ struct StftArgs {
     int64_t chunks;       // blocks per utterance over all resolutions
 };
 
-__device__ __forceinline__ float2 stft_cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// forward radix-4 DFT of v[0..3] (exp(-2 pi i rk / 4)), Stockham output order
-__device__ __forceinline__ void stft_radix4(float2* v) {
-    const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y);
-    const float2 a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
-    const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y);
-    const float2 a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);   // -i (v1 - v3)
-    v[0] = make_float2(a0.x + a2.x, a0.y + a2.y);
-    v[1] = make_float2(a1.x + a3.x, a1.y + a3.y);
-    v[2] = make_float2(a0.x - a2.x, a0.y - a2.y);
-    v[3] = make_float2(a1.x - a3.x, a1.y - a3.y);
-}
-
-// sample at padded position P of a row of n samples (numpy 'reflect' by half = n_fft/2; n >= half + 1 keeps one
-// reflection in range on either side)
-__device__ __forceinline__ float stft_padded_sample(const float* __restrict__ xr, int64_t n, int half, int64_t P) {
-    int64_t q = P - half;
-    if (q < 0) q = -q;
-    if (q >= n) q = 2 * (n - 1) - q;
-    return xr[q];
-}
-
-// One wave's two Nc-point buffers z[0..Nc) and z[Nc..2Nc): buffer s holds frame t[s] of row src[s] (t[s] < 0: zeros).
-// Pass 1 (Ns = 1, no twiddles) gathers its inputs straight from global memory: z[m] = (w f)[2m] + i (w f)[2m+1].
-template <int Nc>
-__device__ __forceinline__ void stft_gather_pass(float2* __restrict__ z, const float* const* src, const int64_t* t,
-                                                 const float* __restrict__ win, int64_t n, int hop, int wlen,
-                                                 int lpad, int lane) {
-    constexpr int Nq = Nc / 4, Q = Nc / 128;   // butterflies per buffer; per lane over both buffers
-    const int half = Nc;                       // n_fft / 2
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int J = lane + 64 * q, s = J / Nq, j = J % Nq;
-        float2 v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = j + Nq * r;
-            const int i0 = 2 * m - lpad, i1 = i0 + 1;   // window taps of samples 2m, 2m + 1
-            float2 e = make_float2(0.f, 0.f);
-            if (t[s] >= 0) {
-                const int64_t P = t[s] * hop + 2 * m;
-                if (i0 >= 0 && i0 < wlen) e.x = win[i0] * stft_padded_sample(src[s], n, half, P);
-                if (i1 >= 0 && i1 < wlen) e.y = win[i1] * stft_padded_sample(src[s], n, half, P + 1);
-            }
-            v[r] = e;
-        }
-        stft_radix4(v);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z[s * Nc + 4 * j + r] = v[r];
-    }
-    __syncthreads();
-}
-
-// Stockham radix-4 pass with sub-transform size Ns: butterfly j reads z[j + Nc/4 r], writes
-// z[(j/Ns)*4Ns + j%Ns + Ns r]; in place (every read of the pass before any write)
-template <int Nc, int Ns>
-__device__ __forceinline__ void stft_pass4(float2* __restrict__ z, const float2* __restrict__ tw, int lane) {
-    constexpr int Nq = Nc / 4, Q = Nc / 128;
-    float2 v[Q][4];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int J = lane + 64 * q, s = J / Nq, j = J % Nq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[q][r] = z[s * Nc + j + Nq * r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int J = lane + 64 * q, s = J / Nq, j = J % Nq;
-        const int ti = (j % Ns) * (Nc / (4 * Ns));   // r * ti < Nc
-#pragma unroll
-        for (int r = 1; r < 4; ++r) v[q][r] = stft_cmul(v[q][r], tw[r * ti]);
-        stft_radix4(v[q]);
-        const int d = (j / Ns) * Ns * 4 + (j % Ns);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z[s * Nc + d + Ns * r] = v[q][r];
-    }
-    __syncthreads();
-}
-
-// Stockham radix-2 pass (the last pass of Nc = 512 = 2 * 4^4)
-template <int Nc, int Ns>
-__device__ __forceinline__ void stft_pass2(float2* __restrict__ z, const float2* __restrict__ tw, int lane) {
-    constexpr int Nh = Nc / 2, Q = Nc / 64;
-    float2 v[Q][2];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int J = lane + 64 * q, s = J / Nh, j = J % Nh;
-        v[q][0] = z[s * Nc + j];
-        v[q][1] = z[s * Nc + j + Nh];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int J = lane + 64 * q, s = J / Nh, j = J % Nh;
-        const float2 b = stft_cmul(v[q][1], tw[(j % Ns) * (Nc / (2 * Ns))]);
-        const int d = (j / Ns) * Ns * 2 + (j % Ns);
-        z[s * Nc + d] = make_float2(v[q][0].x + b.x, v[q][0].y + b.y);
-        z[s * Nc + d + Ns] = make_float2(v[q][0].x - b.x, v[q][0].y - b.y);
-    }
-    __syncthreads();
-}
-
-// both buffers' complex FFTs, natural order out (the gather pass is pass 1)
-template <int Nc>
-__device__ __forceinline__ void stft_fft_rest(float2* __restrict__ z, const float2* __restrict__ tw, int lane) {
-    stft_pass4<Nc, 4>(z, tw, lane);
-    stft_pass4<Nc, 16>(z, tw, lane);
-    stft_pass4<Nc, 64>(z, tw, lane);
-    if constexpr (Nc == 512) stft_pass2<Nc, 256>(z, tw, lane);
-    if constexpr (Nc == 1024) stft_pass4<Nc, 256>(z, tw, lane);
-}
-
 // split step for bin k < Nc of one buffer (sp = W^k), then the clamped magnitude of the reference
 __device__ __forceinline__ float stft_bin_mag(const float2* __restrict__ zb, int k, int Nc, float2 sp) {
-    const float2 a = zb[k], c = zb[(Nc - k) & (Nc - 1)];
-    const float2 e = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));    // (Z[k] + conj Z[N-k]) / 2
-    const float2 o = make_float2(0.5f * (a.y + c.y), -0.5f * (a.x - c.x));   // (Z[k] - conj Z[N-k]) / 2i
-    const float2 wo = stft_cmul(sp, o);
-    const float re = e.x + wo.x, im = e.y + wo.y;
+    const float2 X = split_bin(zb, k, Nc, sp).k;
+    const float re = X.x, im = X.y;
     return sqrtf(fmaxf(re * re + im * im, 1e-7f));
 }
 
@@ -186,14 +64,15 @@ __device__ void stft_distance_block(const float* __restrict__ x, const float* __
     for (int i = threadIdx.x; i < Nc; i += kStftThreads) tw[i] = twg[i];
     float2* z = zs + (size_t)wv * 2 * Nc;
     const float* src[2] = {x, y};
+    const auto fetch = [&](int s, int64_t P) { return src[s][reflect_index(n, Nc, P)]; };   // half = n_fft / 2 = Nc
     double dsum = 0.0, rsum = 0.0, lsum = 0.0;
     __syncthreads();
     for (int f = 0; f < kStftLoop; ++f) {
         const int64_t tf = (chunk * kStftLoop + f) * kStftWaves + wv;
         const bool live = tf < rs.T;
         const int64_t t[2] = {live ? tf : -1, live ? tf : -1};
-        stft_gather_pass<Nc>(z, src, t, win, n, rs.hop, rs.win, lpad, lane);
-        stft_fft_rest<Nc>(z, tw, lane);
+        gather_pass<Nc, 2>(z, fetch, t, win, rs.hop, rs.win, lpad, lane);
+        fft_rest<Nc, 2>(z, tw, lane);
         if (live) {
             float sd = 0.f, sr = 0.f, sl = 0.f;
 #pragma unroll
@@ -295,8 +174,9 @@ __device__ void stft_magnitude_block(const float* __restrict__ xr, float* __rest
     const int64_t t0 = (int64_t)blockIdx.x * 2 * kStftWaves + 2 * wv;
     const float* src[2] = {xr, xr};
     const int64_t t[2] = {t0 < T ? t0 : -1, t0 + 1 < T ? t0 + 1 : -1};
-    stft_gather_pass<Nc>(z, src, t, win, n, hop, wlen, lpad, lane);
-    stft_fft_rest<Nc>(z, tw, lane);
+    gather_pass<Nc, 2>(z, [&](int s, int64_t P) { return src[s][reflect_index(n, Nc, P)]; }, t, win, hop, wlen, lpad,
+                       lane);
+    fft_rest<Nc, 2>(z, tw, lane);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         if (t[s] < 0) continue;

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from .._stft_tables import device_cached, rfft_twiddles
 
 _tables = {}
 
@@ -42,24 +43,13 @@ def _stft_table_host(n_fft, win_length, window="hann_window"):
         w = _window_fn(window)(win_length, dtype=torch.float64).numpy()
     if w.shape != (win_length,):
         raise _native.NativeError(f"stft: the window has {w.size} taps, win_length is {win_length}")
-    nc = n_fft // 2
-    tw = np.exp(-2j * np.pi * np.arange(nc) / nc)
-    sp = np.exp(-2j * np.pi * np.arange(nc) / n_fft)
-    tab = np.concatenate([np.stack([tw.real, tw.imag], 1).ravel(), np.stack([sp.real, sp.imag], 1).ravel(), w])
-    return tab.astype(np.float32)
+    return np.concatenate([*rfft_twiddles(n_fft), w]).astype(np.float32)
 
 
 def stft_tables(device, n_fft, win_length, window="hann_window"):
     """The device copy of one resolution's table, built once per (device, n_fft, win_length, window name)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _native.NativeError(f"stft tables live on the ROCm device, not {device}")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (device, int(n_fft), int(win_length), window)
-    if key not in _tables:
-        _tables[key] = torch.from_numpy(_stft_table_host(n_fft, win_length, window)).to(device)
-    return _tables[key]
+    return device_cached(_tables, device, (int(n_fft), int(win_length), window),
+                         lambda: _stft_table_host(n_fft, win_length, window), "stft tables")
 
 
 def _signal(t, name):

@@ -11,6 +11,7 @@ import scipy.fft
 import scipy.signal
 
 from . import mel_reference as mr
+from . import stft_reference as sr
 
 N_FFT, HOP, WIN = mr.N_FFT, mr.HOP, mr.WIN
 N_FREQ = 1 + N_FFT // 2
@@ -35,12 +36,7 @@ def inv_preemphasis(y, dtype=np.float64):
 def stft(y, dtype=np.float64):
     """librosa.stft(y, 2048, 240, 1200): centred, 'reflect' padding by 1024, periodic Hann of 1200 taps centred
     in 2048.  Complex [1025, 1 + len(y) // 240]."""
-    y = np.asarray(y, dtype=dtype)
-    padded = np.pad(y, N_FFT // 2, mode="reflect")
-    T = 1 + len(y) // HOP
-    idx = np.arange(T)[:, None] * HOP + np.arange(N_FFT)[None, :]
-    frames = padded[idx] * mr.hann_window().astype(dtype)[None, :]
-    return scipy.fft.rfft(frames, axis=1).T.astype(_cdtype(dtype))
+    return sr.stft(y, N_FFT, HOP, WIN, dtype=dtype).T.astype(_cdtype(dtype))
 
 
 def window_sumsquare(T, dtype=np.float64):

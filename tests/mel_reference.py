@@ -3,6 +3,8 @@ hparams.py:4-15, librosa < 0.10 semantics): the test oracle of fastvocoder_amd.a
 Deliberately independent of fastvocoder_amd (no import of it)."""
 import numpy as np
 
+from . import stft_reference as sr
+
 SR, N_FFT, HOP, WIN, N_MELS, FMIN = 24000, 2048, 240, 1200, 80, 40.0
 PREEMPHASIS, MIN_LEVEL_DB, REF_LEVEL_DB = 0.97, -100.0, 20.0
 
@@ -39,11 +41,7 @@ def mel_basis(sr=SR, n_fft=N_FFT, n_mels=N_MELS, fmin=FMIN, fmax=None):
 
 def hann_window():
     """Periodic Hann of WIN taps (scipy.signal.get_window('hann', WIN, fftbins=True)), centred in N_FFT."""
-    w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(WIN) / WIN)
-    out = np.zeros(N_FFT)
-    lpad = (N_FFT - WIN) // 2
-    out[lpad:lpad + WIN] = w
-    return out
+    return sr.padded_window(N_FFT, WIN)
 
 
 def stft_magnitude(y):
@@ -52,11 +50,7 @@ def stft_magnitude(y):
     p = np.empty_like(y)
     p[0] = y[0]
     p[1:] = y[1:] - PREEMPHASIS * y[:-1]                   # lfilter([1, -0.97], [1], y)
-    padded = np.pad(p, N_FFT // 2, mode="reflect")
-    T = 1 + len(y) // HOP
-    idx = np.arange(T)[:, None] * HOP + np.arange(N_FFT)[None, :]
-    frames = padded[idx] * hann_window()[None, :]
-    return np.abs(np.fft.rfft(frames, axis=1)).T
+    return np.abs(sr.stft(p, N_FFT, HOP, WIN)).T
 
 
 def melspectrogram(y):

@@ -3,42 +3,14 @@ model/loss/loss.py): the test oracle of fastvocoder_amd.loss.  Deliberately inde
 (no import of it)."""
 import numpy as np
 
+from .stft_reference import padded_window, stft  # noqa: F401  (test_stft_loss_host reads padded_window from here)
+
 RESOLUTIONS = ((2048, 240, 1200), (1024, 120, 600), (512, 50, 240))   # (n_fft, hop, win_length)
-
-
-def hann(win_length):
-    """torch.hann_window(win_length), periodic: 0.5 - 0.5 cos(2 pi i / win_length); one tap is [1] in torch."""
-    if win_length == 1:
-        return np.ones(1)
-    return 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)
-
-
-def padded_window(n_fft, win_length, window=None):
-    """The win_length window centred in n_fft with zeros around it (left offset (n_fft - win_length) // 2)."""
-    w = hann(win_length) if window is None else np.asarray(window, dtype=np.float64)
-    out = np.zeros(n_fft)
-    lpad = (n_fft - win_length) // 2
-    out[lpad:lpad + win_length] = w
-    return out
-
-
-def reflect_pad(x, p):
-    """numpy 'reflect' (no edge repeat) by p on both sides of the last axis; needs p < x.shape[-1]."""
-    n = x.shape[-1]
-    assert p < n, (p, n)
-    idx = np.concatenate([np.arange(p, 0, -1), np.arange(n), n - 2 - np.arange(p)])
-    return x[..., idx]
 
 
 def stft_magnitude(x, n_fft, hop, win_length, window=None):
     """sqrt(max(|torch.stft(x, n_fft, hop, win_length, window)|^2, 1e-7)): (B, 1 + n // hop, n_fft // 2 + 1)."""
-    x = np.atleast_2d(np.asarray(x, dtype=np.float64))
-    n = x.shape[-1]
-    padded = reflect_pad(x, n_fft // 2)
-    T = 1 + n // hop
-    idx = np.arange(T)[:, None] * hop + np.arange(n_fft)[None, :]
-    frames = padded[:, idx] * padded_window(n_fft, win_length, window)[None, None, :]
-    spec = np.fft.rfft(frames, axis=-1)
+    spec = stft(np.atleast_2d(np.asarray(x, dtype=np.float64)), n_fft, hop, win_length, window)
     return np.sqrt(np.maximum(spec.real ** 2 + spec.imag ** 2, 1e-7))
 
 

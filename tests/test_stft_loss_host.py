@@ -76,6 +76,18 @@ def test_tables_hold_the_window_and_exact_twiddles():
     assert np.array_equal(stft_loss._stft_table_host(512, 240, w)[1024:], w.numpy())
 
 
+def test_mel_griffin_lim_and_stft_tables_share_their_twiddles_bit_for_bit():
+    """The three n_fft = 2048 tables come from one host helper: the same bits in each."""
+    from fastvocoder_amd import audio
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)  # noqa: E731
+    mel, gl, st = audio._mel_table_host(), audio._gl_table_host(), stft_loss._stft_table_host(2048, 1200)
+    t0, s0 = audio._MEL_TAB_TWIDDLE, audio._MEL_TAB_SPLIT
+    for tab in (mel, gl):
+        assert np.array_equal(bits(tab[t0:t0 + 2048]), bits(st[:2048]))          # FFT twiddles
+        assert np.array_equal(bits(tab[s0:s0 + 2048]), bits(st[2048:4096]))      # split twiddles
+    assert np.array_equal(bits(mel[:1200]), bits(gl[:1200]))                     # window
+
+
 def test_table_layout_matches_the_header():
     header = open(os.path.join(cases.ROOT, "include", "fastvocoder_hip.h")).read()
     defs = dict(re.findall(r"#define (FV_STFT_\w+(?:\(n_fft\))?) (.+)", header))
