@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "griffin_lim.hip", "stft_loss.hip", "disc.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -31,7 +31,7 @@ PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outp
 POST_NONE, POST_TANH, POST_RELU = 0, 1, 2
 SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0, MAX_SLOTS = -1, 0, 1, 2, 32
 SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = 28, 29, 30    # caller-provided tensors of Plan.run(aux=..., out2=...)
-ABI_VERSION = 17
+ABI_VERSION = 18
 PAIR_F32, PAIR_SPLIT_F16 = 0, 1   # arithmetic of the fused ResBlock-pair kernels (fastvocoder_hip.h)
 
 
@@ -241,6 +241,11 @@ def lib():
     L.fv_stft_distance.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
                                    ctypes.POINTER(i), vp, vp, ctypes.c_size_t, vp]
     L.fv_stft_magnitude_bins.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
+    L.fv_stft_distance_grad_workspace_bytes.argtypes = [i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
+                                                        ctypes.POINTER(i)]
+    L.fv_stft_distance_grad_workspace_bytes.restype = i64
+    L.fv_stft_distance_grad.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
+                                        ctypes.POINTER(i), vp, vp, vp, ctypes.c_size_t, vp]
     L.fv_grouped_conv1d.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
     L.fv_avg_pool1d.argtypes = [vp, vp, i, i64, i, i, i, vp]
     L.fv_disc_score_workspace_bytes.argtypes = [i, i, ctypes.POINTER(i64)]
@@ -1044,6 +1049,36 @@ def stft_distance(x, y, tables, n_ffts, hops, win_lengths):
         check(lib().fv_stft_distance(_ptr(x, "x"), _ptr(y, "y"), tab_a, B, n, R, nf_a, hop_a, wl_a, out.data_ptr(),
                                      ws.data_ptr(), ws.numel() * 8, stream))
     return out
+
+
+def stft_distance_grad(x, y, tables, n_ffts, hops, win_lengths, coef):
+    """x, y [B,n] fp32 device, coef [R,B,2] fp32 (dL/dS_diff, dL/dS_log per resolution and row) -> dL/dx [B,n] fp32
+    (fv_stft_distance_grad: two launches on the current stream, the frames workspace from torch's allocator)."""
+    if x.dim() != 2 or x.shape != y.shape:
+        raise NativeError(f"stft_distance_grad: x and y must both be [B, n], got {tuple(x.shape)} and "
+                          f"{tuple(y.shape)}")
+    B, n = x.shape
+    R = len(tables)
+    if not (len(n_ffts) == len(hops) == len(win_lengths) == R):
+        raise NativeError("stft_distance_grad: one table, n_fft, hop and win_length per resolution")
+    if tuple(coef.shape) != (R, B, 2):
+        raise NativeError(f"stft_distance_grad: coef must be [R, B, 2] = {(R, B, 2)}, got {tuple(coef.shape)}")
+    for t, nf, wl in zip(tables, n_ffts, win_lengths):
+        if t.numel() != stft_table_floats(nf, wl):
+            raise NativeError(f"stft_distance_grad: a table holds {t.numel()} floats, the library reads "
+                              f"{stft_table_floats(nf, wl)}")
+    ia = ctypes.c_int * R
+    nf_a, hop_a, wl_a = ia(*map(int, n_ffts)), ia(*map(int, hops)), ia(*map(int, win_lengths))
+    need = lib().fv_stft_distance_grad_workspace_bytes(B, n, R, nf_a, hop_a, wl_a)
+    if need < 0:
+        check(int(need))
+    gx = torch.empty((B, n), dtype=torch.float32, device=x.device)
+    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.float32, device=x.device)
+    with _on(x, y, coef, gx, ws, *tables) as stream:
+        tab_a = (ctypes.c_void_p * R)(*[_ptr(t, "table") for t in tables])
+        check(lib().fv_stft_distance_grad(_ptr(x, "x"), _ptr(y, "y"), tab_a, B, n, R, nf_a, hop_a, wl_a,
+                                          _ptr(coef, "coef"), _ptr(gx), ws.data_ptr(), ws.numel() * 4, stream))
+    return gx
 
 
 def stft_magnitude_bins(x, table, n_fft, hop, win_length):

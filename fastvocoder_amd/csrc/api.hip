@@ -669,6 +669,43 @@ int fv_stft_distance(const float* x, const float* y, const float* const* tables,
                                 static_cast<double*>(workspace), (hipStream_t)stream);
 }
 
+static int64_t stft_grad_check(int B, int64_t n, int R, const int* n_fft, const int* hop, const int* win) {
+    if (R < 1 || R > FV_STFT_MAX_RES || !n_fft || !hop || !win)
+        return fail(FV_ERR_INVALID_ARG, "stft_distance_grad: R=%d resolutions (1..%d) or a null parameter array", R,
+                    FV_STFT_MAX_RES);
+    if (B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "stft_distance_grad: B=%d", B);
+    int64_t chunks = 0, floats = 0;
+    for (int r = 0; r < R; ++r) {
+        if (int rc = stft_check_res("stft_distance_grad", n, n_fft[r], hop[r], win[r])) return rc;
+        chunks += stft_grad_chunks(n, hop[r]);
+        floats += (int64_t)B * (1 + n / hop[r]) * win[r];
+    }
+    if (chunks >= (int64_t)1 << 31 || (n + 255) / 256 >= (int64_t)1 << 31 || floats >= (int64_t)1 << 40)
+        return fail(FV_ERR_INVALID_ARG, "stft_distance_grad: n=%lld too long", (long long)n);
+    return floats * (int64_t)sizeof(float);
+}
+
+int64_t fv_stft_distance_grad_workspace_bytes(int B, int64_t n, int R, const int* n_fft, const int* hop,
+                                              const int* win_length) {
+    return stft_grad_check(B, n, R, n_fft, hop, win_length);
+}
+
+int fv_stft_distance_grad(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
+                          const int* n_fft, const int* hop, const int* win_length, const float* coef, float* gx,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    const int64_t need = stft_grad_check(B, n, R, n_fft, hop, win_length);
+    if (need < 0) return (int)need;
+    if (!x || !y || !tables || !coef || !gx || !workspace)
+        return fail(FV_ERR_INVALID_ARG, "stft_distance_grad: null pointer");
+    for (int r = 0; r < R; ++r)
+        if (!tables[r]) return fail(FV_ERR_INVALID_ARG, "stft_distance_grad: table %d is null", r);
+    if ((uint64_t)workspace_bytes < (uint64_t)need || ((uintptr_t)workspace & 3))
+        return fail(FV_ERR_INVALID_ARG, "stft_distance_grad: workspace of %zu bytes, needs %lld (4-byte aligned)",
+                    workspace_bytes, (long long)need);
+    return launch_stft_distance_grad(x, y, tables, B, n, R, n_fft, hop, win_length, coef, gx,
+                                     static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
 int fv_stft_magnitude_bins(const float* x, float* mag, const float* table, int B, int64_t n, int n_fft, int hop,
                            int win_length, void* stream) {
     if (int rc = stft_check_res("stft_magnitude_bins", n, n_fft, hop, win_length)) return rc;

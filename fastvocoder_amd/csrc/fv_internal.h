@@ -445,6 +445,11 @@ int launch_stft_distance(const float* x, const float* y, const float* const* tab
                          const int* nfft, const int* hop, const int* win, double* out, double* ws, hipStream_t s);
 int launch_stft_magnitude(const float* x, float* mag, const float* tab, int B, int64_t n, int nfft, int hop, int win,
                           hipStream_t s, bool bins_major = false);   // bins_major: [B, bins, T] (fv_stft_magnitude_bins)
+// gradient of the distance w.r.t. x (stft_loss_grad.hip); ws: the frames slabs, sum_r B T_r win[r] floats
+int64_t stft_grad_chunks(int64_t n, int hop);   // frame-kernel blocks per utterance and resolution
+int launch_stft_distance_grad(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
+                              const int* nfft, const int* hop, const int* win, const float* coef, float* gx,
+                              float* ws, hipStream_t s);
 // discriminator kernels (disc.hip)
 size_t grouped_conv_lds_bytes(int k, int s, int ocb);
 int launch_grouped_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout,

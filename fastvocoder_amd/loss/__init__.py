@@ -1,6 +1,8 @@
-"""The reference's STFT losses (model/loss/) as forward-only GPU evaluators: ``stft``, ``STFTLoss``,
+"""The reference's STFT losses (model/loss/) as GPU evaluators: ``stft``, ``STFTLoss``,
 ``MultiResolutionSTFTLoss`` (stft_loss.py) and ``Loss`` (loss.py).  The magnitudes and the partial sums
-come from one HIP launch per call (csrc/stft_loss.hip); there is no CPU path and no autograd.
+come from one HIP launch per call (csrc/stft_loss.hip); there is no CPU path.  They are forward-only by default;
+setting a module's ``differentiable`` attribute gives the gradient with respect to the estimate, from fused HIP
+kernels as well (csrc/stft_loss_grad.hip).  The target and the discriminator scores have no gradient.
 ``discriminator_terms`` forms the reference's adversarial / feature-map / discriminator scores from the outputs of
 fastvocoder_amd.discriminator in one fused reduction (csrc/disc.hip)."""
 from .discriminator_loss import discriminator_terms

@@ -1,9 +1,31 @@
-"""The reference's composed generator loss (model/loss/loss.py), forward only: the multi-resolution STFT loss of
-a full-band estimate, or of the sub-bands and their PQMF synthesis for the multiband generators, plus the
-Basis-MelGAN weight L1 term."""
+"""The reference's composed generator loss (model/loss/loss.py): the multi-resolution STFT loss of a full-band
+estimate, or of the sub-bands and their PQMF synthesis for the multiband generators, plus the Basis-MelGAN weight L1
+term.  Forward only by default; ``Loss.differentiable = True`` switches the gradient with respect to the estimate on
+(stft_loss.py), through the PQMF synthesis too on the multiband path."""
 import torch
 
+from .. import _native
 from .stft_loss import MultiResolutionSTFTLoss, _signal
+
+
+class _PqmfSynthesis(torch.autograd.Function):
+    """pqmf.synthesis with its adjoint.  synthesis is y[m] = S sum_k sum_t g_k[S t + taps/2 - m] x[k, t] (zero
+    stuffing by S, then the zero-padded FIR g_k), so dL/dx[k, t] = sum_m (S g_k[taps - j]) dL/dy[m] at
+    j = m - S t + taps/2: the analysis kernel (a zero-padded FIR decimated by S) with the filter S * flip(g_k)."""
+
+    @staticmethod
+    def forward(ctx, x, pqmf):
+        ctx.save_for_backward(pqmf.synthesis_filter)
+        ctx.subbands = pqmf.subbands
+        return pqmf.synthesis(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (g,) = ctx.saved_tensors
+        S = ctx.subbands
+        adjoint = (S * torch.flip(g[0], dims=(-1,))).reshape(S, 1, -1)
+        return _native.pqmf_analysis(gy.contiguous().float(), adjoint), None
 
 
 class Loss(torch.nn.Module):
@@ -11,6 +33,14 @@ class Loss(torch.nn.Module):
         super().__init__()
         self.stft_loss = MultiResolutionSTFTLoss()
         self.l1_loss = torch.nn.L1Loss()
+
+    @property
+    def differentiable(self):
+        return self.stft_loss.differentiable
+
+    @differentiable.setter
+    def differentiable(self, value):
+        self.stft_loss.differentiable = value
 
     def forward(self, est_source, wav, est_weight=None, weight=None, pqmf=None):
         """-> (stft_loss, weight_loss).  Single band: est_source, wav (B, T); stft_loss = sc + mag.
@@ -25,7 +55,10 @@ class Loss(torch.nn.Module):
             wav_full_band = _signal(wav, "wav")
             est_source_sub_band = est_source.contiguous().float()
             wav_sub_band = pqmf.analysis(wav_full_band.unsqueeze(1))
-            est_source_full_band = pqmf.synthesis(est_source_sub_band)[:, 0, :]
+            if self.differentiable and est_source_sub_band.requires_grad and torch.is_grad_enabled():
+                est_source_full_band = _PqmfSynthesis.apply(est_source_sub_band, pqmf)[:, 0, :]
+            else:
+                est_source_full_band = pqmf.synthesis(est_source_sub_band)[:, 0, :]
             est_source_sub_band = est_source_sub_band.view(-1, est_source_sub_band.size(2))
             wav_sub_band = wav_sub_band.reshape(-1, wav_sub_band.size(2))
             if est_source_sub_band.shape != wav_sub_band.shape:

@@ -1,4 +1,4 @@
-"""STFT-based distances of the reference (model/loss/stft_loss.py), forward only, on the MI355X.
+"""STFT-based distances of the reference (model/loss/stft_loss.py) on the MI355X, with an opt-in gradient.
 
 ``stft`` returns the reference's clamped magnitudes (B, #frames, #bins) from one fv_stft_magnitude launch.
 ``STFTLoss`` and ``MultiResolutionSTFTLoss`` keep the reference's names, constructor arguments and batch-level
@@ -10,8 +10,14 @@ terms are formed from them:
     mag = sum_b S_log / (B * frames * bins)                (LogSTFTMagnitudeLoss: F.l1_loss(log Y, log X))
 
 each averaged over the resolutions.  ``per_utterance`` gives the same two terms for every row on its own from the
-same sums.  The loss is inference-only: an input that requires grad while grad mode is on is refused rather than
-have its gradient dropped.
+same sums.  By default the loss is inference-only: an input that requires grad while grad mode is on is refused
+rather than have its gradient dropped.
+
+``differentiable = True`` on a module (STFTLoss, MultiResolutionSTFTLoss, or Loss in loss.py; a policy attribute,
+not a constructor argument) switches the gradient with respect to the estimate on: the sums then come from one
+autograd Function whose forward is the same fv_stft_distance call (the same bits) and whose backward hands
+dL/dS_diff and dL/dS_log per (resolution, row) to fv_stft_distance_grad, which returns dL/dx [B, n] in fp32.  Only x,
+y, the tables and the sums are kept for backward, never spectra or magnitudes.  The target has no gradient.
 """
 import numpy as np
 import torch
@@ -52,16 +58,21 @@ def stft_tables(device, n_fft, win_length, window="hann_window"):
                          lambda: _stft_table_host(n_fft, win_length, window), "stft tables")
 
 
-def _signal(t, name):
-    """A [B, n] fp32 contiguous device tensor, or a clear error."""
+def _signal(t, name, differentiable=False):
+    """A [B, n] fp32 contiguous device tensor, or a clear error.  ``differentiable``: t may require grad."""
     if not torch.is_tensor(t):
         raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
     if not t.is_cuda:
         raise _native.NativeError(f"{name} lives on {t.device}; the STFT loss runs on the ROCm device "
                                   "(there is no CPU path in fastvocoder_amd)")
-    if t.requires_grad and torch.is_grad_enabled():
+    if t.requires_grad and torch.is_grad_enabled() and not differentiable:
+        if name == "x":
+            raise RuntimeError("x requires grad: the fastvocoder_amd STFT loss is inference-only (forward, no "
+                               "autograd) unless the module's `differentiable` attribute is set; set it, call the "
+                               "loss under torch.no_grad() or pass a detached tensor")
         raise RuntimeError(f"{name} requires grad: the fastvocoder_amd STFT loss is inference-only (forward, no "
-                           "autograd); call it under torch.no_grad() or pass a detached tensor")
+                           "autograd) and has no gradient with respect to the target; call it under "
+                           "torch.no_grad() or pass a detached tensor")
     if t.dim() != 2:
         raise ValueError(f"{name} must be (B, T), got shape {tuple(t.shape)}")
     if not t.is_floating_point():
@@ -84,16 +95,41 @@ def stft(x, fft_size, hop_size, win_length, window):
                                   int(win_length))
 
 
-def _sums(x, y, resolutions):
-    """float64 [R, B, 3] partial sums of (x, y) over resolutions [(n_fft, hop, win_length, window)]."""
-    x, y = _signal(x, "x"), _signal(y, "y")
+class _DistanceSums(torch.autograd.Function):
+    """float64 [R, B, 3] sums of fv_stft_distance with the gradient of fv_stft_distance_grad with respect to x."""
+
+    @staticmethod
+    def forward(ctx, x, y, geometry, *tables):
+        sums = _native.stft_distance(x, y, list(tables), *geometry)
+        ctx.geometry = geometry
+        ctx.save_for_backward(x, y, sums, *tables)
+        return sums
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sums):
+        x, y, sums, *tables = ctx.saved_tensors
+        # S_ref does not depend on x.  A row with S_diff == 0 has X == Y in every bin, so dS_diff/dx is exactly 0
+        # there, whatever the coefficient: sqrt'(0) = inf of the spectral convergence must not make it inf * 0.
+        c_diff = torch.where(sums[:, :, 0] == 0, torch.zeros_like(grad_sums[:, :, 0]), grad_sums[:, :, 0])
+        coef = torch.stack([c_diff, grad_sums[:, :, 2]], dim=2).float().contiguous()
+        gx = _native.stft_distance_grad(x, y, tables, *ctx.geometry, coef)
+        return (gx, None, None) + (None,) * len(tables)
+
+
+def _sums(x, y, resolutions, differentiable=False):
+    """float64 [R, B, 3] partial sums of (x, y) over resolutions [(n_fft, hop, win_length, window)].
+    ``differentiable``: the sums carry the gradient with respect to x when x requires grad."""
+    x, y = _signal(x, "x", differentiable), _signal(y, "y")
     if x.shape != y.shape:
         raise ValueError(f"x and y must have the same shape, got {tuple(x.shape)} and {tuple(y.shape)}")
     if x.device != y.device:
         raise _native.NativeError(f"x and y live on different devices ({x.device}, {y.device})")
     tables = [_table_for(x, nf, wl, w) for nf, _, wl, w in resolutions]
-    return _native.stft_distance(x, y, tables, [r[0] for r in resolutions], [r[1] for r in resolutions],
-                                 [r[2] for r in resolutions])
+    geometry = ([r[0] for r in resolutions], [r[1] for r in resolutions], [r[2] for r in resolutions])
+    if differentiable and x.requires_grad and torch.is_grad_enabled():
+        return _DistanceSums.apply(x, y, geometry, *tables)
+    return _native.stft_distance(x, y, tables, *geometry)
 
 
 def _counts(resolutions, n):
@@ -133,7 +169,10 @@ class LogSTFTMagnitudeLoss(torch.nn.Module):
 
 
 class STFTLoss(torch.nn.Module):
-    """One resolution of the reference's STFT loss (stft_loss.py:83-121)."""
+    """One resolution of the reference's STFT loss (stft_loss.py:83-121).  ``differentiable`` (default False)
+    switches the gradient with respect to x on."""
+
+    differentiable = False
 
     def __init__(self, fft_size=1024, shift_size=120, win_length=600, window="hann_window"):
         super().__init__()
@@ -153,7 +192,7 @@ class STFTLoss(torch.nn.Module):
 
     def partial_sums(self, x, y):
         """float64 [1, B, 3]: S_diff, S_ref, S_log per row (include/fastvocoder_hip.h fv_stft_distance)."""
-        return _sums(x, y, [self.resolution()])
+        return _sums(x, y, [self.resolution()], self.differentiable)
 
     def forward(self, x, y):
         """x predicted, y ground truth, both (B, T) -> (sc_loss, mag_loss), 0-d fp32 device tensors."""
@@ -165,7 +204,9 @@ class STFTLoss(torch.nn.Module):
 
 
 class MultiResolutionSTFTLoss(torch.nn.Module):
-    """The reference's multi-resolution STFT loss (stft_loss.py:124-155): all resolutions in one call."""
+    """The reference's multi-resolution STFT loss (stft_loss.py:124-155): all resolutions in one call.
+    ``differentiable`` (default False) switches the gradient with respect to x on, here and in the STFTLoss
+    children."""
 
     def __init__(self, fft_sizes=[2048, 1024, 512], hop_sizes=[240, 120, 50], win_lengths=[1200, 600, 240],
                  window="hann_window"):
@@ -175,12 +216,21 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         for fs, ss, wl in zip(fft_sizes, hop_sizes, win_lengths):
             self.stft_losses += [STFTLoss(fs, ss, wl, window)]
 
+    @property
+    def differentiable(self):
+        return all(f.differentiable for f in self.stft_losses)
+
+    @differentiable.setter
+    def differentiable(self, value):
+        for f in self.stft_losses:
+            f.differentiable = bool(value)
+
     def resolutions(self):
         return [f.resolution() for f in self.stft_losses]
 
     def partial_sums(self, x, y):
         """float64 [R, B, 3]: S_diff, S_ref, S_log per resolution and row, from one fv_stft_distance call."""
-        return _sums(x, y, self.resolutions())
+        return _sums(x, y, self.resolutions(), self.differentiable)
 
     def forward(self, x, y):
         """x predicted, y ground truth, both (B, T) -> (sc_loss, mag_loss), 0-d fp32 device tensors with the

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 17   /* 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, fv_mel_to_linear, fv_inv_preemphasis) */
+#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad; 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -559,6 +559,29 @@ int64_t fv_stft_distance_workspace_bytes(int B, int64_t n, int R, const int* n_f
 int fv_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
                      const int* n_fft, const int* hop, const int* win_length, double* out, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/*
+ * The gradient of fv_stft_distance's sums with respect to the estimate x.  For a scalar L that depends on x through
+ * out[r, b, 0] = S_diff and out[r, b, 2] = S_log (S_ref depends on y alone), with the caller's coefficients
+ *   coef[r, b, 0] = dL/dS_diff,  coef[r, b, 1] = dL/dS_log        (fp32 device [R, B, 2], finite)
+ * it writes gx = dL/dx, fp32 device [B, n].  Per bin, with (re, im) the spectrum of x and X, Y the magnitudes,
+ *   G = coef0 * -2 (Y - X) + coef1 * -sign(ln Y - ln X) / X        (sign(0) = 0)
+ *   dL/d(re, im) = G (re, im) / X where re^2 + im^2 > 1e-7, else 0 (the clamp passes no gradient)
+ * then the adjoint of the windowed one-sided real FFT (n_fft * irfft of the bins with the interior bins halved, times
+ * the window), the overlap-add of the frames at `hop`, the reflect padding folded back onto the samples it was read
+ * from, and the sum over the resolutions.  x == y gives exactly 0.  The target has no gradient here.
+ * Two launches on `stream`: one wave per frame transforms frame t of x and y, forms the bins' gradient in registers,
+ * runs the inverse transform and writes the frame's win_length taps to `workspace`; then a gather sums, in a fixed
+ * order, the taps that land on each sample and writes gx once.  No atomics: identical calls return identical bits, and
+ * a row's gradient does not depend on B or on the other rows.  workspace: device memory of at least
+ * fv_stft_distance_grad_workspace_bytes(...) = 4 B sum_r T_r win_length[r] bytes (4-byte aligned).  Parameter
+ * checks and error codes as fv_stft_distance.
+ */
+int64_t fv_stft_distance_grad_workspace_bytes(int B, int64_t n, int R, const int* n_fft, const int* hop,
+                                              const int* win_length);
+int fv_stft_distance_grad(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
+                          const int* n_fft, const int* hop, const int* win_length, const float* coef, float* gx,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * fv_stft_magnitude in the discriminator's layout (model/discriminator/mfd.py:19-41 stft, which does not transpose):
