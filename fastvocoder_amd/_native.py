@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -225,6 +225,9 @@ def lib():
     L.fv_encode_16bits.argtypes = [vp, vp, vp, i, i64, f, i, vp]
     L.fv_pqmf_analysis.argtypes = [vp, vp, vp, i, i, i, i64, vp]
     L.fv_melspectrogram.argtypes = [vp, vp, vp, i, i64, i, i, i, i, i, f, vp]
+    L.fv_resample_out_len.argtypes = [i64, i, i]
+    L.fv_resample_out_len.restype = i64
+    L.fv_resample.argtypes = [vp, i, vp, vp, i, i64, i64, i, i, i, vp]
     L.fv_istft_workspace_bytes.argtypes = [i, i]
     L.fv_istft_workspace_bytes.restype = i64
     L.fv_griffin_lim_workspace_bytes.argtypes = [i, i]
@@ -895,6 +898,33 @@ def melspectrogram(x, tables, sample_rate=24000, n_fft=2048, hop=240, win_length
         check(lib().fv_melspectrogram(_ptr(x, "x"), _ptr(mel), _ptr(tables, "tables"), B, n, int(sample_rate),
                                       int(n_fft), int(hop), int(win_length), int(n_mels), float(fmin), stream))
     return mel
+
+
+PCM_F32, PCM_S16 = 0, 1          # fv_resample's x_format (fastvocoder_hip.h FV_PCM_*)
+# fv_resample's limits (FV_RESAMPLE_MAX_*): L and M, floats of the table, floats of a block's input window
+RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_TABLE_FLOATS, RESAMPLE_MAX_WINDOW = 1 << 20, 1 << 20, 16384
+
+
+def resample(x, table, L, M, half):
+    """x [B, n_in] float32 or int16 (PCM, read as s / 32768) device waveforms -> float32 [B, ceil(n_in L / M)]
+    (fv_resample, one launch on the current stream); table: the fp32 device table of audio.resample_tables for L / M,
+    (2 half + 2) L floats, tap-major."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.int16):
+        raise NativeError(f"resample: x must be a float32 or int16 [B, n] tensor, got {x.dtype} {tuple(x.shape)}")
+    if not x.is_cuda or not x.is_contiguous():
+        raise NativeError(f"resample: x must be a contiguous ROCm device tensor (on {x.device}, "
+                          f"contiguous={x.is_contiguous()}; there is no CPU path in fastvocoder_amd)")
+    if table.numel() != (2 * half + 2) * L:
+        raise NativeError(f"resample: the table holds {table.numel()} floats, L={L} half={half} reads {(2 * half + 2) * L}")
+    B, n_in = x.shape
+    n_out = lib().fv_resample_out_len(n_in, int(L), int(M))
+    if n_out < 0:
+        check(int(n_out))
+    y = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
+    with _on(x, table, y) as stream:
+        check(lib().fv_resample(x.data_ptr(), PCM_S16 if x.dtype == torch.int16 else PCM_F32, _ptr(y), _ptr(table, "table"),
+                                B, n_in, n_out, int(L), int(M), int(half), stream))
+    return y
 
 
 def gl_table_floats():

@@ -3,7 +3,7 @@
 input from a wav (load_wav / melspectrogram, data/audio.py:17-21,58-61) for copy-synthesis and
 MODE=preprocess, and the inverse direction: Griffin-Lim (inv_mel_spectrogram / inv_spectrogram,
 data/audio.py:37-47,66-95,179-190), the baseline the synthesize flow writes beside the vocoder's wav.
-The TensorFlow helpers of the reference and the resampling in ``load_wav`` stay out of scope.
+The resampling inside the reference's ``load_wav`` is ``resample`` here; its TensorFlow helpers stay out of scope.
 
 ``encode_16bits`` / ``save_wav`` take what the reference's take (a float numpy array, scaled IN
 PLACE) and, additionally, a float32 tensor on the ROCm device: then the peak reduction, scaling and
@@ -17,6 +17,11 @@ launch (csrc/mel.hip, fv_melspectrogram); there is no CPU arithmetic path.  The 
 below carry the reference's names; ``_build_mel_basis`` is the float64 restatement of
 ``librosa.filters.mel`` the kernel's filter table is built from.
 
+``resample`` is the sample-rate conversion ``librosa.load(sr=...)`` does inside the reference's ``load_wav``
+(librosa < 0.10: resampy's ``kaiser_best``, band-limited interpolation with a Kaiser-windowed sinc) as one HIP launch
+(csrc/resample.hip, fv_resample); ``load_wav(resample=True)`` and ``MODE=preprocess --resample`` run it on files
+at another rate.  ``_resample_table_host`` is the float64 statement of the filter the kernel's table is built from.
+
 ``inv_mel_spectrogram`` is the reference's chain mel -> linear magnitude (pseudo-inverse of the mel
 filters, ** power) -> Griffin-Lim (griffin_lim_iters projections) -> inverse preemphasis, all on the
 GPU (csrc/griffin_lim.hip: fv_mel_to_linear, fv_griffin_lim, fv_inv_preemphasis).  The reference draws
@@ -25,9 +30,12 @@ run can be repeated.  Device tensors hold spectra FRAMES-MAJOR ([B, T, 1025], as
 the numpy-facing helpers (``_stft``, ``_istft``, ``_mel_to_linear``, ``_griffin_lim``) take and return
 librosa's [1025, T].
 """
+import math
+
 import numpy as np
 import scipy.io.wavfile
 import scipy.signal
+import scipy.special
 import torch
 
 from . import _native
@@ -48,23 +56,35 @@ def encode_16bits(x, rescale_out=1.0):
     return x.astype(np.int16)
 
 
-def load_wav(filename, sample_rate=24000, encode=True):
+def load_wav(filename, sample_rate=24000, encode=True, resample=False, keep_on_device=False):
     """The reference's ``load_wav`` without librosa: the samples as float32 (16-bit integer wavs divided by
-    32768, as librosa returns them; float wavs as stored), multi-channel averaged to mono.  Unlike ``librosa.load`` it does not resample: a file at another rate raises ValueError.
+    32768, as librosa returns them; float wavs as stored), multi-channel averaged to mono.
+    A file at another rate raises ValueError unless ``resample=True``: then it is converted to ``sample_rate`` on
+    the GPU (``resample`` below, what ``librosa.load(sr=sample_rate)`` does in the reference) -- a mono 16-bit file goes to
+    the device as int16, stereo and float files after the host conversion to mono float32.  A file already at the
+    rate never touches the GPU.  ``keep_on_device=True`` returns a resampled waveform as the device tensor it was
+    computed into instead of copying it to the host (a file at the rate is a host array all the same).
     ``encode=True`` applies ``encode_16bits`` as the reference does."""
     sr, x = scipy.io.wavfile.read(filename)
-    if sr != sample_rate:
+    if sr != sample_rate and not resample:
         raise ValueError(f"{filename}: sample rate {sr} Hz, expected {sample_rate} Hz "
                          "(load_wav does not resample; convert the file first)")
-    if x.dtype == np.int16:
-        x = x.astype(np.float32) / 32768.0
-    elif x.dtype in (np.float32, np.float64):
-        x = x.astype(np.float32)
-    else:
+    if x.dtype != np.int16 and x.dtype not in (np.float32, np.float64):
         raise ValueError(f"{filename}: {x.dtype} samples; load_wav reads 16-bit integer or float wavs")
-    if x.ndim == 2:
-        x = x.mean(axis=1, dtype=np.float32)
-    x = np.ascontiguousarray(x, dtype=np.float32)
+    if sr != sample_rate and x.dtype == np.int16 and x.ndim == 1:
+        x = _resample(_to_device(x, "load_wav(resample=True)", np.int16), int(sr), sample_rate)
+    else:
+        if x.dtype == np.int16:
+            x = x.astype(np.float32) / 32768.0
+        else:
+            x = x.astype(np.float32)
+        if x.ndim == 2:
+            x = x.mean(axis=1, dtype=np.float32)
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if sr != sample_rate:
+            x = _resample(_to_device(x, "load_wav(resample=True)"), int(sr), sample_rate)
+    if torch.is_tensor(x) and not keep_on_device:
+        x = x.cpu().numpy()
     if encode:
         x = encode_16bits(x)
     return x
@@ -182,6 +202,92 @@ def melspectrogram(y):
         raise _native.NativeError("melspectrogram runs on the ROCm device (there is no CPU path in fastvocoder_amd)")
     x = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to("cuda")
     return melspectrogram(x)[0].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
+# sample-rate conversion (csrc/resample.hip)
+# ---------------------------------------------------------------------------
+
+# resampy's kaiser_best: zero crossings of the sinc kept on each side, cutoff as a fraction of the lower Nyquist rate, Kaiser beta
+RESAMPLE_NUM_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA = 64, 0.9475937167399596, 14.769656459379492
+_resample_tables = {}
+
+
+def _resample_geometry(orig_sr, target_sr):
+    """(L, M, scale, half) of the polyphase filter orig_sr -> target_sr; ValueError for rates that are not positive
+    integers and for a pair beyond fv_resample's limits (include/fastvocoder_hip.h): a table of (2 half + 2) L floats
+    above 2^20 (4 MiB; every pair of the usual rates 8000 ... 96000 Hz stays below 2^18) or a block's input window above
+    16384 floats of LDS (ratios beyond about 1 : 50)."""
+    for name, sr in (("orig_sr", orig_sr), ("target_sr", target_sr)):
+        if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or sr <= 0:
+            raise ValueError(f"resample: {name}={sr!r}; sample rates are positive integers")
+    g = math.gcd(int(orig_sr), int(target_sr))
+    L, M = int(target_sr) // g, int(orig_sr) // g
+    scale = min(1.0, L / M) * RESAMPLE_ROLLOFF
+    half = math.ceil(RESAMPLE_NUM_ZEROS / scale)
+    table, window = (2 * half + 2) * L, (L - 1 + 255 * M) // L + 2 * half + 2
+    if (max(L, M) > _native.RESAMPLE_MAX_FACTOR or table > _native.RESAMPLE_MAX_TABLE_FLOATS
+            or window > _native.RESAMPLE_MAX_WINDOW):
+        raise ValueError(f"resample: {orig_sr} -> {target_sr} Hz is the ratio {L}/{M}: a filter table of {table} floats "
+                         f"(at most {_native.RESAMPLE_MAX_TABLE_FLOATS}) and an input window of {window} per block (at most "
+                         f"{_native.RESAMPLE_MAX_WINDOW}); convert through a rate with a larger common divisor")
+    return L, M, scale, half
+
+
+def _resample_table_host(orig_sr, target_sr):
+    """The fp32 table fv_resample reads for orig_sr -> target_sr, built in float64 and rounded once: [2 half + 2, L]
+    (tap-major), entry [t, r] = scale h(scale (half - t + p_r / L)) with p_r = (r M) mod L, the coefficient output
+    j = r (mod L) applies to x[c - half + t];  h(u) = sinc(u) I0(beta sqrt(1 - (u / zeros)^2)) / I0(beta), |u| < zeros."""
+    L, M, scale, half = _resample_geometry(orig_sr, target_sr)
+    frac = (np.arange(L, dtype=np.int64) * M % L) / L
+    u = scale * (half - np.arange(2 * half + 2, dtype=np.float64)[:, None] + frac[None, :])
+    inside = np.abs(u) < RESAMPLE_NUM_ZEROS
+    arg = np.sqrt(np.where(inside, 1.0 - (u / RESAMPLE_NUM_ZEROS) ** 2, 0.0))
+    h = np.where(inside, np.sinc(u) * scipy.special.i0(RESAMPLE_BETA * arg) / scipy.special.i0(RESAMPLE_BETA), 0.0)
+    return np.ascontiguousarray(scale * h).astype(np.float32)
+
+
+def resample_tables(device, orig_sr, target_sr):
+    """The device copy of the filter table for orig_sr -> target_sr, built once per device and pair."""
+    return device_cached(_resample_tables, device, (int(orig_sr), int(target_sr)),
+                         lambda: _resample_table_host(orig_sr, target_sr), "resampling tables")
+
+
+def resample(y, orig_sr, target_sr):
+    """``librosa.resample(y, orig_sr, target_sr)`` of librosa < 0.10 (res_type='kaiser_best', fix=True) on the GPU, one
+    fv_resample launch: ceil(n target_sr / orig_sr) samples.
+
+    - numpy 1-D array (float32 or float64) -> numpy float32 (computed on the current ROCm device);
+    - float32 or int16 (PCM, read as s / 32768) device tensor [n] or [B, n] -> float32 device tensor of the same rank,
+      enqueued on the current stream with no host copy.
+    ``orig_sr == target_sr`` returns the samples as float32 with no launch.  The filter is resampy's kaiser_best DESIGN
+    evaluated exactly per phase (resampy interpolates in a table): the same filter, not the same bits."""
+    L, M, _, half = _resample_geometry(orig_sr, target_sr)
+    if torch.is_tensor(y):
+        if not y.is_cuda:
+            raise _native.NativeError("resample: a tensor argument must live on the ROCm device; pass a numpy array for "
+                                      "the host route")
+        if y.dtype not in (torch.float32, torch.int16) or y.dim() not in (1, 2):
+            raise _native.NativeError(f"resample: expected a float32 or int16 [n] or [B, n] tensor, got {y.dtype} "
+                                      f"{tuple(y.shape)}")
+        if y.shape[-1] == 0:
+            raise ValueError("resample: an empty waveform")
+        if L == M:
+            return y.to(torch.float32) / 32768.0 if y.dtype == torch.int16 else y
+        x = (y.reshape(1, -1) if y.dim() == 1 else y).contiguous()
+        out = _native.resample(x, resample_tables(y.device, orig_sr, target_sr), L, M, half)
+        return out[0] if y.dim() == 1 else out
+    y = np.asarray(y)
+    if y.ndim != 1 or y.dtype not in (np.float32, np.float64):
+        raise ValueError(f"resample: expected a 1-D float32 or float64 waveform, got {y.dtype} {y.shape}")
+    if y.shape[0] == 0:
+        raise ValueError("resample: an empty waveform")
+    if L == M:
+        return y.astype(np.float32)
+    return resample(_to_device(y, "resample"), orig_sr, target_sr).cpu().numpy()
+
+
+_resample = resample      # for load_wav, whose ``resample`` argument hides the function
 
 
 # ---------------------------------------------------------------------------

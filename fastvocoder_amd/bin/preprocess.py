@@ -4,20 +4,26 @@ waveform, under --save_path), the same printed ``min length of mel spectrogram i
 the same shuffled train / valid / eval index files.  The wavs are processed one after another in
 this process, each mel in one launch on the GPU (audio.melspectrogram), instead of the reference's
 pool of cpu_count() // 2 librosa workers.
+
+``--resample`` (off by default; not a flag of the reference, whose ``librosa.load`` always resamples): a wav at another
+rate than ``hparams.sample_rate`` is converted on the GPU (audio.resample) instead of being reported and left out; the
+resampled waveform stays on the device for the mel, and both come back to the host once.
 """
 import argparse
 import os
 import random
 
 import numpy as np
+import torch
 
 from .. import audio
 from .. import hparams as hp
 
 
-def preprocess(data_path_file, save_path):
+def preprocess(data_path_file, save_path, resample=False):
     """Mel and waveform files for every wav listed in ``data_path_file`` -> (audio_index, mel_index, lengths).
-    A wav that fails is reported and left out of the indices (the reference's sequential path)."""
+    A wav that fails is reported and left out of the indices (the reference's sequential path); without ``resample``
+    that includes every wav at another rate than hparams.sample_rate."""
     os.makedirs(save_path, exist_ok=True)
     audio_index, mel_index, lengths = [], [], []
     with open(data_path_file, "r") as f:
@@ -29,8 +35,13 @@ def preprocess(data_path_file, save_path):
             wav_filename = wav_filepath.split("/")[-1]
             mel_filepath = os.path.join(save_path, f"{wav_filename}.mel.npy")
             new_wav_filepath = os.path.join(save_path, f"{wav_filename}.npy")
-            y = audio.load_wav(wav_filepath, sample_rate=hp.sample_rate, encode=False)
-            mel = audio.melspectrogram(y)
+            y = audio.load_wav(wav_filepath, sample_rate=hp.sample_rate, encode=False, resample=resample,
+                               keep_on_device=resample)
+            if torch.is_tensor(y):      # resampled: the mel from the device tensor, then one copy of each to the host
+                mel = audio.melspectrogram(y)[0].cpu().numpy()
+                y = y.cpu().numpy()
+            else:
+                mel = audio.melspectrogram(y)
             np.save(mel_filepath, mel.astype(np.float64))
             np.save(new_wav_filepath, y)
             audio_index.append(new_wav_filepath)
@@ -52,14 +63,20 @@ def write_file(audio_index, mel_index, index_list, file_name, audio_index_path, 
             f.write(mel_index[index] + "\n")
 
 
-def run_preprocess(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--data_path', type=str, default=os.path.join("dataset", "ljspeech.txt"))
     parser.add_argument('--save_path', type=str, default=os.path.join("dataset", "processed"))
     parser.add_argument('--audio_index_path', type=str, default=os.path.join("dataset", "audio"))
     parser.add_argument('--mel_index_path', type=str, default=os.path.join("dataset", "mel"))
-    args = parser.parse_args(argv)
-    audio_index, mel_index, _ = preprocess(args.data_path, args.save_path)
+    parser.add_argument('--resample', action='store_true',
+                        help="convert wavs at another rate than hparams.sample_rate on the GPU instead of skipping them")
+    return parser
+
+
+def run_preprocess(argv=None):
+    args = build_parser().parse_args(argv)
+    audio_index, mel_index, _ = preprocess(args.data_path, args.save_path, resample=args.resample)
 
     os.makedirs(args.audio_index_path, exist_ok=True)
     os.makedirs(args.mel_index_path, exist_ok=True)

@@ -526,6 +526,37 @@ int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, in
 }
 
 // ---------------------------------------------------------------------------
+// resampling (resample.hip)
+// ---------------------------------------------------------------------------
+int64_t fv_resample_out_len(int64_t n_in, int L, int M) {
+    if (n_in < 0 || n_in > FV_RESAMPLE_MAX_SAMPLES || L < 1 || L > FV_RESAMPLE_MAX_FACTOR || M < 1 ||
+        M > FV_RESAMPLE_MAX_FACTOR)
+        return fail(FV_ERR_INVALID_ARG, "resample: n_in=%lld L=%d M=%d", (long long)n_in, L, M);
+    return (n_in * L + M - 1) / M;
+}
+
+int fv_resample(const void* x, int x_format, float* y, const float* table, int B, int64_t n_in, int64_t n_out, int L,
+                int M, int half, void* stream) {
+    if (x_format != FV_PCM_F32 && x_format != FV_PCM_S16)
+        return fail(FV_ERR_INVALID_ARG, "resample: x_format=%d (FV_PCM_F32 or FV_PCM_S16)", x_format);
+    if (!x || !y || !table || B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "resample: null tensor or B=%d", B);
+    if (n_in < 1) return fail(FV_ERR_INVALID_ARG, "resample: n_in=%lld", (long long)n_in);
+    const int64_t want = fv_resample_out_len(n_in, L, M);
+    if (want < 0) return (int)want;
+    if (n_out != want)
+        return fail(FV_ERR_INVALID_ARG, "resample: n_out=%lld, %lld samples at L/M = %d/%d give %lld", (long long)n_out,
+                    (long long)n_in, L, M, (long long)want);
+    if (half < 1 || half > FV_RESAMPLE_MAX_WINDOW || (2 * (int64_t)half + 2) * L > FV_RESAMPLE_MAX_TABLE_FLOATS ||
+        resample_window(L, M, half) > FV_RESAMPLE_MAX_WINDOW)
+        return fail(FV_ERR_UNSUPPORTED,
+                    "resample: L/M = %d/%d with half=%d needs a table of %lld floats (at most %d) and a window of %lld "
+                    "(at most %d)", L, M, half, (long long)((2 * (int64_t)half + 2) * L), FV_RESAMPLE_MAX_TABLE_FLOATS,
+                    (long long)resample_window(L, M, half), FV_RESAMPLE_MAX_WINDOW);
+    if ((n_out + 255) / 256 > 0x7fffffffLL) return fail(FV_ERR_INVALID_ARG, "resample: n_out=%lld", (long long)n_out);
+    return launch_resample(x, x_format, y, table, B, n_in, n_out, L, M, half, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
 // Griffin-Lim (griffin_lim.hip)
 // ---------------------------------------------------------------------------
 static int gl_check_geometry(const char* who, int n_fft, int hop, int win_length) {

@@ -440,6 +440,13 @@ int launch_griffin_lim(const float* S, const float* phase0, float* y, const floa
                        float* frames, hipStream_t s);
 int launch_mel_to_linear(const float* mel, const float* invb, float* S, int B, int T, float power, hipStream_t s);
 int launch_inv_preemphasis(const float* y, float* out, int B, int64_t n, float coef, hipStream_t s);
+// resampling (resample.hip): floats of input a block of 256 outputs stages in LDS -- the span of their first taps,
+// floor((L - 1 + 255 M) / L) + 1, plus the other 2 half + 1 taps of the last one (FV_RESAMPLE_MAX_WINDOW bounds it)
+static inline int64_t resample_window(int L, int M, int half) {
+    return ((int64_t)L - 1 + 255 * (int64_t)M) / L + 2 * (int64_t)half + 2;
+}
+int launch_resample(const void* x, int format, float* y, const float* tab, int B, int64_t n_in, int64_t n_out, int L,
+                    int M, int half, hipStream_t s);
 int64_t stft_chunks(int64_t n, int hop);   // distance-kernel blocks per utterance and resolution (stft_loss.hip)
 int launch_stft_distance(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
                          const int* nfft, const int* hop, const int* win, double* out, double* ws, hipStream_t s);

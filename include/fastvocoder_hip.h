@@ -462,6 +462,34 @@ int fv_melspectrogram(const float* x, float* mel, const float* tables, int B, in
                       int hop, int win_length, int n_mels, float fmin, void* stream);
 
 /*
+ * (added within v18: an additive entry, the version stays)
+ * Sample-rate conversion by a rational ratio: the resampling inside the reference's load_wav (data/audio.py:17-18,
+ * librosa.load(sr=...), with librosa < 0.10 resampy's kaiser_best: band-limited interpolation with a Kaiser-windowed
+ * sinc) as a polyphase FIR, per row of x [B, n_in].  With g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g:
+ *   n_out = ceil(n_in L / M)                                    (fv_resample_out_len; librosa.resample(fix=True))
+ *   c, p = divmod(j M, L);   y[b, j] = sum_{t < 2 half + 2} table[t L + (j mod L)] * x[b, c - half + t]
+ * with x = 0 outside [0, n_in).  The filter is the caller's: `table` holds, TAP-MAJOR, row r = j mod L of the
+ * 2 half + 2 coefficients  scale h(scale (half - t + p_r / L)),  p_r = (r M) mod L  (fastvocoder_amd/audio.py
+ * resample_tables builds it in float64 and rounds once; scale, half and h are its business, the kernel applies them).
+ * x: device [B, n_in], fp32 (FV_PCM_F32) or 16-bit PCM (FV_PCM_S16, converted on load as s / 32768, which is exact:
+ * a 16-bit file crosses PCIe at 2 bytes per sample); y: fp32 device [B, n_out]; table: fp32 device.
+ * One launch; an output is one thread's fp32 FMA chain over its taps in increasing t, so its bits depend only on the
+ * 2 half + 2 inputs around it and on j mod L -- not on the row, the batch size or the grid.  j M and c are 64-bit.
+ * Limits: 1 <= L, M <= FV_RESAMPLE_MAX_FACTOR, 1 <= n_in <= FV_RESAMPLE_MAX_SAMPLES, B in 1..65535 (FV_ERR_INVALID_ARG,
+ * as a wrong n_out); a table above FV_RESAMPLE_MAX_TABLE_FLOATS floats or a block's input window
+ * floor((L - 1 + 255 M) / L) + 2 half + 2 above FV_RESAMPLE_MAX_WINDOW floats of LDS returns FV_ERR_UNSUPPORTED.
+ */
+#define FV_PCM_F32 0
+#define FV_PCM_S16 1
+#define FV_RESAMPLE_MAX_FACTOR (1 << 20)
+#define FV_RESAMPLE_MAX_SAMPLES ((int64_t)1 << 40)
+#define FV_RESAMPLE_MAX_TABLE_FLOATS (1 << 20)
+#define FV_RESAMPLE_MAX_WINDOW 16384
+int64_t fv_resample_out_len(int64_t n_in, int L, int M);
+int fv_resample(const void* x, int x_format, float* y, const float* table, int B, int64_t n_in, int64_t n_out, int L,
+                int M, int half, void* stream);
+
+/*
  * Griffin-Lim: the reference's inv_mel_spectrogram (data/audio.py:66-95,179-190 with hparams.py as shipped, librosa < 0.10
  * semantics), the inverse direction of fv_melspectrogram.  Geometry n_fft 2048 / hop 240 / win_length 1200 (a periodic
  * Hann window centred in the frame) only; anything else returns FV_ERR_UNSUPPORTED.  Spectra and magnitudes are
