@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "mpd.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -255,6 +255,11 @@ def lib():
     L.fv_disc_score_workspace_bytes.restype = i64
     L.fv_disc_score_sums.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i, i, vp, vp,
                                      ctypes.c_size_t, vp]
+    L.fv_mpd_conv_first.argtypes = [vp, vp, vp, vp, i, i64, i, f, vp]
+    L.fv_packed_period_conv_floats.argtypes = [i, i]
+    L.fv_packed_period_conv_floats.restype = i64
+    L.fv_pack_period_conv.argtypes = [vp, vp, i, i, vp]
+    L.fv_period_conv.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, vp]
     L.fv_fold_batchnorm_conv.argtypes = [vp, vp, vp, vp, vp, vp, f, vp, vp, i, i, i, vp]
     L.fv_packed_upsample_conv1d_floats.argtypes = [i, i, i, i, i]
     L.fv_packed_upsample_conv1d_floats.restype = i64
@@ -1156,9 +1161,60 @@ def avg_pool1d(x, k, stride, pad):
     return out
 
 
+def mpd_reflect_tail(T, period):
+    """Samples DiscriminatorP's reflect pad appends to T (mpd.py:150-153)."""
+    return period - T % period if T % period else 0
+
+
+def mpd_conv_first(x, w, bias, period, slope=0.1):
+    """x [B,1,T] waveform, w [32,5] folded weight, bias [32] or None -> lrelu(conv, slope) [B,32,H',period]: the
+    reflect tail pad, the [H, period] view and DiscriminatorP's first conv (fv_mpd_conv_first, one launch)."""
+    if x.dim() != 3 or x.shape[1] != 1 or tuple(w.shape) != (32, 5):
+        raise NativeError(f"mpd_conv_first: x [B,1,T] and w [32,5], got {tuple(x.shape)} and {tuple(w.shape)}")
+    B, _, T = x.shape
+    H = (T + mpd_reflect_tail(T, period)) // period if period > 0 else 0
+    out = torch.empty((B, 32, max((H - 1) // 3 + 1, 0), max(period, 0)), dtype=torch.float32, device=x.device)
+    with _on(x, w, bias, out) as stream:
+        check(lib().fv_mpd_conv_first(_ptr(x, "x"), _ptr(w, "w"), _ptr(bias, "bias", True), _ptr(out, "out"), B, T,
+                                      int(period), float(slope), stream))
+    return out
+
+
+def pack_period_conv(w):
+    """Folded weight [Cout,Cin,5] of a strided period conv -> the image fv_period_conv reads (flat tensor)."""
+    w = w.detach().contiguous().float()
+    if w.dim() != 3 or w.shape[2] != 5:
+        raise NativeError(f"pack_period_conv: w must be [Cout, Cin, 5], got {tuple(w.shape)}")
+    cout, cin, _ = w.shape
+    out = torch.empty(max(lib().fv_packed_period_conv_floats(cout, cin), 1), dtype=torch.float32, device=w.device)
+    with _on(w) as stream:
+        check(lib().fv_pack_period_conv(_ptr(w, "w"), _ptr(out), cout, cin, stream))
+    return out
+
+
+def period_conv(x, packed, bias, cout, slope=0.1):
+    """x [B,Cin,H,p] -> lrelu(Conv2d(Cin, cout, (5,1), (3,1), padding (2,0)), slope) [B,cout,(H-1)//3+1,p]
+    (fv_period_conv, one launch on the fp32 matrix cores); packed = pack_period_conv(w)."""
+    if x.dim() != 4:
+        raise NativeError(f"period_conv: x must be [B,Cin,H,p], got {tuple(x.shape)}")
+    B, cin, H, p = x.shape
+    out = torch.empty((B, cout, (H - 1) // 3 + 1 if H > 0 else 0, p), dtype=torch.float32, device=x.device)
+    with _on(x, packed, bias, out) as stream:
+        check(lib().fv_period_conv(_ptr(x, "x"), _ptr(packed, "packed"), _ptr(bias, "bias", True), _ptr(out, "out"),
+                                   B, cin, int(cout), H, p, float(slope), stream))
+    return out
+
+
+DISC_MAX_MAPS = 48      # FV_DISC_MAX_MAPS: maps per fv_disc_score_sums call
+
+
 def disc_score_sums(es, rs):
     """Lists of M map pairs, each e_m and r_m fp32 device [B, ...] of one shape -> float64 [M, B, 4]:
-    sum|e-r|, sum(e-1)^2, sum e^2, sum(r-1)^2 per map and row (fv_disc_score_sums: two launches)."""
+    sum|e-r|, sum(e-1)^2, sum e^2, sum(r-1)^2 per map and row (fv_disc_score_sums: two launches per DISC_MAX_MAPS
+    maps; a map's sums do not depend on which other maps share its call)."""
+    if len(es) == len(rs) and len(es) > DISC_MAX_MAPS:
+        return torch.cat([disc_score_sums(es[i:i + DISC_MAX_MAPS], rs[i:i + DISC_MAX_MAPS])
+                          for i in range(0, len(es), DISC_MAX_MAPS)])
     M = len(es)
     if M != len(rs) or M == 0:
         raise NativeError(f"disc_score_sums: {len(es)} estimate maps and {len(rs)} real maps")

@@ -10,8 +10,9 @@ resolutions), one utterance at a time, on the GPU.  Output, one line per utteran
 (numbers printed with ``%.8e``; sc and mag are each averaged over the three resolutions).
 
 With ``--discriminator`` the checkpoint's ``'discriminator'`` entry (a training checkpoint of the reference holds it
-beside ``'model'``, bin/train.py:235-247) is loaded into fastvocoder_amd.discriminator.Discriminator, and every
-utterance is also scored with the adversarial / feature-map / discriminator terms of the reference's training loop
+beside ``'model'``, bin/train.py:235-247) is loaded into fastvocoder_amd.discriminator.Discriminator (with
+``use_mpd=True`` when the entry carries ``mpd.`` keys: a checkpoint trained with the reference's multi-period
+discriminator enabled, discriminator.py:11, 16), and every utterance is also scored with the adversarial / feature-map / discriminator terms of the reference's training loop
 (loss.discriminator_terms), estimate against target:
 
     eval-d <i> adv=<adversarial> fm=<feature map> real=<real> fake=<fake> d=<real + fake>
@@ -80,6 +81,11 @@ def score_griffin_lim(loss, wav, mel, device, seed):
     return n, sc, mag
 
 
+def discriminator_uses_mpd(state_dict):
+    """Does a checkpoint's 'discriminator' entry hold the multi-period discriminator (``mpd.`` keys)?"""
+    return any(k.startswith("mpd.") for k in state_dict)
+
+
 def load_discriminator(synthesizer):
     """The checkpoint's discriminator on the synthesizer's device, or a clear exit when the checkpoint has none."""
     from ..discriminator import Discriminator
@@ -87,7 +93,7 @@ def load_discriminator(synthesizer):
     if sd is None:
         raise SystemExit("evaluation: --discriminator needs a checkpoint with a 'discriminator' entry (a training "
                          "checkpoint of the reference); this one has none")
-    d = Discriminator().to(synthesizer.device)
+    d = Discriminator(use_mpd=discriminator_uses_mpd(sd)).to(synthesizer.device)
     d.load_state_dict(sd)
     return d.eval()
 

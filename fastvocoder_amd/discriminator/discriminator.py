@@ -1,22 +1,30 @@
-"""The reference's Discriminator (model/discriminator/discriminator.py): MSD + MFD; the MPD stays out, as there."""
+"""The reference's Discriminator (model/discriminator/discriminator.py): MSD + MFD, and with ``use_mpd=True`` the
+MPD the reference keeps one commented line away (discriminator.py:11, 16), registered first as there."""
 from ..generator.engine import NativeModule
 from .common import check_length, device_input
 from .mfd import MultiResolutionSTFTDiscriminator
+from .mpd import MultiPeriodDiscriminator
 from .msd import MelGANMultiScaleDiscriminator
 
 
 class Discriminator(NativeModule):
-    def __init__(self):
+    def __init__(self, use_mpd=False):
         super().__init__()
+        self.use_mpd = bool(use_mpd)
+        if self.use_mpd:
+            self.mpd = MultiPeriodDiscriminator()
         self.msd = MelGANMultiScaleDiscriminator()
         self.mfd = MultiResolutionSTFTDiscriminator()
 
     def min_length(self):
-        """Shortest input both discriminators accept (1680 samples with the default resolutions)."""
-        return max(self.msd.min_length(), self.mfd.min_length())
+        """Shortest input every discriminator accepts (1680 samples with the default resolutions)."""
+        need = max(self.msd.min_length(), self.mfd.min_length())
+        return max(need, self.mpd.min_length()) if self.use_mpd else need
 
     def forward(self, x):
-        """x (B, 1, T) -> msd(x) + mfd(x): 6 lists of feature maps, the last map of each the score."""
+        """x (B, 1, T) -> msd(x) + mfd(x): 6 lists of feature maps, the last map of each the score; with ``use_mpd``
+        mpd(x) + msd(x) + mfd(x): 11 lists, 71 maps."""
         x = device_input(x, "x", 3)
         check_length(self, x.shape[-1])
-        return self.msd(x) + self.mfd(x)
+        outs = self.msd(x) + self.mfd(x)
+        return self.mpd(x) + outs if self.use_mpd else outs

@@ -1,0 +1,125 @@
+"""HiFi-GAN's multi-period discriminator (reference: model/discriminator/mpd.py:131-164, 288-304) on the MI355X.
+
+``DiscriminatorP(p)`` reflect-pads the waveform to a multiple of p, views it as [B, 1, H, p] and runs six weight-normed
+Conv2d((k, 1)) layers along H.  Here the first layer reads the raw waveform (fv_mpd_conv_first: pad and view are
+address arithmetic), the three strided 32 -> 128 -> 512 -> 1024 layers run on the fp32 matrix cores
+(fv_period_conv, csrc/mpd.hip), and the two stride-1 layers are dilated conv1ds on the flattened axis n = h p + c
+(fv_conv1d_fused with dilation p and zero padding 2 p / p).  The convs live in the reference's containers
+(``convs.<j>``, ``conv_post``) so that ``state_dict`` keys and 4-D shapes match; their ``forward`` is never called."""
+import torch
+from torch.nn.utils import weight_norm
+
+from .. import _native
+from ..generator.engine import PAD_ZERO, NativeModule, effective_weight
+from .common import check_length, device_input, first_length
+
+LRELU_SLOPE = 0.1
+PERIODS = (2, 3, 5, 7, 11)
+
+
+def period_heights(T, period, stride=3, layers=4):
+    """(n_pad, [H, H_1 .. H_layers]): the reflect tail of T samples and the map heights, H' = (H - 1) // stride + 1."""
+    n_pad = _native.mpd_reflect_tail(T, period)
+    hs = [(T + n_pad) // period]
+    for _ in range(layers):
+        hs.append((hs[-1] - 1) // stride + 1)
+    return n_pad, hs
+
+
+class DiscriminatorP(NativeModule):
+    """mpd.py:131-164."""
+
+    def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
+        super().__init__()
+        if use_spectral_norm:
+            raise NotImplementedError("DiscriminatorP(use_spectral_norm=True): the period convs fold weight norm only "
+                                      "(the reference's MultiPeriodDiscriminator never asks for spectral norm)")
+        if kernel_size != 5 or stride != 3:
+            raise NotImplementedError(f"DiscriminatorP(kernel_size={kernel_size}, stride={stride}): the period conv "
+                                      "kernel has 5 taps and stride 3, the reference's only configuration")
+        if period not in PERIODS:
+            raise NotImplementedError(f"DiscriminatorP(period={period}): the period conv kernel is built for periods "
+                                      f"{PERIODS}")
+        self.period = period
+        conv = torch.nn.Conv2d
+        self.convs = torch.nn.ModuleList([
+            weight_norm(conv(1, 32, (kernel_size, 1), (stride, 1), padding=(2, 0))),
+            weight_norm(conv(32, 128, (kernel_size, 1), (stride, 1), padding=(2, 0))),
+            weight_norm(conv(128, 512, (kernel_size, 1), (stride, 1), padding=(2, 0))),
+            weight_norm(conv(512, 1024, (kernel_size, 1), (stride, 1), padding=(2, 0))),
+            weight_norm(conv(1024, 1024, (kernel_size, 1), 1, padding=(2, 0))),
+        ])
+        self.conv_post = weight_norm(conv(1024, 1, (3, 1), 1, padding=(1, 0)))
+
+    def min_length(self):
+        """Shortest T whose reflect tail (period - T % period samples) is shorter than T, as torch's pad demands."""
+        p = self.period
+        return first_length(lambda n: all(_native.mpd_reflect_tail(t, p) < t for t in range(n, max(n, p) + 1)))
+
+    def _native_layers(self):
+        """[(weight, bias)]: layer 0 folded [32, 5]; layers 1-3 packed for fv_period_conv; layers 4-5 packed for
+        fv_conv1d_fused.  Cached against the module state."""
+        state = self._fv_state()
+        hit = self._fv_plans.get("layers")
+        if hit is not None and hit[0] == state:
+            return hit[1]
+        self._device()
+        with torch.no_grad():
+            layers = []
+            for j, conv in enumerate(list(self.convs) + [self.conv_post]):
+                w = effective_weight(conv)
+                w = w.reshape(w.shape[0], w.shape[1], w.shape[2])
+                b = None if conv.bias is None else conv.bias.detach().contiguous().float()
+                if j == 0:
+                    w = w.reshape(32, 5).contiguous()
+                elif j < 4:
+                    w = _native.pack_period_conv(w)
+                else:
+                    w = _native.pack_conv1d(w)
+                layers.append((w, b))
+        self._fv_plans["layers"] = (self._fv_state(), layers)
+        return layers
+
+    def forward(self, x):
+        """x (B, 1, T) -> (score [B, H_6 p], the six feature maps [B, C, H_l, p])."""
+        x = device_input(x, "x", 3)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        p = self.period
+        layers = self._native_layers()
+        x = _native.mpd_conv_first(x, layers[0][0], layers[0][1], p, LRELU_SLOPE)
+        fmap = [x]
+        for j in (1, 2, 3):
+            x = _native.period_conv(x, layers[j][0], layers[j][1], self.convs[j].out_channels, LRELU_SLOPE)
+            fmap.append(x)
+        B, C, H, _ = x.shape
+        x = _native.conv1d_fused(x.view(B, C, H * p), layers[4][0], layers[4][1], 1024, 5, dil=p, pad=2 * p,
+                                 pad_mode=PAD_ZERO, act_slope=LRELU_SLOPE)
+        fmap.append(x.view(B, 1024, H, p))
+        x = _native.conv1d_fused(x, layers[5][0], layers[5][1], 1, 3, dil=p, pad=p, pad_mode=PAD_ZERO)
+        fmap.append(x.view(B, 1, H, p))
+        return x.view(B, H * p), fmap
+
+
+class MultiPeriodDiscriminator(NativeModule):
+    """mpd.py:288-304, the single-input form: one list per period, its six maps followed by the score [B, 1, H p]."""
+
+    def __init__(self):
+        super().__init__()
+        self.discriminators = torch.nn.ModuleList([DiscriminatorP(p) for p in PERIODS])
+
+    def min_length(self):
+        """Shortest input every period's reflect pad accepts."""
+        return max(d.min_length() for d in self.discriminators)
+
+    def forward(self, x):
+        x = device_input(x, "x", 3)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        outs = []
+        for d in self.discriminators:
+            score, fmap = d(x)
+            outs.append(fmap + [score.unsqueeze(1)])
+        return outs

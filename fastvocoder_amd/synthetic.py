@@ -187,6 +187,22 @@ STFT_KW = dict(fft_size=1024, shift_size=120, win_length=600, kernel_sizes=[5, 3
 MFD_RESOLUTIONS = ([2048, 1024, 512], [240, 120, 50], [1200, 600, 240])
 
 
+# The MPD (mpd.py:131-164).  Per-layer factors on DISCRIMINATOR_GAIN, so that every map's standard deviation stays
+# near the input's: with w ~ U(-g / sqrt(fan), g / sqrt(fan)) a layer multiplies the second moment by g^2 / 3, and a
+# leaky ReLU(0.1) about halves it.  The first layer sees the zero rows of the padding and the raw (zero-mean) signal,
+# the last has no activation (tests/golden/make_mpd_golden.py prints every map's std; test_mpd_host.py checks them).
+MPD_PERIODS = (2, 3, 5, 7, 11)
+MPD_LAYER_GAIN = (1.0, 1.0, 1.0, 1.0, 1.0, 0.7)
+
+
+def _conv2d(spec, prefix, cout, cin, k, factor):
+    """weight-normed torch.nn.Conv2d(cin, cout, (k, 1)) keys; ``factor`` scales the gain of this layer."""
+    fan = cin * k / factor ** 2
+    spec.append((prefix + ".bias", (cout,), ("b", fan)))
+    spec.append((prefix + ".weight_g", (cout, 1, 1, 1), ("g", prefix)))
+    spec.append((prefix + ".weight_v", (cout, cin, k, 1), ("v", fan)))
+
+
 def _conv_stack_spec(spec, prefix, cin, kernel_sizes, channels, max_downsample_channels, bias, downsample_scales,
                      tap, wn):
     k0 = int(np.prod(kernel_sizes))
@@ -205,8 +221,8 @@ def _conv_stack_spec(spec, prefix, cin, kernel_sizes, channels, max_downsample_c
 def discriminator_spec(kind="discriminator", weight_norm=True, prefix="", **kw):
     """[(key, shape, kind)] of fastvocoder_amd.discriminator's (and the reference's) modules: kind "melgan"
     (MelGANDiscriminator), "msd" (MelGANMultiScaleDiscriminator), "stft" (STFTDiscriminator), "mfd"
-    (MultiResolutionSTFTDiscriminator) or "discriminator" (Discriminator(), no kwargs), with the shape kwargs of
-    the constructor.  ``weight_norm``: g / v pairs (every module but a bare MelGANDiscriminator has them)."""
+    (MultiResolutionSTFTDiscriminator), "mpd" (MultiPeriodDiscriminator, no kwargs) or "discriminator"
+    (Discriminator(); ``use_mpd=True`` is its only kwarg), with the shape kwargs of the constructor.  ``weight_norm``: g / v pairs (every module but a bare MelGANDiscriminator has them)."""
     spec = []
     if kind == "melgan":
         c = dict(MSD_KW, **kw)
@@ -228,7 +244,17 @@ def discriminator_spec(kind="discriminator", weight_norm=True, prefix="", **kw):
         for i, (nf, hop, wl) in enumerate(zip(ffts, hops, wins)):
             spec += discriminator_spec("stft", weight_norm, f"{prefix}stft_discriminator.{i}.", fft_size=nf,
                                        shift_size=hop, win_length=wl)
+    elif kind == "mpd":
+        if not weight_norm or kw:
+            raise ValueError("the MPD has no constructor arguments and always carries weight norm")
+        for i in range(len(MPD_PERIODS)):
+            chans = [(32, 1), (128, 32), (512, 128), (1024, 512), (1024, 1024)]
+            for j, (cout, cin) in enumerate(chans):
+                _conv2d(spec, f"{prefix}discriminators.{i}.convs.{j}", cout, cin, 5, MPD_LAYER_GAIN[j])
+            _conv2d(spec, f"{prefix}discriminators.{i}.conv_post", 1, 1024, 3, MPD_LAYER_GAIN[5])
     elif kind == "discriminator":
+        if kw.pop("use_mpd", False):
+            spec += discriminator_spec("mpd", weight_norm, f"{prefix}mpd.")
         spec += discriminator_spec("msd", weight_norm, f"{prefix}msd.")
         spec += discriminator_spec("mfd", weight_norm, f"{prefix}mfd.")
     else:

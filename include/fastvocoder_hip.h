@@ -666,6 +666,36 @@ int64_t fv_disc_score_workspace_bytes(int B, int M, const int64_t* n);
 int fv_disc_score_sums(const float* const* e, const float* const* r, const int64_t* n, int M, int B, double* out,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The multi-period discriminator's convs (model/discriminator/mpd.py:131-164 DiscriminatorP).  A map [B, C, H, p] is
+ * contiguous (flattened time n = h p + c); additions of ABI 18, no existing entry changes.
+ *
+ * fv_mpd_conv_first: the first layer, Conv2d(1, 32, (5, 1), (3, 1), padding (2, 0)) + LeakyReLU, straight from the
+ * waveform x [B, T]: the reflect tail pad to a multiple of `period` (n_pad = period - T % period samples, flat index
+ * n >= T reads x[2 (T - 1) - n]) and the [H, period] view are address arithmetic, no padded copy exists.
+ *     y[b, co, h', c] = lrelu( bias[co] + sum_{j<5} w[co, j] * xpad[b, (3 h' + j - 2) period + c], slope )
+ * with zeros for rows outside [0, H), H = (T + n_pad) / period.  w [32, 5] (the folded weight); bias [32] or NULL;
+ * y [B, 32, H', period], H' = (H - 1) / 3 + 1.  Exact fp32 on the VALU, summed j = 0..4, then + bias.
+ *
+ * fv_period_conv: Conv2d(Cin, Cout, (5, 1), (3, 1), padding (2, 0)) + LeakyReLU on a map x [B, Cin, H, period]:
+ *     y[b, co, h', c] = lrelu( bias[co] + sum_{ci, j<5} w[co, ci, j] * x[b, ci, 3 h' + j - 2, c], slope )
+ * y [B, Cout, H', period].  packed: fv_pack_period_conv of the folded weight [Cout, Cin, 5]
+ * (fv_packed_period_conv_floats(Cout, Cin) floats; 0 for an unsupported shape).  An implicit GEMM on the exact-fp32
+ * matrix instructions, summed in the fixed order (ci, ci + 1) pairs ascending, j = 0..4, then + bias: a row's values
+ * do not depend on B, on the grid or on any switch.  y must not alias x.
+ *
+ * Supported: period 2, 3, 5, 7 or 11; Cin 32, 128 or 512; Cout 128, 512 or 1024; anything else returns
+ * FV_ERR_UNSUPPORTED (checked before everything else: nothing is launched).  A null pointer, aliasing, B outside
+ * 1..65535, T < 1, n_pad >= T (torch's reflect pad refuses it too), H < 1 or 2^31 flattened samples and more return
+ * FV_ERR_INVALID_ARG.  One launch each.
+ */
+int fv_mpd_conv_first(const float* x, const float* w, const float* bias, float* y, int B, int64_t T, int period,
+                      float slope, void* stream);
+int64_t fv_packed_period_conv_floats(int Cout, int Cin);
+int fv_pack_period_conv(const float* w, float* packed, int Cout, int Cin, void* stream);
+int fv_period_conv(const float* x, const float* packed, const float* bias, float* y, int B, int Cin, int Cout, int H,
+                   int period, float slope, void* stream);
+
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
  * ------------------------------------------------------------------ */
