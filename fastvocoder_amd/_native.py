@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "mpd.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "disc_grad.hip", "mpd.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -255,6 +255,12 @@ def lib():
     L.fv_disc_score_workspace_bytes.restype = i64
     L.fv_disc_score_sums.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i, i, vp, vp,
                                      ctypes.c_size_t, vp]
+    L.fv_disc_map_grad.argtypes = [vp, vp, vp, vp, i64, f, vp]
+    L.fv_grouped_conv1d_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
+    L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
+    L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
+    L.fv_disc_score_grad.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
+                                     ctypes.POINTER(f), i, i, vp]
     L.fv_mpd_conv_first.argtypes = [vp, vp, vp, vp, i, i64, i, f, vp]
     L.fv_packed_period_conv_floats.argtypes = [i, i]
     L.fv_packed_period_conv_floats.restype = i64
@@ -1234,6 +1240,96 @@ def disc_score_sums(es, rs):
         r_a = (ctypes.c_void_p * M)(*[_ptr(r, "r") for r in rs])
         check(lib().fv_disc_score_sums(e_a, r_a, n, M, B, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream))
     return out
+
+
+def disc_map_grad(g_up, g_map, y, slope=1.0):
+    """(g_up + g_map) * (y > 0 ? 1 : slope), elementwise (fv_disc_map_grad, one launch): the gradient in front of a
+    layer's LeakyReLU.  g_up or g_map may be None; y (the layer's output) may be None when slope is 1."""
+    like = g_up if g_up is not None else g_map
+    if like is None:
+        raise NativeError("disc_map_grad: g_up and g_map are both None")
+    for t in (g_up, g_map, y):
+        if t is not None and t.shape != like.shape:
+            raise NativeError(f"disc_map_grad: shapes {tuple(t.shape)} and {tuple(like.shape)} differ")
+    out = torch.empty_like(like)
+    with _on(g_up, g_map, y, out) as stream:
+        check(lib().fv_disc_map_grad(_ptr(g_up, "g_up", True), _ptr(g_map, "g_map", True), _ptr(y, "y", True),
+                                     _ptr(out), like.numel(), float(slope), stream))
+    return out
+
+
+def grouped_conv1d_input_grad(g_up, g_map, y, w, cin, tin, k, stride, pad, slope=1.0):
+    """The gradient of grouped_conv1d with respect to its input x [B, cin, tin] (fv_grouped_conv1d_input_grad, one
+    launch): g_up / g_map / y [B,Cout,Tout] as disc_map_grad takes them (the mask is applied while the gradient is
+    staged), w [Cout,4,k] the forward's weight -> dx [B, cin, tin]."""
+    like = g_up if g_up is not None else g_map
+    if like is None or like.dim() != 3 or w.dim() != 3 or w.shape[1:] != (4, k) or w.shape[0] != like.shape[1]:
+        raise NativeError(f"grouped_conv1d_input_grad: a gradient [B,Cout,Tout] and w [Cout,4,{k}] expected, got "
+                          f"{None if like is None else tuple(like.shape)} and {tuple(w.shape)}")
+    B, cout, tout = like.shape
+    for t in (g_up, g_map, y):
+        if t is not None and t.shape != like.shape:
+            raise NativeError(f"grouped_conv1d_input_grad: shapes {tuple(t.shape)} and {tuple(like.shape)} differ")
+    if stride > 0 and tin + 2 * pad >= k and tout != (tin + 2 * pad - k) // stride + 1:
+        raise NativeError(f"grouped_conv1d_input_grad: {tout} output times do not belong to an input of {tin} samples")
+    dx = torch.empty((B, int(cin), max(int(tin), 0)), dtype=torch.float32, device=like.device)
+    with _on(g_up, g_map, y, w, dx) as stream:
+        check(lib().fv_grouped_conv1d_input_grad(_ptr(g_up, "g_up", True), _ptr(g_map, "g_map", True),
+                                                 _ptr(y, "y", True), _ptr(w, "w"), _ptr(dx), B, int(cin), cout,
+                                                 int(tin), int(k), int(stride), int(pad), float(slope), stream))
+    return dx
+
+
+def reflect_pad_fold(gp, pad):
+    """The adjoint of ReflectionPad1d(pad): gp [..., T + 2 pad] -> [..., T] (fv_reflect_pad_fold, one launch)."""
+    T = gp.shape[-1] - 2 * int(pad)
+    rows = gp.numel() // gp.shape[-1] if gp.shape[-1] else 0
+    dx = torch.empty(tuple(gp.shape[:-1]) + (max(T, 0),), dtype=torch.float32, device=gp.device)
+    with _on(gp, dx) as stream:
+        check(lib().fv_reflect_pad_fold(_ptr(gp, "gp"), _ptr(dx), rows, T, int(pad), stream))
+    return dx
+
+
+def avg_pool1d_input_grad(g, tin, k, stride, pad):
+    """The adjoint of avg_pool1d: g [..., Tout] -> dx [..., tin] (fv_avg_pool1d_input_grad, one launch)."""
+    tout = g.shape[-1]
+    rows = g.numel() // tout if tout else 0
+    if stride > 0 and tin + 2 * pad >= k and tout != (tin + 2 * pad - k) // stride + 1:
+        raise NativeError(f"avg_pool1d_input_grad: {tout} windows do not belong to an input of {tin} samples")
+    dx = torch.empty(tuple(g.shape[:-1]) + (max(int(tin), 0),), dtype=torch.float32, device=g.device)
+    with _on(g, dx) as stream:
+        check(lib().fv_avg_pool1d_input_grad(_ptr(g, "g"), _ptr(dx), rows, int(tin), int(k), int(stride), int(pad),
+                                             stream))
+    return dx
+
+
+def disc_score_grad(es, rs, coef, skip=None):
+    """Lists of M map pairs as disc_score_sums takes them and M host triples (c_l1, c_adv, c_fake) -> the list of
+    g_m = c_l1 sign(e_m - r_m) + 2 c_adv (e_m - 1) + 2 c_fake e_m (fv_disc_score_grad: one launch per DISC_MAX_MAPS
+    maps).  ``skip``: M flags; a flagged map gets no gradient (None)."""
+    M = len(es)
+    if M != len(rs) or M == 0 or len(coef) != M:
+        raise NativeError(f"disc_score_grad: {len(es)} estimate maps, {len(rs)} real maps, {len(coef)} coefficients")
+    skip = [False] * M if skip is None else list(skip)
+    if M > DISC_MAX_MAPS:
+        out = []
+        for i in range(0, M, DISC_MAX_MAPS):
+            j = i + DISC_MAX_MAPS
+            out += disc_score_grad(es[i:j], rs[i:j], coef[i:j], skip[i:j])
+        return out
+    B = es[0].shape[0]
+    for e, r in zip(es, rs):
+        if e.shape != r.shape or e.shape[0] != B:
+            raise NativeError(f"disc_score_grad: map shapes {tuple(e.shape)} and {tuple(r.shape)} (batch {B})")
+    gs = [None if s else torch.empty_like(e) for e, s in zip(es, skip)]
+    n = (ctypes.c_int64 * M)(*[e[0].numel() for e in es])
+    c = (ctypes.c_float * (3 * M))(*[float(v) for t in coef for v in t])
+    with _on(*es, *rs, *gs) as stream:
+        e_a = (ctypes.c_void_p * M)(*[_ptr(e, "e") for e in es])
+        r_a = (ctypes.c_void_p * M)(*[_ptr(r, "r") for r in rs])
+        g_a = (ctypes.c_void_p * M)(*[_ptr(g, "g", True) for g in gs])
+        check(lib().fv_disc_score_grad(e_a, r_a, g_a, n, c, M, B, stream))
+    return gs
 
 
 def pqmf_synthesis(x, synthesis_filter, y):

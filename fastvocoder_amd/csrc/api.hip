@@ -795,6 +795,71 @@ int fv_disc_score_sums(const float* const* e, const float* const* r, const int64
     return launch_disc_score_sums(e, r, n, M, B, out, static_cast<double*>(workspace), (hipStream_t)stream);
 }
 
+int fv_grouped_conv1d_input_grad(const float* g_up, const float* g_map, const float* y, const float* w, float* dx,
+                                 int B, int Cin, int Cout, int Tin, int k, int stride, int pad, float slope,
+                                 void* stream) {
+    if (Cin < 4 || Cin % 4 || Cout < 1 || Cout % (Cin / 4) || k < 1 || stride < 1)
+        return fail(FV_ERR_UNSUPPORTED, "grouped_conv1d_input_grad: Cin=%d Cout=%d k=%d stride=%d (Cin %% 4 == 0, "
+                    "groups = Cin/4 dividing Cout, k >= 1, stride >= 1)", Cin, Cout, k, stride);
+    const int opg = Cout / (Cin / 4);
+    if (grouped_conv_lds_bytes(k, stride, opg % 16 == 0 ? 16 : 4) > 65536)     // the forward's own bound
+        return fail(FV_ERR_UNSUPPORTED, "grouped_conv1d_input_grad: k=%d stride=%d exceed a block's shared memory", k,
+                    stride);
+    if ((!g_up && !g_map) || !w || !dx || B <= 0 || B > 65535 || Tin < 1 || pad < 0)
+        return fail(FV_ERR_INVALID_ARG, "grouped_conv1d_input_grad: null tensor, B=%d, Tin=%d or pad=%d", B, Tin, pad);
+    if (!y && slope != 1.f)
+        return fail(FV_ERR_INVALID_ARG, "grouped_conv1d_input_grad: slope=%g needs the layer's output y", slope);
+    if (dx == g_up || dx == g_map || dx == y || dx == w)
+        return fail(FV_ERR_INVALID_ARG, "grouped_conv1d_input_grad: dx must not alias an input");
+    const int64_t span = (int64_t)Tin + 2 * (int64_t)pad - k;
+    if (span < 0)
+        return fail(FV_ERR_INVALID_ARG, "grouped_conv1d_input_grad: empty output (Tin=%d pad=%d k=%d)", Tin, pad, k);
+    return launch_grouped_conv1d_input_grad(g_up, g_map, y, w, dx, B, Cin, Cout, Tin, (int)(span / stride + 1), k,
+                                            stride, pad, slope, (hipStream_t)stream);
+}
+
+int fv_disc_map_grad(const float* g_up, const float* g_map, const float* y, float* g_pre, int64_t n, float slope,
+                     void* stream) {
+    if ((!g_up && !g_map) || !g_pre || n < 1 || (n + 255) / 256 >= (int64_t)1 << 31)
+        return fail(FV_ERR_INVALID_ARG, "disc_map_grad: null tensor or n=%lld", (long long)n);
+    if (!y && slope != 1.f) return fail(FV_ERR_INVALID_ARG, "disc_map_grad: slope=%g needs the layer's output y", slope);
+    return launch_disc_map_grad(g_up, g_map, y, g_pre, n, slope, (hipStream_t)stream);
+}
+
+int fv_reflect_pad_fold(const float* gp, float* dx, int rows, int64_t T, int P, void* stream) {
+    if (!gp || !dx || gp == dx || rows < 1 || rows > 65535 || P < 0)
+        return fail(FV_ERR_INVALID_ARG, "reflect_pad_fold: null tensor, rows=%d or P=%d", rows, P);
+    if (T <= P || (T + 255) / 256 >= (int64_t)1 << 31)
+        return fail(FV_ERR_INVALID_ARG, "reflect_pad_fold: T=%lld must exceed the pad %d", (long long)T, P);
+    return launch_reflect_pad_fold(gp, dx, rows, T, P, (hipStream_t)stream);
+}
+
+int fv_avg_pool1d_input_grad(const float* g, float* dx, int rows, int64_t Tin, int k, int stride, int pad,
+                             void* stream) {
+    if (!g || !dx || g == dx || rows < 1 || rows > 65535 || k < 1 || stride < 1 || pad < 0 || 2 * pad > k)
+        return fail(FV_ERR_INVALID_ARG, "avg_pool1d_input_grad: rows=%d k=%d stride=%d pad=%d", rows, k, stride, pad);
+    const int64_t span = Tin + 2 * (int64_t)pad - k;
+    if (Tin < 1 || span < 0 || (Tin + 255) / 256 >= (int64_t)1 << 31)
+        return fail(FV_ERR_INVALID_ARG, "avg_pool1d_input_grad: empty output (Tin=%lld k=%d pad=%d)", (long long)Tin, k,
+                    pad);
+    return launch_avg_pool1d_input_grad(g, dx, rows, Tin, span / stride + 1, k, stride, pad, (hipStream_t)stream);
+}
+
+int fv_disc_score_grad(const float* const* e, const float* const* r, float* const* g, const int64_t* n,
+                       const float* coef, int M, int B, void* stream) {
+    if (M < 1 || M > FV_DISC_MAX_MAPS || !n)
+        return fail(FV_ERR_INVALID_ARG, "disc_score_grad: M=%d maps (1..%d)", M, FV_DISC_MAX_MAPS);
+    if (B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "disc_score_grad: B=%d", B);
+    if (!e || !r || !g || !coef) return fail(FV_ERR_INVALID_ARG, "disc_score_grad: null pointer");
+    for (int m = 0; m < M; ++m) {
+        if (n[m] < 1) return fail(FV_ERR_INVALID_ARG, "disc_score_grad: map %d has %lld elements", m, (long long)n[m]);
+        if (!e[m] || !r[m] || g[m] == e[m] || g[m] == r[m])
+            return fail(FV_ERR_INVALID_ARG, "disc_score_grad: map %d is null or its gradient aliases it", m);
+    }
+    if (score_grad_chunks(M, n) >= (int64_t)1 << 31) return fail(FV_ERR_INVALID_ARG, "disc_score_grad: maps too large");
+    return launch_disc_score_grad(e, r, g, n, coef, M, B, (hipStream_t)stream);
+}
+
 int fv_conv1d_2src_fused(const float* x, const float* x2, const float* packed, const float* bias,
                          const float* res, float* y, float* y_act, int B, int Cin1, int Cin2, int Cout,
                          int T, int post, float act_slope, void* stream) {

@@ -466,6 +466,18 @@ int launch_avg_pool1d(const float* x, float* y, int rows, int64_t Tin, int64_t T
 int64_t score_chunks(int M, const int64_t* n);   // score-sum blocks per row over all maps
 int launch_disc_score_sums(const float* const* e, const float* const* r, const int64_t* n, int M, int B, double* out,
                            double* ws, hipStream_t st);
+// the discriminator's input gradient (disc_grad.hip)
+int launch_grouped_conv1d_input_grad(const float* g_up, const float* g_map, const float* y, const float* w, float* dx,
+                                     int B, int Cin, int Cout, int Tin, int Tout, int k, int s, int pad, float slope,
+                                     hipStream_t st);
+int launch_disc_map_grad(const float* g_up, const float* g_map, const float* y, float* g_pre, int64_t n, float slope,
+                         hipStream_t st);
+int launch_reflect_pad_fold(const float* gp, float* dx, int rows, int64_t T, int P, hipStream_t st);
+int launch_avg_pool1d_input_grad(const float* g, float* dx, int rows, int64_t Tin, int64_t Tout, int k, int s, int p,
+                                 hipStream_t st);
+int64_t score_grad_chunks(int M, const int64_t* n);   // score-gradient blocks per row over all maps
+int launch_disc_score_grad(const float* const* e, const float* const* r, float* const* g, const int64_t* n,
+                           const float* coef, int M, int B, hipStream_t st);
 
 // self-check of pair_kernels.hpp div_exact against the device's division (fv_div_probe; pair_inst_c16.hip)
 int launch_div_probe(unsigned first, long long n, float d, unsigned long long* mismatches, hipStream_t s);

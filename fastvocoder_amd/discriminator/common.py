@@ -29,14 +29,15 @@ def check_grouped(in_chs):
                                   "4 input channels per group (in_chs a multiple of 4)")
 
 
-def device_input(x, name, dims):
-    """x as a contiguous fp32 device tensor of rank ``dims``, or a clear error (the checks of fastvocoder_amd.loss)."""
+def device_input(x, name, dims, differentiable=False):
+    """x as a contiguous fp32 device tensor of rank ``dims``, or a clear error (the checks of fastvocoder_amd.loss).
+    ``differentiable``: x may require grad (the module's ``differentiable`` attribute is set)."""
     if not torch.is_tensor(x):
         raise TypeError(f"{name} must be a tensor, got {type(x).__name__}")
     if not x.is_cuda:
         raise _native.NativeError(f"{name} lives on {x.device}; the discriminators run on the ROCm device "
                                   "(there is no CPU path in fastvocoder_amd)")
-    if x.requires_grad and torch.is_grad_enabled():
+    if x.requires_grad and torch.is_grad_enabled() and not differentiable:
         raise RuntimeError(f"{name} requires grad: the fastvocoder_amd discriminators are inference-only (forward, no "
                            "autograd); call them under torch.no_grad() or pass a detached tensor")
     if x.dim() != dims:
@@ -68,8 +69,48 @@ def first_length(ok, start=1):
     return lo
 
 
+class NotDifferentiable:
+    """Mix-in of the modules without an input gradient: ``differentiable`` reads False, and setting it raises."""
+
+    @property
+    def differentiable(self):
+        return False
+
+    @differentiable.setter
+    def differentiable(self, value):
+        if value:
+            raise NotImplementedError(
+                f"{type(self).__name__} is not differentiable: only the MelGAN multi-scale discriminator "
+                "(MelGANDiscriminator, MelGANMultiScaleDiscriminator) has an input gradient; the STFT-magnitude "
+                "adjoint of the STFT discriminators and the period convs of the MPD have none yet")
+
+
+class _StackGrad(torch.autograd.Function):
+    """ConvStack._run_stack with the gradient with respect to the input: the outputs are all the layer maps, the
+    saved tensors the input and the maps.  The parameters are constants."""
+
+    @staticmethod
+    def forward(ctx, stack, x):
+        outs = stack._run_stack(x)
+        ctx.stack = stack
+        ctx.save_for_backward(x, *outs)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, *outs = ctx.saved_tensors
+        return None, ctx.stack._input_grad(x, outs, grads)
+
+
 class ConvStack(NativeModule):
-    """Base of the two sub-discriminators: ``layers`` as in the reference, ``_spec`` one entry per layer."""
+    """Base of the two sub-discriminators: ``layers`` as in the reference, ``_spec`` one entry per layer.
+
+    ``differentiable`` (default False): with True, a forward whose input requires grad runs the same launches through
+    an autograd Function (the same bits) whose backward is the input gradient of csrc/disc_grad.hip.  The parameters
+    are constants of that graph: their ``.grad`` stays None."""
+
+    differentiable = False
 
     def _build_stack(self, in_channels, out_channels, kernel_sizes, channels, max_downsample_channels, bias,
                      downsample_scales, slope, tap, pad_name, pad_params):
@@ -129,6 +170,57 @@ class ConvStack(NativeModule):
                                conv.out_channels))
         self._fv_plans["layers"] = (self._fv_state(), layers)
         return layers
+
+    def _native_grad_layers(self):
+        """Per layer what its input gradient reads: the folded weight [Cout, 4, k] of a grouped layer (the forward's
+        tensor), the packed W'[ci, co, j] = W[co, ci, k-1-j] of a dense one.  Cached against the module state."""
+        state = self._fv_state()
+        hit = self._fv_plans.get("grad_layers")
+        if hit is not None and hit[0] == state:
+            return hit[1]
+        self._device()
+        fwd = self._native_layers()
+        with torch.no_grad():
+            layers = []
+            for (spec, w, _, _), conv in zip(fwd, self._convs()):
+                if spec[0] != "grouped":
+                    w = _native.pack_conv1d(effective_weight(conv).flip(2).transpose(0, 1).contiguous())
+                layers.append((spec, w, conv.in_channels))
+        self._fv_plans["grad_layers"] = (self._fv_state(), layers)
+        return layers
+
+    def _input_grad(self, x, outs, grads):
+        """d/dx of sum_l <grads[l], outs[l]> (None = zero), walking the layers downwards: the LeakyReLU mask of a
+        layer from its stored output, then the layer's data gradient, to which the next map's gradient is added."""
+        layers = self._native_grad_layers()
+        g_up = None
+        for l in range(len(layers) - 1, -1, -1):
+            spec, w, cin = layers[l]
+            g_map = None if grads[l] is None else grads[l].to(torch.float32).contiguous()
+            if g_up is None and g_map is None:
+                continue
+            tin = (outs[l - 1] if l else x).shape[-1]
+            if spec[0] == "grouped":
+                _, k, pad, stride, slope = spec
+                g_up = _native.grouped_conv1d_input_grad(g_up, g_map, outs[l] if slope != 1.0 else None, w, cin, tin,
+                                                         k, stride, pad, slope)
+                continue
+            _, k, pad, mode, slope = spec
+            if slope != 1.0 or (g_up is not None and g_map is not None):
+                g_pre = _native.disc_map_grad(g_up, g_map, outs[l] if slope != 1.0 else None, slope)
+            else:
+                g_pre = g_up if g_up is not None else g_map
+            if mode == PAD_REFLECT:      # the gradient of the padded input (pad' = k - 1), folded back onto the input
+                g_up = _native.reflect_pad_fold(_native.conv1d_fused(g_pre, w, None, cin, k, pad=k - 1), pad)
+            else:
+                g_up = _native.conv1d_fused(g_pre, w, None, cin, k, pad=k - 1 - pad)
+        return torch.zeros_like(x) if g_up is None else g_up
+
+    def _stack(self, x):
+        """_run_stack, through the autograd Function when the module is differentiable and x requires grad."""
+        if self.differentiable and x.requires_grad and torch.is_grad_enabled():
+            return list(_StackGrad.apply(self, x))
+        return self._run_stack(x)
 
     def _run_stack(self, x):
         """x [B, C, T] fp32 device -> the list of every layer's output (the reference's ``outs``)."""

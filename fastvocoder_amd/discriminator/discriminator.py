@@ -1,13 +1,13 @@
 """The reference's Discriminator (model/discriminator/discriminator.py): MSD + MFD, and with ``use_mpd=True`` the
 MPD the reference keeps one commented line away (discriminator.py:11, 16), registered first as there."""
 from ..generator.engine import NativeModule
-from .common import check_length, device_input
+from .common import NotDifferentiable, check_length, device_input
 from .mfd import MultiResolutionSTFTDiscriminator
 from .mpd import MultiPeriodDiscriminator
 from .msd import MelGANMultiScaleDiscriminator
 
 
-class Discriminator(NativeModule):
+class Discriminator(NotDifferentiable, NativeModule):
     def __init__(self, use_mpd=False):
         super().__init__()
         self.use_mpd = bool(use_mpd)

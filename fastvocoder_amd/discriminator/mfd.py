@@ -4,10 +4,10 @@ import torch
 from .. import _native
 from ..generator.engine import NativeModule
 from ..loss.stft_loss import _stft_table_host, _window_fn
-from .common import ConvStack, check_activation, check_length, check_pad, device_input
+from .common import ConvStack, NotDifferentiable, check_activation, check_length, check_pad, device_input
 
 
-class STFTDiscriminator(ConvStack):
+class STFTDiscriminator(NotDifferentiable, ConvStack):
     """mfd.py:44-136: the clamped STFT magnitude (B, bins, frames) -- bins as channels, no transpose -- then a conv
     stack: reflect-padded Conv1d(bins -> channels, prod(kernel_sizes)), grouped strided downsamples (k = 6 s + 1),
     Conv1d(k0), Conv1d(k1 -> 1).  Weight norm is applied at construction, as in the reference.  The window is the
@@ -55,7 +55,7 @@ class STFTDiscriminator(ConvStack):
         return self._run_stack(mag)
 
 
-class MultiResolutionSTFTDiscriminator(NativeModule):
+class MultiResolutionSTFTDiscriminator(NotDifferentiable, NativeModule):
     """mfd.py:139-178: one STFTDiscriminator per (fft_size, hop_size, win_length)."""
 
     def __init__(self, fft_sizes=[2048, 1024, 512], hop_sizes=[240, 120, 50], win_lengths=[1200, 600, 240],

@@ -11,7 +11,7 @@ from torch.nn.utils import weight_norm
 
 from .. import _native
 from ..generator.engine import PAD_ZERO, NativeModule, effective_weight
-from .common import check_length, device_input, first_length
+from .common import NotDifferentiable, check_length, device_input, first_length
 
 LRELU_SLOPE = 0.1
 PERIODS = (2, 3, 5, 7, 11)
@@ -26,7 +26,7 @@ def period_heights(T, period, stride=3, layers=4):
     return n_pad, hs
 
 
-class DiscriminatorP(NativeModule):
+class DiscriminatorP(NotDifferentiable, NativeModule):
     """mpd.py:131-164."""
 
     def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
@@ -102,7 +102,7 @@ class DiscriminatorP(NativeModule):
         return x.view(B, H * p), fmap
 
 
-class MultiPeriodDiscriminator(NativeModule):
+class MultiPeriodDiscriminator(NotDifferentiable, NativeModule):
     """mpd.py:288-304, the single-input form: one list per period, its six maps followed by the score [B, 1, H p]."""
 
     def __init__(self):

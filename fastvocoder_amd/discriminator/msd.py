@@ -6,9 +6,24 @@ from ..generator.engine import NativeModule
 from .common import ConvStack, check_activation, check_length, check_pad, device_input, first_length
 
 
+class _AvgPool(torch.autograd.Function):
+    """fv_avg_pool1d with its adjoint fv_avg_pool1d_input_grad."""
+
+    @staticmethod
+    def forward(ctx, x, pool):
+        ctx.pool, ctx.tin = pool, x.shape[-1]
+        return _native.avg_pool1d(x, *pool)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _native.avg_pool1d_input_grad(g.to(torch.float32).contiguous(), ctx.tin, *ctx.pool), None
+
+
 class MelGANDiscriminator(ConvStack):
     """msd.py:13-118: reflect-padded Conv1d(1 -> channels, prod(kernel_sizes)), grouped strided downsamples
-    (k = 10 s + 1, groups = in_chs // 4), Conv1d(k0) and Conv1d(k1 -> 1); LeakyReLU after all but the last."""
+    (k = 10 s + 1, groups = in_chs // 4), Conv1d(k0) and Conv1d(k1 -> 1); LeakyReLU after all but the last.
+    ``differentiable``: see ConvStack (the gradient with respect to x; the parameters' ``.grad`` stays None)."""
 
     def __init__(self, in_channels=1, out_channels=1, kernel_sizes=[5, 3], channels=16, max_downsample_channels=1024,
                  bias=True, downsample_scales=[4, 4, 4, 4], nonlinear_activation="LeakyReLU",
@@ -28,11 +43,11 @@ class MelGANDiscriminator(ConvStack):
 
     def forward(self, x):
         """x (B, 1, T) -> list of every layer's output."""
-        x = device_input(x, "x", 3)
+        x = device_input(x, "x", 3, self.differentiable)
         if x.shape[1] != 1:
             raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
         check_length(self, x.shape[-1])
-        return self._run_stack(x)
+        return self._stack(x)
 
 
 class MelGANMultiScaleDiscriminator(NativeModule):
@@ -67,6 +82,18 @@ class MelGANMultiScaleDiscriminator(NativeModule):
             self.apply_weight_norm()
         self.reset_parameters()
 
+    @property
+    def differentiable(self):
+        """True when every scale carries the gradient with respect to its input (ConvStack.differentiable); setting
+        it sets every scale.  The pool between the scales then runs through its own autograd Function, and the
+        gradient of x is the sum over the scales."""
+        return all(d.differentiable for d in self.discriminators)
+
+    @differentiable.setter
+    def differentiable(self, value):
+        for d in self.discriminators:
+            d.differentiable = bool(value)
+
     def _pooled_length(self, n):
         k, s, p = self._pool
         return (n + 2 * p - k) // s + 1
@@ -84,13 +111,14 @@ class MelGANMultiScaleDiscriminator(NativeModule):
 
     def forward(self, x):
         """x (B, 1, T) -> list over the scales of each scale's list of layer outputs."""
-        x = device_input(x, "x", 3)
+        x = device_input(x, "x", 3, self.differentiable)
         if x.shape[1] != 1:
             raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
         check_length(self, x.shape[-1])
+        grad = self.differentiable and x.requires_grad and torch.is_grad_enabled()
         outs = []
         for i, f in enumerate(self.discriminators):
             outs += [f(x)]
             if i + 1 < len(self.discriminators):
-                x = _native.avg_pool1d(x, *self._pool)
+                x = _AvgPool.apply(x, self._pool) if grad else _native.avg_pool1d(x, *self._pool)
         return outs

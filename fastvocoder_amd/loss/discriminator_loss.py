@@ -1,4 +1,5 @@
-"""The discriminator scores of the reference's training loop (bin/train.py:97-117, 157-169), forward only.
+"""The discriminator scores of the reference's training loop (bin/train.py:97-117, 157-169); with
+``differentiable=True`` they carry the gradient with respect to the estimate's maps.
 
 With est_p = D(estimate) and p = D(real), lists of L lists of feature maps (the last map of each list its score):
 
@@ -11,6 +12,10 @@ With est_p = D(estimate) and p = D(real), lists of L lists of feature maps (the 
 MSE and L1 are means over the whole batch tensor.  The feature-map divisor uses the length of the FIRST list for
 every list, as the reference does (6 x 6 = 36 for Discriminator(), whose MFD lists add only 4 terms each).  All the
 sums come from one fv_disc_score_sums call (two launches) in float64.
+
+The gradient (one fv_disc_score_grad launch) reaches est_p only: p is detached in the reference
+(``p[ii][jj].detach()``), so ``real`` is a constant of the estimate, and ``fake`` and ``discriminator`` differentiate
+through sum e^2.
 """
 import torch
 
@@ -43,14 +48,72 @@ def compose_terms(sums, counts, lengths, per_utterance=False):
     return {"adversarial": adv, "feature_map": fm, "real": real, "fake": fake, "discriminator": real + fake}
 
 
-def discriminator_terms(est_p, p, per_utterance=False):
+def _map_index(lengths):
+    """(indices of the feature maps, indices of the score maps) in the flattened lists."""
+    last, fm_idx, m = [], [], 0
+    for n in lengths:
+        fm_idx += range(m, m + n - 1)
+        last.append(m + n - 1)
+        m += n
+    return fm_idx, last
+
+
+def grad_coefficients(grad_terms, counts, lengths, batch):
+    """Per map the (c_l1, c_adv, c_fake) of fv_disc_score_grad from the gradients of the five TERMS: a feature map m
+    carries c_l1 = g_fm / (L (len(est_p[0]) - 1) n_m B), a score map c_adv = g_adv / (L n_m B) and
+    c_fake = (g_fake + g_discriminator) / (L n_m B); ``real`` does not depend on the estimate."""
+    g = dict(zip(TERMS, (float(v) for v in grad_terms)))
+    L = len(lengths)
+    fm_idx, last = _map_index(lengths)
+    fm_den = float(L * (lengths[0] - 1))
+    coef = [[0.0, 0.0, 0.0] for _ in counts]
+    for m in fm_idx:
+        coef[m][0] = g["feature_map"] / (fm_den * counts[m] * batch)
+    for m in last:
+        coef[m][1] = g["adversarial"] / (L * counts[m] * batch)
+        coef[m][2] = (g["fake"] + g["discriminator"]) / (L * counts[m] * batch)
+    return coef
+
+
+class _Terms(torch.autograd.Function):
+    """The five TERMS as one float64 [5] tensor: the forward of discriminator_terms, the backward one
+    fv_disc_score_grad launch for every estimate map that requires grad."""
+
+    @staticmethod
+    def forward(ctx, lengths, *maps):
+        M = len(maps) // 2
+        es, rs = list(maps[:M]), list(maps[M:])
+        sums = _native.disc_score_sums(es, rs)
+        terms = compose_terms(sums, [e[0].numel() for e in es], lengths)
+        ctx.lengths = lengths
+        ctx.save_for_backward(*maps)
+        return torch.stack([terms[k] for k in TERMS])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_terms):
+        maps = ctx.saved_tensors
+        M = len(maps) // 2
+        es, rs = list(maps[:M]), list(maps[M:])
+        coef = grad_coefficients(grad_terms.detach().cpu().tolist(), [e[0].numel() for e in es], ctx.lengths,
+                                 es[0].shape[0])
+        skip = [not need for need in ctx.needs_input_grad[1:M + 1]]
+        return (None,) + tuple(_native.disc_score_grad(es, rs, coef, skip)) + (None,) * M
+
+
+def discriminator_terms(est_p, p, per_utterance=False, differentiable=False):
     """The reference's adversarial, feature-map, real, fake and discriminator scores (module docstring) of the
     discriminator outputs est_p = D(estimate) and p = D(real), nested lists of device maps of matching shapes.
-    -> dict of fp32 device tensors: 0-d (batch-level, as train.py logs them), or [B] with ``per_utterance``."""
+    -> dict of fp32 device tensors: 0-d (batch-level, as train.py logs them), or [B] with ``per_utterance``.
+    ``differentiable``: the (batch-level) terms are attached to the graph of the est_p maps that require grad; p
+    never gets a gradient."""
     if len(est_p) != len(p) or not est_p or any(len(a) != len(b) for a, b in zip(est_p, p)):
         raise ValueError("est_p and p must be lists of the same number of lists of the same lengths")
     if any(len(a) < 1 for a in est_p) or len(est_p[0]) < 2:
         raise ValueError("every list needs its score map, and the first at least one feature map before it")
+    if differentiable and per_utterance:
+        raise NotImplementedError("discriminator_terms(differentiable=True) gives the batch-level terms only: "
+                                  "per_utterance terms are not differentiable")
     es = [m for lst in est_p for m in lst]
     rs = [m for lst in p for m in lst]
     for e, r in zip(es, rs):
@@ -58,13 +121,18 @@ def discriminator_terms(est_p, p, per_utterance=False):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise _native.NativeError(f"{name} maps must be ROCm device tensors (there is no CPU path in "
                                           "fastvocoder_amd)")
-            if t.requires_grad and torch.is_grad_enabled():
+            if t.requires_grad and torch.is_grad_enabled() and not differentiable:
                 raise RuntimeError(f"{name} requires grad: discriminator_terms is inference-only; call it under "
                                    "torch.no_grad()")
         if e.shape != r.shape:
             raise ValueError(f"map shapes differ: {tuple(e.shape)} and {tuple(r.shape)}")
     es = [e.to(torch.float32).contiguous() for e in es]
-    rs = [r.to(torch.float32).contiguous() for r in rs]
-    sums = _native.disc_score_sums(es, rs)
-    terms = compose_terms(sums, [e[0].numel() for e in es], [len(lst) for lst in est_p], per_utterance)
+    rs = [r.detach().to(torch.float32).contiguous() if differentiable else r.to(torch.float32).contiguous()
+          for r in rs]
+    lengths = [len(lst) for lst in est_p]
+    if differentiable and torch.is_grad_enabled() and any(e.requires_grad for e in es):
+        terms = dict(zip(TERMS, _Terms.apply(lengths, *es, *rs)))
+    else:
+        sums = _native.disc_score_sums(es, rs)
+        terms = compose_terms(sums, [e[0].numel() for e in es], lengths, per_utterance)
     return {k: v.float() for k, v in terms.items()}

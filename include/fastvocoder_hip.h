@@ -667,6 +667,55 @@ int fv_disc_score_sums(const float* const* e, const float* const* r, const int64
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The input gradient of the multi-scale discriminator (model/discriminator/msd.py) under the adversarial and
+ * feature-map terms of bin/train.py:97-117; additions of ABI 18, no existing entry changes.  Exact fp32, no atomics:
+ * every element is summed by one thread in a fixed order, so identical calls return identical bits and a row's values
+ * do not depend on B or on the grid.  All entries launch on `stream` and own no device memory.
+ *
+ * fv_disc_map_grad: the gradient in front of a layer's LeakyReLU from the gradient behind it,
+ *     g_pre[i] = (g_up[i] + g_map[i]) * (y[i] > 0 ? 1 : slope),   i < n
+ * g_up: what the layer above hands down; g_map: what the loss puts on this layer's own map; either may be NULL (not
+ * both).  y: the layer's stored output (the sign survives a positive slope; y == 0 takes `slope`, as torch's
+ * leaky_relu backward); NULL with slope = 1 gives the plain sum (the last layer has no activation).  One launch.
+ *
+ * fv_grouped_conv1d_input_grad: the data gradient of fv_grouped_conv1d with fv_disc_map_grad as its load stage,
+ *     dx[b, 4 g + ci, i] = sum_{oc in group g} sum_{j : (i + pad - j) % stride == 0, 0 <= (i + pad - j) / stride < Tout}
+ *                            w[oc, ci, j] * g_pre[b, oc, (i + pad - j) / stride]
+ * g_up, g_map, y [B,Cout,Tout] as above (the masked gradient is never written to memory); w [Cout, 4, k], the
+ * forward's tensor; dx [B,Cin,Tin], all of it written: positions past the last window ((Tin + 2 pad - k) / stride
+ * floors) receive exactly 0.  Evaluated polyphase (an input position meets only the taps of its phase
+ * (i + pad) % stride), each element summed oc ascending, then j ascending.  Supported shapes and error codes as
+ * fv_grouped_conv1d (FV_ERR_UNSUPPORTED first, before any launch); slope != 1 without y, both gradients NULL or dx
+ * aliasing an input return FV_ERR_INVALID_ARG.  One launch.
+ *
+ * fv_reflect_pad_fold: the adjoint of ReflectionPad1d(P) on rows of T samples, from gp [rows, T + 2 P]:
+ *     dx[r, i] = gp[i + P] + (1 <= i <= P ? gp[P - i] : 0) + (T - 1 - P <= i <= T - 2 ? gp[P + 2 (T - 1) - i] : 0)
+ * summed in that order.  T > P (torch's own limit for the pad), else FV_ERR_INVALID_ARG.  One launch.
+ *
+ * fv_avg_pool1d_input_grad: the adjoint of fv_avg_pool1d: g [rows, Tout] -> dx [rows, Tin],
+ *     dx[r, i] = sum over t ascending with t*stride - pad <= i < t*stride - pad + k of g[r, t] / count(t)
+ * (count(t): the window's samples inside [0, Tin)); a gather over at most ceil(k / stride) windows.  Arguments and
+ * checks as fv_avg_pool1d.  One launch.
+ *
+ * fv_disc_score_grad: the gradient of the sums of fv_disc_score_sums with respect to the estimate's maps, every map
+ * in one launch.  e, r, g: HOST arrays of M device pointers ([B, n_m] rows each; g[m] NULL skips the map); n: HOST
+ * array of M element counts; coef: HOST array [M, 3] of (c_l1, c_adv, c_fake) per map:
+ *     g_m[b, i] = c_l1 * sign(e - r) + 2 c_adv (e - 1) + 2 c_fake e,      sign(0) = 0
+ * The coefficients carry the means, the reference's divisors and the incoming gradient of the terms.  Checks as
+ * fv_disc_score_sums.
+ */
+int fv_disc_map_grad(const float* g_up, const float* g_map, const float* y, float* g_pre, int64_t n, float slope,
+                     void* stream);
+int fv_grouped_conv1d_input_grad(const float* g_up, const float* g_map, const float* y, const float* w, float* dx,
+                                 int B, int Cin, int Cout, int Tin, int k, int stride, int pad, float slope,
+                                 void* stream);
+int fv_reflect_pad_fold(const float* gp, float* dx, int rows, int64_t T, int P, void* stream);
+int fv_avg_pool1d_input_grad(const float* g, float* dx, int rows, int64_t Tin, int k, int stride, int pad,
+                             void* stream);
+int fv_disc_score_grad(const float* const* e, const float* const* r, float* const* g, const int64_t* n,
+                       const float* coef, int M, int B, void* stream);
+
+/*
  * The multi-period discriminator's convs (model/discriminator/mpd.py:131-164 DiscriminatorP).  A map [B, C, H, p] is
  * contiguous (flattened time n = h p + c); additions of ABI 18, no existing entry changes.
  *
