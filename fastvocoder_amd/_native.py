@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "disc.hip", "disc_grad.hip", "mpd.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "mpd.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -249,6 +249,9 @@ def lib():
     L.fv_stft_distance_grad_workspace_bytes.restype = i64
     L.fv_stft_distance_grad.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
                                         ctypes.POINTER(i), vp, vp, vp, ctypes.c_size_t, vp]
+    L.fv_stft_magnitude_bins_grad_workspace_bytes.argtypes = [i, i64, i, i, i]
+    L.fv_stft_magnitude_bins_grad_workspace_bytes.restype = i64
+    L.fv_stft_magnitude_bins_grad.argtypes = [vp, vp, vp, i, i64, i, i, i, vp, vp, ctypes.c_size_t, vp]
     L.fv_grouped_conv1d.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
     L.fv_avg_pool1d.argtypes = [vp, vp, i, i64, i, i, i, vp]
     L.fv_disc_score_workspace_bytes.argtypes = [i, i, ctypes.POINTER(i64)]
@@ -1136,6 +1139,32 @@ def stft_magnitude_bins(x, table, n_fft, hop, win_length):
         check(lib().fv_stft_magnitude_bins(_ptr(x, "x"), _ptr(mag), _ptr(table, "table"), B, n, int(n_fft), int(hop),
                                            int(win_length), stream))
     return mag
+
+
+def stft_magnitude_bins_grad(x, gmag, table, n_fft, hop, win_length):
+    """x [B,n], gmag = dL/dmag [B, n_fft//2+1, 1+n//hop] fp32 device -> dL/dx [B,n] fp32, the adjoint of
+    stft_magnitude_bins (fv_stft_magnitude_bins_grad: two launches on the current stream, the frames workspace from
+    torch's allocator)."""
+    if x.dim() != 2:
+        raise NativeError(f"stft_magnitude_bins_grad: x must be [B, n], got {tuple(x.shape)}")
+    B, n = x.shape
+    want = (B, n_fft // 2 + 1, 1 + n // hop if hop > 0 else 0)
+    if tuple(gmag.shape) != want:
+        raise NativeError(f"stft_magnitude_bins_grad: gmag must be [B, bins, frames] = {want}, got "
+                          f"{tuple(gmag.shape)}")
+    if table.numel() != stft_table_floats(n_fft, win_length):
+        raise NativeError(f"stft_magnitude_bins_grad: table holds {table.numel()} floats, the library reads "
+                          f"{stft_table_floats(n_fft, win_length)}")
+    need = lib().fv_stft_magnitude_bins_grad_workspace_bytes(B, n, int(n_fft), int(hop), int(win_length))
+    if need < 0:
+        check(int(need))
+    gx = torch.empty((B, n), dtype=torch.float32, device=x.device)
+    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.float32, device=x.device)
+    with _on(x, gmag, table, gx, ws) as stream:
+        check(lib().fv_stft_magnitude_bins_grad(_ptr(x, "x"), _ptr(gmag, "gmag"), _ptr(table, "table"), B, n,
+                                                int(n_fft), int(hop), int(win_length), _ptr(gx), ws.data_ptr(),
+                                                ws.numel() * 4, stream))
+    return gx
 
 
 def grouped_conv1d(x, w, bias, k, stride, pad, slope=1.0, out=None):

@@ -745,6 +745,41 @@ int fv_stft_magnitude_bins(const float* x, float* mag, const float* table, int B
     return launch_stft_magnitude(x, mag, table, B, n, n_fft, hop, win_length, (hipStream_t)stream, true);
 }
 
+static int64_t stft_mag_grad_check(int B, int64_t n, int n_fft, int hop, int win) {
+    if (int rc = stft_check_res("stft_magnitude_bins_grad", n, n_fft, hop, win)) return rc;
+    if (B <= 0 || B > 65535) return fail(FV_ERR_INVALID_ARG, "stft_magnitude_bins_grad: B=%d", B);
+    const int64_t floats = (int64_t)B * (1 + n / hop) * win;
+    if (stft_mag_grad_chunks(n, hop) >= (int64_t)1 << 31 || (n + 255) / 256 >= (int64_t)1 << 31 ||
+        floats >= (int64_t)1 << 40)
+        return fail(FV_ERR_INVALID_ARG, "stft_magnitude_bins_grad: n=%lld too long", (long long)n);
+    return floats * (int64_t)sizeof(float);
+}
+
+int64_t fv_stft_magnitude_bins_grad_workspace_bytes(int B, int64_t n, int n_fft, int hop, int win_length) {
+    return stft_mag_grad_check(B, n, n_fft, hop, win_length);
+}
+
+int fv_stft_magnitude_bins_grad(const float* x, const float* gmag, const float* table, int B, int64_t n, int n_fft,
+                                int hop, int win_length, float* gx, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    const int64_t need = stft_mag_grad_check(B, n, n_fft, hop, win_length);
+    if (need < 0) return (int)need;
+    if (!x || !gmag || !table || !gx || !workspace)
+        return fail(FV_ERR_INVALID_ARG, "stft_magnitude_bins_grad: null pointer");
+    if ((uint64_t)workspace_bytes < (uint64_t)need || ((uintptr_t)workspace & 3))
+        return fail(FV_ERR_INVALID_ARG, "stft_magnitude_bins_grad: workspace of %zu bytes, needs %lld (4-byte "
+                    "aligned)", workspace_bytes, (long long)need);
+    const auto overlaps = [&](const void* p, int64_t bytes) {
+        const uintptr_t a = (uintptr_t)gx, ae = a + (uintptr_t)B * n * sizeof(float), c = (uintptr_t)p;
+        return a < c + (uintptr_t)bytes && c < ae;
+    };
+    const int64_t gbytes = (int64_t)B * (n_fft / 2 + 1) * (1 + n / hop) * (int64_t)sizeof(float);
+    if (overlaps(x, (int64_t)B * n * (int64_t)sizeof(float)) || overlaps(gmag, gbytes) || overlaps(workspace, need))
+        return fail(FV_ERR_INVALID_ARG, "stft_magnitude_bins_grad: gx aliases x, gmag or the workspace");
+    return launch_stft_magnitude_bins_grad(x, gmag, table, B, n, n_fft, hop, win_length, gx,
+                                           static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
 int fv_grouped_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Tin,
                       int k, int stride, int pad, float slope, void* stream) {
     if (Cin < 4 || Cin % 4 || Cout < 1 || Cout % (Cin / 4) || k < 1 || stride < 1)

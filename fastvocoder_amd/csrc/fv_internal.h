@@ -457,6 +457,12 @@ int64_t stft_grad_chunks(int64_t n, int hop);   // frame-kernel blocks per utter
 int launch_stft_distance_grad(const float* x, const float* y, const float* const* tables, int B, int64_t n, int R,
                               const int* nfft, const int* hop, const int* win, const float* coef, float* gx,
                               float* ws, hipStream_t s);
+int launch_stft_grad_ola(const float* ws, const float* tab, int B, int64_t n, int nfft, int hop, int win, float* gx,
+                         hipStream_t s);   // its overlap-add gather alone, one resolution (ws: [B][T][win])
+// adjoint of the bins-major magnitude (stft_mag_grad.hip); ws: B T win floats
+int64_t stft_mag_grad_chunks(int64_t n, int hop);   // frame-kernel blocks per utterance
+int launch_stft_magnitude_bins_grad(const float* x, const float* gmag, const float* tab, int B, int64_t n, int nfft,
+                                    int hop, int win, float* gx, float* ws, hipStream_t s);
 // discriminator kernels (disc.hip)
 size_t grouped_conv_lds_bytes(int k, int s, int ocb);
 int launch_grouped_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout,

@@ -200,4 +200,16 @@ int launch_stft_distance_grad(const float* x, const float* y, const float* const
     return 0;
 }
 
+// the gather alone over one resolution's frames ws[B][T][win] (stft_mag_grad.hip): R = 1, slab 0
+int launch_stft_grad_ola(const float* ws, const float* tab, int B, int64_t n, int nfft, int hop, int win, float* gx,
+                         hipStream_t s) {
+    StftGradArgs a{};
+    a.R = 1;
+    a.res[0] = StftGradRes{tab, nfft, hop, win, 1 + n / hop, 0, 0};
+    hipLaunchKernelGGL(stft_grad_ola_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, ws, a, n,
+                       gx);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace fv

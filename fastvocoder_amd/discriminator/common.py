@@ -80,9 +80,10 @@ class NotDifferentiable:
     def differentiable(self, value):
         if value:
             raise NotImplementedError(
-                f"{type(self).__name__} is not differentiable: only the MelGAN multi-scale discriminator "
-                "(MelGANDiscriminator, MelGANMultiScaleDiscriminator) has an input gradient; the STFT-magnitude "
-                "adjoint of the STFT discriminators and the period convs of the MPD have none yet")
+                f"{type(self).__name__} is not differentiable through this attribute: only the MelGAN multi-scale "
+                "discriminator (MelGANDiscriminator, MelGANMultiScaleDiscriminator) takes it.  The generator-side "
+                "gradient through the STFT discriminators and Discriminator() comes from "
+                "fastvocoder_amd.loss.generator_adversarial_terms; the period convs of the MPD have none yet")
 
 
 class _StackGrad(torch.autograd.Function):
@@ -219,6 +220,13 @@ class ConvStack(NativeModule):
     def _stack(self, x):
         """_run_stack, through the autograd Function when the module is differentiable and x requires grad."""
         if self.differentiable and x.requires_grad and torch.is_grad_enabled():
+            return list(_StackGrad.apply(self, x))
+        return self._run_stack(x)
+
+    def _graph_stack(self, x):
+        """_run_stack on the graph of x whatever ``differentiable`` says (the graph-mode forwards behind
+        loss.generator_adversarial_terms): the same launches, the same bits."""
+        if x.requires_grad and torch.is_grad_enabled():
             return list(_StackGrad.apply(self, x))
         return self._run_stack(x)
 

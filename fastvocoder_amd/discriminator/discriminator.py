@@ -28,3 +28,15 @@ class Discriminator(NotDifferentiable, NativeModule):
         check_length(self, x.shape[-1])
         outs = self.msd(x) + self.mfd(x)
         return self.mpd(x) + outs if self.use_mpd else outs
+
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x (loss.generator_adversarial_terms): msd then mfd, as ``forward``.  Autograd
+        adds the sub-discriminators' gradients into x in the reverse of that order (a node built later runs
+        earlier): the MFD's resolutions from the last to the first, then the MSD's scales from the coarsest, each
+        through its pools, to scale 0 -- the same order, hence the same bits, on every call."""
+        if self.use_mpd:
+            raise NotImplementedError("Discriminator(use_mpd=True) has no input gradient: the period convs of the "
+                                      "MPD have no data-gradient kernel yet")
+        x = device_input(x, "x", 3, differentiable=True)
+        check_length(self, x.shape[-1])
+        return self.msd._graph_forward(x) + self.mfd._graph_forward(x)

@@ -7,6 +7,24 @@ from ..loss.stft_loss import _stft_table_host, _window_fn
 from .common import ConvStack, NotDifferentiable, check_activation, check_length, check_pad, device_input
 
 
+class _MagnitudeBins(torch.autograd.Function):
+    """fv_stft_magnitude_bins with its adjoint fv_stft_magnitude_bins_grad.  Saves the signal only: the backward
+    recomputes the spectrum (the forward's FFT code, so the clamp decisions are the forward's)."""
+
+    @staticmethod
+    def forward(ctx, x, table, geometry):
+        ctx.table, ctx.geometry = table, geometry
+        ctx.save_for_backward(x)
+        return _native.stft_magnitude_bins(x, table, *geometry)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return _native.stft_magnitude_bins_grad(x, g.to(torch.float32).contiguous(), ctx.table, *ctx.geometry), \
+            None, None
+
+
 class STFTDiscriminator(NotDifferentiable, ConvStack):
     """mfd.py:44-136: the clamped STFT magnitude (B, bins, frames) -- bins as channels, no transpose -- then a conv
     stack: reflect-padded Conv1d(bins -> channels, prod(kernel_sizes)), grouped strided downsamples (k = 6 s + 1),
@@ -54,6 +72,16 @@ class STFTDiscriminator(NotDifferentiable, ConvStack):
         mag = _native.stft_magnitude_bins(x, self._table(), self.fft_size, self.shift_size, self.win_length)
         return self._run_stack(mag)
 
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x (loss.generator_adversarial_terms): the same launches and bits, the
+        magnitude through _MagnitudeBins and the stack through _StackGrad.  The parameters are constants."""
+        x = device_input(x, "x", 2, differentiable=True)
+        check_length(self, x.shape[-1])
+        geometry = (self.fft_size, self.shift_size, self.win_length)
+        if x.requires_grad and torch.is_grad_enabled():
+            return self._graph_stack(_MagnitudeBins.apply(x, self._table(), geometry))
+        return self._run_stack(_native.stft_magnitude_bins(x, self._table(), *geometry))
+
 
 class MultiResolutionSTFTDiscriminator(NotDifferentiable, NativeModule):
     """mfd.py:139-178: one STFTDiscriminator per (fft_size, hop_size, win_length)."""
@@ -78,3 +106,12 @@ class MultiResolutionSTFTDiscriminator(NotDifferentiable, NativeModule):
         check_length(self, x.shape[-1])
         x = x.squeeze(1)
         return [f(x) for f in self.stft_discriminator]
+
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x; autograd sums the resolutions' gradients into x."""
+        x = device_input(x, "x", 3, differentiable=True)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        x = x.squeeze(1)
+        return [f._graph_forward(x) for f in self.stft_discriminator]

@@ -49,6 +49,14 @@ class MelGANDiscriminator(ConvStack):
         check_length(self, x.shape[-1])
         return self._stack(x)
 
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x whatever ``differentiable`` says (loss.generator_adversarial_terms)."""
+        x = device_input(x, "x", 3, differentiable=True)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        return self._graph_stack(x)
+
 
 class MelGANMultiScaleDiscriminator(NativeModule):
     """msd.py:121-241: ``scales`` MelGANDiscriminators, the input average-pooled between scales; weight norm applied
@@ -119,6 +127,21 @@ class MelGANMultiScaleDiscriminator(NativeModule):
         outs = []
         for i, f in enumerate(self.discriminators):
             outs += [f(x)]
+            if i + 1 < len(self.discriminators):
+                x = _AvgPool.apply(x, self._pool) if grad else _native.avg_pool1d(x, *self._pool)
+        return outs
+
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x whatever ``differentiable`` says (loss.generator_adversarial_terms): the
+        scales through _StackGrad, the pools through _AvgPool."""
+        x = device_input(x, "x", 3, differentiable=True)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        grad = x.requires_grad and torch.is_grad_enabled()
+        outs = []
+        for i, f in enumerate(self.discriminators):
+            outs += [f._graph_stack(x)]
             if i + 1 < len(self.discriminators):
                 x = _AvgPool.apply(x, self._pool) if grad else _native.avg_pool1d(x, *self._pool)
         return outs

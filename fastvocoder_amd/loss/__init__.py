@@ -4,9 +4,11 @@ come from one HIP launch per call (csrc/stft_loss.hip); there is no CPU path.  T
 setting a module's ``differentiable`` attribute gives the gradient with respect to the estimate, from fused HIP
 kernels as well (csrc/stft_loss_grad.hip).  The target and the discriminator scores have no gradient.
 ``discriminator_terms`` forms the reference's adversarial / feature-map / discriminator scores from the outputs of
-fastvocoder_amd.discriminator in one fused reduction (csrc/disc.hip)."""
-from .discriminator_loss import discriminator_terms
+fastvocoder_amd.discriminator in one fused reduction (csrc/disc.hip); ``generator_adversarial_terms`` runs a
+discriminator on an estimate that requires grad and returns the generator's adversarial and feature-map terms on its
+graph (csrc/disc_grad.hip, csrc/stft_mag_grad.hip)."""
+from .discriminator_loss import discriminator_terms, generator_adversarial_terms
 from .loss import Loss
 from .stft_loss import MultiResolutionSTFTLoss, STFTLoss, stft, stft_tables
 
-__all__ = ["Loss", "discriminator_terms", "MultiResolutionSTFTLoss", "STFTLoss", "stft", "stft_tables"]
+__all__ = ["Loss", "discriminator_terms", "generator_adversarial_terms", "MultiResolutionSTFTLoss", "STFTLoss", "stft", "stft_tables"]

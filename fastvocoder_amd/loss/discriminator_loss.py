@@ -101,6 +101,68 @@ class _Terms(torch.autograd.Function):
         return (None,) + tuple(_native.disc_score_grad(es, rs, coef, skip)) + (None,) * M
 
 
+def _adversarial(es):
+    """sum_i MSE(es[i], 1) / L as a float64 0-d tensor (fv_disc_score_sums on the score maps against themselves)."""
+    sums = torch.as_tensor(_native.disc_score_sums(es, es), dtype=torch.float64)
+    counts = torch.as_tensor([e[0].numel() for e in es], dtype=torch.float64, device=sums.device)
+    return (sums[..., 1].sum(dim=1) / (counts * sums.shape[1])).sum() / len(es)
+
+
+class _Adversarial(torch.autograd.Function):
+    """The adversarial term of the score maps alone (generator_adversarial_terms with real=None): no feature map is
+    reduced in the forward or given a gradient in the backward."""
+
+    @staticmethod
+    def forward(ctx, *es):
+        ctx.save_for_backward(*es)
+        return _adversarial(list(es))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        es = list(ctx.saved_tensors)
+        g, L, B = float(g), len(es), es[0].shape[0]
+        coef = [(0.0, g / (L * e[0].numel() * B), 0.0) for e in es]
+        return tuple(_native.disc_score_grad(es, es, coef, [not n for n in ctx.needs_input_grad]))
+
+
+def generator_adversarial_terms(discriminator, estimate, real=None):
+    """The generator's adversarial and feature-map terms (bin/train.py:97-120) as one call, attached to the graph of
+    ``estimate``: {"adversarial", "feature_map"} as 0-d fp32 device tensors with the reference's divisors
+    (len(est_p[0]) - 1 for every list).  ``estimate`` and ``real`` are (B, 1, T) fp32 device tensors ((B, T) for an
+    STFTDiscriminator, as its forward takes them); ``estimate`` may require grad.  The discriminator's graph-mode
+    forward runs on ``estimate`` (the launches and bits of its plain forward, the input gradient from
+    csrc/disc_grad.hip and csrc/stft_mag_grad.hip), its plain forward on ``real`` under torch.no_grad().  With
+    ``real=None`` (the reference's use_feature_map_loss = False) only "adversarial" is returned and D(real) is not
+    run.  The module's ``differentiable`` attribute is not consulted; its parameters are constants (``.grad`` stays
+    None).  Under torch.no_grad(), or when ``estimate`` does not require grad, the same values come back with no
+    graph.  Accepted: MelGANDiscriminator, MelGANMultiScaleDiscriminator, STFTDiscriminator,
+    MultiResolutionSTFTDiscriminator and Discriminator(); the period discriminators are refused."""
+    from ..discriminator import Discriminator, DiscriminatorP, MultiPeriodDiscriminator
+    if isinstance(discriminator, (DiscriminatorP, MultiPeriodDiscriminator)) or \
+            (isinstance(discriminator, Discriminator) and discriminator.use_mpd):
+        raise NotImplementedError(f"generator_adversarial_terms: {type(discriminator).__name__} holds the period "
+                                  "convs of the MPD, which have no input gradient yet")
+    graph = getattr(discriminator, "_graph_forward", None)
+    if graph is None:
+        raise TypeError(f"generator_adversarial_terms: {type(discriminator).__name__} is not a fastvocoder_amd "
+                        "discriminator with an input gradient")
+    est_p = graph(estimate)
+    if torch.is_tensor(est_p[0]):
+        est_p = [est_p]
+    if real is None:      # the score maps alone: adversarial = sum_i MSE(score_i, 1) / L reads nothing else
+        es = [lst[-1].to(torch.float32).contiguous() for lst in est_p]
+        if torch.is_grad_enabled() and any(e.requires_grad for e in es):
+            return {"adversarial": _Adversarial.apply(*es).float()}
+        return {"adversarial": _adversarial(es).float()}
+    with torch.no_grad():
+        p = discriminator(real)
+    if torch.is_tensor(p[0]):
+        p = [p]
+    terms = discriminator_terms(est_p, p, differentiable=True)
+    return {"adversarial": terms["adversarial"], "feature_map": terms["feature_map"]}
+
+
 def discriminator_terms(est_p, p, per_utterance=False, differentiable=False):
     """The reference's adversarial, feature-map, real, fake and discriminator scores (module docstring) of the
     discriminator outputs est_p = D(estimate) and p = D(real), nested lists of device maps of matching shapes.

@@ -621,6 +621,29 @@ int fv_stft_magnitude_bins(const float* x, float* mag, const float* table, int B
                            int win_length, void* stream);
 
 /*
+ * The adjoint of fv_stft_magnitude_bins: from gmag = dL/dmag, fp32 device [B, n_fft/2 + 1, T] in that function's
+ * layout (T = 1 + n / hop), and the signal x [B, n] it was computed from, gx = dL/dx, fp32 device [B, n], all of it
+ * written.  Per bin, with (re, im) the spectrum of frame t of x (the forward's own FFT code, so the clamp decisions
+ * are the forward's),
+ *   dL/d(re, im) = gmag[b, k, t] (re, im) / sqrt(max(re^2 + im^2, 1e-7)) where re^2 + im^2 > 1e-7, else 0
+ * then, as in fv_stft_distance_grad, the adjoint of the windowed one-sided real FFT (n_fft * irfft of the bins with
+ * the interior bins halved, times the window), the overlap-add of the frames at `hop` and the reflect padding folded
+ * back.  gmag == 0 gives exactly 0; so does x == 0 (every bin is clamped).  table: as for fv_stft_magnitude.
+ * Two launches on `stream`: one wave per frame (a block of 8 waves owns 16 consecutive frames and stages their gmag
+ * tile in LDS with 64-byte runs per bin) writes the frame's win_length taps to `workspace`; then the gather of
+ * fv_stft_distance_grad sums, frames in increasing order, the taps that land on each sample.  No atomics: identical
+ * calls return identical bits, and a row's result does not depend on B or on the other rows.  workspace: device
+ * memory of at least fv_stft_magnitude_bins_grad_workspace_bytes(...) = 4 B T win_length bytes (4-byte aligned).
+ * Parameter checks and error codes as fv_stft_magnitude_bins (FV_ERR_UNSUPPORTED, FV_ERR_INVALID_ARG), before any
+ * launch; a small workspace, or gx overlapping x, gmag or the workspace, returns FV_ERR_INVALID_ARG.  The
+ * workspace function returns a negative FV_ERR_* code for arguments fv_stft_magnitude_bins_grad would refuse.
+ */
+int64_t fv_stft_magnitude_bins_grad_workspace_bytes(int B, int64_t n, int n_fft, int hop, int win_length);
+int fv_stft_magnitude_bins_grad(const float* x, const float* gmag, const float* table, int B, int64_t n, int n_fft,
+                                int hop, int win_length, float* gx, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/*
  * The discriminators' strided grouped conv (model/discriminator/msd.py:67-80, mfd.py:85-98: torch.nn.Conv1d with
  * groups = Cin / 4, zero padding, then LeakyReLU):
  *     y[b, c, t] = lrelu( bias[c] + sum_{ci<4, j<k} w[c, ci, j] * x[b, 4 (c / (Cout/G)) + ci, t*stride + j - pad], slope )

@@ -1,4 +1,4 @@
-"""Registers, spills, scratch and LDS of every kernel in libfastvocoder_hip.so (from the code object's metadata notes).
+"""Registers, spills, scratch and LDS bytes of every kernel in libfastvocoder_hip.so (from the code object's metadata notes).
 
     python tools/kernel_resources.py [filter]
 
@@ -38,12 +38,12 @@ def kernels_of(obj):
 
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
-    print(f"{'vgpr':>5} {'vspill':>6} {'sspill':>6} {'scratch':>7}  kernel")
+    print(f"{'vgpr':>5} {'vspill':>6} {'sspill':>6} {'scratch':>7} {'lds':>7}  kernel")
     for obj in sorted(glob.glob(os.path.join(ROOT, "fastvocoder_amd", "build", "*.o"))):
         for name, vg, vs, ss, scr, lds in kernels_of(obj):
             short = re.sub(r"^void ", "", name).split("(")[0]
             if flt in short:
-                print(f"{vg:>5} {vs:>6} {ss:>6} {scr:>7}  {short}")
+                print(f"{vg:>5} {vs:>6} {ss:>6} {scr:>7} {lds:>7}  {short}")
 
 
 if __name__ == "__main__":
