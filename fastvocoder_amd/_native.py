@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "mpd.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "mpd.hip", "mpd_grad.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -269,6 +269,11 @@ def lib():
     L.fv_packed_period_conv_floats.restype = i64
     L.fv_pack_period_conv.argtypes = [vp, vp, i, i, vp]
     L.fv_period_conv.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, vp]
+    L.fv_packed_period_conv_grad_floats.argtypes = [i, i]
+    L.fv_packed_period_conv_grad_floats.restype = i64
+    L.fv_pack_period_conv_grad.argtypes = [vp, vp, i, i, vp]
+    L.fv_period_conv_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
+    L.fv_mpd_first_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i64, i, f, vp]
     L.fv_fold_batchnorm_conv.argtypes = [vp, vp, vp, vp, vp, vp, f, vp, vp, i, i, i, vp]
     L.fv_packed_upsample_conv1d_floats.argtypes = [i, i, i, i, i]
     L.fv_packed_upsample_conv1d_floats.restype = i64
@@ -1238,6 +1243,65 @@ def period_conv(x, packed, bias, cout, slope=0.1):
         check(lib().fv_period_conv(_ptr(x, "x"), _ptr(packed, "packed"), _ptr(bias, "bias", True), _ptr(out, "out"),
                                    B, cin, int(cout), H, p, float(slope), stream))
     return out
+
+
+def pack_period_conv_grad(w):
+    """Folded weight [Cout,Cin,5] of a strided period conv -> the image fv_period_conv_input_grad reads (flat
+    tensor)."""
+    w = w.detach().contiguous().float()
+    if w.dim() != 3 or w.shape[2] != 5:
+        raise NativeError(f"pack_period_conv_grad: w must be [Cout, Cin, 5], got {tuple(w.shape)}")
+    cout, cin, _ = w.shape
+    out = torch.empty(max(lib().fv_packed_period_conv_grad_floats(cout, cin), 1), dtype=torch.float32,
+                      device=w.device)
+    with _on(w) as stream:
+        check(lib().fv_pack_period_conv_grad(_ptr(w, "w"), _ptr(out), cout, cin, stream))
+    return out
+
+
+def _period_grad_like(name, g_up, g_map, y):
+    like = g_up if g_up is not None else g_map
+    if like is None or like.dim() != 4:
+        raise NativeError(f"{name}: a gradient [B,Cout,Hout,p] expected, got "
+                          f"{None if like is None else tuple(like.shape)}")
+    for t in (g_up, g_map, y):
+        if t is not None and t.shape != like.shape:
+            raise NativeError(f"{name}: shapes {tuple(t.shape)} and {tuple(like.shape)} differ")
+    return like
+
+
+def period_conv_input_grad(g_up, g_map, y, packed, cin, H, slope=0.1):
+    """The gradient of period_conv with respect to its input x [B,cin,H,p] (fv_period_conv_input_grad, one launch on
+    the fp32 matrix cores): g_up / g_map / y [B,Cout,(H-1)//3+1,p] as disc_map_grad takes them (the mask is applied
+    while the gradient is staged), packed = pack_period_conv_grad(w) -> dx [B,cin,H,p]."""
+    like = _period_grad_like("period_conv_input_grad", g_up, g_map, y)
+    B, cout, hout, p = like.shape
+    if H < 1 or hout != (H - 1) // 3 + 1:
+        raise NativeError(f"period_conv_input_grad: {hout} output rows do not belong to an input of {H} rows")
+    dx = torch.empty((B, int(cin), int(H), p), dtype=torch.float32, device=like.device)
+    with _on(g_up, g_map, y, packed, dx) as stream:
+        check(lib().fv_period_conv_input_grad(_ptr(g_up, "g_up", True), _ptr(g_map, "g_map", True),
+                                              _ptr(y, "y", True), _ptr(packed, "packed"), _ptr(dx), B, int(cin), cout,
+                                              int(H), p, float(slope), stream))
+    return dx
+
+
+def mpd_first_input_grad(g_up, g_map, y0, w, T, slope=0.1):
+    """The gradient of mpd_conv_first with respect to the waveform x [B,1,T] (fv_mpd_first_input_grad, one launch):
+    g_up / g_map / y0 [B,32,H1,p] as disc_map_grad takes them, w [32,5] the folded weight -> dx [B,1,T], the adjoint
+    of the reflect tail folded in."""
+    like = _period_grad_like("mpd_first_input_grad", g_up, g_map, y0)
+    B, c, h1, p = like.shape
+    H = (T + mpd_reflect_tail(T, p)) // p if p > 0 else 0
+    if c != 32 or tuple(w.shape) != (32, 5) or T < 1 or h1 != (H - 1) // 3 + 1:
+        raise NativeError(f"mpd_first_input_grad: a gradient [B,32,H1,p] of a waveform of {T} samples and w [32,5] "
+                          f"expected, got {tuple(like.shape)} and {tuple(w.shape)}")
+    dx = torch.empty((B, 1, int(T)), dtype=torch.float32, device=like.device)
+    with _on(g_up, g_map, y0, w, dx) as stream:
+        check(lib().fv_mpd_first_input_grad(_ptr(g_up, "g_up", True), _ptr(g_map, "g_map", True),
+                                            _ptr(y0, "y0", True), _ptr(w, "w"), _ptr(dx), B, int(T), p, float(slope),
+                                            stream))
+    return dx
 
 
 DISC_MAX_MAPS = 48      # FV_DISC_MAX_MAPS: maps per fv_disc_score_sums call

@@ -83,7 +83,8 @@ class NotDifferentiable:
                 f"{type(self).__name__} is not differentiable through this attribute: only the MelGAN multi-scale "
                 "discriminator (MelGANDiscriminator, MelGANMultiScaleDiscriminator) takes it.  The generator-side "
                 "gradient through the STFT discriminators and Discriminator() comes from "
-                "fastvocoder_amd.loss.generator_adversarial_terms; the period convs of the MPD have none yet")
+                "fastvocoder_amd.loss.generator_adversarial_terms, for the period convs of the MPD with its keyword "
+                "period_grad=True")
 
 
 class _StackGrad(torch.autograd.Function):

@@ -30,13 +30,12 @@ class Discriminator(NotDifferentiable, NativeModule):
         return self.mpd(x) + outs if self.use_mpd else outs
 
     def _graph_forward(self, x):
-        """``forward`` on the graph of x (loss.generator_adversarial_terms): msd then mfd, as ``forward``.  Autograd
-        adds the sub-discriminators' gradients into x in the reverse of that order (a node built later runs
-        earlier): the MFD's resolutions from the last to the first, then the MSD's scales from the coarsest, each
-        through its pools, to scale 0 -- the same order, hence the same bits, on every call."""
-        if self.use_mpd:
-            raise NotImplementedError("Discriminator(use_mpd=True) has no input gradient: the period convs of the "
-                                      "MPD have no data-gradient kernel yet")
+        """``forward`` on the graph of x (loss.generator_adversarial_terms): msd then mfd, as ``forward``, with
+        ``use_mpd`` mpd first.  Autograd adds the sub-discriminators' gradients into x in the reverse of that order
+        (a node built later runs earlier): the MFD's resolutions from the last to the first, then the MSD's scales
+        from the coarsest, each through its pools, to scale 0, then the MPD's periods from 11 down to 2 -- the same
+        order, hence the same bits, on every call."""
         x = device_input(x, "x", 3, differentiable=True)
         check_length(self, x.shape[-1])
-        return self.msd._graph_forward(x) + self.mfd._graph_forward(x)
+        mpd = self.mpd._graph_forward(x) if self.use_mpd else []
+        return mpd + self.msd._graph_forward(x) + self.mfd._graph_forward(x)

@@ -26,6 +26,25 @@ def period_heights(T, period, stride=3, layers=4):
     return n_pad, hs
 
 
+class _PeriodGrad(torch.autograd.Function):
+    """DiscriminatorP._run_layers with the gradient with respect to the waveform: the outputs are the six maps, the
+    saved tensors the input and the maps.  The parameters are constants."""
+
+    @staticmethod
+    def forward(ctx, module, x):
+        outs = module._run_layers(x)
+        ctx.module = module
+        ctx.set_materialize_grads(False)                   # a map without a gradient arrives as None, not as zeros
+        ctx.save_for_backward(x, *outs)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, *outs = ctx.saved_tensors
+        return None, ctx.module._input_grad(x, outs, grads)
+
+
 class DiscriminatorP(NotDifferentiable, NativeModule):
     """mpd.py:131-164."""
 
@@ -80,12 +99,32 @@ class DiscriminatorP(NotDifferentiable, NativeModule):
         self._fv_plans["layers"] = (self._fv_state(), layers)
         return layers
 
-    def forward(self, x):
-        """x (B, 1, T) -> (score [B, H_6 p], the six feature maps [B, C, H_l, p])."""
-        x = device_input(x, "x", 3)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
+    def _native_grad_layers(self):
+        """Per layer what its input gradient reads: layer 0 the folded weight [32, 5] (the forward's tensor); layers
+        1-3 packed for fv_period_conv_input_grad; layers 4-5 the packed W'[ci, co, j] = W[co, ci, k-1-j] of
+        fv_conv1d_fused.  Cached against the module state."""
+        state = self._fv_state()
+        hit = self._fv_plans.get("grad_layers")
+        if hit is not None and hit[0] == state:
+            return hit[1]
+        self._device()
+        fwd = self._native_layers()
+        with torch.no_grad():
+            layers = [fwd[0][0]]
+            for j, conv in enumerate(list(self.convs) + [self.conv_post]):
+                if j == 0:
+                    continue
+                w = effective_weight(conv)
+                w = w.reshape(w.shape[0], w.shape[1], w.shape[2])
+                if j < 4:
+                    layers.append(_native.pack_period_conv_grad(w))
+                else:
+                    layers.append(_native.pack_conv1d(w.flip(2).transpose(0, 1).contiguous()))
+        self._fv_plans["grad_layers"] = (self._fv_state(), layers)
+        return layers
+
+    def _run_layers(self, x):
+        """x [B, 1, T] fp32 device -> the six feature maps [B, C, H_l, p]: one launch per layer."""
         p = self.period
         layers = self._native_layers()
         x = _native.mpd_conv_first(x, layers[0][0], layers[0][1], p, LRELU_SLOPE)
@@ -99,7 +138,56 @@ class DiscriminatorP(NotDifferentiable, NativeModule):
         fmap.append(x.view(B, 1024, H, p))
         x = _native.conv1d_fused(x, layers[5][0], layers[5][1], 1, 3, dil=p, pad=p, pad_mode=PAD_ZERO)
         fmap.append(x.view(B, 1, H, p))
-        return x.view(B, H * p), fmap
+        return fmap
+
+    def _input_grad(self, x, outs, grads):
+        """d/dx of sum_l <grads[l], outs[l]> (None = zero), walking the six layers downwards: conv_post and the
+        dilated 1024 -> 1024 layer as fv_conv1d_fused on flipped, transposed weights behind fv_disc_map_grad, the
+        three strided layers as fv_period_conv_input_grad and the first as fv_mpd_first_input_grad, both of which
+        apply the LeakyReLU mask of the layer's stored output while they stage the gradient."""
+        p = self.period
+        layers = self._native_grad_layers()
+        gm = [None if g is None else g.to(torch.float32).contiguous() for g in grads]
+        B, _, H, _ = outs[5].shape
+        g_up = None
+        if gm[5] is not None:                              # conv_post: no activation; its map's gradient alone
+            g_up = _native.conv1d_fused(gm[5].view(B, 1, H * p), layers[5], None, 1024, 3, dil=p, pad=p,
+                                        pad_mode=PAD_ZERO).view(B, 1024, H, p)
+        if g_up is not None or gm[4] is not None:
+            g_pre = _native.disc_map_grad(g_up, gm[4], outs[4], LRELU_SLOPE)
+            g_up = _native.conv1d_fused(g_pre.view(B, 1024, H * p), layers[4], None, 1024, 5, dil=p, pad=2 * p,
+                                        pad_mode=PAD_ZERO).view(B, 1024, H, p)
+        for j in (3, 2, 1):
+            if g_up is None and gm[j] is None:
+                continue
+            g_up = _native.period_conv_input_grad(g_up, gm[j], outs[j], layers[j], self.convs[j].in_channels,
+                                                  outs[j - 1].shape[2], LRELU_SLOPE)
+        if g_up is None and gm[0] is None:
+            return torch.zeros_like(x)
+        return _native.mpd_first_input_grad(g_up, gm[0], outs[0], layers[0], x.shape[-1], LRELU_SLOPE)
+
+    def forward(self, x):
+        """x (B, 1, T) -> (score [B, H_6 p], the six feature maps [B, C, H_l, p])."""
+        x = device_input(x, "x", 3)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        fmap = self._run_layers(x)
+        return fmap[5].flatten(1), fmap
+
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x (loss.generator_adversarial_terms(..., period_grad=True)): the same launches,
+        the same bits, through an autograd Function whose backward is the input gradient of csrc/mpd_grad.hip.  The
+        parameters are constants of that graph: their ``.grad`` stays None."""
+        x = device_input(x, "x", 3, differentiable=True)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        if x.requires_grad and torch.is_grad_enabled():
+            fmap = list(_PeriodGrad.apply(self, x))
+        else:
+            fmap = self._run_layers(x)
+        return fmap[5].flatten(1), fmap
 
 
 class MultiPeriodDiscriminator(NotDifferentiable, NativeModule):
@@ -121,5 +209,19 @@ class MultiPeriodDiscriminator(NotDifferentiable, NativeModule):
         outs = []
         for d in self.discriminators:
             score, fmap = d(x)
+            outs.append(fmap + [score.unsqueeze(1)])
+        return outs
+
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x: the periods in the order of ``forward``.  Autograd adds their gradients
+        into x in the reverse of that order (a node built later runs earlier), period 11 first and period 2 last:
+        the same order, hence the same bits, on every call."""
+        x = device_input(x, "x", 3, differentiable=True)
+        if x.shape[1] != 1:
+            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+        check_length(self, x.shape[-1])
+        outs = []
+        for d in self.discriminators:
+            score, fmap = d._graph_forward(x)
             outs.append(fmap + [score.unsqueeze(1)])
         return outs

@@ -126,29 +126,35 @@ class _Adversarial(torch.autograd.Function):
         return tuple(_native.disc_score_grad(es, es, coef, [not n for n in ctx.needs_input_grad]))
 
 
-def generator_adversarial_terms(discriminator, estimate, real=None):
+def generator_adversarial_terms(discriminator, estimate, real=None, *, period_grad=False):
     """The generator's adversarial and feature-map terms (bin/train.py:97-120) as one call, attached to the graph of
     ``estimate``: {"adversarial", "feature_map"} as 0-d fp32 device tensors with the reference's divisors
     (len(est_p[0]) - 1 for every list).  ``estimate`` and ``real`` are (B, 1, T) fp32 device tensors ((B, T) for an
     STFTDiscriminator, as its forward takes them); ``estimate`` may require grad.  The discriminator's graph-mode
     forward runs on ``estimate`` (the launches and bits of its plain forward, the input gradient from
-    csrc/disc_grad.hip and csrc/stft_mag_grad.hip), its plain forward on ``real`` under torch.no_grad().  With
+    csrc/disc_grad.hip, csrc/stft_mag_grad.hip and csrc/mpd_grad.hip), its plain forward on ``real`` under
+    torch.no_grad().  With
     ``real=None`` (the reference's use_feature_map_loss = False) only "adversarial" is returned and D(real) is not
     run.  The module's ``differentiable`` attribute is not consulted; its parameters are constants (``.grad`` stays
     None).  Under torch.no_grad(), or when ``estimate`` does not require grad, the same values come back with no
     graph.  Accepted: MelGANDiscriminator, MelGANMultiScaleDiscriminator, STFTDiscriminator,
-    MultiResolutionSTFTDiscriminator and Discriminator(); the period discriminators are refused."""
+    MultiResolutionSTFTDiscriminator and Discriminator().  The modules that hold the period convs of the MPD
+    (DiscriminatorP, MultiPeriodDiscriminator, Discriminator(use_mpd=True)) are refused unless ``period_grad=True``
+    is passed: their gradient is opt-in, and for every other module the keyword changes nothing."""
     from ..discriminator import Discriminator, DiscriminatorP, MultiPeriodDiscriminator
     if isinstance(discriminator, (DiscriminatorP, MultiPeriodDiscriminator)) or \
             (isinstance(discriminator, Discriminator) and discriminator.use_mpd):
-        raise NotImplementedError(f"generator_adversarial_terms: {type(discriminator).__name__} holds the period "
-                                  "convs of the MPD, which have no input gradient yet")
+        if not period_grad:
+            raise NotImplementedError(f"generator_adversarial_terms: {type(discriminator).__name__} holds the period "
+                                      "convs of the MPD, whose input gradient is opt-in: pass period_grad=True")
     graph = getattr(discriminator, "_graph_forward", None)
     if graph is None:
         raise TypeError(f"generator_adversarial_terms: {type(discriminator).__name__} is not a fastvocoder_amd "
                         "discriminator with an input gradient")
     est_p = graph(estimate)
-    if torch.is_tensor(est_p[0]):
+    if isinstance(discriminator, DiscriminatorP):      # (score, maps) -> one list, the score last
+        est_p = [est_p[1] + [est_p[0].unsqueeze(1)]]
+    elif torch.is_tensor(est_p[0]):
         est_p = [est_p]
     if real is None:      # the score maps alone: adversarial = sum_i MSE(score_i, 1) / L reads nothing else
         es = [lst[-1].to(torch.float32).contiguous() for lst in est_p]
@@ -157,7 +163,9 @@ def generator_adversarial_terms(discriminator, estimate, real=None):
         return {"adversarial": _adversarial(es).float()}
     with torch.no_grad():
         p = discriminator(real)
-    if torch.is_tensor(p[0]):
+    if isinstance(discriminator, DiscriminatorP):
+        p = [p[1] + [p[0].unsqueeze(1)]]
+    elif torch.is_tensor(p[0]):
         p = [p]
     terms = discriminator_terms(est_p, p, differentiable=True)
     return {"adversarial": terms["adversarial"], "feature_map": terms["feature_map"]}

@@ -768,6 +768,44 @@ int fv_pack_period_conv(const float* w, float* packed, int Cout, int Cin, void* 
 int fv_period_conv(const float* x, const float* packed, const float* bias, float* y, int B, int Cin, int Cout, int H,
                    int period, float slope, void* stream);
 
+/*
+ * The input gradient of the multi-period discriminator (model/discriminator/mpd.py:131-164) under the adversarial and
+ * feature-map terms of bin/train.py:97-117; additions of ABI 18, no existing entry changes.  Exact fp32, no atomics:
+ * every element is summed by one lane in a fixed order, so identical calls return identical bits and a row's values do
+ * not depend on B or on the grid.  Both entries launch on `stream` and own no device memory.  The two stride-1 layers
+ * (1024 -> 1024 at dilation p, conv_post) need no entry of their own: their data gradients are fv_conv1d_fused on
+ * flipped, transposed weights (dilation p, padding 2 p and p) behind fv_disc_map_grad.
+ *
+ * fv_period_conv_input_grad: the data gradient of fv_period_conv with fv_disc_map_grad as its load stage,
+ *     dx[b, ci, r, c] = sum_co sum_{j : (r + 2 - j) % 3 == 0, 0 <= (r + 2 - j) / 3 < Hout}
+ *                         w[co, ci, j] * g_pre[b, co, (r + 2 - j) / 3, c]
+ * g_up, g_map, y [B, Cout, Hout, period], Hout = (H - 1) / 3 + 1, as fv_disc_map_grad takes them (either gradient
+ * may be NULL, not both; y is the layer's stored output, NULL with slope = 1); the masked gradient
+ * g_pre = (g_up + g_map) * (y > 0 ? 1 : slope) is never written to memory.  packed: fv_pack_period_conv_grad of the
+ * folded weight [Cout, Cin, 5] (fv_packed_period_conv_grad_floats(Cout, Cin) floats; 0 for an unsupported shape).
+ * dx [B, Cin, H, period], all of it written.  Evaluated polyphase as an implicit GEMM on the exact-fp32 matrix
+ * instructions (M = Cin, N = flattened positions, K = Cout x the taps of a phase): with r + 2 = 3 m + ph an input row
+ * meets tap ph at output row m and tap ph + 3 at row m - 1; each element is summed over the pairs (co, co + 1)
+ * ascending, tap ph before tap ph + 3.  One launch.
+ *
+ * fv_mpd_first_input_grad: the gradient of fv_mpd_conv_first down to the waveform, the adjoint of the reflect tail
+ * folded in.  g_up, g_map, y0 [B, 32, H1, period] as above; w [32, 5] (the folded weight); dx [B, T]:
+ *     dx[b, i] = P(i) + (T - 1 - n_pad <= i <= T - 2 ? P(2 (T - 1) - i) : 0)
+ * P(n): the gradient of the padded flat sample n = (r, c), summed co ascending, then the taps of n's phase ascending;
+ * the sample's own position first, then its mirror.  One thread per sample, VALU.  One launch.
+ *
+ * Supported: period 2, 3, 5, 7 or 11; (Cin, Cout) = (32, 128), (128, 512) or (512, 1024); anything else returns
+ * FV_ERR_UNSUPPORTED (checked before everything else: nothing is launched).  Both gradients NULL, another null
+ * pointer, slope != 1 without y, dx aliasing an input, B outside 1..65535, H < 1, T < 1, n_pad >= T or 2^31
+ * flattened samples and more return FV_ERR_INVALID_ARG.
+ */
+int64_t fv_packed_period_conv_grad_floats(int Cout, int Cin);
+int fv_pack_period_conv_grad(const float* w, float* packed, int Cout, int Cin, void* stream);
+int fv_period_conv_input_grad(const float* g_up, const float* g_map, const float* y, const float* packed, float* dx,
+                              int B, int Cin, int Cout, int H, int period, float slope, void* stream);
+int fv_mpd_first_input_grad(const float* g_up, const float* g_map, const float* y0, const float* w, float* dx, int B,
+                            int64_t T, int period, float slope, void* stream);
+
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
  * ------------------------------------------------------------------ */
