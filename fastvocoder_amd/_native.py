@@ -1259,11 +1259,14 @@ def pack_period_conv_grad(w):
     return out
 
 
-def _period_grad_like(name, g_up, g_map, y):
+def _grad_like(name, g_up, g_map, y, dims=None):
+    """The first of g_up / g_map that is given, after the check every input-gradient wrapper makes: at least one of
+    the two is given (with ``dims`` dimensions where the wrapper names a rank), and g_up / g_map / y have one shape."""
     like = g_up if g_up is not None else g_map
-    if like is None or like.dim() != 4:
-        raise NativeError(f"{name}: a gradient [B,Cout,Hout,p] expected, got "
-                          f"{None if like is None else tuple(like.shape)}")
+    if like is None:
+        raise NativeError(f"{name}: g_up and g_map are both None")
+    if dims is not None and like.dim() != dims:
+        raise NativeError(f"{name}: a gradient of {dims} dimensions expected, got {tuple(like.shape)}")
     for t in (g_up, g_map, y):
         if t is not None and t.shape != like.shape:
             raise NativeError(f"{name}: shapes {tuple(t.shape)} and {tuple(like.shape)} differ")
@@ -1274,7 +1277,7 @@ def period_conv_input_grad(g_up, g_map, y, packed, cin, H, slope=0.1):
     """The gradient of period_conv with respect to its input x [B,cin,H,p] (fv_period_conv_input_grad, one launch on
     the fp32 matrix cores): g_up / g_map / y [B,Cout,(H-1)//3+1,p] as disc_map_grad takes them (the mask is applied
     while the gradient is staged), packed = pack_period_conv_grad(w) -> dx [B,cin,H,p]."""
-    like = _period_grad_like("period_conv_input_grad", g_up, g_map, y)
+    like = _grad_like("period_conv_input_grad", g_up, g_map, y, 4)
     B, cout, hout, p = like.shape
     if H < 1 or hout != (H - 1) // 3 + 1:
         raise NativeError(f"period_conv_input_grad: {hout} output rows do not belong to an input of {H} rows")
@@ -1290,7 +1293,7 @@ def mpd_first_input_grad(g_up, g_map, y0, w, T, slope=0.1):
     """The gradient of mpd_conv_first with respect to the waveform x [B,1,T] (fv_mpd_first_input_grad, one launch):
     g_up / g_map / y0 [B,32,H1,p] as disc_map_grad takes them, w [32,5] the folded weight -> dx [B,1,T], the adjoint
     of the reflect tail folded in."""
-    like = _period_grad_like("mpd_first_input_grad", g_up, g_map, y0)
+    like = _grad_like("mpd_first_input_grad", g_up, g_map, y0, 4)
     B, c, h1, p = like.shape
     H = (T + mpd_reflect_tail(T, p)) // p if p > 0 else 0
     if c != 32 or tuple(w.shape) != (32, 5) or T < 1 or h1 != (H - 1) // 3 + 1:
@@ -1338,12 +1341,7 @@ def disc_score_sums(es, rs):
 def disc_map_grad(g_up, g_map, y, slope=1.0):
     """(g_up + g_map) * (y > 0 ? 1 : slope), elementwise (fv_disc_map_grad, one launch): the gradient in front of a
     layer's LeakyReLU.  g_up or g_map may be None; y (the layer's output) may be None when slope is 1."""
-    like = g_up if g_up is not None else g_map
-    if like is None:
-        raise NativeError("disc_map_grad: g_up and g_map are both None")
-    for t in (g_up, g_map, y):
-        if t is not None and t.shape != like.shape:
-            raise NativeError(f"disc_map_grad: shapes {tuple(t.shape)} and {tuple(like.shape)} differ")
+    like = _grad_like("disc_map_grad", g_up, g_map, y)
     out = torch.empty_like(like)
     with _on(g_up, g_map, y, out) as stream:
         check(lib().fv_disc_map_grad(_ptr(g_up, "g_up", True), _ptr(g_map, "g_map", True), _ptr(y, "y", True),
@@ -1355,14 +1353,11 @@ def grouped_conv1d_input_grad(g_up, g_map, y, w, cin, tin, k, stride, pad, slope
     """The gradient of grouped_conv1d with respect to its input x [B, cin, tin] (fv_grouped_conv1d_input_grad, one
     launch): g_up / g_map / y [B,Cout,Tout] as disc_map_grad takes them (the mask is applied while the gradient is
     staged), w [Cout,4,k] the forward's weight -> dx [B, cin, tin]."""
-    like = g_up if g_up is not None else g_map
-    if like is None or like.dim() != 3 or w.dim() != 3 or w.shape[1:] != (4, k) or w.shape[0] != like.shape[1]:
+    like = _grad_like("grouped_conv1d_input_grad", g_up, g_map, y, 3)
+    if w.dim() != 3 or w.shape[1:] != (4, k) or w.shape[0] != like.shape[1]:
         raise NativeError(f"grouped_conv1d_input_grad: a gradient [B,Cout,Tout] and w [Cout,4,{k}] expected, got "
-                          f"{None if like is None else tuple(like.shape)} and {tuple(w.shape)}")
+                          f"{tuple(like.shape)} and {tuple(w.shape)}")
     B, cout, tout = like.shape
-    for t in (g_up, g_map, y):
-        if t is not None and t.shape != like.shape:
-            raise NativeError(f"grouped_conv1d_input_grad: shapes {tuple(t.shape)} and {tuple(like.shape)} differ")
     if stride > 0 and tin + 2 * pad >= k and tout != (tin + 2 * pad - k) // stride + 1:
         raise NativeError(f"grouped_conv1d_input_grad: {tout} output times do not belong to an input of {tin} samples")
     dx = torch.empty((B, int(cin), max(int(tin), 0)), dtype=torch.float32, device=like.device)

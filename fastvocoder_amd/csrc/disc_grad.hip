@@ -11,7 +11,7 @@
 // consecutive words for every tap -- and the weights as ws[oc][j][ci], one float4 that every lane reads (a broadcast).
 // The sum runs oc ascending, then j ascending (m ascending), one fmaf each.  Groups with more output channels than the
 // LDS holds at once are staged in chunks of `occ` channels, in the same order.  The staging applies the leaky-ReLU
-// mask of the layer that produced the gradient (map_grad below), so the masked [B, Cout, Tout] gradient never exists
+// mask of the layer that produced the gradient (map_grad of fv_internal.h), so the masked [B, Cout, Tout] gradient never exists
 // in memory.  Times outside [0, Tout) are staged as 0: input positions past the last window come out as exactly 0.
 //
 // map_grad_kernel: g_pre = (g_up + g_map) * (y > 0 ? 1 : slope), elementwise.
@@ -21,14 +21,6 @@
 #include "fv_internal.h"
 
 namespace fv {
-
-__device__ __forceinline__ float map_grad(const float* __restrict__ g_up, const float* __restrict__ g_map,
-                                          const float* __restrict__ y, size_t at, float slope) {
-    float g = g_up ? g_up[at] : 0.f;
-    if (g_map) g = g_up ? g + g_map[at] : g_map[at];
-    if (y) g *= y[at] > 0.f ? 1.f : slope;
-    return g;
-}
 
 constexpr int kGradU = 2;                            // values of q per thread (strided by the block)
 

@@ -327,6 +327,20 @@ int launch_pack_convtn(const float* w, float* packed, const float* inv, int* ran
 inline bool convk_shape(int C, int k, int dil) { return (C == 32 || C == 64 || C == 128 || C == 256) && k == 3 && (dil == 1 || dil == 3 || dil == 9); }
 inline int convk_tile_columns(int C) { return C == 256 ? 32 : 256 / (C / 32); }   // a block holds every row of a column tile
 int launch_convk(const PairParams& p, int C, int dil, hipStream_t s);
+// the multi-period discriminator (mpd.hip, mpd_grad.hip): the periods its kernels are built for, the output rows of a
+// period conv (5 taps, stride 3, padding 2) over H rows, and DiscriminatorP's view of a waveform of T >= 1 samples: the
+// reflect tail n_pad that makes T + n_pad a multiple of the period, the rows H of the [H, period] view and the rows H1
+// of the first conv's output
+inline bool mpd_period_ok(int p) { return p == 2 || p == 3 || p == 5 || p == 7 || p == 11; }
+inline int64_t period_conv_rows(int64_t H) { return (H - 1) / 3 + 1; }
+struct MpdView {
+    int64_t n_pad, H, H1;
+};
+inline MpdView mpd_view(int64_t T, int period) {
+    const int64_t n_pad = T % period ? period - T % period : 0;
+    const int64_t H = (T + n_pad) / period;
+    return MpdView{n_pad, H, period_conv_rows(H)};
+}
 int launch_pack_convk(const float* w1, const float* w2, const float* ws, float* packed, int C, int* range_flag, hipStream_t s);
 // y = post(W1 lrelu(x, slope) + W2 x2 + bias + res), 1-tap convs C -> C with split-f16 operands (convg_kernel): member 0
 // uses x, x2, w1 (fv_pack_conv1x1_2src_split_f16 image), b1, res, y, y_act; C = 128, 256 or 512
@@ -481,6 +495,15 @@ int launch_disc_map_grad(const float* g_up, const float* g_map, const float* y, 
 int launch_reflect_pad_fold(const float* gp, float* dx, int rows, int64_t T, int P, hipStream_t st);
 int launch_avg_pool1d_input_grad(const float* g, float* dx, int rows, int64_t Tin, int64_t Tout, int k, int s, int p,
                                  hipStream_t st);
+// g_pre = (g_up + g_map) * (y > 0 ? 1 : slope) at one element: the gradient in front of a layer's LeakyReLU, as the
+// kernels of disc_grad.hip and mpd_grad.hip apply it while they stage a gradient (g_up, g_map or y may be null)
+__device__ __forceinline__ float map_grad(const float* __restrict__ g_up, const float* __restrict__ g_map,
+                                          const float* __restrict__ y, size_t at, float slope) {
+    float g = g_up ? g_up[at] : 0.f;
+    if (g_map) g = g_up ? g + g_map[at] : g_map[at];
+    if (y) g *= y[at] > 0.f ? 1.f : slope;
+    return g;
+}
 int64_t score_grad_chunks(int M, const int64_t* n);   // score-gradient blocks per row over all maps
 int launch_disc_score_grad(const float* const* e, const float* const* r, float* const* g, const int64_t* n,
                            const float* coef, int M, int B, hipStream_t st);

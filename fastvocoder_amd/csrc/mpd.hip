@@ -40,8 +40,6 @@ constexpr int kPStr = 160;                 // words of one (channel, phase) line
 constexpr int kPSpan = 3 * kPStr;          // flattened inputs staged per channel (an upper bound)
 constexpr int kPIters = (kPSpan + kPThreads - 1) / kPThreads;
 
-bool mpd_period_ok(int p) { return p == 2 || p == 3 || p == 5 || p == 7 || p == 11; }
-
 }  // namespace
 
 // grid (ceil(Hout p / 256), B)
@@ -196,16 +194,15 @@ int fv_mpd_conv_first(const float* x, const float* w, const float* bias, float* 
         return fail(FV_ERR_UNSUPPORTED, "mpd_conv_first: period %d (2, 3, 5, 7 or 11)", period);
     if (!x || !w || !y || y == x || B <= 0 || B > 65535 || T < 1)
         return fail(FV_ERR_INVALID_ARG, "mpd_conv_first: null tensor, aliasing, B=%d or T=%lld", B, (long long)T);
-    const int64_t n_pad = T % period ? period - T % period : 0;
-    if (n_pad >= T)
+    const MpdView v = mpd_view(T, period);
+    if (v.n_pad >= T)
         return fail(FV_ERR_INVALID_ARG, "mpd_conv_first: T=%lld is not longer than the reflect tail of %lld samples",
-                    (long long)T, (long long)n_pad);
-    const int64_t H = (T + n_pad) / period;
-    if (T + n_pad >= (int64_t)1 << 31) return fail(FV_ERR_INVALID_ARG, "mpd_conv_first: T=%lld too long", (long long)T);
-    const int64_t Hout = (H - 1) / 3 + 1;
-    const int64_t blocks = (Hout * period + 255) / 256;
+                    (long long)T, (long long)v.n_pad);
+    if (T + v.n_pad >= (int64_t)1 << 31)
+        return fail(FV_ERR_INVALID_ARG, "mpd_conv_first: T=%lld too long", (long long)T);
+    const int64_t blocks = (v.H1 * period + 255) / 256;
     hipLaunchKernelGGL(mpd_first_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w,
-                       bias, y, T, (int)H, (int)Hout, period, slope);
+                       bias, y, T, (int)v.H, (int)v.H1, period, slope);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -240,7 +237,7 @@ int fv_period_conv(const float* x, const float* packed, const float* bias, float
         return fail(FV_ERR_INVALID_ARG, "period_conv: null tensor, aliasing, B=%d or H=%d", B, H);
     if ((int64_t)H * period >= (int64_t)1 << 31)
         return fail(FV_ERR_INVALID_ARG, "period_conv: H=%d x period %d too long", H, period);
-    const int Hout = (H - 1) / 3 + 1;
+    const int Hout = (int)period_conv_rows(H);
     const dim3 grid((unsigned)(((int64_t)Hout * period + kPN - 1) / kPN), (unsigned)(Cout / kPM), (unsigned)B);
     const hipStream_t st = (hipStream_t)stream;
 #define FV_PERIOD(P)                                                                                              \

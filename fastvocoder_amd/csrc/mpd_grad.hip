@@ -15,7 +15,7 @@
 //     each 32 x 32, NT = 128 (M is not padded).  A wave keeps one accumulator fragment per phase and M fragment
 //     (3 x 2 x 16 or 3 x 16 registers); a channel pair costs 5 MFMAs per M fragment from 5 A words and 2 B words.
 //   * Gradient tile.  gs[co][i] holds g_pre at n = n0 - p + i, i < NT + p (a p-word halo in front), staged flat and
-//     coalesced; the staging applies (g_up + g_map) * (y > 0 ? 1 : slope) (map_grad of disc_grad.hip), so the masked
+//     coalesced; the staging applies (g_up + g_map) * (y > 0 ? 1 : slope) (map_grad of fv_internal.h), so the masked
 //     gradient never exists in memory.  n < 0 and n >= Hout p are staged as 0: row m = -1 and rows past the last
 //     output contribute nothing.  A lane group reads 32 consecutive words for either tap.
 //   * Weights.  Packed once as [Cin / MT][Cout][5][MT] (fv_pack_period_conv_grad): a chunk is 8 x 5 x MT contiguous
@@ -45,16 +45,6 @@ constexpr int kGT = 5;                     // taps
 constexpr int kGCK = 8;                    // output channels (K) per chunk
 constexpr int kGThreads = 256;
 constexpr int kGHalo = 11;                 // the largest period
-
-bool mpdg_period_ok(int p) { return p == 2 || p == 3 || p == 5 || p == 7 || p == 11; }
-
-__device__ __forceinline__ float mpdg_map_grad(const float* __restrict__ g_up, const float* __restrict__ g_map,
-                                               const float* __restrict__ y, size_t at, float slope) {
-    float g = g_up ? g_up[at] : 0.f;
-    if (g_map) g = g_up ? g + g_map[at] : g_map[at];
-    if (y) g *= y[at] > 0.f ? 1.f : slope;
-    return g;
-}
 
 }  // namespace
 
@@ -131,7 +121,7 @@ __global__ __launch_bounds__(kGThreads) void period_grad_kernel(const float* __r
 #pragma unroll
         for (int u = 0; u < kGIters; ++u)
             if (s_lds[u] >= 0)
-                gs[s_lds[u]] = s_n[u] >= 0 ? mpdg_map_grad(g_up, g_map, y, cb + (size_t)s_cl[u] * Nout + s_n[u], slope)
+                gs[s_lds[u]] = s_n[u] >= 0 ? map_grad(g_up, g_map, y, cb + (size_t)s_cl[u] * Nout + s_n[u], slope)
                                            : 0.f;
         const float4* wsrc = reinterpret_cast<const float4*>(wp + ((size_t)mt * Cout + co0) * (kGT * MT));
         float4* wdst = reinterpret_cast<float4*>(ws);
@@ -221,8 +211,8 @@ __global__ __launch_bounds__(256) void mpd_first_grad_kernel(const float* __rest
         const size_t at0 = gb + (size_t)m * p + c, at1 = at0 - p;
         float acc = 0.f;
         for (int co = 0; co < kGFirstC; ++co) {
-            if (t0) acc = fmaf(wsh[co * kGT + ph], mpdg_map_grad(g_up, g_map, y, at0 + (size_t)co * N1, slope), acc);
-            if (t1) acc = fmaf(wsh[co * kGT + ph + 3], mpdg_map_grad(g_up, g_map, y, at1 + (size_t)co * N1, slope), acc);
+            if (t0) acc = fmaf(wsh[co * kGT + ph], map_grad(g_up, g_map, y, at0 + (size_t)co * N1, slope), acc);
+            if (t1) acc = fmaf(wsh[co * kGT + ph + 3], map_grad(g_up, g_map, y, at1 + (size_t)co * N1, slope), acc);
         }
         v = pass ? v + acc : acc;
     }
@@ -259,7 +249,7 @@ int fv_pack_period_conv_grad(const float* w, float* packed, int Cout, int Cin, v
 
 int fv_period_conv_input_grad(const float* g_up, const float* g_map, const float* y, const float* packed, float* dx,
                               int B, int Cin, int Cout, int H, int period, float slope, void* stream) {
-    if (!mpdg_period_ok(period))
+    if (!mpd_period_ok(period))
         return fail(FV_ERR_UNSUPPORTED, "period_conv_input_grad: period %d (2, 3, 5, 7 or 11)", period);
     if (int rc = period_grad_shape("period_conv_input_grad", Cin, Cout)) return rc;
     if ((!g_up && !g_map) || !packed || !dx || B <= 0 || B > 65535 || H < 1)
@@ -270,7 +260,7 @@ int fv_period_conv_input_grad(const float* g_up, const float* g_map, const float
         return fail(FV_ERR_INVALID_ARG, "period_conv_input_grad: dx must not alias an input");
     if (((int64_t)H + 5) * period >= (int64_t)1 << 31)
         return fail(FV_ERR_INVALID_ARG, "period_conv_input_grad: H=%d x period %d too long", H, period);
-    const int Hout = (H - 1) / 3 + 1;
+    const int Hout = (int)period_conv_rows(H);
     const int64_t nm = ((int64_t)(H + 1) / 3 + 1) * period;      // m-space positions: r + 2 = 3 m + ph, r < H
     const hipStream_t st = (hipStream_t)stream;
     const bool narrow = Cin == 32;
@@ -295,7 +285,7 @@ int fv_period_conv_input_grad(const float* g_up, const float* g_map, const float
 
 int fv_mpd_first_input_grad(const float* g_up, const float* g_map, const float* y0, const float* w, float* dx, int B,
                             int64_t T, int period, float slope, void* stream) {
-    if (!mpdg_period_ok(period))
+    if (!mpd_period_ok(period))
         return fail(FV_ERR_UNSUPPORTED, "mpd_first_input_grad: period %d (2, 3, 5, 7 or 11)", period);
     if ((!g_up && !g_map) || !w || !dx || B <= 0 || B > 65535 || T < 1)
         return fail(FV_ERR_INVALID_ARG, "mpd_first_input_grad: null tensor, B=%d or T=%lld", B, (long long)T);
@@ -303,16 +293,14 @@ int fv_mpd_first_input_grad(const float* g_up, const float* g_map, const float* 
         return fail(FV_ERR_INVALID_ARG, "mpd_first_input_grad: slope=%g needs the layer's output y0", slope);
     if (dx == g_up || dx == g_map || dx == y0 || dx == w)
         return fail(FV_ERR_INVALID_ARG, "mpd_first_input_grad: dx must not alias an input");
-    const int64_t n_pad = T % period ? period - T % period : 0;
-    if (n_pad >= T)
+    const MpdView v = mpd_view(T, period);
+    if (v.n_pad >= T)
         return fail(FV_ERR_INVALID_ARG, "mpd_first_input_grad: T=%lld is not longer than the reflect tail of %lld "
-                    "samples", (long long)T, (long long)n_pad);
-    if (T + n_pad >= (int64_t)1 << 31)
+                    "samples", (long long)T, (long long)v.n_pad);
+    if (T + v.n_pad >= (int64_t)1 << 31)
         return fail(FV_ERR_INVALID_ARG, "mpd_first_input_grad: T=%lld too long", (long long)T);
-    const int64_t H = (T + n_pad) / period;
-    const int64_t H1 = (H - 1) / 3 + 1;
     hipLaunchKernelGGL(mpd_first_grad_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0,
-                       (hipStream_t)stream, g_up, g_map, y0, w, dx, T, (int)n_pad, (int)H1, period, slope);
+                       (hipStream_t)stream, g_up, g_map, y0, w, dx, T, (int)v.n_pad, (int)v.H1, period, slope);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -1,4 +1,6 @@
-"""What the discriminators share: the argument checks and the native run of one conv stack.
+"""What the discriminators share: the argument checks, the cache of packed weights (``cached``), the one forward path
+(``DiscriminatorModule``: ``forward`` and ``_graph_forward`` over a module's ``_forward(x, graph)``), the one autograd
+Function of a layer stack (``_LayersGrad``) and the native run of one conv stack.
 
 A sub-discriminator keeps its convs in the reference's containers (``layers.<i>`` Sequentials of pad / Conv1d /
 LeakyReLU) so that ``state_dict`` keys match; their ``forward`` is never called.  ``ConvStack`` folds weight norm and
@@ -54,6 +56,34 @@ def check_length(module, n):
                          f"least {need} samples")
 
 
+def checked_input(module, x, dims, graph, mono=True):
+    """What every ``_forward`` starts with: device_input (``graph``: x may require grad), the (B, 1, T) check of a
+    waveform (``mono``) and check_length."""
+    x = device_input(x, "x", dims, graph)
+    if mono and x.shape[1] != 1:
+        raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
+    check_length(module, x.shape[-1])
+    return x
+
+
+def wants_grad(x, graph):
+    """Whether a ``_forward`` runs through the autograd Functions: the caller permits it and autograd asks for it."""
+    return bool(graph) and x.requires_grad and torch.is_grad_enabled()
+
+
+def cached(module, key, build):
+    """``module._fv_plans[key]``, rebuilt with ``build()`` (under torch.no_grad()) when the module state moved.  The
+    value is stored against the state read AFTER the build: a build that touches the module leaves no stale key."""
+    hit = module._fv_plans.get(key)
+    if hit is not None and hit[0] == module._fv_state():
+        return hit[1]
+    module._device()
+    with torch.no_grad():
+        value = build()
+    module._fv_plans[key] = (module._fv_state(), value)
+    return value
+
+
 def first_length(ok, start=1):
     """Smallest n >= start with ok(n), for ok monotone in n."""
     hi = max(start, 1)
@@ -87,14 +117,15 @@ class NotDifferentiable:
                 "period_grad=True")
 
 
-class _StackGrad(torch.autograd.Function):
-    """ConvStack._run_stack with the gradient with respect to the input: the outputs are all the layer maps, the
+class _LayersGrad(torch.autograd.Function):
+    """``module._run_layers`` with the gradient with respect to the input: the outputs are all the layer maps, the
     saved tensors the input and the maps.  The parameters are constants."""
 
     @staticmethod
-    def forward(ctx, stack, x):
-        outs = stack._run_stack(x)
-        ctx.stack = stack
+    def forward(ctx, module, x):
+        outs = module._run_layers(x)
+        ctx.module = module
+        ctx.set_materialize_grads(module._MATERIALIZE_GRADS)
         ctx.save_for_backward(x, *outs)
         return tuple(outs)
 
@@ -102,10 +133,27 @@ class _StackGrad(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
         x, *outs = ctx.saved_tensors
-        return None, ctx.stack._input_grad(x, outs, grads)
+        return None, ctx.module._input_grad(x, outs, grads)
 
 
-class ConvStack(NativeModule):
+class DiscriminatorModule(NativeModule):
+    """Base of every discriminator: one ``_forward(x, graph)`` per module, ``graph`` the permission for x to require
+    grad (then the launches run through the autograd Functions: the same launches, the same bits)."""
+
+    def forward(self, x):
+        return self._forward(x, self.differentiable)
+
+    def _graph_forward(self, x):
+        """``forward`` on the graph of x whatever ``differentiable`` says (loss.generator_adversarial_terms)."""
+        return self._forward(x, True)
+
+    def _stack(self, x, grad):
+        """``_run_layers(x)`` of a module with layers of its own, through _LayersGrad (backward: the module's
+        ``_input_grad``) when ``grad``."""
+        return list(_LayersGrad.apply(self, x)) if grad else self._run_layers(x)
+
+
+class ConvStack(DiscriminatorModule):
     """Base of the two sub-discriminators: ``layers`` as in the reference, ``_spec`` one entry per layer.
 
     ``differentiable`` (default False): with True, a forward whose input requires grad runs the same launches through
@@ -113,6 +161,7 @@ class ConvStack(NativeModule):
     are constants of that graph: their ``.grad`` stays None."""
 
     differentiable = False
+    _MATERIALIZE_GRADS = True     # a map without a gradient arrives as zeros: _input_grad launches for every layer
 
     def _build_stack(self, in_channels, out_channels, kernel_sizes, channels, max_downsample_channels, bias,
                      downsample_scales, slope, tap, pad_name, pad_params):
@@ -158,38 +207,27 @@ class ConvStack(NativeModule):
     def _native_layers(self):
         """[(spec, weight, bias)] with weight norm folded (grouped: [Cout, 4, k]; dense: packed), cached against the
         module state."""
-        state = self._fv_state()
-        hit = self._fv_plans.get("layers")
-        if hit is not None and hit[0] == state:
-            return hit[1]
-        self._device()
-        with torch.no_grad():
+        def build():
             layers = []
             for spec, conv in zip(self._spec, self._convs()):
                 w = effective_weight(conv)
                 b = None if conv.bias is None else conv.bias.detach().contiguous().float()
                 layers.append((spec, w.contiguous() if spec[0] == "grouped" else _native.pack_conv1d(w), b,
                                conv.out_channels))
-        self._fv_plans["layers"] = (self._fv_state(), layers)
-        return layers
+            return layers
+        return cached(self, "layers", build)
 
     def _native_grad_layers(self):
         """Per layer what its input gradient reads: the folded weight [Cout, 4, k] of a grouped layer (the forward's
         tensor), the packed W'[ci, co, j] = W[co, ci, k-1-j] of a dense one.  Cached against the module state."""
-        state = self._fv_state()
-        hit = self._fv_plans.get("grad_layers")
-        if hit is not None and hit[0] == state:
-            return hit[1]
-        self._device()
-        fwd = self._native_layers()
-        with torch.no_grad():
+        def build():
             layers = []
-            for (spec, w, _, _), conv in zip(fwd, self._convs()):
+            for (spec, w, _, _), conv in zip(self._native_layers(), self._convs()):
                 if spec[0] != "grouped":
                     w = _native.pack_conv1d(effective_weight(conv).flip(2).transpose(0, 1).contiguous())
                 layers.append((spec, w, conv.in_channels))
-        self._fv_plans["grad_layers"] = (self._fv_state(), layers)
-        return layers
+            return layers
+        return cached(self, "grad_layers", build)
 
     def _input_grad(self, x, outs, grads):
         """d/dx of sum_l <grads[l], outs[l]> (None = zero), walking the layers downwards: the LeakyReLU mask of a
@@ -218,20 +256,7 @@ class ConvStack(NativeModule):
                 g_up = _native.conv1d_fused(g_pre, w, None, cin, k, pad=k - 1 - pad)
         return torch.zeros_like(x) if g_up is None else g_up
 
-    def _stack(self, x):
-        """_run_stack, through the autograd Function when the module is differentiable and x requires grad."""
-        if self.differentiable and x.requires_grad and torch.is_grad_enabled():
-            return list(_StackGrad.apply(self, x))
-        return self._run_stack(x)
-
-    def _graph_stack(self, x):
-        """_run_stack on the graph of x whatever ``differentiable`` says (the graph-mode forwards behind
-        loss.generator_adversarial_terms): the same launches, the same bits."""
-        if x.requires_grad and torch.is_grad_enabled():
-            return list(_StackGrad.apply(self, x))
-        return self._run_stack(x)
-
-    def _run_stack(self, x):
+    def _run_layers(self, x):
         """x [B, C, T] fp32 device -> the list of every layer's output (the reference's ``outs``)."""
         outs = []
         for (spec, w, b, cout) in self._native_layers():

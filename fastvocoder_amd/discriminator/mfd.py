@@ -2,9 +2,9 @@
 import torch
 
 from .. import _native
-from ..generator.engine import NativeModule
 from ..loss.stft_loss import _stft_table_host, _window_fn
-from .common import ConvStack, NotDifferentiable, check_activation, check_length, check_pad, device_input
+from .common import (ConvStack, DiscriminatorModule, NotDifferentiable, cached, check_activation, check_pad,
+                     checked_input, wants_grad)
 
 
 class _MagnitudeBins(torch.autograd.Function):
@@ -57,33 +57,21 @@ class STFTDiscriminator(NotDifferentiable, ConvStack):
         return max(self.fft_size // 2 + 1, self._first_pad * self.shift_size)
 
     def _table(self):
-        state = self._fv_state()
-        hit = self._fv_plans.get("table")
-        if hit is not None and hit[0] == state:
-            return hit[1]
-        tab = torch.from_numpy(_stft_table_host(self.fft_size, self.win_length, self.window)).to(self._device())
-        self._fv_plans["table"] = (state, tab)
-        return tab
+        return cached(self, "table", lambda: torch.from_numpy(
+            _stft_table_host(self.fft_size, self.win_length, self.window)).to(self._device()))
 
-    def forward(self, x):
-        """x (B, T) -> list of every layer's output (the reference's STFTDiscriminator takes the squeezed signal)."""
-        x = device_input(x, "x", 2)
-        check_length(self, x.shape[-1])
-        mag = _native.stft_magnitude_bins(x, self._table(), self.fft_size, self.shift_size, self.win_length)
-        return self._run_stack(mag)
-
-    def _graph_forward(self, x):
-        """``forward`` on the graph of x (loss.generator_adversarial_terms): the same launches and bits, the
-        magnitude through _MagnitudeBins and the stack through _StackGrad.  The parameters are constants."""
-        x = device_input(x, "x", 2, differentiable=True)
-        check_length(self, x.shape[-1])
+    def _forward(self, x, graph):
+        """x (B, T) -> list of every layer's output (the reference's STFTDiscriminator takes the squeezed signal).  On
+        the graph the magnitude runs through _MagnitudeBins and the stack through _LayersGrad."""
+        x = checked_input(self, x, 2, graph, mono=False)
+        grad = wants_grad(x, graph)
         geometry = (self.fft_size, self.shift_size, self.win_length)
-        if x.requires_grad and torch.is_grad_enabled():
-            return self._graph_stack(_MagnitudeBins.apply(x, self._table(), geometry))
-        return self._run_stack(_native.stft_magnitude_bins(x, self._table(), *geometry))
+        mag = _MagnitudeBins.apply(x, self._table(), geometry) if grad else \
+            _native.stft_magnitude_bins(x, self._table(), *geometry)
+        return self._stack(mag, grad)
 
 
-class MultiResolutionSTFTDiscriminator(NotDifferentiable, NativeModule):
+class MultiResolutionSTFTDiscriminator(NotDifferentiable, DiscriminatorModule):
     """mfd.py:139-178: one STFTDiscriminator per (fft_size, hop_size, win_length)."""
 
     def __init__(self, fft_sizes=[2048, 1024, 512], hop_sizes=[240, 120, 50], win_lengths=[1200, 600, 240],
@@ -98,20 +86,8 @@ class MultiResolutionSTFTDiscriminator(NotDifferentiable, NativeModule):
     def min_length(self):
         return max(d.min_length() for d in self.stft_discriminator)
 
-    def forward(self, x):
-        """x (B, 1, T) -> list over the resolutions of each one's list of layer outputs."""
-        x = device_input(x, "x", 3)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        x = x.squeeze(1)
-        return [f(x) for f in self.stft_discriminator]
-
-    def _graph_forward(self, x):
-        """``forward`` on the graph of x; autograd sums the resolutions' gradients into x."""
-        x = device_input(x, "x", 3, differentiable=True)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        x = x.squeeze(1)
-        return [f._graph_forward(x) for f in self.stft_discriminator]
+    def _forward(self, x, graph):
+        """x (B, 1, T) -> list over the resolutions of each one's list of layer outputs; on the graph autograd sums
+        the resolutions' gradients into x."""
+        x = checked_input(self, x, 3, graph).squeeze(1)
+        return [f._forward(x, graph) for f in self.stft_discriminator]

@@ -10,8 +10,8 @@ import torch
 from torch.nn.utils import weight_norm
 
 from .. import _native
-from ..generator.engine import PAD_ZERO, NativeModule, effective_weight
-from .common import NotDifferentiable, check_length, device_input, first_length
+from ..generator.engine import PAD_ZERO, effective_weight
+from .common import DiscriminatorModule, NotDifferentiable, cached, checked_input, first_length, wants_grad
 
 LRELU_SLOPE = 0.1
 PERIODS = (2, 3, 5, 7, 11)
@@ -26,27 +26,16 @@ def period_heights(T, period, stride=3, layers=4):
     return n_pad, hs
 
 
-class _PeriodGrad(torch.autograd.Function):
-    """DiscriminatorP._run_layers with the gradient with respect to the waveform: the outputs are the six maps, the
-    saved tensors the input and the maps.  The parameters are constants."""
-
-    @staticmethod
-    def forward(ctx, module, x):
-        outs = module._run_layers(x)
-        ctx.module = module
-        ctx.set_materialize_grads(False)                   # a map without a gradient arrives as None, not as zeros
-        ctx.save_for_backward(x, *outs)
-        return tuple(outs)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        x, *outs = ctx.saved_tensors
-        return None, ctx.module._input_grad(x, outs, grads)
+def _folded(conv):
+    """The weight of a (k, 1) conv with weight norm folded, as [Cout, Cin, k]."""
+    w = effective_weight(conv)
+    return w.reshape(w.shape[0], w.shape[1], w.shape[2])
 
 
-class DiscriminatorP(NotDifferentiable, NativeModule):
+class DiscriminatorP(NotDifferentiable, DiscriminatorModule):
     """mpd.py:131-164."""
+
+    _MATERIALIZE_GRADS = False    # a map without a gradient arrives as None: _input_grad skips the layers above it
 
     def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
         super().__init__()
@@ -75,19 +64,16 @@ class DiscriminatorP(NotDifferentiable, NativeModule):
         p = self.period
         return first_length(lambda n: all(_native.mpd_reflect_tail(t, p) < t for t in range(n, max(n, p) + 1)))
 
+    def _convs(self):
+        return list(self.convs) + [self.conv_post]
+
     def _native_layers(self):
         """[(weight, bias)]: layer 0 folded [32, 5]; layers 1-3 packed for fv_period_conv; layers 4-5 packed for
         fv_conv1d_fused.  Cached against the module state."""
-        state = self._fv_state()
-        hit = self._fv_plans.get("layers")
-        if hit is not None and hit[0] == state:
-            return hit[1]
-        self._device()
-        with torch.no_grad():
+        def build():
             layers = []
-            for j, conv in enumerate(list(self.convs) + [self.conv_post]):
-                w = effective_weight(conv)
-                w = w.reshape(w.shape[0], w.shape[1], w.shape[2])
+            for j, conv in enumerate(self._convs()):
+                w = _folded(conv)
                 b = None if conv.bias is None else conv.bias.detach().contiguous().float()
                 if j == 0:
                     w = w.reshape(32, 5).contiguous()
@@ -96,32 +82,23 @@ class DiscriminatorP(NotDifferentiable, NativeModule):
                 else:
                     w = _native.pack_conv1d(w)
                 layers.append((w, b))
-        self._fv_plans["layers"] = (self._fv_state(), layers)
-        return layers
+            return layers
+        return cached(self, "layers", build)
 
     def _native_grad_layers(self):
         """Per layer what its input gradient reads: layer 0 the folded weight [32, 5] (the forward's tensor); layers
         1-3 packed for fv_period_conv_input_grad; layers 4-5 the packed W'[ci, co, j] = W[co, ci, k-1-j] of
         fv_conv1d_fused.  Cached against the module state."""
-        state = self._fv_state()
-        hit = self._fv_plans.get("grad_layers")
-        if hit is not None and hit[0] == state:
-            return hit[1]
-        self._device()
-        fwd = self._native_layers()
-        with torch.no_grad():
-            layers = [fwd[0][0]]
-            for j, conv in enumerate(list(self.convs) + [self.conv_post]):
-                if j == 0:
-                    continue
-                w = effective_weight(conv)
-                w = w.reshape(w.shape[0], w.shape[1], w.shape[2])
+        def build():
+            layers = [self._native_layers()[0][0]]
+            for j, conv in enumerate(self._convs()[1:], 1):
+                w = _folded(conv)
                 if j < 4:
                     layers.append(_native.pack_period_conv_grad(w))
                 else:
                     layers.append(_native.pack_conv1d(w.flip(2).transpose(0, 1).contiguous()))
-        self._fv_plans["grad_layers"] = (self._fv_state(), layers)
-        return layers
+            return layers
+        return cached(self, "grad_layers", build)
 
     def _run_layers(self, x):
         """x [B, 1, T] fp32 device -> the six feature maps [B, C, H_l, p]: one launch per layer."""
@@ -166,31 +143,16 @@ class DiscriminatorP(NotDifferentiable, NativeModule):
             return torch.zeros_like(x)
         return _native.mpd_first_input_grad(g_up, gm[0], outs[0], layers[0], x.shape[-1], LRELU_SLOPE)
 
-    def forward(self, x):
-        """x (B, 1, T) -> (score [B, H_6 p], the six feature maps [B, C, H_l, p])."""
-        x = device_input(x, "x", 3)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        fmap = self._run_layers(x)
-        return fmap[5].flatten(1), fmap
-
-    def _graph_forward(self, x):
-        """``forward`` on the graph of x (loss.generator_adversarial_terms(..., period_grad=True)): the same launches,
-        the same bits, through an autograd Function whose backward is the input gradient of csrc/mpd_grad.hip.  The
-        parameters are constants of that graph: their ``.grad`` stays None."""
-        x = device_input(x, "x", 3, differentiable=True)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        if x.requires_grad and torch.is_grad_enabled():
-            fmap = list(_PeriodGrad.apply(self, x))
-        else:
-            fmap = self._run_layers(x)
+    def _forward(self, x, graph):
+        """x (B, 1, T) -> (score [B, H_6 p], the six feature maps [B, C, H_l, p]).  On the graph
+        (loss.generator_adversarial_terms(..., period_grad=True)) the same launches run through _LayersGrad, whose
+        backward is the input gradient of csrc/mpd_grad.hip; the parameters are constants (``.grad`` stays None)."""
+        x = checked_input(self, x, 3, graph)
+        fmap = self._stack(x, wants_grad(x, graph))
         return fmap[5].flatten(1), fmap
 
 
-class MultiPeriodDiscriminator(NotDifferentiable, NativeModule):
+class MultiPeriodDiscriminator(NotDifferentiable, DiscriminatorModule):
     """mpd.py:288-304, the single-input form: one list per period, its six maps followed by the score [B, 1, H p]."""
 
     def __init__(self):
@@ -201,27 +163,13 @@ class MultiPeriodDiscriminator(NotDifferentiable, NativeModule):
         """Shortest input every period's reflect pad accepts."""
         return max(d.min_length() for d in self.discriminators)
 
-    def forward(self, x):
-        x = device_input(x, "x", 3)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
+    def _forward(self, x, graph):
+        """The periods in the order of PERIODS.  On the graph autograd adds their gradients into x in the reverse of
+        that order (a node built later runs earlier), period 11 first and period 2 last: the same order, hence the
+        same bits, on every call."""
+        x = checked_input(self, x, 3, graph)
         outs = []
         for d in self.discriminators:
-            score, fmap = d(x)
-            outs.append(fmap + [score.unsqueeze(1)])
-        return outs
-
-    def _graph_forward(self, x):
-        """``forward`` on the graph of x: the periods in the order of ``forward``.  Autograd adds their gradients
-        into x in the reverse of that order (a node built later runs earlier), period 11 first and period 2 last:
-        the same order, hence the same bits, on every call."""
-        x = device_input(x, "x", 3, differentiable=True)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        outs = []
-        for d in self.discriminators:
-            score, fmap = d._graph_forward(x)
+            score, fmap = d._forward(x, graph)
             outs.append(fmap + [score.unsqueeze(1)])
         return outs

@@ -2,8 +2,8 @@
 import torch
 
 from .. import _native
-from ..generator.engine import NativeModule
-from .common import ConvStack, check_activation, check_length, check_pad, device_input, first_length
+from .common import (ConvStack, DiscriminatorModule, check_activation, check_pad, checked_input, first_length,
+                     wants_grad)
 
 
 class _AvgPool(torch.autograd.Function):
@@ -41,24 +41,13 @@ class MelGANDiscriminator(ConvStack):
         """Shortest input the reflection pad accepts (more samples than the pad)."""
         return self._first_pad + 1
 
-    def forward(self, x):
+    def _forward(self, x, graph):
         """x (B, 1, T) -> list of every layer's output."""
-        x = device_input(x, "x", 3, self.differentiable)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        return self._stack(x)
-
-    def _graph_forward(self, x):
-        """``forward`` on the graph of x whatever ``differentiable`` says (loss.generator_adversarial_terms)."""
-        x = device_input(x, "x", 3, differentiable=True)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        return self._graph_stack(x)
+        x = checked_input(self, x, 3, graph)
+        return self._stack(x, wants_grad(x, graph))
 
 
-class MelGANMultiScaleDiscriminator(NativeModule):
+class MelGANMultiScaleDiscriminator(DiscriminatorModule):
     """msd.py:121-241: ``scales`` MelGANDiscriminators, the input average-pooled between scales; weight norm applied
     and the weights re-drawn from N(0, 0.02) at construction, as in the reference."""
 
@@ -117,31 +106,15 @@ class MelGANMultiScaleDiscriminator(NativeModule):
             return True
         return first_length(ok)
 
-    def forward(self, x):
-        """x (B, 1, T) -> list over the scales of each scale's list of layer outputs."""
-        x = device_input(x, "x", 3, self.differentiable)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        grad = self.differentiable and x.requires_grad and torch.is_grad_enabled()
+    def _forward(self, x, graph):
+        """x (B, 1, T) -> list over the scales of each scale's list of layer outputs.  The scales run as ``_stack``,
+        without their own input checks: min_length() above already guarantees every pooled length, and
+        ``differentiable`` is "all scales" -- with only some set, an x that requires grad is refused right here."""
+        x = checked_input(self, x, 3, graph)
+        grad = wants_grad(x, graph)
         outs = []
         for i, f in enumerate(self.discriminators):
-            outs += [f(x)]
-            if i + 1 < len(self.discriminators):
-                x = _AvgPool.apply(x, self._pool) if grad else _native.avg_pool1d(x, *self._pool)
-        return outs
-
-    def _graph_forward(self, x):
-        """``forward`` on the graph of x whatever ``differentiable`` says (loss.generator_adversarial_terms): the
-        scales through _StackGrad, the pools through _AvgPool."""
-        x = device_input(x, "x", 3, differentiable=True)
-        if x.shape[1] != 1:
-            raise ValueError(f"x must be (B, 1, T), got {tuple(x.shape)}")
-        check_length(self, x.shape[-1])
-        grad = x.requires_grad and torch.is_grad_enabled()
-        outs = []
-        for i, f in enumerate(self.discriminators):
-            outs += [f._graph_stack(x)]
+            outs += [f._stack(x, grad)]
             if i + 1 < len(self.discriminators):
                 x = _AvgPool.apply(x, self._pool) if grad else _native.avg_pool1d(x, *self._pool)
         return outs

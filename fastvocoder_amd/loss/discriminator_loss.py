@@ -24,6 +24,16 @@ from .. import _native
 TERMS = ("adversarial", "feature_map", "real", "fake", "discriminator")
 
 
+def _map_index(lengths):
+    """(indices of the feature maps, indices of the score maps) in the flattened lists."""
+    last, fm_idx, m = [], [], 0
+    for n in lengths:
+        fm_idx += range(m, m + n - 1)
+        last.append(m + n - 1)
+        m += n
+    return fm_idx, last
+
+
 def compose_terms(sums, counts, lengths, per_utterance=False):
     """The five terms from the sums of fv_disc_score_sums.  sums: float64 [M, B, 4] (sum|e-r|, sum(e-1)^2, sum e^2,
     sum(r-1)^2) over the maps of the flattened lists; counts: elements per row of each map [M]; lengths: the number
@@ -35,27 +45,13 @@ def compose_terms(sums, counts, lengths, per_utterance=False):
     else:
         means = sums.sum(dim=1) / (counts[:, None] * sums.shape[1])   # [M, 4]
     L = len(lengths)
-    last, fm_idx, m = [], [], 0
-    for n in lengths:
-        fm_idx += range(m, m + n - 1)
-        last.append(m + n - 1)
-        m += n
+    fm_idx, last = _map_index(lengths)
     fm_den = float(L * (lengths[0] - 1))
     fm = means[fm_idx, ..., 0].sum(dim=0) / fm_den
     adv = means[last, ..., 1].sum(dim=0) / L
     fake = means[last, ..., 2].sum(dim=0) / L
     real = means[last, ..., 3].sum(dim=0) / L
     return {"adversarial": adv, "feature_map": fm, "real": real, "fake": fake, "discriminator": real + fake}
-
-
-def _map_index(lengths):
-    """(indices of the feature maps, indices of the score maps) in the flattened lists."""
-    last, fm_idx, m = [], [], 0
-    for n in lengths:
-        fm_idx += range(m, m + n - 1)
-        last.append(m + n - 1)
-        m += n
-    return fm_idx, last
 
 
 def grad_coefficients(grad_terms, counts, lengths, batch):
@@ -126,6 +122,15 @@ class _Adversarial(torch.autograd.Function):
         return tuple(_native.disc_score_grad(es, es, coef, [not n for n in ctx.needs_input_grad]))
 
 
+def _as_lists(discriminator, out):
+    """A module's output as a list of lists of maps, the score last in each: DiscriminatorP's (score, maps) and the
+    bare list of a single stack become one list."""
+    from ..discriminator import DiscriminatorP
+    if isinstance(discriminator, DiscriminatorP):
+        return [out[1] + [out[0].unsqueeze(1)]]
+    return [out] if torch.is_tensor(out[0]) else out
+
+
 def generator_adversarial_terms(discriminator, estimate, real=None, *, period_grad=False):
     """The generator's adversarial and feature-map terms (bin/train.py:97-120) as one call, attached to the graph of
     ``estimate``: {"adversarial", "feature_map"} as 0-d fp32 device tensors with the reference's divisors
@@ -151,22 +156,14 @@ def generator_adversarial_terms(discriminator, estimate, real=None, *, period_gr
     if graph is None:
         raise TypeError(f"generator_adversarial_terms: {type(discriminator).__name__} is not a fastvocoder_amd "
                         "discriminator with an input gradient")
-    est_p = graph(estimate)
-    if isinstance(discriminator, DiscriminatorP):      # (score, maps) -> one list, the score last
-        est_p = [est_p[1] + [est_p[0].unsqueeze(1)]]
-    elif torch.is_tensor(est_p[0]):
-        est_p = [est_p]
+    est_p = _as_lists(discriminator, graph(estimate))
     if real is None:      # the score maps alone: adversarial = sum_i MSE(score_i, 1) / L reads nothing else
         es = [lst[-1].to(torch.float32).contiguous() for lst in est_p]
         if torch.is_grad_enabled() and any(e.requires_grad for e in es):
             return {"adversarial": _Adversarial.apply(*es).float()}
         return {"adversarial": _adversarial(es).float()}
     with torch.no_grad():
-        p = discriminator(real)
-    if isinstance(discriminator, DiscriminatorP):
-        p = [p[1] + [p[0].unsqueeze(1)]]
-    elif torch.is_tensor(p[0]):
-        p = [p]
+        p = _as_lists(discriminator, discriminator(real))
     terms = discriminator_terms(est_p, p, differentiable=True)
     return {"adversarial": terms["adversarial"], "feature_map": terms["feature_map"]}
 

@@ -8,8 +8,10 @@ import pytest
 import torch
 
 from fastvocoder_amd import _native
-from fastvocoder_amd.discriminator import (Discriminator, MelGANDiscriminator, MelGANMultiScaleDiscriminator,
+from fastvocoder_amd.discriminator import (Discriminator, DiscriminatorP, MelGANDiscriminator,
+                                           MelGANMultiScaleDiscriminator, MultiPeriodDiscriminator,
                                            MultiResolutionSTFTDiscriminator, STFTDiscriminator)
+from fastvocoder_amd.discriminator.common import DiscriminatorModule, cached
 from fastvocoder_amd.loss.discriminator_loss import compose_terms
 from fastvocoder_amd.synthetic import discriminator_spec, seeded_discriminator_state_dict
 from tests import discriminator_reference as ref
@@ -156,3 +158,33 @@ def test_score_composition_matches_the_training_loop():
         one = train_py([[m[b:b + 1] for m in lst] for lst in est_p], [[m[b:b + 1] for m in lst] for lst in p])
         for k, v in one.items():
             assert abs(float(per[k][b]) - v) <= 1e-12 * max(1.0, abs(v)), (k, b)
+
+
+def test_cached_follows_the_module_state():
+    """common.cached: one build for calls in a row, a new one after an in-place update of a parameter and after
+    load_state_dict, one entry per key; the build runs under torch.no_grad()."""
+    m = MelGANDiscriminator(**SMALL_MSD)
+    m._device = lambda: torch.device("cpu")              # the builds below launch nothing
+    builds = []
+
+    def build():
+        builds.append(torch.is_grad_enabled())
+        return len(builds)
+
+    assert cached(m, "a", build) == 1 and cached(m, "a", build) == 1 and builds == [False]
+    with torch.no_grad():
+        next(m.parameters()).mul_(1.5)
+    assert cached(m, "a", build) == 2 and cached(m, "a", build) == 2
+    m.load_state_dict(m.state_dict())
+    assert cached(m, "a", build) == 3 and cached(m, "a", build) == 3
+    assert cached(m, "b", build) == 4
+    assert cached(m, "a", build) == 3 and cached(m, "b", build) == 4 and len(builds) == 4
+
+
+def test_every_discriminator_takes_the_shared_forward_and_graph_forward():
+    """One ``_forward(x, graph)`` per module: ``forward`` and ``_graph_forward`` are DiscriminatorModule's."""
+    for cls in (MelGANDiscriminator, MelGANMultiScaleDiscriminator, STFTDiscriminator,
+                MultiResolutionSTFTDiscriminator, DiscriminatorP, MultiPeriodDiscriminator, Discriminator):
+        assert cls.forward is DiscriminatorModule.forward, cls
+        assert cls._graph_forward is DiscriminatorModule._graph_forward, cls
+        assert "_forward" in vars(cls), cls

@@ -11,8 +11,9 @@ import pytest
 import torch
 
 from fastvocoder_amd import _native
-from fastvocoder_amd.discriminator import Discriminator, MelGANDiscriminator, MelGANMultiScaleDiscriminator
-from fastvocoder_amd.loss import discriminator_terms
+from fastvocoder_amd.discriminator import (Discriminator, DiscriminatorP, MelGANDiscriminator,
+                                           MelGANMultiScaleDiscriminator)
+from fastvocoder_amd.loss import discriminator_terms, generator_adversarial_terms
 from fastvocoder_amd.synthetic import seeded_discriminator_state_dict
 from tests import disc_grad_reference as gref
 
@@ -230,3 +231,29 @@ def test_out_of_scope_modules_refuse():
         discriminator_terms(out, out, per_utterance=True, differentiable=True)
     with torch.no_grad():
         assert not d(x)[0][0].requires_grad
+
+
+@pytest.mark.parametrize("make,T", [(lambda: MelGANMultiScaleDiscriminator(**SMALL_MSD), 100),
+                                    (lambda: DiscriminatorP(3), 20)], ids=["small_msd", "period_3"])
+def test_the_gradient_caches_follow_the_weights(make, T):
+    """An in-place update of a weight reaches the cached forward and gradient weights ("layers", "grad_layers") of
+    both autograd paths: the gradient after it is the gradient of a fresh module with the same state."""
+    rs = np.random.RandomState(T)
+    est, real = rs.randn(2, 1, T), rs.randn(2, 1, T)
+    torch.manual_seed(T)
+
+    def grad(module):
+        x = _t(est).requires_grad_(True)
+        terms = generator_adversarial_terms(module, x, _t(real), period_grad=True)
+        (terms["adversarial"] + terms["feature_map"]).backward()
+        return x.grad
+
+    m = make().to(_dev()).eval()
+    first = grad(m)
+    with torch.no_grad():
+        next(q for name, q in m.named_parameters() if name.endswith("weight_g")).mul_(1.5)
+    second = grad(m)
+    fresh = make()
+    fresh.load_state_dict(m.state_dict())
+    assert torch.equal(second, grad(fresh.to(_dev()).eval()))
+    assert not torch.equal(second, first)
