@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "mpd.hip", "mpd_grad.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -260,6 +260,11 @@ def lib():
                                      ctypes.c_size_t, vp]
     L.fv_disc_map_grad.argtypes = [vp, vp, vp, vp, i64, f, vp]
     L.fv_grouped_conv1d_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
+    L.fv_conv_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i, i]
+    L.fv_conv_weight_grad_workspace_bytes.restype = i64
+    L.fv_conv1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_grouped_conv1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_weight_norm_grad.argtypes = [vp, vp, vp, vp, vp, i, i64, vp]
     L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
     L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
     L.fv_disc_score_grad.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
@@ -1366,6 +1371,72 @@ def grouped_conv1d_input_grad(g_up, g_map, y, w, cin, tin, k, stride, pad, slope
                                                  _ptr(y, "y", True), _ptr(w, "w"), _ptr(dx), B, int(cin), cout,
                                                  int(tin), int(k), int(stride), int(pad), float(slope), stream))
     return dx
+
+
+def conv_weight_grad_workspace_floats(grouped, B, cin, cout, tin, k, stride=1, pad=0, pad_mode=PAD_ZERO):
+    """fp32 words of workspace conv1d_weight_grad (``grouped`` False) or grouped_conv1d_weight_grad needs for these
+    shapes (fv_conv_weight_grad_workspace_bytes); raises for shapes the entries refuse."""
+    need = lib().fv_conv_weight_grad_workspace_bytes(int(bool(grouped)), int(B), int(cin), int(cout), int(tin), int(k),
+                                                     int(stride), int(pad), int(pad_mode))
+    if need < 0:
+        check(int(need))
+    return (need + 3) // 4
+
+
+def _weight_grad(name, grouped, g_pre, x, k, stride, pad, pad_mode, want_dw, want_db, workspace):
+    """What conv1d_weight_grad and grouped_conv1d_weight_grad share: the shape checks, the workspace and the call."""
+    if g_pre.dim() != 3 or x.dim() != 3 or g_pre.shape[0] != x.shape[0]:
+        raise NativeError(f"{name}: g_pre [B,Cout,Tout] and x [B,Cin,Tin] expected, got {tuple(g_pre.shape)} and "
+                          f"{tuple(x.shape)}")
+    if not (want_dw or want_db):
+        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
+    B, cout, tout = g_pre.shape
+    cin, tin = x.shape[1], x.shape[2]
+    k, stride, pad = int(k), int(stride), int(pad)
+    if stride > 0 and tin + 2 * pad >= k and tout != (tin + 2 * pad - k) // stride + 1:
+        raise NativeError(f"{name}: {tout} output times do not belong to an input of {tin} samples")
+    dev = g_pre.device
+    if workspace is None:
+        workspace = torch.empty(conv_weight_grad_workspace_floats(grouped, B, cin, cout, tin, k, stride, pad, pad_mode),
+                                dtype=torch.float32, device=dev)
+    dw = torch.empty((cout, 4 if grouped else cin, k), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
+    with _on(g_pre, x, workspace, dw, db) as stream:
+        ptrs = (_ptr(g_pre, "g_pre"), _ptr(x, "x"), _ptr(dw, "dw", True), _ptr(db, "db", True))
+        ws = (_ptr(workspace, "workspace"), workspace.numel() * 4, stream)
+        if grouped:
+            check(lib().fv_grouped_conv1d_weight_grad(*ptrs, B, cin, cout, tin, k, stride, pad, *ws))
+        else:
+            check(lib().fv_conv1d_weight_grad(*ptrs, B, cin, cout, tin, k, pad, int(pad_mode), *ws))
+    return dw, db
+
+
+def conv1d_weight_grad(g_pre, x, k, pad=0, pad_mode=PAD_ZERO, want_dw=True, want_db=False, workspace=None):
+    """The weight (and bias) gradient of a dense stride-1 conv (fv_conv1d_weight_grad, two launches): g_pre
+    [B,Cout,Tout] the gradient in front of the LeakyReLU (disc_map_grad), x [B,Cin,Tin] the layer's input, padded by
+    indexing -> (dw [Cout,Cin,k] or None, db [Cout] or None).  ``workspace``: an fp32 device tensor to use instead
+    of a fresh one (its contents do not matter)."""
+    return _weight_grad("conv1d_weight_grad", False, g_pre, x, k, 1, pad, pad_mode, want_dw, want_db, workspace)
+
+
+def grouped_conv1d_weight_grad(g_pre, x, k, stride, pad, want_dw=True, want_db=False, workspace=None):
+    """The weight (and bias) gradient of grouped_conv1d (fv_grouped_conv1d_weight_grad, two launches): g_pre
+    [B,Cout,Tout], x [B,Cin,Tin] -> (dw [Cout,4,k] or None, db [Cout] or None)."""
+    return _weight_grad("grouped_conv1d_weight_grad", True, g_pre, x, k, stride, pad, PAD_ZERO, want_dw, want_db,
+                        workspace)
+
+
+def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):
+    """The adjoint of fold_weight_norm (fv_weight_norm_grad, one launch): dw and v of one shape [dim0, ...], g with
+    dim0 elements -> (dv like v or None, dg like g or None)."""
+    if dw.shape != v.shape or v.dim() < 1 or g.numel() != v.shape[0] or not (want_dv or want_dg):
+        raise NativeError(f"weight_norm_grad: dw {tuple(dw.shape)}, v {tuple(v.shape)}, g {tuple(g.shape)}")
+    dv = torch.empty_like(v) if want_dv else None
+    dg = torch.empty_like(g) if want_dg else None
+    with _on(dw, v, g, dv, dg) as stream:
+        check(lib().fv_weight_norm_grad(_ptr(dw, "dw"), _ptr(v, "v"), _ptr(g, "g"), _ptr(dv, "dv", True),
+                                        _ptr(dg, "dg", True), v.shape[0], v[0].numel(), stream))
+    return dv, dg
 
 
 def reflect_pad_fold(gp, pad):

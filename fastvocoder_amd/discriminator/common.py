@@ -1,6 +1,7 @@
 """What the discriminators share: the argument checks, the cache of packed weights (``cached``), the one forward path
-(``DiscriminatorModule``: ``forward`` and ``_graph_forward`` over a module's ``_forward(x, graph)``), the one autograd
-Function of a layer stack (``_LayersGrad``) and the native run of one conv stack.
+(``DiscriminatorModule``: ``forward`` and ``_graph_forward`` over a module's ``_forward(x, graph)``), the autograd
+Functions of a layer stack (``_LayersGrad``: the input gradient; ``_LayersParamGrad``: the parameters' gradient, and
+the input's when asked for) and the native run of one conv stack.
 
 A sub-discriminator keeps its convs in the reference's containers (``layers.<i>`` Sequentials of pad / Conv1d /
 LeakyReLU) so that ``state_dict`` keys match; their ``forward`` is never called.  ``ConvStack`` folds weight norm and
@@ -100,7 +101,19 @@ def first_length(ok, start=1):
 
 
 class NotDifferentiable:
-    """Mix-in of the modules without an input gradient: ``differentiable`` reads False, and setting it raises."""
+    """Mix-in of the modules without an input gradient: ``differentiable`` reads False, and setting it raises.  They
+    have no parameter gradient either: ``parameter_grad`` behaves the same way."""
+
+    @property
+    def parameter_grad(self):
+        return False
+
+    @parameter_grad.setter
+    def parameter_grad(self, value):
+        if value:
+            raise NotImplementedError(
+                f"{type(self).__name__} has no parameter gradient yet: parameter_grad is supported by the MelGAN "
+                "multi-scale discriminator only (MelGANDiscriminator, MelGANMultiScaleDiscriminator)")
 
     @property
     def differentiable(self):
@@ -136,6 +149,29 @@ class _LayersGrad(torch.autograd.Function):
         return None, ctx.module._input_grad(x, outs, grads)
 
 
+class _LayersParamGrad(torch.autograd.Function):
+    """``module._run_layers`` with the conv parameters as inputs of the graph: the same forward launches as
+    _LayersGrad, the backward ``module._param_grad`` (csrc/disc_wgrad.hip), which also hands down the input gradient
+    when x requires grad.  A map without a gradient arrives as None and costs no launch."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        outs = module._run_layers(x)
+        ctx.module, ctx.n_outs = module, len(outs)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, *outs, *params)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, *rest = ctx.saved_tensors
+        outs, params = rest[:ctx.n_outs], rest[ctx.n_outs:]
+        gx, gparams = ctx.module._param_grad(x, outs, params, grads, ctx.needs_input_grad[1],
+                                             ctx.needs_input_grad[2:])
+        return (None, gx) + tuple(gparams)
+
+
 class DiscriminatorModule(NativeModule):
     """Base of every discriminator: one ``_forward(x, graph)`` per module, ``graph`` the permission for x to require
     grad (then the launches run through the autograd Functions: the same launches, the same bits)."""
@@ -158,9 +194,16 @@ class ConvStack(DiscriminatorModule):
 
     ``differentiable`` (default False): with True, a forward whose input requires grad runs the same launches through
     an autograd Function (the same bits) whose backward is the input gradient of csrc/disc_grad.hip.  The parameters
-    are constants of that graph: their ``.grad`` stays None."""
+    are constants of that graph: their ``.grad`` stays None.
+
+    ``parameter_grad`` (default False): with True, grad enabled and at least one conv parameter requiring grad, the
+    same launches run through _LayersParamGrad, whose inputs are the conv parameters: autograd accumulates into the
+    ``.grad`` of ``weight_g`` / ``weight_v`` / ``bias`` (``weight`` without weight norm) from the kernels of
+    csrc/disc_wgrad.hip.  A frozen parameter gets no gradient and costs no launch.  An x that requires grad still
+    needs ``differentiable``."""
 
     differentiable = False
+    parameter_grad = False
     _MATERIALIZE_GRADS = True     # a map without a gradient arrives as zeros: _input_grad launches for every layer
 
     def _build_stack(self, in_channels, out_channels, kernel_sizes, channels, max_downsample_channels, bias,
@@ -228,6 +271,88 @@ class ConvStack(DiscriminatorModule):
                 layers.append((spec, w, conv.in_channels))
             return layers
         return cached(self, "grad_layers", build)
+
+    def _conv_params(self):
+        """Per layer the conv's parameters in the order _LayersParamGrad takes them: (weight_g, weight_v[, bias]) under
+        weight norm, (weight[, bias]) without."""
+        out = []
+        for conv in self._convs():
+            if hasattr(conv, "weight_g") and hasattr(conv, "weight_v"):
+                ps = [conv.weight_g, conv.weight_v]
+            else:
+                ps = [conv.weight]
+            out.append(ps + ([] if conv.bias is None else [conv.bias]))
+        return out
+
+    def _stack(self, x, grad, params=False):
+        """``_run_layers(x)``; on the parameters' graph (_LayersParamGrad) when ``params`` and grad is enabled and a
+        conv parameter requires grad, else as DiscriminatorModule._stack."""
+        if params and torch.is_grad_enabled():
+            flat = [q for ps in self._conv_params() for q in ps]
+            if any(q.requires_grad for q in flat):
+                return list(_LayersParamGrad.apply(self, x, *flat))
+        return super()._stack(x, grad)
+
+    def _param_grad(self, x, outs, params, grads, need_x, need):
+        """The backward of _LayersParamGrad, walking the layers downwards: per layer g_pre once (fv_disc_map_grad), the
+        weight and bias gradient from g_pre and the layer's stored input, the weight-norm adjoint, and the data
+        gradient for the layer below with the kernels of _input_grad.  ``need``: one flag per entry of ``params``; the
+        walk ends at the lowest layer with a flagged parameter unless ``need_x``.  -> (gx or None, [gradient or None
+        per parameter])."""
+        layers = self._native_grad_layers()
+        convs = self._convs()
+        counts = [len(ps) for ps in self._conv_params()]
+        first = [sum(counts[:l]) for l in range(len(counts))]
+        wanted = [any(need[first[l]:first[l] + counts[l]]) for l in range(len(layers))]
+        stop = 0 if need_x else min([l for l, w in enumerate(wanted) if w], default=len(layers))
+        out = [None] * len(params)
+        g_up = None
+        for l in range(len(layers) - 1, stop - 1, -1):
+            spec, w, cin = layers[l]
+            g_map = None if grads[l] is None else grads[l].to(torch.float32).contiguous()
+            if g_up is None and g_map is None:
+                continue
+            xin = outs[l - 1] if l else x
+            slope = spec[4]
+            if slope != 1.0 or (g_up is not None and g_map is not None):
+                g_pre = _native.disc_map_grad(g_up, g_map, outs[l] if slope != 1.0 else None, slope)
+            else:
+                g_pre = g_up if g_up is not None else g_map
+            if wanted[l]:
+                conv, at = convs[l], first[l]
+                norm = hasattr(conv, "weight_g") and hasattr(conv, "weight_v")
+                nw = 2 if norm else 1
+                want_dw = any(need[at:at + nw])
+                want_db = conv.bias is not None and need[at + nw]
+                if spec[0] == "grouped":
+                    dw, db = _native.grouped_conv1d_weight_grad(g_pre, xin, spec[1], spec[3], spec[2], want_dw, want_db)
+                else:
+                    dw, db = _native.conv1d_weight_grad(g_pre, xin, spec[1], spec[2], spec[3], want_dw, want_db)
+                if want_db:
+                    out[at + nw] = db
+                if want_dw and norm:
+                    g, v = params[at], params[at + 1]
+                    dv, dg = _native.weight_norm_grad(dw, v.detach().contiguous(), g.detach().contiguous(),
+                                                      need[at + 1], need[at])
+                    out[at], out[at + 1] = dg, dv
+                elif want_dw:
+                    out[at] = dw
+            if l == stop and not need_x:
+                break
+            tin = xin.shape[-1]
+            if spec[0] == "grouped":
+                _, k, pad, stride, _ = spec
+                g_up = _native.grouped_conv1d_input_grad(g_pre, None, None, w, cin, tin, k, stride, pad, 1.0)
+                continue
+            _, k, pad, mode, _ = spec
+            if mode == PAD_REFLECT:
+                g_up = _native.reflect_pad_fold(_native.conv1d_fused(g_pre, w, None, cin, k, pad=k - 1), pad)
+            else:
+                g_up = _native.conv1d_fused(g_pre, w, None, cin, k, pad=k - 1 - pad)
+        gx = None
+        if need_x:
+            gx = torch.zeros_like(x) if g_up is None else g_up
+        return gx, out
 
     def _input_grad(self, x, outs, grads):
         """d/dx of sum_l <grads[l], outs[l]> (None = zero), walking the layers downwards: the LeakyReLU mask of a

@@ -23,7 +23,8 @@ class _AvgPool(torch.autograd.Function):
 class MelGANDiscriminator(ConvStack):
     """msd.py:13-118: reflect-padded Conv1d(1 -> channels, prod(kernel_sizes)), grouped strided downsamples
     (k = 10 s + 1, groups = in_chs // 4), Conv1d(k0) and Conv1d(k1 -> 1); LeakyReLU after all but the last.
-    ``differentiable``: see ConvStack (the gradient with respect to x; the parameters' ``.grad`` stays None)."""
+    ``differentiable``: see ConvStack (the gradient with respect to x; the parameters' ``.grad`` stays None).
+    ``parameter_grad``: see ConvStack (the gradient of the conv parameters, csrc/disc_wgrad.hip)."""
 
     def __init__(self, in_channels=1, out_channels=1, kernel_sizes=[5, 3], channels=16, max_downsample_channels=1024,
                  bias=True, downsample_scales=[4, 4, 4, 4], nonlinear_activation="LeakyReLU",
@@ -41,10 +42,15 @@ class MelGANDiscriminator(ConvStack):
         """Shortest input the reflection pad accepts (more samples than the pad)."""
         return self._first_pad + 1
 
-    def _forward(self, x, graph):
-        """x (B, 1, T) -> list of every layer's output."""
+    def _forward(self, x, graph, params=None):
+        """x (B, 1, T) -> list of every layer's output.  ``params``: the parameters' graph (None: as the
+        ``parameter_grad`` attribute says)."""
         x = checked_input(self, x, 3, graph)
-        return self._stack(x, wants_grad(x, graph))
+        return self._stack(x, wants_grad(x, graph), self.parameter_grad if params is None else params)
+
+    def _param_forward(self, x):
+        """``forward`` on the parameters' graph whatever ``parameter_grad`` says (loss.discriminator_step_terms)."""
+        return self._forward(x, self.differentiable, True)
 
 
 class MelGANMultiScaleDiscriminator(DiscriminatorModule):
@@ -91,6 +97,17 @@ class MelGANMultiScaleDiscriminator(DiscriminatorModule):
         for d in self.discriminators:
             d.differentiable = bool(value)
 
+    @property
+    def parameter_grad(self):
+        """True when every scale carries the gradient of its parameters (ConvStack.parameter_grad); setting it sets
+        every scale."""
+        return all(d.parameter_grad for d in self.discriminators)
+
+    @parameter_grad.setter
+    def parameter_grad(self, value):
+        for d in self.discriminators:
+            d.parameter_grad = bool(value)
+
     def _pooled_length(self, n):
         k, s, p = self._pool
         return (n + 2 * p - k) // s + 1
@@ -106,15 +123,20 @@ class MelGANMultiScaleDiscriminator(DiscriminatorModule):
             return True
         return first_length(ok)
 
-    def _forward(self, x, graph):
+    def _forward(self, x, graph, params=None):
         """x (B, 1, T) -> list over the scales of each scale's list of layer outputs.  The scales run as ``_stack``,
         without their own input checks: min_length() above already guarantees every pooled length, and
-        ``differentiable`` is "all scales" -- with only some set, an x that requires grad is refused right here."""
+        ``differentiable`` is "all scales" -- with only some set, an x that requires grad is refused right here.
+        ``params``: the parameters' graph for every scale (None: as each scale's ``parameter_grad`` says)."""
         x = checked_input(self, x, 3, graph)
         grad = wants_grad(x, graph)
         outs = []
         for i, f in enumerate(self.discriminators):
-            outs += [f._stack(x, grad)]
+            outs += [f._stack(x, grad, f.parameter_grad if params is None else params)]
             if i + 1 < len(self.discriminators):
                 x = _AvgPool.apply(x, self._pool) if grad else _native.avg_pool1d(x, *self._pool)
         return outs
+
+    def _param_forward(self, x):
+        """``forward`` on the parameters' graph whatever ``parameter_grad`` says (loss.discriminator_step_terms)."""
+        return self._forward(x, self.differentiable, True)

@@ -1,5 +1,6 @@
 """The discriminator scores of the reference's training loop (bin/train.py:97-117, 157-169); with
-``differentiable=True`` they carry the gradient with respect to the estimate's maps.
+``differentiable=True`` they carry the gradient with respect to the estimate's maps, and discriminator_step_terms
+carries the gradient of the discriminator's own update with respect to its parameters.
 
 With est_p = D(estimate) and p = D(real), lists of L lists of feature maps (the last map of each list its score):
 
@@ -166,6 +167,75 @@ def generator_adversarial_terms(discriminator, estimate, real=None, *, period_gr
         p = _as_lists(discriminator, discriminator(real))
     terms = discriminator_terms(est_p, p, differentiable=True)
     return {"adversarial": terms["adversarial"], "feature_map": terms["feature_map"]}
+
+
+def _step_terms(es, rs):
+    """(real, fake, discriminator) as one float64 [3] tensor from the score maps alone (es the estimate's, rs the real
+    signal's): the sums, means and divisors of compose_terms, hence its bits."""
+    sums = torch.as_tensor(_native.disc_score_sums(es, rs), dtype=torch.float64)
+    counts = torch.as_tensor([e[0].numel() for e in es], dtype=torch.float64, device=sums.device)
+    means = sums.sum(dim=1) / (counts[:, None] * sums.shape[1])
+    L, last = len(es), list(range(len(es)))
+    fake = means[last, ..., 2].sum(dim=0) / L
+    real = means[last, ..., 3].sum(dim=0) / L
+    return torch.stack([real, fake, real + fake])
+
+
+class _StepTerms(torch.autograd.Function):
+    """_step_terms on the graph of the score maps of both passes: the backward is one fv_disc_score_grad launch per
+    pass, the (e - 1)^2 coefficient on the real signal's score maps and the e^2 coefficient on the estimate's."""
+
+    @staticmethod
+    def forward(ctx, *maps):
+        L = len(maps) // 2
+        ctx.save_for_backward(*maps)
+        return _step_terms(list(maps[:L]), list(maps[L:]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        maps = ctx.saved_tensors
+        L = len(maps) // 2
+        es, rs = list(maps[:L]), list(maps[L:])
+        g_real, g_fake, g_disc = (float(v) for v in g.detach().cpu().tolist())
+        B = es[0].shape[0]
+        need = ctx.needs_input_grad
+        ge, gr = [None] * L, [None] * L
+        if any(need[:L]):
+            coef = [(0.0, 0.0, (g_fake + g_disc) / (L * e[0].numel() * B)) for e in es]
+            ge = _native.disc_score_grad(es, es, coef, [not n for n in need[:L]])
+        if any(need[L:]):
+            coef = [(0.0, (g_real + g_disc) / (L * r[0].numel() * B), 0.0) for r in rs]
+            gr = _native.disc_score_grad(rs, rs, coef, [not n for n in need[L:]])
+        return tuple(ge) + tuple(gr)
+
+
+def discriminator_step_terms(discriminator, estimate, real):
+    """The terms of the discriminator's own update (bin/train.py:157-169) as one call, attached to the graph of the
+    discriminator's PARAMETERS: {"real", "fake", "discriminator"} as 0-d fp32 device tensors with the reference's
+    divisors, real = sum_i MSE(D(real)[i][-1], 1) / L and fake = sum_i MSE(D(estimate.detach())[i][-1], 0) / L.
+    ``estimate`` and ``real`` are (B, 1, T) fp32 device tensors; ``estimate`` is detached, as train.py:159 does.  The
+    module's parameter-gradient forward runs on both signals whatever its ``parameter_grad`` attribute says (the
+    launches and bits of its plain forward); ``terms["discriminator"].backward()`` accumulates into the ``.grad`` of
+    every conv parameter that requires grad (csrc/disc_wgrad.hip).  The feature maps get no gradient.  Under
+    torch.no_grad(), or with every parameter frozen, the same values come back with no graph.  Accepted:
+    MelGANDiscriminator and MelGANMultiScaleDiscriminator; the STFT discriminators, the period discriminators and
+    Discriminator() have no parameter gradient yet and are refused."""
+    from ..discriminator import MelGANDiscriminator, MelGANMultiScaleDiscriminator
+    if not isinstance(discriminator, (MelGANDiscriminator, MelGANMultiScaleDiscriminator)):
+        raise NotImplementedError(f"discriminator_step_terms: {type(discriminator).__name__} has no parameter gradient "
+                                  "yet; supported: MelGANDiscriminator, MelGANMultiScaleDiscriminator")
+    if not torch.is_tensor(estimate):
+        raise TypeError(f"estimate must be a tensor, got {type(estimate).__name__}")
+    p = _as_lists(discriminator, discriminator._param_forward(real))
+    est_p = _as_lists(discriminator, discriminator._param_forward(estimate.detach()))
+    es = [lst[-1].to(torch.float32).contiguous() for lst in est_p]
+    rs = [lst[-1].to(torch.float32).contiguous() for lst in p]
+    if torch.is_grad_enabled() and any(m.requires_grad for m in es + rs):
+        terms = _StepTerms.apply(*es, *rs)
+    else:
+        terms = _step_terms(es, rs)
+    return {k: terms[i].float() for i, k in enumerate(("real", "fake", "discriminator"))}
 
 
 def discriminator_terms(est_p, p, per_utterance=False, differentiable=False):

@@ -739,6 +739,43 @@ int fv_disc_score_grad(const float* const* e, const float* const* r, float* cons
                        const float* coef, int M, int B, void* stream);
 
 /*
+ * The parameter gradient of the multi-scale discriminator (bin/train.py:143-188, the discriminator's update);
+ * additions of ABI 18, no existing entry changes.  Exact fp32, no atomics: the reduction over (b, t) is cut into a
+ * number of splits that depends on the shape alone, a first launch writes every split's partial sums to `workspace`,
+ * a second adds them in ascending order, so identical calls return identical bits.  Workgroups never wait on each
+ * other.  workspace: device memory of at least fv_conv_weight_grad_workspace_bytes(...) bytes (4-byte aligned), which
+ * returns a negative FV_ERR_* code for arguments the entry itself would refuse; its contents on entry do not matter.
+ *
+ * fv_conv1d_weight_grad: the weight gradient of a dense stride-1 conv with zero or reflection padding,
+ *     dw[co, ci, j] = sum_{b, t} g_pre[b, co, t] * xpad[b, ci, t + j],      db[co] = sum_{b, t} g_pre[b, co, t]
+ * g_pre [B,Cout,Tout], Tout = Tin + 2 pad - k + 1, the gradient in front of the layer's LeakyReLU as fv_disc_map_grad
+ * writes it; x [B,Cin,Tin] the layer's stored input, padded by indexing (pad_mode FV_PAD_ZERO or FV_PAD_REFLECT);
+ * dw [Cout,Cin,k]; db [Cout] or NULL (dw may be NULL when db is not).  Cout >= 64 with Cin k >= 64 runs as a GEMM on
+ * v_mfma_f32_32x32x2_f32 (each element one k-ordered fmaf chain per split), every other shape as a plain reduction.
+ * Any Cin, Cout, k >= 1 with Cin Cout k < 2^31; another pad_mode returns FV_ERR_UNSUPPORTED.  Tout < 1, pad < 0, a
+ * reflection pad >= Tin, a null pointer, a result aliasing an input, a small workspace or B outside 1..65535 returns
+ * FV_ERR_INVALID_ARG.
+ *
+ * fv_grouped_conv1d_weight_grad: the weight gradient of fv_grouped_conv1d,
+ *     dw[oc, ci, j] = sum_{b, t} g_pre[b, oc, t] * x[b, 4 g + ci, t stride + j - pad]      (oc in group g)
+ * with x read as 0 outside [0, Tin); dw [Cout,4,k]; db as above.  Exact fp32 on the VALU.  Supported shapes and error
+ * codes as fv_grouped_conv1d_input_grad (FV_ERR_UNSUPPORTED first, before any launch).
+ *
+ * fv_weight_norm_grad: the adjoint of fv_fold_weight_norm.  Per row r of dw, v [dim0, inner] and g [dim0]:
+ *     dot = <dw_r, v_r>, n = |v_r|;   dg[r] = dot / n;   dv_r = (g[r] / n) (dw_r - (dot / n^2) v_r)
+ * dv or dg may be NULL (not both).  One launch, one block per row, fixed order.
+ */
+int64_t fv_conv_weight_grad_workspace_bytes(int grouped, int B, int Cin, int Cout, int Tin, int k, int stride, int pad,
+                                            int pad_mode);
+int fv_conv1d_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout, int Tin,
+                          int k, int pad, int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
+int fv_grouped_conv1d_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout,
+                                  int Tin, int k, int stride, int pad, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int fv_weight_norm_grad(const float* dw, const float* v, const float* g, float* dv, float* dg, int dim0, int64_t inner,
+                        void* stream);
+
+/*
  * The multi-period discriminator's convs (model/discriminator/mpd.py:131-164 DiscriminatorP).  A map [B, C, H, p] is
  * contiguous (flattened time n = h p + c); additions of ABI 18, no existing entry changes.
  *
