@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -264,6 +264,12 @@ def lib():
     L.fv_conv_weight_grad_workspace_bytes.restype = i64
     L.fv_conv1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
     L.fv_grouped_conv1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_period_conv_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.fv_period_conv_weight_grad_workspace_bytes.restype = i64
+    L.fv_period_conv_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_mpd_first_weight_grad_workspace_bytes.argtypes = [i, i64, i]
+    L.fv_mpd_first_weight_grad_workspace_bytes.restype = i64
+    L.fv_mpd_first_weight_grad.argtypes = [vp, vp, vp, vp, i, i64, i, vp, ctypes.c_size_t, vp]
     L.fv_weight_norm_grad.argtypes = [vp, vp, vp, vp, vp, i, i64, vp]
     L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
     L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
@@ -1424,6 +1430,76 @@ def grouped_conv1d_weight_grad(g_pre, x, k, stride, pad, want_dw=True, want_db=F
     [B,Cout,Tout], x [B,Cin,Tin] -> (dw [Cout,4,k] or None, db [Cout] or None)."""
     return _weight_grad("grouped_conv1d_weight_grad", True, g_pre, x, k, stride, pad, PAD_ZERO, want_dw, want_db,
                         workspace)
+
+
+PERIOD_WGRAD_UNIT = 32       # flat positions h' p + c per unit of period_wgrad_mfma_kernel (csrc/mpd_wgrad.hip kPwTK)
+PERIOD_WGRAD_CHUNK = 1024    # ... of its plain path and of the first layer's kernel (kPwChunk)
+
+
+def period_conv_weight_grad_workspace_floats(B, cin, cout, H, period, k, stride):
+    """fp32 words of workspace period_conv_weight_grad needs for these shapes
+    (fv_period_conv_weight_grad_workspace_bytes); raises for shapes the entry refuses."""
+    need = lib().fv_period_conv_weight_grad_workspace_bytes(int(B), int(cin), int(cout), int(H), int(period), int(k),
+                                                            int(stride))
+    if need < 0:
+        check(int(need))
+    return (need + 3) // 4
+
+
+def period_conv_weight_grad(g_pre, x, k, stride, want_dw=True, want_db=False, workspace=None):
+    """The weight (and bias) gradient of a (k, 1) conv along H with zero padding (k - 1) // 2
+    (fv_period_conv_weight_grad, two launches): g_pre [B,Cout,(H-1)//stride+1,p] the gradient in front of the
+    LeakyReLU, x [B,Cin,H,p] the layer's input -> (dw [Cout,Cin,k] or None, db [Cout] or None).  ``workspace``: an
+    fp32 device tensor to use instead of a fresh one (its contents do not matter)."""
+    if g_pre.dim() != 4 or x.dim() != 4 or g_pre.shape[0] != x.shape[0] or g_pre.shape[3] != x.shape[3]:
+        raise NativeError(f"period_conv_weight_grad: g_pre [B,Cout,H',p] and x [B,Cin,H,p] expected, got "
+                          f"{tuple(g_pre.shape)} and {tuple(x.shape)}")
+    if not (want_dw or want_db):
+        raise NativeError("period_conv_weight_grad: neither the weight nor the bias gradient is asked for")
+    B, cout, hout, p = g_pre.shape
+    cin, H = x.shape[1], x.shape[2]
+    k, stride = int(k), int(stride)
+    if stride > 0 and H > 0 and hout != (H - 1) // stride + 1:
+        raise NativeError(f"period_conv_weight_grad: {hout} output rows do not belong to an input of {H} rows")
+    dev = g_pre.device
+    if workspace is None:
+        workspace = torch.empty(period_conv_weight_grad_workspace_floats(B, cin, cout, H, p, k, stride),
+                                dtype=torch.float32, device=dev)
+    dw = torch.empty((cout, cin, k), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
+    with _on(g_pre, x, workspace, dw, db) as stream:
+        check(lib().fv_period_conv_weight_grad(_ptr(g_pre, "g_pre"), _ptr(x, "x"), _ptr(dw, "dw", True),
+                                               _ptr(db, "db", True), B, cin, cout, H, p, k, stride,
+                                               _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
+    return dw, db
+
+
+def mpd_first_weight_grad(g_pre, x, want_dw=True, want_db=False, workspace=None):
+    """The weight (and bias) gradient of mpd_conv_first (fv_mpd_first_weight_grad, two launches): g_pre [B,32,H1,p],
+    x [B,1,T] the waveform -> (dw [32,5] or None, db [32] or None)."""
+    if g_pre.dim() != 4 or g_pre.shape[1] != 32 or x.dim() != 3 or x.shape[1] != 1 or x.shape[0] != g_pre.shape[0]:
+        raise NativeError(f"mpd_first_weight_grad: g_pre [B,32,H1,p] and x [B,1,T] expected, got "
+                          f"{tuple(g_pre.shape)} and {tuple(x.shape)}")
+    if not (want_dw or want_db):
+        raise NativeError("mpd_first_weight_grad: neither the weight nor the bias gradient is asked for")
+    B, _, h1, p = g_pre.shape
+    T = x.shape[2]
+    H = (T + mpd_reflect_tail(T, p)) // p if p > 0 else 0
+    if T < 1 or h1 != (H - 1) // 3 + 1:
+        raise NativeError(f"mpd_first_weight_grad: {h1} output rows do not belong to a waveform of {T} samples")
+    dev = g_pre.device
+    if workspace is None:
+        need = lib().fv_mpd_first_weight_grad_workspace_bytes(B, T, p)
+        if need < 0:
+            check(int(need))
+        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+    dw = torch.empty((32, 5), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty((32,), dtype=torch.float32, device=dev) if want_db else None
+    with _on(g_pre, x, workspace, dw, db) as stream:
+        check(lib().fv_mpd_first_weight_grad(_ptr(g_pre, "g_pre"), _ptr(x, "x"), _ptr(dw, "dw", True),
+                                             _ptr(db, "db", True), B, T, p, _ptr(workspace, "workspace"),
+                                             workspace.numel() * 4, stream))
+    return dw, db
 
 
 def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):

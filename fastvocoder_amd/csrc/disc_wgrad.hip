@@ -55,27 +55,6 @@ __device__ __forceinline__ float wg_xpad(const float* __restrict__ row, int q, i
     return row[p];
 }
 
-// sum over the block's 256 threads in a fixed order: the shuffle tree of each wave, then the 4 waves ascending
-__device__ __forceinline__ float wg_block_sum(float v, float* part) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                  // (the previous sum's readers are done)
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-struct WgArgs {
-    const float* g;       // [B, Cout, Tout]
-    const float* x;       // [B, Cin, Tin]
-    float* ws;            // [S][R]
-    int64_t R;            // floats per record: Cout N + Cout
-    int64_t U;            // units
-    int S, nch;           // splits; units per row b
-    int Cin, Cout, Tin, Tout, k, pad, reflect, stride;
-    int with_bias;
-};
-
 // grid (Cout Cin, 1, S)
 __global__ __launch_bounds__(kWgThreads) void dense_wgrad_plain_kernel(WgArgs a) {
     __shared__ float part[4];
@@ -283,20 +262,6 @@ __global__ __launch_bounds__(256) void weight_norm_grad_kernel(const float* __re
 // ---- host side: which kernel, how many splits ----
 enum { kWgPlain = 0, kWgMfma = 1, kWgGrouped16 = 2, kWgGrouped4 = 3 };
 
-struct WgPlan {
-    int path, S, nch, TT, threads;
-    int64_t U, R;
-    size_t lds;
-    dim3 grid;
-};
-
-static int wg_splits(int64_t base, int64_t U, int aim) {
-    int64_t S = (aim + base - 1) / base;
-    if (S > U) S = U;
-    if (S > 4096) S = 4096;
-    return S < 1 ? 1 : (int)S;
-}
-
 static size_t wg_mfma_lds(int k) { return sizeof(float) * ((size_t)kWmTile * kWmGS + (size_t)(127 / k + 2) * (kWmTK + k)); }
 
 static int dense_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int pad, int pad_mode, WgPlan* p) {
@@ -367,8 +332,15 @@ static int grouped_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int stri
     return 0;
 }
 
-static int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes,
-                     const char* who, hipStream_t st) {
+int launch_wgrad_combine(const float* ws, float* dw, float* db, int64_t MN, int Cout, int64_t R, int S, hipStream_t st) {
+    hipLaunchKernelGGL(wgrad_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, ws, dw, db, MN, Cout, R,
+                       S);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes, const char* who,
+              hipStream_t st) {
     const size_t need = sizeof(float) * (size_t)p.S * (size_t)p.R;
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
         return fail(FV_ERR_INVALID_ARG, "%s: workspace of %zu bytes, needs %zu (4-byte aligned)", who, workspace_bytes,
@@ -394,11 +366,7 @@ static int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* work
         break;
     }
     FV_HIP(hipGetLastError());
-    const int64_t MN = p.R - a.Cout;
-    hipLaunchKernelGGL(wgrad_combine_kernel, dim3((unsigned)((p.R + 255) / 256)), dim3(256), 0, st, a.ws, dw, db, MN,
-                       a.Cout, p.R, p.S);
-    FV_HIP(hipGetLastError());
-    return 0;
+    return launch_wgrad_combine(a.ws, dw, db, p.R - a.Cout, a.Cout, p.R, p.S, st);
 }
 
 }  // namespace fv

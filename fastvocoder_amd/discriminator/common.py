@@ -101,8 +101,11 @@ def first_length(ok, start=1):
 
 
 class NotDifferentiable:
-    """Mix-in of the modules without an input gradient: ``differentiable`` reads False, and setting it raises.  They
-    have no parameter gradient either: ``parameter_grad`` behaves the same way."""
+    """Mix-in of the modules without an input gradient: ``differentiable`` reads False, and setting it raises.
+    ``parameter_grad`` behaves the same way: the parameter gradient of these modules (the STFT discriminators, the
+    period discriminators, Discriminator()) is opt-in per call, through
+    fastvocoder_amd.loss.discriminator_step_terms with its keywords stft_grad=True / period_grad=True, never through
+    an attribute."""
 
     @property
     def parameter_grad(self):
@@ -183,10 +186,57 @@ class DiscriminatorModule(NativeModule):
         """``forward`` on the graph of x whatever ``differentiable`` says (loss.generator_adversarial_terms)."""
         return self._forward(x, True)
 
-    def _stack(self, x, grad):
-        """``_run_layers(x)`` of a module with layers of its own, through _LayersGrad (backward: the module's
-        ``_input_grad``) when ``grad``."""
+    def _conv_params(self):
+        """Per layer (``_convs()``) the conv's parameters in the order _LayersParamGrad takes them: (weight_g,
+        weight_v[, bias]) under weight norm, (weight[, bias]) without."""
+        out = []
+        for conv in self._convs():
+            if hasattr(conv, "weight_g") and hasattr(conv, "weight_v"):
+                ps = [conv.weight_g, conv.weight_v]
+            else:
+                ps = [conv.weight]
+            out.append(ps + ([] if conv.bias is None else [conv.bias]))
+        return out
+
+    def _stack(self, x, grad, params=False):
+        """``_run_layers(x)`` of a module with layers of its own: on the parameters' graph (_LayersParamGrad, backward
+        the module's ``_param_grad``) when ``params`` and grad is enabled and a conv parameter requires grad; else
+        through _LayersGrad (backward: the module's ``_input_grad``) when ``grad``."""
+        if params and torch.is_grad_enabled():
+            flat = [q for ps in self._conv_params() for q in ps]
+            if any(q.requires_grad for q in flat):
+                return list(_LayersParamGrad.apply(self, x, *flat))
         return list(_LayersGrad.apply(self, x)) if grad else self._run_layers(x)
+
+    def _param_plan(self, need):
+        """What both ``_param_grad`` walks start from: (index of each layer's first parameter, whether a parameter of
+        the layer is flagged in ``need``)."""
+        counts = [len(ps) for ps in self._conv_params()]
+        first = [sum(counts[:l]) for l in range(len(counts))]
+        return first, [any(need[first[l]:first[l] + counts[l]]) for l in range(len(counts))]
+
+    @staticmethod
+    def _param_wants(conv, need, at):
+        """(the weight gradient is needed, the bias gradient is needed) of a conv whose parameters start at ``at``."""
+        nw = 2 if hasattr(conv, "weight_g") and hasattr(conv, "weight_v") else 1
+        return any(need[at:at + nw]), conv.bias is not None and need[at + nw]
+
+    @staticmethod
+    def _param_store(conv, params, need, at, dw, db, out):
+        """A layer's dw (shaped like its weight, or None) and db (or None) into ``out``: the bias gradient, and the
+        weight gradient through the weight-norm adjoint (fv_weight_norm_grad on [Cout, the rest]) where the conv has
+        one."""
+        norm = hasattr(conv, "weight_g") and hasattr(conv, "weight_v")
+        nw = 2 if norm else 1
+        if db is not None:
+            out[at + nw] = db
+        if dw is not None and norm:
+            g, v = params[at], params[at + 1]
+            dv, dg = _native.weight_norm_grad(dw.view_as(v), v.detach().contiguous(), g.detach().contiguous(),
+                                              need[at + 1], need[at])
+            out[at], out[at + 1] = dg, dv
+        elif dw is not None:
+            out[at] = dw.view_as(params[at])
 
 
 class ConvStack(DiscriminatorModule):
@@ -272,27 +322,6 @@ class ConvStack(DiscriminatorModule):
             return layers
         return cached(self, "grad_layers", build)
 
-    def _conv_params(self):
-        """Per layer the conv's parameters in the order _LayersParamGrad takes them: (weight_g, weight_v[, bias]) under
-        weight norm, (weight[, bias]) without."""
-        out = []
-        for conv in self._convs():
-            if hasattr(conv, "weight_g") and hasattr(conv, "weight_v"):
-                ps = [conv.weight_g, conv.weight_v]
-            else:
-                ps = [conv.weight]
-            out.append(ps + ([] if conv.bias is None else [conv.bias]))
-        return out
-
-    def _stack(self, x, grad, params=False):
-        """``_run_layers(x)``; on the parameters' graph (_LayersParamGrad) when ``params`` and grad is enabled and a
-        conv parameter requires grad, else as DiscriminatorModule._stack."""
-        if params and torch.is_grad_enabled():
-            flat = [q for ps in self._conv_params() for q in ps]
-            if any(q.requires_grad for q in flat):
-                return list(_LayersParamGrad.apply(self, x, *flat))
-        return super()._stack(x, grad)
-
     def _param_grad(self, x, outs, params, grads, need_x, need):
         """The backward of _LayersParamGrad, walking the layers downwards: per layer g_pre once (fv_disc_map_grad), the
         weight and bias gradient from g_pre and the layer's stored input, the weight-norm adjoint, and the data
@@ -301,9 +330,7 @@ class ConvStack(DiscriminatorModule):
         per parameter])."""
         layers = self._native_grad_layers()
         convs = self._convs()
-        counts = [len(ps) for ps in self._conv_params()]
-        first = [sum(counts[:l]) for l in range(len(counts))]
-        wanted = [any(need[first[l]:first[l] + counts[l]]) for l in range(len(layers))]
+        first, wanted = self._param_plan(need)
         stop = 0 if need_x else min([l for l, w in enumerate(wanted) if w], default=len(layers))
         out = [None] * len(params)
         g_up = None
@@ -320,23 +347,12 @@ class ConvStack(DiscriminatorModule):
                 g_pre = g_up if g_up is not None else g_map
             if wanted[l]:
                 conv, at = convs[l], first[l]
-                norm = hasattr(conv, "weight_g") and hasattr(conv, "weight_v")
-                nw = 2 if norm else 1
-                want_dw = any(need[at:at + nw])
-                want_db = conv.bias is not None and need[at + nw]
+                want_dw, want_db = self._param_wants(conv, need, at)
                 if spec[0] == "grouped":
                     dw, db = _native.grouped_conv1d_weight_grad(g_pre, xin, spec[1], spec[3], spec[2], want_dw, want_db)
                 else:
                     dw, db = _native.conv1d_weight_grad(g_pre, xin, spec[1], spec[2], spec[3], want_dw, want_db)
-                if want_db:
-                    out[at + nw] = db
-                if want_dw and norm:
-                    g, v = params[at], params[at + 1]
-                    dv, dg = _native.weight_norm_grad(dw, v.detach().contiguous(), g.detach().contiguous(),
-                                                      need[at + 1], need[at])
-                    out[at], out[at + 1] = dg, dv
-                elif want_dw:
-                    out[at] = dw
+                self._param_store(conv, params, need, at, dw, db, out)
             if l == stop and not need_x:
                 break
             tin = xin.shape[-1]

@@ -34,3 +34,17 @@ class Discriminator(NotDifferentiable, DiscriminatorModule):
         if self.use_mpd and not graph:
             mpd = self.mpd._forward(x, graph)
         return mpd + outs
+
+    def _param_forward(self, x):
+        """``_forward`` with every sub-discriminator on its parameters' graph (loss.discriminator_step_terms with
+        stft_grad=True, and period_grad=True with ``use_mpd``): the lists in the order of ``_forward``.  The launch
+        order is fixed: forward, the MPD's periods in the order of PERIODS (with ``use_mpd``), then the MSD's scales
+        from scale 0, each behind its pool, then the MFD's resolutions in the order of the list; backward, autograd
+        runs the nodes in the reverse of the build order (a node built later runs earlier) -- the MFD's resolutions
+        from the last to the first, the MSD's scales from the coarsest to scale 0, the MPD's periods from 11 down to
+        2 -- and inside a node the layers from the score downwards, per layer the weight and bias gradient, the
+        weight-norm adjoint, then the data gradient for the layer below.  No two nodes share a parameter, so every
+        ``.grad`` is written by one node: the same order, hence the same bits, on every call."""
+        x = checked_input(self, x, 3, False, mono=False)
+        mpd = self.mpd._param_forward(x) if self.use_mpd else []
+        return mpd + self.msd._param_forward(x) + self.mfd._param_forward(x)

@@ -70,6 +70,14 @@ class STFTDiscriminator(NotDifferentiable, ConvStack):
             _native.stft_magnitude_bins(x, self._table(), *geometry)
         return self._stack(mag, grad)
 
+    def _param_forward(self, x):
+        """``forward`` on the parameters' graph (loss.discriminator_step_terms(..., stft_grad=True)): the clamped
+        magnitude is a constant of the parameters, the stack runs through _LayersParamGrad (ConvStack._param_grad,
+        csrc/disc_wgrad.hip) -- the launches and bits of the plain forward."""
+        x = checked_input(self, x, 2, False, mono=False)
+        mag = _native.stft_magnitude_bins(x, self._table(), self.fft_size, self.shift_size, self.win_length)
+        return self._stack(mag, False, True)
+
 
 class MultiResolutionSTFTDiscriminator(NotDifferentiable, DiscriminatorModule):
     """mfd.py:139-178: one STFTDiscriminator per (fft_size, hop_size, win_length)."""
@@ -91,3 +99,9 @@ class MultiResolutionSTFTDiscriminator(NotDifferentiable, DiscriminatorModule):
         the resolutions' gradients into x."""
         x = checked_input(self, x, 3, graph).squeeze(1)
         return [f._forward(x, graph) for f in self.stft_discriminator]
+
+    def _param_forward(self, x):
+        """``_forward`` with every resolution on its parameters' graph (loss.discriminator_step_terms), in the order
+        of the list; the resolutions share no parameter."""
+        x = checked_input(self, x, 3, False).squeeze(1)
+        return [f._param_forward(x) for f in self.stft_discriminator]

@@ -143,6 +143,62 @@ class DiscriminatorP(NotDifferentiable, DiscriminatorModule):
             return torch.zeros_like(x)
         return _native.mpd_first_input_grad(g_up, gm[0], outs[0], layers[0], x.shape[-1], LRELU_SLOPE)
 
+    def _param_grad(self, x, outs, params, grads, need_x, need):
+        """The backward of _LayersParamGrad, the layer walk of _input_grad: per layer g_pre once (fv_disc_map_grad;
+        conv_post has no activation), the weight and bias gradient (fv_period_conv_weight_grad from g_pre and the
+        layer's stored input, fv_mpd_first_weight_grad from the waveform; csrc/mpd_wgrad.hip), the weight-norm adjoint
+        on the 4-D ``weight_v`` viewed as [Cout, Cin k], and the data gradient for the layer below with the kernels
+        of _input_grad.  ``need``: one flag per entry of ``params``; the walk ends at the lowest layer with a flagged
+        parameter.  The waveform gets no gradient on this route (``need_x`` is refused: loss.discriminator_step_terms
+        detaches the estimate and refuses an input that requires grad).  -> (None, [gradient or None per
+        parameter])."""
+        if need_x:
+            raise NotImplementedError("DiscriminatorP: the parameters' graph carries no input gradient")
+        p = self.period
+        layers = self._native_grad_layers()
+        convs = self._convs()
+        first, wanted = self._param_plan(need)
+        stop = min([l for l, w in enumerate(wanted) if w], default=len(convs))
+        out = [None] * len(params)
+        gm = [None if g is None else g.to(torch.float32).contiguous() for g in grads]
+        B, _, H, _ = outs[5].shape
+        g_up = None
+        for l in range(5, stop - 1, -1):
+            if g_up is None and gm[l] is None:
+                continue
+            if l == 5:
+                g_pre = gm[5]
+            else:
+                g_pre = _native.disc_map_grad(g_up, gm[l], outs[l], LRELU_SLOPE)
+            if wanted[l]:
+                conv, at = convs[l], first[l]
+                want_dw, want_db = self._param_wants(conv, need, at)
+                if l == 0:
+                    dw, db = _native.mpd_first_weight_grad(g_pre, x, want_dw, want_db)
+                else:
+                    dw, db = _native.period_conv_weight_grad(g_pre, outs[l - 1], conv.kernel_size[0], conv.stride[0],
+                                                             want_dw, want_db)
+                self._param_store(conv, params, need, at, dw, db, out)
+            if l == stop:
+                break
+            if l == 5:
+                g_up = _native.conv1d_fused(g_pre.view(B, 1, H * p), layers[5], None, 1024, 3, dil=p, pad=p,
+                                            pad_mode=PAD_ZERO).view(B, 1024, H, p)
+            elif l == 4:
+                g_up = _native.conv1d_fused(g_pre.view(B, 1024, H * p), layers[4], None, 1024, 5, dil=p, pad=2 * p,
+                                            pad_mode=PAD_ZERO).view(B, 1024, H, p)
+            else:
+                g_up = _native.period_conv_input_grad(g_pre, None, None, layers[l], convs[l].in_channels,
+                                                      outs[l - 1].shape[2], 1.0)
+        return None, out
+
+    def _param_forward(self, x):
+        """``forward`` on the parameters' graph (loss.discriminator_step_terms(..., period_grad=True)): the launches
+        and bits of the plain forward through _LayersParamGrad, whose backward is ``_param_grad``."""
+        x = checked_input(self, x, 3, False)
+        fmap = self._stack(x, False, True)
+        return fmap[5].flatten(1), fmap
+
     def _forward(self, x, graph):
         """x (B, 1, T) -> (score [B, H_6 p], the six feature maps [B, C, H_l, p]).  On the graph
         (loss.generator_adversarial_terms(..., period_grad=True)) the same launches run through _LayersGrad, whose
@@ -171,5 +227,16 @@ class MultiPeriodDiscriminator(NotDifferentiable, DiscriminatorModule):
         outs = []
         for d in self.discriminators:
             score, fmap = d._forward(x, graph)
+            outs.append(fmap + [score.unsqueeze(1)])
+        return outs
+
+    def _param_forward(self, x):
+        """``_forward`` with every period on its parameters' graph (loss.discriminator_step_terms), in the order of
+        PERIODS; the periods share no parameter, and autograd runs their backward nodes in the reverse of that
+        order."""
+        x = checked_input(self, x, 3, False)
+        outs = []
+        for d in self.discriminators:
+            score, fmap = d._param_forward(x)
             outs.append(fmap + [score.unsqueeze(1)])
         return outs

@@ -1,6 +1,7 @@
 """The discriminator scores of the reference's training loop (bin/train.py:97-117, 157-169); with
 ``differentiable=True`` they carry the gradient with respect to the estimate's maps, and discriminator_step_terms
-carries the gradient of the discriminator's own update with respect to its parameters.
+carries the gradient of the discriminator's own update with respect to its parameters (the MSD as it is, the STFT and
+period discriminators and Discriminator() with its keywords stft_grad / period_grad).
 
 With est_p = D(estimate) and p = D(real), lists of L lists of feature maps (the last map of each list its score):
 
@@ -210,21 +211,37 @@ class _StepTerms(torch.autograd.Function):
         return tuple(ge) + tuple(gr)
 
 
-def discriminator_step_terms(discriminator, estimate, real):
+def discriminator_step_terms(discriminator, estimate, real, *, stft_grad=False, period_grad=False):
     """The terms of the discriminator's own update (bin/train.py:157-169) as one call, attached to the graph of the
     discriminator's PARAMETERS: {"real", "fake", "discriminator"} as 0-d fp32 device tensors with the reference's
-    divisors, real = sum_i MSE(D(real)[i][-1], 1) / L and fake = sum_i MSE(D(estimate.detach())[i][-1], 0) / L.
-    ``estimate`` and ``real`` are (B, 1, T) fp32 device tensors; ``estimate`` is detached, as train.py:159 does.  The
-    module's parameter-gradient forward runs on both signals whatever its ``parameter_grad`` attribute says (the
-    launches and bits of its plain forward); ``terms["discriminator"].backward()`` accumulates into the ``.grad`` of
-    every conv parameter that requires grad (csrc/disc_wgrad.hip).  The feature maps get no gradient.  Under
-    torch.no_grad(), or with every parameter frozen, the same values come back with no graph.  Accepted:
-    MelGANDiscriminator and MelGANMultiScaleDiscriminator; the STFT discriminators, the period discriminators and
-    Discriminator() have no parameter gradient yet and are refused."""
-    from ..discriminator import MelGANDiscriminator, MelGANMultiScaleDiscriminator
-    if not isinstance(discriminator, (MelGANDiscriminator, MelGANMultiScaleDiscriminator)):
+    divisors, real = sum_i MSE(D(real)[i][-1], 1) / L and fake = sum_i MSE(D(estimate.detach())[i][-1], 0) / L
+    (L = 3 for the MSD and the MFD, 5 for the MPD, 6 for Discriminator(), 11 with use_mpd).  ``estimate`` and
+    ``real`` are (B, 1, T) fp32 device tensors ((B, T) for a single STFTDiscriminator, as its forward takes them);
+    ``estimate`` is detached, as train.py:159 does, and neither may require grad.  The module's parameter-gradient
+    forward runs on both signals whatever its ``parameter_grad`` attribute says (the launches and bits of its plain
+    forward); ``terms["discriminator"].backward()`` accumulates into the ``.grad`` of every conv parameter that
+    requires grad (csrc/disc_wgrad.hip, csrc/mpd_wgrad.hip).  The feature maps get no gradient.  Under
+    torch.no_grad(), or with every parameter frozen, the same values come back with no graph; a frozen parameter gets
+    no gradient and costs no launch.  Accepted as they are: MelGANDiscriminator and MelGANMultiScaleDiscriminator.
+    The other families are opt-in: ``stft_grad=True`` admits STFTDiscriminator and MultiResolutionSTFTDiscriminator,
+    ``period_grad=True`` admits DiscriminatorP and MultiPeriodDiscriminator, Discriminator() needs ``stft_grad=True``
+    and Discriminator(use_mpd=True) both; without the keyword it needs a module is refused.  For the MSD modules the
+    keywords change nothing."""
+    from ..discriminator import (Discriminator, DiscriminatorP, MelGANDiscriminator, MelGANMultiScaleDiscriminator,
+                                 MultiPeriodDiscriminator, MultiResolutionSTFTDiscriminator, STFTDiscriminator)
+    missing = []
+    if isinstance(discriminator, (STFTDiscriminator, MultiResolutionSTFTDiscriminator, Discriminator)) \
+            and not stft_grad:
+        missing.append("stft_grad=True")
+    if (isinstance(discriminator, (DiscriminatorP, MultiPeriodDiscriminator))
+            or (isinstance(discriminator, Discriminator) and discriminator.use_mpd)) and not period_grad:
+        missing.append("period_grad=True")
+    known = (MelGANDiscriminator, MelGANMultiScaleDiscriminator, STFTDiscriminator, MultiResolutionSTFTDiscriminator,
+             DiscriminatorP, MultiPeriodDiscriminator, Discriminator)
+    if missing or not isinstance(discriminator, known):
+        hint = f"; the gradient of this module is opt-in: pass {' and '.join(missing)}" if missing else ""
         raise NotImplementedError(f"discriminator_step_terms: {type(discriminator).__name__} has no parameter gradient "
-                                  "yet; supported: MelGANDiscriminator, MelGANMultiScaleDiscriminator")
+                                  f"yet; supported: MelGANDiscriminator, MelGANMultiScaleDiscriminator{hint}")
     if not torch.is_tensor(estimate):
         raise TypeError(f"estimate must be a tensor, got {type(estimate).__name__}")
     p = _as_lists(discriminator, discriminator._param_forward(real))

@@ -843,6 +843,37 @@ int fv_period_conv_input_grad(const float* g_up, const float* g_map, const float
 int fv_mpd_first_input_grad(const float* g_up, const float* g_map, const float* y0, const float* w, float* dx, int B,
                             int64_t T, int period, float slope, void* stream);
 
+/*
+ * The parameter gradient of the multi-period discriminator (bin/train.py:143-188, the discriminator's update);
+ * additions of ABI 18, no existing entry changes.  Exact fp32, no atomics, and the scheme of fv_conv1d_weight_grad: a
+ * number of splits that depends on the shape alone, a first launch that writes every split's partial sums to
+ * `workspace`, a second that adds them in ascending order, so identical calls return identical bits.  workspace: device
+ * memory of at least fv_..._workspace_bytes(...) bytes (4-byte aligned), which returns a negative FV_ERR_* code for
+ * arguments the entry itself would refuse; its contents on entry do not matter.
+ *
+ * fv_period_conv_weight_grad: the weight and bias gradient of a (k, 1) conv along H with zero padding (k - 1) / 2,
+ *     dw[co, ci, j] = sum_{b, h', c} g_pre[b, co, h', c] * x[b, ci, stride h' + j - (k - 1) / 2, c]
+ *     db[co]        = sum_{b, h', c} g_pre[b, co, h', c]
+ * g_pre [B, Cout, H', period], H' = (H - 1) / stride + 1, the gradient in front of the layer's LeakyReLU as
+ * fv_disc_map_grad writes it; x [B, Cin, H, period] the layer's stored input, rows outside [0, H) read as 0;
+ * dw [Cout, Cin, k]; db [Cout] or NULL (dw may be NULL when db is not).  Cout >= 64 with Cin k >= 64 runs as a GEMM
+ * [Cout] x [Cin k] over B H' period on v_mfma_f32_32x32x2_f32 in units of 32 flat positions h' period + c (each
+ * element one position-ordered fmaf chain per split), every other shape (conv_post) as a plain reduction in units of
+ * 1024 positions.  Supported: period 2, 3, 5, 7 or 11; k 1, 3 or 5; stride 1, 2 or 3; Cin Cout k < 2^31; anything else
+ * returns FV_ERR_UNSUPPORTED before any launch.  A null pointer, a result aliasing an input, a small workspace, H < 1,
+ * B outside 1..65535 or a map of 2^31 words and more returns FV_ERR_INVALID_ARG.
+ *
+ * fv_mpd_first_weight_grad: the gradient of fv_mpd_conv_first's weight [32, 5] and bias [32], straight from the
+ * waveform x [B, T]: the reflect tail and the [H, period] view are address arithmetic.  g_pre [B, 32, H1, period].
+ * A block reduction per output channel.  Checks as fv_mpd_first_input_grad.
+ */
+int64_t fv_period_conv_weight_grad_workspace_bytes(int B, int Cin, int Cout, int H, int period, int k, int stride);
+int fv_period_conv_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout, int H,
+                               int period, int k, int stride, void* workspace, size_t workspace_bytes, void* stream);
+int64_t fv_mpd_first_weight_grad_workspace_bytes(int B, int64_t T, int period);
+int fv_mpd_first_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int64_t T, int period,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
  * ------------------------------------------------------------------ */
