@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -271,6 +271,16 @@ def lib():
     L.fv_mpd_first_weight_grad_workspace_bytes.restype = i64
     L.fv_mpd_first_weight_grad.argtypes = [vp, vp, vp, vp, i, i64, i, vp, ctypes.c_size_t, vp]
     L.fv_weight_norm_grad.argtypes = [vp, vp, vp, vp, vp, i, i64, vp]
+    L.fv_conv1d_weight_grad_dilated_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.fv_conv1d_weight_grad_dilated_workspace_bytes.restype = i64
+    L.fv_conv1d_weight_grad_dilated.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_conv_transpose1d_input_grad.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, vp]
+    L.fv_conv_transpose1d_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
+    L.fv_conv_transpose1d_weight_grad_workspace_bytes.restype = i64
+    L.fv_conv_transpose1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_tanh_grad.argtypes = [vp, vp, vp, i64, vp]
+    L.fv_residual_merge_grad.argtypes = [vp, vp, vp, vp, vp, i64, f, vp]
+    L.fv_grad_div.argtypes = [vp, vp, i64, f, vp]
     L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
     L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
     L.fv_disc_score_grad.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
@@ -1513,6 +1523,146 @@ def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):
         check(lib().fv_weight_norm_grad(_ptr(dw, "dw"), _ptr(v, "v"), _ptr(g, "g"), _ptr(dv, "dv", True),
                                         _ptr(dg, "dg", True), v.shape[0], v[0].numel(), stream))
     return dv, dg
+
+
+# ---------------------------------------------------------------------------
+# the generators' parameter gradient (csrc/gen_grad.hip)
+# ---------------------------------------------------------------------------
+
+def conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil=1, pad=0):
+    """fp32 words of workspace conv1d_weight_grad_dilated needs for these shapes
+    (fv_conv1d_weight_grad_dilated_workspace_bytes); raises for shapes the entry refuses."""
+    need = lib().fv_conv1d_weight_grad_dilated_workspace_bytes(int(B), int(cin), int(cout), int(tin), int(k), int(dil),
+                                                               int(pad))
+    if need < 0:
+        check(int(need))
+    return (need + 3) // 4
+
+
+def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db=False, workspace=None):
+    """The weight (and bias) gradient of a dense stride-1 dilated conv with zero padding
+    (fv_conv1d_weight_grad_dilated, two launches): g_pre [B,Cout,Tout], xa [B,Cin,Tin] the conv's input as it saw it
+    -> (dw [Cout,Cin,k] or None, db [Cout] or None).  ``workspace``: an fp32 device tensor to use instead of a fresh
+    one (its contents do not matter)."""
+    name = "conv1d_weight_grad_dilated"
+    if g_pre.dim() != 3 or xa.dim() != 3 or g_pre.shape[0] != xa.shape[0]:
+        raise NativeError(f"{name}: g_pre [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g_pre.shape)} and "
+                          f"{tuple(xa.shape)}")
+    if not (want_dw or want_db):
+        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
+    B, cout, tout = g_pre.shape
+    cin, tin = xa.shape[1], xa.shape[2]
+    k, dil, pad = int(k), int(dil), int(pad)
+    if k > 0 and dil > 0 and tin + 2 * pad - dil * (k - 1) >= 1 and tout != tin + 2 * pad - dil * (k - 1):
+        raise NativeError(f"{name}: {tout} output times do not belong to an input of {tin} samples")
+    dev = g_pre.device
+    if workspace is None:
+        workspace = torch.empty(conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad),
+                                dtype=torch.float32, device=dev)
+    dw = torch.empty((cout, cin, k), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
+    with _on(g_pre, xa, workspace, dw, db) as stream:
+        check(lib().fv_conv1d_weight_grad_dilated(_ptr(g_pre, "g_pre"), _ptr(xa, "xa"), _ptr(dw, "dw", True),
+                                                  _ptr(db, "db", True), B, cin, cout, tin, k, dil, pad,
+                                                  _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
+    return dw, db
+
+
+def _convt_grad_shapes(name, g, cin_tin, w_shape, k, stride, pad, out_pad):
+    if g.dim() != 3:
+        raise NativeError(f"{name}: g [B,Cout,Tout] expected, got {tuple(g.shape)}")
+    tin = int(cin_tin)
+    if stride > 0 and tin >= 1 and g.shape[2] != (tin - 1) * stride - 2 * pad + k + out_pad:
+        raise NativeError(f"{name}: {g.shape[2]} output times do not belong to an input of {tin} samples")
+    if w_shape is not None and (len(w_shape) != 3 or w_shape[1] != g.shape[1] or w_shape[2] != k):
+        raise NativeError(f"{name}: w [Cin,{g.shape[1]},{k}] expected, got {tuple(w_shape)}")
+
+
+def conv_transpose1d_input_grad(g, w, tin, stride, pad, out_pad=0):
+    """The data gradient of ConvTranspose1d (fv_conv_transpose1d_input_grad, one launch): g [B,Cout,Tout], w
+    [Cin,Cout,k] the forward's (folded) weight -> dxa [B,Cin,tin]."""
+    stride, pad, out_pad = int(stride), int(pad), int(out_pad)
+    k = int(w.shape[2]) if w.dim() == 3 else 0
+    _convt_grad_shapes("conv_transpose1d_input_grad", g, tin, tuple(w.shape), k, stride, pad, out_pad)
+    B, cout, _ = g.shape
+    cin = w.shape[0]
+    dxa = torch.empty((B, cin, max(int(tin), 0)), dtype=torch.float32, device=g.device)
+    with _on(g, w, dxa) as stream:
+        check(lib().fv_conv_transpose1d_input_grad(_ptr(g, "g"), _ptr(w, "w"), _ptr(dxa), B, cin, cout, int(tin), k,
+                                                   stride, pad, out_pad, stream))
+    return dxa
+
+
+def conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, stride, pad, out_pad=0):
+    """fp32 words of workspace conv_transpose1d_weight_grad needs for these shapes
+    (fv_conv_transpose1d_weight_grad_workspace_bytes); raises for shapes the entry refuses."""
+    need = lib().fv_conv_transpose1d_weight_grad_workspace_bytes(int(B), int(cin), int(cout), int(tin), int(k),
+                                                                 int(stride), int(pad), int(out_pad))
+    if need < 0:
+        check(int(need))
+    return (need + 3) // 4
+
+
+def conv_transpose1d_weight_grad(g, xa, k, stride, pad, out_pad=0, want_dw=True, want_db=False, workspace=None):
+    """The weight (and bias) gradient of ConvTranspose1d (fv_conv_transpose1d_weight_grad, two launches): g
+    [B,Cout,Tout], xa [B,Cin,Tin] the layer's input as it saw it -> (dw [Cin,Cout,k] or None, db [Cout] or None)."""
+    name = "conv_transpose1d_weight_grad"
+    k, stride, pad, out_pad = int(k), int(stride), int(pad), int(out_pad)
+    if xa.dim() != 3 or g.dim() != 3 or g.shape[0] != xa.shape[0]:
+        raise NativeError(f"{name}: g [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g.shape)} and "
+                          f"{tuple(xa.shape)}")
+    if not (want_dw or want_db):
+        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
+    B, cin, tin = xa.shape
+    _convt_grad_shapes(name, g, tin, None, k, stride, pad, out_pad)
+    cout = g.shape[1]
+    dev = g.device
+    if workspace is None:
+        workspace = torch.empty(conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, stride, pad, out_pad),
+                                dtype=torch.float32, device=dev)
+    dw = torch.empty((cin, cout, k), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
+    with _on(g, xa, workspace, dw, db) as stream:
+        check(lib().fv_conv_transpose1d_weight_grad(_ptr(g, "g"), _ptr(xa, "xa"), _ptr(dw, "dw", True),
+                                                    _ptr(db, "db", True), B, cin, cout, tin, k, stride, pad, out_pad,
+                                                    _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
+    return dw, db
+
+
+def _same_shape(name, *tensors):
+    like = tensors[0]
+    for t in tensors[1:]:
+        if t is not None and t.shape != like.shape:
+            raise NativeError(f"{name}: operands of one shape expected, got {[tuple(t.shape) for t in tensors if t is not None]}")
+    return like
+
+
+def tanh_grad(g, y):
+    """g * (1 - y * y), elementwise (fv_tanh_grad, one launch): the gradient in front of y = tanh(z)."""
+    like = _same_shape("tanh_grad", g, y)
+    out = torch.empty_like(like)
+    with _on(g, y, out) as stream:
+        check(lib().fv_tanh_grad(_ptr(g, "g"), _ptr(y, "y"), _ptr(out), like.numel(), stream))
+    return out
+
+
+def residual_merge_grad(g_y, d, x, slope, acc=None):
+    """[acc +] (g_y + (x > 0 ? 1 : slope) * d), elementwise (fv_residual_merge_grad, one launch): the gradient of x in
+    x_next = x + conv(lrelu(x, slope)) from g_y = dL/dx_next and the conv's data gradient d."""
+    like = _same_shape("residual_merge_grad", g_y, d, x, acc)
+    out = torch.empty_like(like)
+    with _on(g_y, d, x, acc, out) as stream:
+        check(lib().fv_residual_merge_grad(_ptr(g_y, "g_y"), _ptr(d, "d"), _ptr(x, "x"), _ptr(acc, "acc", True),
+                                           _ptr(out), like.numel(), float(slope), stream))
+    return out
+
+
+def grad_div(g, div):
+    """g / div, elementwise (fv_grad_div, one launch): the adjoint of the MRF mean."""
+    out = torch.empty_like(g)
+    with _on(g, out) as stream:
+        check(lib().fv_grad_div(_ptr(g, "g"), _ptr(out), g.numel(), float(div), stream))
+    return out
 
 
 def reflect_pad_fold(gp, pad):

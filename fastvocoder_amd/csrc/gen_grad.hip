@@ -1,0 +1,504 @@
+// Parameter gradient of the HiFi-GAN generators (reference: model/generator/hifigan.py:92-106, the generator's half of
+// bin/train.py:67-136; include/fastvocoder_hip.h fv_conv1d_weight_grad_dilated, fv_conv_transpose1d_input_grad,
+// fv_conv_transpose1d_weight_grad, fv_tanh_grad, fv_residual_merge_grad, fv_grad_div).  Exact fp32, no atomics, no
+// waiting between workgroups.
+//
+// All three GEMMs run on one tile engine (GgTile<MT>): a block of 4 waves owns MT rows x 128 columns and consumes
+// staged tiles of 32 reduction steps, both operands K-contiguous in LDS -- as[row][step], bs[column][step].
+//     MT = 128: 2 x 2 waves of 2 x 2 fragments of v_mfma_f32_32x32x2_f32        MT = 64: 2 x 2 waves of 1 x 2
+//     MT =  32: 1 x 4 waves of 1 x 1 fragments (32 rows, every one a channel)    MT = 16: 1 x 4 waves of 1 x 2 fragments
+//                                                                                 of v_mfma_f32_16x16x4_f32
+// so 16 and 32 channels fill their fragments.  Row stride 33 words for the 32-wide fragments (a lane group of 32 reads
+// rows 0..31 at one step: banks 33 r + c = 32 different ones), 34 words for the 16-wide ones (a group of 32 lanes reads
+// rows 0..15 at two consecutive steps: banks 2 r + {0, 1}, 32 different ones); the staging writes put the 32 lanes of
+// a group on 32 consecutive words of one row.  Each result is one step-ordered fmaf chain.
+//
+// The B operand is an im2col column resolved WHILE STAGING, as period_wgrad_mfma_kernel does: bs[n][t] with
+// n = (channel, tap) reads source[channel][t sB + j dB - pad] (zero outside the row) from per-thread offsets computed
+// before the unit loop -- (sB, dB) = (1, dil) for the dilated conv's weight gradient, (stride, 1) for the transposed
+// conv's.  The MFMA loop's B read is therefore the same conflict-free pattern for every dilation and stride; a staged
+// span xs[ci][tile + dil (k - 1)] would be read at lane stride (row stride + dil-dependent tap offset) and collide for
+// dil 3 and 5 at the tap counts 7 and 11.  The price: a source element is loaded once per tap that touches it, from L2
+// after the first (a unit's span is a few KB), not once.
+//
+// gen_wgrad_kernel<MT>: dW[m][n] over (b, t) in the split / record / combine scheme of disc_wgrad.hip (units of 32
+// steps, S a function of the shape alone, wgrad_combine_kernel adds the records in ascending order).  One extra block
+// column sums the bias rows of the split's units (wave w owns channels w, w + 4, ...; lanes stride the unit's
+// positions; one shuffle tree at the end), so every record word the combine reads is written by this launch.
+//
+// gen_dgrad_kernel<MT>: the transposed conv's data gradient as the GEMM [Cin] x [B Tin] over Cout k: the columns are
+// the flat positions q = b Tin + i, A = the forward's weight [Cin][Cout k] as it lies in memory, B the stride-s gather
+// g[b, co, i s + j - p].  One launch; every element one (co, j)-ordered chain, whatever the batch or the grid.
+#include <math.h>
+
+#include <type_traits>
+
+#include "fv_internal.h"
+
+namespace fv {
+
+typedef float gg_f32x16 __attribute__((ext_vector_type(16)));
+typedef float gg_f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kGgThreads = 256;
+constexpr int kGgNT = 128;            // columns per block
+constexpr int kGgTK = 32;             // reduction steps per staged tile
+constexpr int kGgBRows = kGgNT / 8;   // rows of the B tile a thread stages (16)
+constexpr int kGgDead = -(1 << 30);   // position of a column / row beyond the problem: below every source row
+
+template <int MT>
+struct GgTile {
+    static constexpr int F = MT >= 32 ? 32 : 16;            // fragment edge
+    static constexpr int WM = MT >= 64 ? 2 : 1, WN = 4 / WM;
+    static constexpr int FM = MT / (WM * F), FN = kGgNT / (WN * F);
+    static constexpr int STR = F == 32 ? 33 : 34;
+    static constexpr int NE = F == 32 ? 16 : 4;
+    static constexpr int ARows = MT / 8;                    // rows of the A tile a thread stages
+    typedef typename std::conditional<F == 32, gg_f32x16, gg_f32x4>::type acc_t;
+
+    acc_t acc[FM][FN];
+    int off_a[FM], off_b[FN];
+    int row0, col0, lr, kq;
+
+    __device__ __forceinline__ void init() {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave / WN, wn = wave % WN;
+        lr = lane & (F - 1);
+        kq = lane / F;
+        row0 = wm * FM * F;
+        col0 = wn * FN * F;
+#pragma unroll
+        for (int f = 0; f < FM; ++f) off_a[f] = (row0 + f * F + lr) * STR + kq;
+#pragma unroll
+        for (int h = 0; h < FN; ++h) off_b[h] = (col0 + h * F + lr) * STR + kq;
+#pragma unroll
+        for (int f = 0; f < FM; ++f)
+#pragma unroll
+            for (int h = 0; h < FN; ++h)
+#pragma unroll
+                for (int e = 0; e < NE; ++e) acc[f][h][e] = 0.f;
+    }
+
+    // one staged tile of kGgTK steps
+    __device__ __forceinline__ void mma(const float* as, const float* bs) {
+        constexpr int KS = F == 32 ? 2 : 4;
+#pragma unroll
+        for (int kk = 0; kk < kGgTK; kk += KS) {
+            float av[FM], bv[FN];
+#pragma unroll
+            for (int f = 0; f < FM; ++f) av[f] = as[off_a[f] + kk];
+#pragma unroll
+            for (int h = 0; h < FN; ++h) bv[h] = bs[off_b[h] + kk];
+#pragma unroll
+            for (int f = 0; f < FM; ++f)
+#pragma unroll
+                for (int h = 0; h < FN; ++h) {
+                    if constexpr (F == 32)
+                        acc[f][h] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[f], bv[h], acc[f][h], 0, 0, 0);
+                    else
+                        acc[f][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[f], bv[h], acc[f][h], 0, 0, 0);
+                }
+        }
+    }
+
+    // C/D maps: 32 x 32: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5);
+    //           16 x 16: col = lane & 15, row = 4 (lane >> 4) + reg
+    __device__ __forceinline__ int row(int f, int e) const {
+        return row0 + f * F + (F == 32 ? (e & 3) + 8 * (e >> 2) + 4 * kq : 4 * kq + e);
+    }
+    __device__ __forceinline__ int col(int h) const { return col0 + h * F + lr; }
+};
+
+struct GgWArgs {
+    const float* a;         // A source [B, M, TR]: row m, step t
+    const float* b;         // B source [B, Cb, TB]: column n = cb k + j reads b[., cb, t sB + j dB - pad]
+    const float* bias_src;  // [B, Cbias, Tbias], or null
+    float* ws;              // [S][R]
+    int64_t R, U;           // floats per record: M N + Cbias; units
+    int S, nch;             // splits; units per row b
+    int M, TR, Cb, TB, k, sB, dB, pad;
+    int Cbias, Tbias, bias_scale;   // a unit's bias positions: [t0 bias_scale, (t0 + 32) bias_scale), the row's last unit to Tbias
+    int x_tiles;            // column tiles of the GEMM (0: the bias alone); blocks beyond them sum the bias
+};
+
+// grid (x_tiles + (bias ? 1 : 0), ceil(M / MT), S)
+template <int MT>
+__global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
+    using T = GgTile<MT>;
+    __shared__ float as[MT * T::STR];
+    __shared__ float bs[kGgNT * T::STR];
+    const int s = blockIdx.z, tid = threadIdx.x;
+    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
+    const int N = a.Cb * a.k;
+    float* rec = a.ws + (size_t)s * a.R;
+    if ((int)blockIdx.x >= a.x_tiles) {                   // the bias column
+        if (blockIdx.y != 0) return;
+        const int lane = tid & 63, wave = tid >> 6;
+        for (int c = wave; c < a.Cbias; c += 4) {
+            float v = 0.f;
+            for (int64_t u = u0; u < u1; ++u) {
+                const int b = (int)(u / a.nch), ch = (int)(u % a.nch);
+                const int64_t p0 = (int64_t)ch * kGgTK * a.bias_scale;
+                int64_t p1 = ch == a.nch - 1 ? a.Tbias : p0 + (int64_t)kGgTK * a.bias_scale;
+                if (p1 > a.Tbias) p1 = a.Tbias;
+                const float* row = a.bias_src + ((size_t)b * a.Cbias + c) * a.Tbias;
+                for (int64_t p = p0 + lane; p < p1; p += 64) v += row[p];
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            if (lane == 0) rec[(size_t)a.M * N + c] = v;
+        }
+        return;
+    }
+    const int n0 = blockIdx.x * kGgNT, m0 = blockIdx.y * MT;
+    const int sc = tid & 31, sr = tid >> 5;
+    int b_off[kGgBRows], b_pos[kGgBRows];                 // cb TB, and j dB - pad
+#pragma unroll
+    for (int i = 0; i < kGgBRows; ++i) {
+        const int n = n0 + sr + 8 * i, cb = n / a.k;
+        b_off[i] = n < N ? cb * a.TB : 0;
+        b_pos[i] = n < N ? (n - cb * a.k) * a.dB - a.pad : kGgDead;
+    }
+    T tile;
+    tile.init();
+    for (int64_t u = u0; u < u1; ++u) {
+        const int b = (int)(u / a.nch), t = (int)(u % a.nch) * kGgTK + sc;
+        const bool live = t < a.TR;
+        const float* ab = a.a + (size_t)b * a.M * a.TR + t;
+        const float* bb = a.b + (size_t)b * a.Cb * a.TB;
+        const int64_t tb = (int64_t)t * a.sB;
+        __syncthreads();                                  // the previous unit's reads are done
+#pragma unroll
+        for (int i = 0; i < T::ARows; ++i) {
+            const int row = sr + 8 * i, m = m0 + row;
+            as[row * T::STR + sc] = (live && m < a.M) ? ab[(size_t)m * a.TR] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < kGgBRows; ++i) {
+            const int64_t pos = tb + b_pos[i];
+            bs[(sr + 8 * i) * T::STR + sc] = (live && pos >= 0 && pos < a.TB) ? bb[(size_t)b_off[i] + pos] : 0.f;
+        }
+        __syncthreads();
+        tile.mma(as, bs);
+    }
+#pragma unroll
+    for (int f = 0; f < T::FM; ++f)
+#pragma unroll
+        for (int e = 0; e < T::NE; ++e) {
+            const int m = m0 + tile.row(f, e);
+            if (m >= a.M) continue;
+#pragma unroll
+            for (int h = 0; h < T::FN; ++h) {
+                const int n = n0 + tile.col(h);
+                if (n < N) rec[(size_t)m * N + n] = tile.acc[f][h][e];
+            }
+        }
+}
+
+struct GgDArgs {
+    const float* w;     // [Cin, Cout k]
+    const float* g;     // [B, Cout, Tout]
+    float* dx;          // [B, Cin, Tin]
+    int64_t Q;          // B Tin
+    int Cin, Cout, Tin, Tout, k, stride, pad;
+};
+
+// grid (ceil(B Tin / 128), ceil(Cin / MT))
+template <int MT>
+__global__ __launch_bounds__(kGgThreads) void gen_dgrad_kernel(GgDArgs a) {
+    using T = GgTile<MT>;
+    __shared__ float as[MT * T::STR];
+    __shared__ float bs[kGgNT * T::STR];
+    const int tid = threadIdx.x, sc = tid & 31, sr = tid >> 5;
+    const int K = a.Cout * a.k, m0 = blockIdx.y * MT;
+    const int64_t q0 = (int64_t)blockIdx.x * kGgNT;
+    int64_t c_base[kGgBRows];                             // b Cout Tout
+    int c_pos[kGgBRows];                                  // i stride - pad
+#pragma unroll
+    for (int i = 0; i < kGgBRows; ++i) {
+        const int64_t q = q0 + sr + 8 * i;
+        const int64_t b = q / a.Tin;
+        c_base[i] = q < a.Q ? b * a.Cout * a.Tout : 0;
+        c_pos[i] = q < a.Q ? (int)(q - b * a.Tin) * a.stride - a.pad : kGgDead;
+    }
+    T tile;
+    tile.init();
+    for (int kc = 0; kc < K; kc += kGgTK) {
+        const int kk = kc + sc;
+        const bool live = kk < K;
+        const int co = kk / a.k, j = kk - co * a.k;
+        __syncthreads();                                  // the previous tile's reads are done
+#pragma unroll
+        for (int i = 0; i < T::ARows; ++i) {
+            const int row = sr + 8 * i, m = m0 + row;
+            as[row * T::STR + sc] = (live && m < a.Cin) ? a.w[(size_t)m * K + kk] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < kGgBRows; ++i) {
+            const int pos = c_pos[i] + j;
+            bs[(sr + 8 * i) * T::STR + sc] =
+                (live && pos >= 0 && pos < a.Tout) ? a.g[(size_t)c_base[i] + (size_t)co * a.Tout + pos] : 0.f;
+        }
+        __syncthreads();
+        tile.mma(as, bs);
+    }
+#pragma unroll
+    for (int h = 0; h < T::FN; ++h) {
+        const int64_t q = q0 + tile.col(h);
+        if (q >= a.Q) continue;
+        const int64_t b = q / a.Tin;
+        float* out = a.dx + (size_t)b * a.Cin * a.Tin + (q - b * a.Tin);
+#pragma unroll
+        for (int f = 0; f < T::FM; ++f)
+#pragma unroll
+            for (int e = 0; e < T::NE; ++e) {
+                const int m = m0 + tile.row(f, e);
+                if (m < a.Cin) out[(size_t)m * a.Tin] = tile.acc[f][h][e];
+            }
+    }
+}
+
+// ---- the elementwise steps of the walk ----
+// the adjoint of y = tanh(z): g (1 - y y)
+__global__ __launch_bounds__(256) void tanh_grad_kernel(const float* __restrict__ g, const float* __restrict__ y,
+                                                        float* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = g[i] * (1.f - y[i] * y[i]);
+}
+
+// the gradient in front of x_next = x + conv(lrelu(x)): g_y + (x > 0 ? 1 : slope) d, plus a running sum
+// (no __restrict__: out may alias g_y, d or acc -- every thread reads its element before it writes it)
+__global__ __launch_bounds__(256) void residual_merge_grad_kernel(const float* g_y, const float* d, const float* x,
+                                                                  const float* acc, float* out, int64_t n, float slope) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = fmaf(x[i] > 0.f ? 1.f : slope, d[i], g_y[i]);
+    out[i] = acc ? acc[i] + v : v;
+}
+
+// the adjoint of the MRF mean: g / div, a true division
+__global__ __launch_bounds__(256) void grad_div_kernel(const float* __restrict__ g, float* __restrict__ out, int64_t n,
+                                                       float div) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = g[i] / div;
+}
+
+// ---- host side ----
+static int gg_rows(int M) { return M > 64 ? 128 : M > 32 ? 64 : M > 16 ? 32 : 16; }
+
+struct GgWPlan {
+    int MT, S, nch, bx, by;
+    int64_t U, R;
+};
+
+// the plan of a weight-gradient GEMM of M rows x N columns over B rows of TR steps, with Cbias bias words per record
+static void gg_wgrad_plan(int B, int M, int64_t N, int TR, int Cbias, GgWPlan* p) {
+    p->MT = gg_rows(M);
+    p->bx = (int)((N + kGgNT - 1) / kGgNT);
+    p->by = (M + p->MT - 1) / p->MT;
+    p->nch = (TR + kGgTK - 1) / kGgTK;
+    p->U = (int64_t)B * p->nch;
+    p->R = (int64_t)M * N + Cbias;
+    p->S = wg_splits((int64_t)p->bx * p->by, p->U, p->MT >= 64 ? 512 : 1024);
+}
+
+static int gg_wgrad_run(const GgWPlan& p, GgWArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes,
+                        const char* who, hipStream_t st) {
+    const size_t need = sizeof(float) * (size_t)p.S * (size_t)p.R;
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
+        return fail(FV_ERR_INVALID_ARG, "%s: workspace of %zu bytes, needs %zu (4-byte aligned)", who, workspace_bytes,
+                    need);
+    a.ws = static_cast<float*>(workspace);
+    a.R = p.R;
+    a.U = p.U;
+    a.S = p.S;
+    a.nch = p.nch;
+    a.x_tiles = dw ? p.bx : 0;
+    if (!db) a.bias_src = nullptr;
+    const dim3 grid((unsigned)(a.x_tiles + (db ? 1 : 0)), (unsigned)(dw ? p.by : 1), (unsigned)p.S);
+    switch (p.MT) {
+    case 128: hipLaunchKernelGGL(gen_wgrad_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
+    case 64: hipLaunchKernelGGL(gen_wgrad_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
+    case 32: hipLaunchKernelGGL(gen_wgrad_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
+    default: hipLaunchKernelGGL(gen_wgrad_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
+    }
+    FV_HIP(hipGetLastError());
+    return launch_wgrad_combine(a.ws, dw, db, p.R - a.Cbias, a.Cbias, p.R, p.S, st);
+}
+
+static int dilated_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int dil, int pad, GgWPlan* p) {
+    if (Cin < 1 || Cout < 1 || k < 1 || dil < 1 || (int64_t)Cin * Cout * k >= (int64_t)1 << 31 ||
+        (int64_t)Cin * k >= (int64_t)1 << 30 || (Cout + 15) / 16 > 65535)
+        return fail(FV_ERR_UNSUPPORTED, "conv1d_weight_grad_dilated: Cin=%d Cout=%d k=%d dil=%d", Cin, Cout, k, dil);
+    if (B <= 0 || B > 65535 || Tin < 1 || pad < 0)
+        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: B=%d, Tin=%d or pad=%d", B, Tin, pad);
+    const int64_t Tout = (int64_t)Tin + 2 * (int64_t)pad - (int64_t)dil * (k - 1);
+    if (Tout < 1)
+        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: empty output (Tin=%d pad=%d k=%d dil=%d)", Tin, pad,
+                    k, dil);
+    const int64_t big = Cin > Cout ? Cin : Cout;
+    if (big * ((int64_t)Tin + 2 * (int64_t)pad) >= (int64_t)1 << 30)
+        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: a map of %lld x %d samples is too long",
+                    (long long)big, Tin);
+    gg_wgrad_plan(B, Cout, (int64_t)Cin * k, (int)Tout, Cout, p);
+    return 0;
+}
+
+// Tout, or an error code
+static int64_t convt_grad_check(const char* who, int B, int Cin, int Cout, int Tin, int k, int stride, int pad,
+                                int out_pad) {
+    if (Cin < 1 || Cout < 1 || k < 1 || stride < 1 || (int64_t)Cin * Cout * k >= (int64_t)1 << 31 ||
+        (int64_t)Cout * k >= (int64_t)1 << 30 || (Cin + 15) / 16 > 65535)
+        return fail(FV_ERR_UNSUPPORTED, "%s: Cin=%d Cout=%d k=%d stride=%d", who, Cin, Cout, k, stride);
+    if (B <= 0 || B > 65535 || Tin < 1 || pad < 0)
+        return fail(FV_ERR_INVALID_ARG, "%s: B=%d, Tin=%d or pad=%d", who, B, Tin, pad);
+    const int64_t Tout = ((int64_t)Tin - 1) * stride - 2 * (int64_t)pad + k + out_pad;
+    if (Tout < 1)
+        return fail(FV_ERR_INVALID_ARG, "%s: empty output (Tin=%d k=%d stride=%d pad=%d out_pad=%d)", who, Tin, k, stride,
+                    pad, out_pad);
+    const int64_t span = (int64_t)Tin * stride + k + pad;
+    if ((int64_t)Cout * (Tout > span ? Tout : span) >= (int64_t)1 << 30 || (int64_t)Cin * Tin >= (int64_t)1 << 30)
+        return fail(FV_ERR_INVALID_ARG, "%s: a map of %d x %lld samples is too long", who, Cout, (long long)Tout);
+    return Tout;
+}
+
+static int gg_elementwise_check(const char* who, const void* a, const void* b, const void* out, int64_t n) {
+    if (!a || !b || !out || n < 1 || (n + 255) / 256 > 0x7fffffff)
+        return fail(FV_ERR_INVALID_ARG, "%s: null tensor or n=%lld", who, (long long)n);
+    return 0;
+}
+
+}  // namespace fv
+
+using namespace fv;
+
+extern "C" {
+
+int64_t fv_conv1d_weight_grad_dilated_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad) {
+    GgWPlan p;
+    if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
+    return (int64_t)sizeof(float) * p.S * p.R;
+}
+
+int fv_conv1d_weight_grad_dilated(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
+                                  int Tin, int k, int dil, int pad, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    GgWPlan p;
+    if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
+    if (!g_pre || !xa || (!dw && !db) || dw == g_pre || dw == xa || db == g_pre || db == xa)
+        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: null tensor, or a result aliases an input");
+    const int Tout = Tin + 2 * pad - dil * (k - 1);
+    GgWArgs a{};
+    a.a = g_pre;
+    a.b = xa;
+    a.bias_src = g_pre;
+    a.M = Cout;
+    a.TR = Tout;
+    a.Cb = Cin;
+    a.TB = Tin;
+    a.k = k;
+    a.sB = 1;
+    a.dB = dil;
+    a.pad = pad;
+    a.Cbias = Cout;
+    a.Tbias = Tout;
+    a.bias_scale = 1;
+    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, "conv1d_weight_grad_dilated", (hipStream_t)stream);
+}
+
+int fv_conv_transpose1d_input_grad(const float* g, const float* w, float* dxa, int B, int Cin, int Cout, int Tin, int k,
+                                   int stride, int pad, int out_pad, void* stream) {
+    const int64_t Tout = convt_grad_check("conv_transpose1d_input_grad", B, Cin, Cout, Tin, k, stride, pad, out_pad);
+    if (Tout < 0) return (int)Tout;
+    if (!g || !w || !dxa || dxa == g || dxa == w)
+        return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_input_grad: null tensor, or the result aliases an input");
+    GgDArgs a{};
+    a.w = w;
+    a.g = g;
+    a.dx = dxa;
+    a.Q = (int64_t)B * Tin;
+    a.Cin = Cin;
+    a.Cout = Cout;
+    a.Tin = Tin;
+    a.Tout = (int)Tout;
+    a.k = k;
+    a.stride = stride;
+    a.pad = pad;
+    const int MT = gg_rows(Cin);
+    const int64_t gx = (a.Q + kGgNT - 1) / kGgNT;
+    if (gx > 0x7fffffff) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_input_grad: B Tin = %lld", (long long)a.Q);
+    const dim3 grid((unsigned)gx, (unsigned)((Cin + MT - 1) / MT));
+    const hipStream_t st = (hipStream_t)stream;
+    switch (MT) {
+    case 128: hipLaunchKernelGGL(gen_dgrad_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
+    case 64: hipLaunchKernelGGL(gen_dgrad_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
+    case 32: hipLaunchKernelGGL(gen_dgrad_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
+    default: hipLaunchKernelGGL(gen_dgrad_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
+    }
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int64_t fv_conv_transpose1d_weight_grad_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int stride, int pad,
+                                                        int out_pad) {
+    const int64_t Tout = convt_grad_check("conv_transpose1d_weight_grad", B, Cin, Cout, Tin, k, stride, pad, out_pad);
+    if (Tout < 0) return Tout;
+    GgWPlan p;
+    gg_wgrad_plan(B, Cin, (int64_t)Cout * k, Tin, Cout, &p);
+    return (int64_t)sizeof(float) * p.S * p.R;
+}
+
+int fv_conv_transpose1d_weight_grad(const float* g, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
+                                    int Tin, int k, int stride, int pad, int out_pad, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    const int64_t Tout = convt_grad_check("conv_transpose1d_weight_grad", B, Cin, Cout, Tin, k, stride, pad, out_pad);
+    if (Tout < 0) return (int)Tout;
+    if (!g || !xa || (!dw && !db) || dw == g || dw == xa || db == g || db == xa)
+        return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_weight_grad: null tensor, or a result aliases an input");
+    GgWPlan p;
+    gg_wgrad_plan(B, Cin, (int64_t)Cout * k, Tin, Cout, &p);
+    GgWArgs a{};
+    a.a = xa;
+    a.b = g;
+    a.bias_src = g;
+    a.M = Cin;
+    a.TR = Tin;
+    a.Cb = Cout;
+    a.TB = (int)Tout;
+    a.k = k;
+    a.sB = stride;
+    a.dB = 1;
+    a.pad = pad;
+    a.Cbias = Cout;
+    a.Tbias = (int)Tout;
+    a.bias_scale = stride;
+    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, "conv_transpose1d_weight_grad", (hipStream_t)stream);
+}
+
+int fv_tanh_grad(const float* g, const float* y, float* out, int64_t n, void* stream) {
+    if (int rc = gg_elementwise_check("tanh_grad", g, y, out, n)) return rc;
+    hipLaunchKernelGGL(tanh_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, y, out,
+                       n);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int fv_residual_merge_grad(const float* g_y, const float* d, const float* x, const float* acc, float* out, int64_t n,
+                           float slope, void* stream) {
+    if (int rc = gg_elementwise_check("residual_merge_grad", g_y, d, out, n)) return rc;
+    if (!x) return fail(FV_ERR_INVALID_ARG, "residual_merge_grad: null tensor");
+    hipLaunchKernelGGL(residual_merge_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       g_y, d, x, acc, out, n, slope);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int fv_grad_div(const float* g, float* out, int64_t n, float div, void* stream) {
+    if (int rc = gg_elementwise_check("grad_div", g, g, out, n)) return rc;
+    if (!(div != 0.f)) return fail(FV_ERR_INVALID_ARG, "grad_div: div = %g", (double)div);
+    hipLaunchKernelGGL(grad_div_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, out, n,
+                       div);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

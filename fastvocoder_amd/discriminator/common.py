@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..generator.engine import PAD_REFLECT, PAD_ZERO, NativeModule, effective_weight
+from ..generator.engine import (PAD_REFLECT, PAD_ZERO, NativeModule, cached, conv_params, effective_weight,  # noqa: F401
+                                param_store, param_wants)
 
 
 def check_activation(nonlinear_activation, nonlinear_activation_params):
@@ -70,19 +71,6 @@ def checked_input(module, x, dims, graph, mono=True):
 def wants_grad(x, graph):
     """Whether a ``_forward`` runs through the autograd Functions: the caller permits it and autograd asks for it."""
     return bool(graph) and x.requires_grad and torch.is_grad_enabled()
-
-
-def cached(module, key, build):
-    """``module._fv_plans[key]``, rebuilt with ``build()`` (under torch.no_grad()) when the module state moved.  The
-    value is stored against the state read AFTER the build: a build that touches the module leaves no stale key."""
-    hit = module._fv_plans.get(key)
-    if hit is not None and hit[0] == module._fv_state():
-        return hit[1]
-    module._device()
-    with torch.no_grad():
-        value = build()
-    module._fv_plans[key] = (module._fv_state(), value)
-    return value
 
 
 def first_length(ok, start=1):
@@ -189,14 +177,7 @@ class DiscriminatorModule(NativeModule):
     def _conv_params(self):
         """Per layer (``_convs()``) the conv's parameters in the order _LayersParamGrad takes them: (weight_g,
         weight_v[, bias]) under weight norm, (weight[, bias]) without."""
-        out = []
-        for conv in self._convs():
-            if hasattr(conv, "weight_g") and hasattr(conv, "weight_v"):
-                ps = [conv.weight_g, conv.weight_v]
-            else:
-                ps = [conv.weight]
-            out.append(ps + ([] if conv.bias is None else [conv.bias]))
-        return out
+        return [conv_params(conv) for conv in self._convs()]
 
     def _stack(self, x, grad, params=False):
         """``_run_layers(x)`` of a module with layers of its own: on the parameters' graph (_LayersParamGrad, backward
@@ -215,28 +196,9 @@ class DiscriminatorModule(NativeModule):
         first = [sum(counts[:l]) for l in range(len(counts))]
         return first, [any(need[first[l]:first[l] + counts[l]]) for l in range(len(counts))]
 
-    @staticmethod
-    def _param_wants(conv, need, at):
-        """(the weight gradient is needed, the bias gradient is needed) of a conv whose parameters start at ``at``."""
-        nw = 2 if hasattr(conv, "weight_g") and hasattr(conv, "weight_v") else 1
-        return any(need[at:at + nw]), conv.bias is not None and need[at + nw]
-
-    @staticmethod
-    def _param_store(conv, params, need, at, dw, db, out):
-        """A layer's dw (shaped like its weight, or None) and db (or None) into ``out``: the bias gradient, and the
-        weight gradient through the weight-norm adjoint (fv_weight_norm_grad on [Cout, the rest]) where the conv has
-        one."""
-        norm = hasattr(conv, "weight_g") and hasattr(conv, "weight_v")
-        nw = 2 if norm else 1
-        if db is not None:
-            out[at + nw] = db
-        if dw is not None and norm:
-            g, v = params[at], params[at + 1]
-            dv, dg = _native.weight_norm_grad(dw.view_as(v), v.detach().contiguous(), g.detach().contiguous(),
-                                              need[at + 1], need[at])
-            out[at], out[at + 1] = dg, dv
-        elif dw is not None:
-            out[at] = dw.view_as(params[at])
+    # (engine.param_wants / engine.param_store: shared with the generators' parameter gradient)
+    _param_wants = staticmethod(param_wants)
+    _param_store = staticmethod(param_store)
 
 
 class ConvStack(DiscriminatorModule):

@@ -34,6 +34,70 @@ def effective_weight(conv):
     return conv.weight.detach().contiguous().float()
 
 
+def cached(module, key, build):
+    """``module._fv_plans[key]``, rebuilt with ``build()`` (under torch.no_grad()) when the module state moved.  The
+    value is stored against the state read AFTER the build: a build that touches the module leaves no stale key."""
+    hit = module._fv_plans.get(key)
+    if hit is not None and hit[0] == module._fv_state():
+        return hit[1]
+    module._device()
+    with torch.no_grad():
+        value = build()
+    module._fv_plans[key] = (module._fv_state(), value)
+    return value
+
+
+# -- what the parameter-gradient walks share (discriminator/common.py, generator/grad.py) ------------------------------
+def conv_params(conv):
+    """A conv's parameters in the order the autograd Functions take them: (weight_g, weight_v[, bias]) under weight
+    norm, (weight[, bias]) without."""
+    if hasattr(conv, "weight_g") and hasattr(conv, "weight_v"):
+        ps = [conv.weight_g, conv.weight_v]
+    else:
+        ps = [conv.weight]
+    return ps + ([] if conv.bias is None else [conv.bias])
+
+
+def param_wants(conv, need, at):
+    """(the weight gradient is needed, the bias gradient is needed) of a conv whose parameters start at ``at``."""
+    nw = 2 if hasattr(conv, "weight_g") and hasattr(conv, "weight_v") else 1
+    return any(need[at:at + nw]), conv.bias is not None and need[at + nw]
+
+
+def param_store(conv, params, need, at, dw, db, out):
+    """A layer's dw (shaped like its weight, or None) and db (or None) into ``out``: the bias gradient, and the
+    weight gradient through the weight-norm adjoint (fv_weight_norm_grad on [dim0, the rest]) where the conv has
+    one."""
+    norm = hasattr(conv, "weight_g") and hasattr(conv, "weight_v")
+    nw = 2 if norm else 1
+    if db is not None:
+        out[at + nw] = db
+    if dw is not None and norm:
+        g, v = params[at], params[at + 1]
+        dv, dg = _native.weight_norm_grad(dw.view_as(v), v.detach().contiguous(), g.detach().contiguous(),
+                                          need[at + 1], need[at])
+        out[at], out[at + 1] = dg, dv
+    elif dw is not None:
+        out[at] = dw.view_as(params[at])
+
+
+class NoParameterGrad:
+    """Mix-in of the generators without a parameter gradient (MelGAN, Basis-MelGAN): ``parameter_grad`` reads False,
+    and setting it raises."""
+
+    @property
+    def parameter_grad(self):
+        return False
+
+    @parameter_grad.setter
+    def parameter_grad(self, value):
+        if value:
+            raise NotImplementedError(
+                f"{type(self).__name__} has no parameter gradient yet: the backward of ResidualStack (and of the "
+                "learned basis / LastLinear's BatchNorm) is missing; parameter_grad is supported by HiFiGANGenerator "
+                "and MultiBandHiFiGANGenerator")
+
+
 def pair_precision(precision, channels):
     """Arithmetic of the ResBlock / ResidualStack / upsampler kernels for a layer of ``channels`` channels under the
     policy ``precision``: "split" = split-f16 operands (csrc/pairh_kernels.hpp, convh_kernels.hpp; fp32-class accuracy,

@@ -18,6 +18,7 @@ import torch
 from .._native import PAIR_SPLIT_F16
 from .engine import (NativeModule, PlanBuilder, POST_TANH, SLOT_IN, SLOT_NONE, SLOT_OUT, pair_precision,  # noqa: F401
                      weight_norm)
+from . import grad
 from .modules import LRELU_SLOPE, ResBlock1, ResBlock2, UpsampleLayer
 from .pqmf import PQMF
 
@@ -44,6 +45,23 @@ def stage32_windows_fit(cols, cus, fill=0.65):
 class _HiFiGANBase(NativeModule):
     _post_channels = 1
     fuse_pqmf = True      # Multiband: conv_post + tanh + PQMF synthesis as one launch (False: two; A/B and bit-identity tests)
+    _parameter_grad = False
+
+    @property
+    def parameter_grad(self):
+        """Default False: ``forward`` is inference (the plans; the output does not require grad).  With True, grad
+        enabled and at least one conv parameter requiring grad, ``forward`` runs the training forward of
+        generator/grad.py -- conv by conv on the exact-fp32 kernels, through one autograd Function whose inputs are
+        the conv parameters -- and ``backward`` accumulates into the ``.grad`` of ``weight_g`` / ``weight_v`` / ``bias``
+        (``weight`` without weight norm) from the kernels of csrc/gen_grad.hip.  The mel is a constant.  A frozen
+        parameter gets no gradient and costs no launch.  ``transposedconv=False`` refuses True."""
+        return self._parameter_grad
+
+    @parameter_grad.setter
+    def parameter_grad(self, value):
+        if value:
+            grad.check_supported(self)
+        self._parameter_grad = bool(value)
 
     def __init__(self, resblock_kernel_sizes, upsample_rates, upsample_initial_channel,
                  resblock_type, upsample_kernel_sizes, resblock_dilation_sizes, transposedconv,
@@ -371,6 +389,8 @@ class HiFiGANGenerator(_HiFiGANBase):
 
     def forward(self, x):
         """x [B,80,T] -> waveform [B, prod(upsample_rates)*T]."""
+        if grad.wants_param_grad(self):
+            return grad.run(self, x)[:, 0, :]
         return self._trunk(self._prepare(x))[:, 0, :]
 
     def inference(self, x):
@@ -399,6 +419,8 @@ class MultiBandHiFiGANGenerator(_HiFiGANBase):
     def forward(self, x):
         """x [B,80,T] -> sub-bands [B,4,T'] (the caller applies pqmf.synthesis,
         reference bin/train.py:96)."""
+        if grad.wants_param_grad(self):
+            return grad.run(self, x)
         return self._trunk(self._prepare(x))
 
     def _emit_full(self, pb, fused=None):

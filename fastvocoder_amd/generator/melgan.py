@@ -11,12 +11,12 @@ it is a parameter container only -- calls go through native plans.
 import torch
 
 from .. import _native
-from .engine import NativeModule, POST_NONE, POST_RELU, POST_TANH, SLOT_IN, SLOT_OUT, SLOT_OUT2  # noqa: F401
+from .engine import NativeModule, NoParameterGrad, POST_NONE, POST_RELU, POST_TANH, SLOT_IN, SLOT_OUT, SLOT_OUT2  # noqa: F401
 from .modules import (BasisSignalLayer, LastLayer, LastLinear, ResidualStack, UpsampleLayer,
                       _activation_slope, _pad_mode)
 
 
-class _MelGANTrunk(NativeModule):
+class _MelGANTrunk(NoParameterGrad, NativeModule):
     _RESET_STD = 0.02  # reference melgan.py:166
 
     def _build_layers(self, in_channels, kernel_size, channels, bias, upsample_scales,

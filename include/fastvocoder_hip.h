@@ -874,6 +874,60 @@ int64_t fv_mpd_first_weight_grad_workspace_bytes(int B, int64_t T, int period);
 int fv_mpd_first_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int64_t T, int period,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The parameter gradient of the HiFi-GAN generators (model/generator/hifigan.py:92-106 under bin/train.py:67-136, the
+ * generator's update); additions of ABI 18, no existing entry changes.  Exact fp32 on v_mfma_f32_32x32x2_f32 (32
+ * channels and more) / v_mfma_f32_16x16x4_f32 (fewer), no atomics, workgroups never wait on each other.  The two
+ * weight gradients follow the scheme of fv_conv1d_weight_grad: a number of splits that depends on the shape alone, a
+ * first launch that writes every split's partial sums to `workspace`, a second that adds them in ascending order, so
+ * identical calls return identical bits.  workspace: device memory of at least fv_..._workspace_bytes(...) bytes
+ * (4-byte aligned), which returns a negative FV_ERR_* code for arguments the entry itself would refuse; its contents
+ * on entry do not matter.
+ *
+ * fv_conv1d_weight_grad_dilated: the weight and bias gradient of a dense stride-1 dilated conv with zero padding,
+ *     dw[co, ci, j] = sum_{b, t} g_pre[b, co, t] * xa[b, ci, t + j dil - pad],      db[co] = sum_{b, t} g_pre[b, co, t]
+ * g_pre [B,Cout,Tout], Tout = Tin + 2 pad - dil (k - 1); xa [B,Cin,Tin] the conv's input as it saw it (after the
+ * activation in front of it), read as 0 outside [0, Tin); dw [Cout,Cin,k] or NULL; db [Cout] or NULL (not both).  The
+ * GEMM [Cout] x [Cin k] over B Tout for every channel count; the dilated read is resolved while the operand is
+ * staged.  Cin, Cout, k, dil >= 1 with Cin Cout k < 2^31, else FV_ERR_UNSUPPORTED.  Tout < 1, pad < 0, a null pointer,
+ * a result aliasing an input, a small workspace, B outside 1..65535 or a map of 2^30 words and more returns
+ * FV_ERR_INVALID_ARG.
+ *
+ * fv_conv_transpose1d_input_grad: the data gradient of ConvTranspose1d (w [Cin,Cout,k], the forward's folded weight as
+ * it lies in memory; stride s, padding p, output padding op; Tout = (Tin - 1) s - 2 p + k + op),
+ *     dxa[b, ci, i] = sum_co sum_j w[ci, co, j] * g[b, co, i s + j - p]          (g read as 0 outside [0, Tout))
+ * g [B,Cout,Tout]; dxa [B,Cin,Tin], all of it written.  The GEMM [Cin] x [B Tin] over Cout k, each element one
+ * (co, j)-ordered fmaf chain: a row's values do not depend on B or on the grid.  One launch.
+ *
+ * fv_conv_transpose1d_weight_grad: its weight and bias gradient,
+ *     dw[ci, co, j] = sum_{b, i} xa[b, ci, i] * g[b, co, i s + j - p],           db[co] = sum_{b, n} g[b, co, n]
+ * xa [B,Cin,Tin] the layer's input as it saw it; dw [Cin,Cout,k] or NULL; db [Cout] or NULL (not both).  The GEMM
+ * [Cin] x [Cout k] over B Tin; the stride-s gather of g is resolved while the operand is staged.  Any k, s >= 1, p >= 0
+ * and op with Tout >= 1 (k % s != 0 and k > 2 s included); error codes as fv_conv1d_weight_grad_dilated.
+ *
+ * The elementwise steps of the walk, one launch each, n elements:
+ * fv_tanh_grad:            out = g (1 - y y)                                   (y = tanh(z): the gradient in front of it)
+ * fv_residual_merge_grad:  out = [acc +] (g_y + (x > 0 ? 1 : slope) d)         (x_next = x + conv(lrelu(x, slope)): the
+ *                          gradient of x from g_y = dL/dx_next and the conv's data gradient d; acc, or NULL: the sum of
+ *                          the other ResBlocks' input gradients of the stage).  out may alias g_y, d or acc.
+ * fv_grad_div:             out = g / div                                       (the MRF mean's adjoint; a true division)
+ */
+int64_t fv_conv1d_weight_grad_dilated_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad);
+int fv_conv1d_weight_grad_dilated(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
+                                  int Tin, int k, int dil, int pad, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int fv_conv_transpose1d_input_grad(const float* g, const float* w, float* dxa, int B, int Cin, int Cout, int Tin, int k,
+                                   int stride, int pad, int out_pad, void* stream);
+int64_t fv_conv_transpose1d_weight_grad_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int stride, int pad,
+                                                        int out_pad);
+int fv_conv_transpose1d_weight_grad(const float* g, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
+                                    int Tin, int k, int stride, int pad, int out_pad, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int fv_tanh_grad(const float* g, const float* y, float* out, int64_t n, void* stream);
+int fv_residual_merge_grad(const float* g_y, const float* d, const float* x, const float* acc, float* out, int64_t n,
+                           float slope, void* stream);
+int fv_grad_div(const float* g, float* out, int64_t n, float div, void* stream);
+
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
  * ------------------------------------------------------------------ */
