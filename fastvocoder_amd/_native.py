@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "optim.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -281,6 +281,10 @@ def lib():
     L.fv_tanh_grad.argtypes = [vp, vp, vp, i64, vp]
     L.fv_residual_merge_grad.argtypes = [vp, vp, vp, vp, vp, i64, f, vp]
     L.fv_grad_div.argtypes = [vp, vp, i64, f, vp]
+    L.fv_grad_sq_norm_workspace_bytes.argtypes = [i64]
+    L.fv_grad_sq_norm_workspace_bytes.restype = i64
+    L.fv_grad_sq_norm.argtypes = [vp, vp, i, i64, f, vp, ctypes.c_size_t, vp, vp]
+    L.fv_adam_step.argtypes = [vp, vp, i, i64, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
     L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
     L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
     L.fv_disc_score_grad.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
@@ -1663,6 +1667,60 @@ def grad_div(g, div):
     with _on(g, out) as stream:
         check(lib().fv_grad_div(_ptr(g, "g"), _ptr(out), g.numel(), float(div), stream))
     return out
+
+
+# ---------------------------------------------------------------------------
+# gradient clipping + Adam over a table of tensors (csrc/optim.hip)
+# ---------------------------------------------------------------------------
+
+ADAM_CHUNK = 4096               # FV_ADAM_CHUNK: elements per table chunk, one workgroup each
+ADAM_ROW_BYTES, ADAM_CHUNK_BYTES = 48, 8      # sizeof(fv_adam_tensor), sizeof(fv_adam_chunk)
+
+
+def _adam_table(table, n_tensors, n_chunks, name):
+    """(rows pointer, chunks pointer) of a device table laid out as optim.adam_table does: n_tensors fv_adam_tensor
+    rows, then n_chunks fv_adam_chunk entries, in one uint8 device tensor."""
+    n_tensors, n_chunks = int(n_tensors), int(n_chunks)
+    need = ADAM_ROW_BYTES * n_tensors + ADAM_CHUNK_BYTES * n_chunks
+    if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.uint8 or not table.is_contiguous():
+        raise NativeError(f"{name}: the table must be a contiguous uint8 ROCm device tensor")
+    if n_tensors < 1 or n_chunks < 1 or table.numel() < need:
+        raise NativeError(f"{name}: a table of {n_tensors} rows and {n_chunks} chunks needs {need} bytes, got "
+                          f"{table.numel()}")
+    return table.data_ptr(), table.data_ptr() + ADAM_ROW_BYTES * n_tensors
+
+
+def grad_sq_norm_workspace_floats(n_chunks):
+    """fp32 words of workspace grad_sq_norm needs for a table of n_chunks chunks (fv_grad_sq_norm_workspace_bytes)."""
+    need = lib().fv_grad_sq_norm_workspace_bytes(int(n_chunks))
+    if need < 0:
+        check(int(need))
+    return (need + 3) // 4
+
+
+def grad_sq_norm(table, n_tensors, n_chunks, max_norm, workspace, out):
+    """The 2-norm of all the gradients of a table and clip_grad_norm_'s factor (fv_grad_sq_norm, two launches): writes
+    out[0] = norm, out[1] = min(1, max_norm / (norm + 1e-6)); ``out``: two fp32 device words, ``workspace``: an fp32
+    device tensor of grad_sq_norm_workspace_floats(n_chunks) words whose contents do not matter."""
+    rows, chunks = _adam_table(table, n_tensors, n_chunks, "grad_sq_norm")
+    if out.numel() < 2:
+        raise NativeError("grad_sq_norm: out must hold two floats")
+    with _on(table, workspace, out) as stream:
+        check(lib().fv_grad_sq_norm(rows, chunks, int(n_tensors), int(n_chunks), float(max_norm),
+                                    _ptr(workspace, "workspace"), workspace.numel() * 4, _ptr(out, "out"), stream))
+
+
+def adam_step(table, n_tensors, n_chunks, coef, beta1, beta2, eps, first_chunk=0, chunk_count=None):
+    """The Adam update of the chunks [first_chunk, first_chunk + chunk_count) of a table (fv_adam_step, one launch);
+    ``coef``: a one-element fp32 device tensor that scales every gradient first (and is written back to it), or None."""
+    rows, chunks = _adam_table(table, n_tensors, n_chunks, "adam_step")
+    first_chunk = int(first_chunk)
+    chunk_count = int(n_chunks) - first_chunk if chunk_count is None else int(chunk_count)
+    if first_chunk < 0 or chunk_count < 1 or first_chunk + chunk_count > int(n_chunks):
+        raise NativeError(f"adam_step: chunks [{first_chunk}, {first_chunk + chunk_count}) of {n_chunks}")
+    with _on(table, coef) as stream:
+        check(lib().fv_adam_step(rows, chunks + ADAM_CHUNK_BYTES * first_chunk, int(n_tensors), chunk_count,
+                                 _ptr(coef, "coef", True), float(beta1), float(beta2), float(eps), stream))
 
 
 def reflect_pad_fold(gp, pad):

@@ -1,6 +1,6 @@
-"""``MODE=<synthesize|test|publish|preprocess|evaluation> python -m fastvocoder_amd.bin.launcher --flags``
--- the reference's $MODE dispatch (bin/launcher.py:7-19) for the inference-side
-modes, the dataset preparation and the evaluation.  ``train`` is out of scope."""
+"""``MODE=<train|synthesize|test|publish|preprocess|evaluation> python -m fastvocoder_amd.bin.launcher --flags``
+-- the reference's $MODE dispatch (bin/launcher.py:7-19): training (HiFi-GAN and
+Multiband-HiFi-GAN), the inference-side modes, the dataset preparation and the evaluation."""
 import os
 import sys
 
@@ -23,10 +23,10 @@ def main():
         from .evaluation import run_evaluation
         run_evaluation()
     elif mode == "train":
-        sys.exit(f"MODE={mode} is a training-side mode of the reference and is not part of "
-                 "fastvocoder_amd (generator inference only)")
+        from .train import run_train
+        run_train()
     else:
-        sys.exit("set MODE=synthesize | test | publish | preprocess | evaluation")
+        sys.exit("set MODE=train | synthesize | test | publish | preprocess | evaluation")
 
 
 if __name__ == "__main__":

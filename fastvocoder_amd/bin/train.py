@@ -1,0 +1,283 @@
+"""``MODE=train``: the reference's bin/train.py for the generators that have a parameter gradient, HiFi-GAN and
+Multiband-HiFi-GAN, on the MI355X kernels: ``train.Trainer`` runs the step, ``optim.Adam`` clips and updates in three
+launches, ``data.BatchIterator`` cuts the crops.
+
+``run_train()`` takes the reference's arguments (train.py:478-499) and, for a test or a short run, ``--max_steps``,
+``--seed``, ``--batch_size``, ``--fixed_length``, ``--discriminator_train_start_steps``, ``--log_step``,
+``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams) and ``--use_mpd``.  ``lamda_stft`` (sic) and
+``use_feature_map_loss`` come from the yaml, as there.  Both optimizers are ``Adam(lr, eps=1e-6)``; ``--use_scheduler 1``
+adds ``CosineAnnealingLR(T_max=2500, eta_min=lr / 10)`` to both.
+
+Every ``log_step`` steps the reference's log lines are printed and appended to ``<logger_path>/<timestamp>/logger.txt``
+(format_log_lines, format_time_line); ``total_loss.txt`` and ``stft_loss.txt`` get one value per step.  Scalars also
+go to tensorboardX when it can be imported (it is optional).  Every ``save_step`` steps
+``<checkpoint_path>/<timestamp>/checkpoint_<step>.pth.tar`` is written with the reference's four keys (``model``,
+``optimizer``, ``discriminator``, ``discriminator_optimizer``), which MODE=synthesize, MODE=evaluation --discriminator
+and the reference itself load.  Every ``valid_step`` steps the mean STFT loss of up to ``valid_num`` whole validation
+utterances is printed as ``valid <step> stft=<%.8e>``.
+
+Deviations from the reference, on purpose: ``--checkpoint_path ""`` starts new, but a path that cannot be loaded exits
+(the reference's bare ``except`` starts a new training silently); whether the checkpoint's discriminator holds the
+multi-period discriminator is read from its ``mpd.`` keys, as MODE=evaluation does; the validation mean divides by the
+number of utterances scored (the reference scores ``valid_num + 1`` and divides by ``valid_num``) and takes them in
+index order; the samples per frame come from the generator's upsample rates, not from ``hparams.hop_size``.
+``--model_name melgan`` / ``basis-melgan`` and ``--mixprecision 1`` exit: those generators have no parameter gradient
+here, and there is no mixed-precision path.
+"""
+import argparse
+import os
+import sys
+import time
+from datetime import datetime
+
+import numpy as np
+import torch
+import yaml
+
+from .. import hparams as hp
+from ..data import BatchIterator, load_data_to_buffer
+from ..discriminator import Discriminator
+from ..generator import PQMF
+from ..optim import Adam
+from ..train import Trainer, fit_estimate, samples_per_frame
+from .evaluation import discriminator_uses_mpd
+from .synthesize import build_generator, default_device, load_checkpoint
+
+SUPPORTED = ("hifigan", "multiband-hifigan")
+CHECKPOINT_KEYS = ("model", "optimizer", "discriminator", "discriminator_optimizer")
+
+
+def format_log_lines(epoch, epochs, current_step, total_step, s_l, w_l, t_l, a_l, d_l, f_l, lr, lr_discriminator):
+    """The four log lines of a step in the reference's format (train.py:201-207); ``epoch`` counts from 0."""
+    return [f"Epoch [{epoch + 1}/{epochs}], Step [{current_step}/{total_step}]:",
+            "STFT Loss: {:.6f}, Weight Loss: {:.6f}, Total Loss: {:.6f};".format(s_l, w_l, t_l),
+            "Adversarial Loss: {:.6f}, Discriminator Loss: {:.6f}, Feature Map Loss: {:.6f};".format(a_l, d_l, f_l),
+            "Current Learning Rate is {:.6f}, discriminator Learning Rate is {:.6f};".format(lr, lr_discriminator)]
+
+
+def format_time_line(used, remaining):
+    """The line that follows them (train.py:208)."""
+    return "Time Used: {:.3f}s, Estimated Time Remaining: {:.3f}s.".format(used, remaining)
+
+
+def build_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--audio_index_path", type=str, default=os.path.join("dataset", "audio", "train"))
+    parser.add_argument("--mel_index_path", type=str, default=os.path.join("dataset", "mel", "train"))
+    parser.add_argument("--audio_index_valid_path", type=str, default=os.path.join("dataset", "audio", "valid"))
+    parser.add_argument("--mel_index_valid_path", type=str, default=os.path.join("dataset", "mel", "valid"))
+    parser.add_argument("--checkpoint_path", type=str, default="")
+    parser.add_argument("--restore_step", type=int, default=0)
+    parser.add_argument("--learning_rate", type=float, default=hp.learning_rate)
+    parser.add_argument("--learning_rate_discriminator", type=float, default=hp.learning_rate_discriminator)
+    parser.add_argument("--model_name", type=str, help="hifigan and multiband-hifigan.")
+    parser.add_argument("--config", type=str, help="path to model configuration file")
+    parser.add_argument("--use_scheduler", type=int, default=0)
+    parser.add_argument("--mixprecision", type=int, default=0)
+    # what a test or a short run needs
+    parser.add_argument("--max_steps", type=int, default=0, help="stop after this many steps (0: run the epochs)")
+    parser.add_argument("--seed", type=int, default=0, help="seed of the crops, the shuffling and the initial weights")
+    parser.add_argument("--batch_size", type=int, default=hp.batch_size)
+    parser.add_argument("--fixed_length", type=int, default=hp.fixed_length, help="frames per training crop")
+    parser.add_argument("--discriminator_train_start_steps", type=int, default=hp.discriminator_train_start_steps)
+    parser.add_argument("--log_step", type=int, default=hp.log_step)
+    parser.add_argument("--save_step", type=int, default=hp.save_step)
+    parser.add_argument("--valid_step", type=int, default=hp.valid_step)
+    parser.add_argument("--valid_num", type=int, default=hp.valid_num)
+    parser.add_argument("--use_mpd", type=int, default=0,
+                        help="1: train Discriminator(use_mpd=True), HiFi-GAN's multi-period discriminator included")
+    return parser
+
+
+def check_args(args):
+    """Exit, with one sentence that names what is missing, for what this loop does not train."""
+    if args.model_name in ("melgan", "basis-melgan"):
+        sys.exit(f"MODE=train: --model_name {args.model_name} cannot be trained here: the ResidualStack generators "
+                 "(MelGAN, Basis-MelGAN) have no parameter gradient yet; supported: " + ", ".join(SUPPORTED))
+    if args.model_name not in SUPPORTED:
+        sys.exit(f"MODE=train: --model_name must be one of {', '.join(SUPPORTED)}, got {args.model_name!r}")
+    if args.mixprecision:
+        sys.exit("MODE=train: --mixprecision 1 is not supported: there is no mixed-precision (apex amp) path, the "
+                 "kernels train in fp32")
+    if not args.config:
+        sys.exit("MODE=train: --config (the model's yaml file) is required")
+    for name in ("batch_size", "fixed_length", "log_step", "save_step", "valid_step"):
+        if getattr(args, name) < 1:
+            sys.exit(f"MODE=train: --{name} must be at least 1")
+    return args
+
+
+def _timestamp():
+    return str(datetime.now()).replace(" ", "-").replace(":", "-").replace(".", "-")
+
+
+def _summary_writer(path):
+    """A tensorboardX SummaryWriter, or None when tensorboardX is not installed."""
+    try:
+        from tensorboardX import SummaryWriter
+    except ImportError:
+        return None
+    return SummaryWriter(path)
+
+
+def validate(model, vocoder_loss, pqmf, buffer, valid_num, device, spf):
+    """(mean STFT loss, utterances scored) over the first ``valid_num`` whole utterances, under no_grad."""
+    losses = []
+    with torch.no_grad():
+        for item in buffer[:max(0, valid_num)]:
+            frames = min(item["mel"].shape[0], item["wav"].shape[0] // spf)
+            if frames < 1:
+                continue
+            mel = item["mel"][:frames].to(device).t().unsqueeze(0).contiguous()
+            wav = item["wav"][:frames * spf].to(device).unsqueeze(0).contiguous()
+            losses.append(vocoder_loss(fit_estimate(model(mel), wav.shape[1], pqmf), wav, pqmf=pqmf)[0].reshape(()))
+        if not losses:
+            return float("nan"), 0
+        return float(torch.stack(losses).mean()), len(losses)
+
+
+def run(args):
+    device = default_device()
+    torch.manual_seed(args.seed)
+    with open(args.config) as f:
+        config = yaml.load(f, Loader=yaml.Loader)
+    lambda_stft = config["lamda_stft"]
+    use_feature_map_loss = config["use_feature_map_loss"]
+    print(f"Loading Model of {args.model_name}...")
+    model = build_generator(args.model_name, config).to(device)
+    pqmf = PQMF().to(device) if config["multiband"] else None
+
+    # the checkpoint first: it decides which discriminator is built
+    checkpoint = None
+    if args.checkpoint_path:
+        try:
+            checkpoint = load_checkpoint(args.checkpoint_path, device)
+            missing = [k for k in ("model", "optimizer") if k not in checkpoint]
+        except Exception as e:                     # noqa: BLE001 -- whatever the loader raises ends the run
+            sys.exit(f"MODE=train: cannot load --checkpoint_path {args.checkpoint_path}: {type(e).__name__}: {e}")
+        if missing:
+            sys.exit(f"MODE=train: --checkpoint_path {args.checkpoint_path} has no {missing} entry: not a training "
+                     "checkpoint")
+    use_mpd = bool(args.use_mpd)
+    if checkpoint is not None and "discriminator" in checkpoint:
+        use_mpd = discriminator_uses_mpd(checkpoint["discriminator"])
+    discriminator = Discriminator(use_mpd=use_mpd).to(device)
+    print(f"Number of Parameters: {sum(p.numel() for p in model.parameters())}")
+
+    optimizer = Adam(model.parameters(), lr=args.learning_rate, eps=1.0e-6, weight_decay=0.0)
+    discriminator_optimizer = Adam(discriminator.parameters(), lr=args.learning_rate_discriminator, eps=1.0e-6,
+                                   weight_decay=0.0)
+    if checkpoint is not None:
+        model.load_state_dict(checkpoint["model"])
+        optimizer.load_state_dict(checkpoint["optimizer"])
+        if "discriminator" in checkpoint:
+            discriminator.load_state_dict(checkpoint["discriminator"])
+            discriminator_optimizer.load_state_dict(checkpoint["discriminator_optimizer"])
+        counts = [int(s["step"]) for s in optimizer.state.values()]
+        print("\n---Model Restored at Step %d---\n" % args.restore_step)
+        print("optimizer state at step count %d" % (max(counts) if counts else 0))
+    else:
+        print("\n---Start New Training---\n")
+    scheduler = discriminator_scheduler = None
+    if args.use_scheduler:
+        from torch.optim.lr_scheduler import CosineAnnealingLR
+        scheduler = CosineAnnealingLR(optimizer, T_max=2500, eta_min=args.learning_rate / 10.)
+        discriminator_scheduler = CosineAnnealingLR(discriminator_optimizer, T_max=2500,
+                                                    eta_min=args.learning_rate_discriminator / 10.)
+
+    stamp = _timestamp()
+    current_checkpoint_path = os.path.join(hp.checkpoint_path, stamp)
+    current_logger_path = os.path.join(hp.logger_path, stamp)
+    os.makedirs(current_checkpoint_path, exist_ok=True)
+    os.makedirs(current_logger_path, exist_ok=True)
+    writer = _summary_writer(os.path.join(hp.tensorboard_path, stamp))
+
+    model.train()
+    trainer = Trainer(model, discriminator, optimizer, discriminator_optimizer, scheduler, discriminator_scheduler,
+                      pqmf, lambda_stft=lambda_stft, use_feature_map_loss=use_feature_map_loss,
+                      discriminator_train_start_steps=args.discriminator_train_start_steps,
+                      grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm)
+    spf = samples_per_frame(model, pqmf)
+
+    print("Load data to buffer")
+    batches = BatchIterator(load_data_to_buffer(args.audio_index_path, args.mel_index_path), args.batch_size,
+                            args.fixed_length, spf, seed=args.seed, name="train")
+    print("Load valid data to buffer")
+    valid_buffer = load_data_to_buffer(args.audio_index_valid_path, args.mel_index_valid_path)
+    if len(batches) < 1:
+        sys.exit(f"MODE=train: {len(batches.items)} usable training utterances do not fill one batch of "
+                 f"{args.batch_size}")
+    print(f"Length of training loader is {len(batches)}")
+    total_step = hp.epochs * len(batches)
+
+    start = time.perf_counter()
+    step_times = []
+    done = 0
+    for epoch in range(hp.epochs):
+        for i, (mel, wav) in enumerate(batches.epoch()):
+            current_step = i + args.restore_step + epoch * len(batches) + 1
+            step_start = time.perf_counter()
+            mel = mel.to(device).transpose(1, 2).contiguous()
+            wav = wav.to(device)
+            out = trainer.step(mel, wav, current_step)
+            s_l, t_l = out["stft"], out["total"]
+            with open(os.path.join(current_logger_path, "total_loss.txt"), "a") as f:
+                f.write(str(t_l) + "\n")
+            with open(os.path.join(current_logger_path, "stft_loss.txt"), "a") as f:
+                f.write(str(s_l) + "\n")
+
+            if current_step % args.log_step == 0:
+                if scheduler is None:
+                    lrs = args.learning_rate, args.learning_rate_discriminator
+                else:
+                    lrs = scheduler.get_last_lr()[-1], discriminator_scheduler.get_last_lr()[-1]
+                now = time.perf_counter()
+                mean_time = float(np.mean(step_times)) if step_times else now - step_start
+                lines = format_log_lines(epoch, hp.epochs, current_step, total_step, s_l, 0., t_l, out["adversarial"],
+                                         out["discriminator"], out["feature_map"], *lrs)
+                lines.append(format_time_line(now - start, (total_step - current_step) * mean_time))
+                print("\n" + "\n".join(lines), flush=True)
+                with open(os.path.join(current_logger_path, "logger.txt"), "a") as f:
+                    f.write("\n".join(lines) + "\n\n")
+                if writer is not None:
+                    for tag, value in (("total_loss", t_l), ("stft_loss", s_l), ("adversarial_loss", out["adversarial"]),
+                                       ("discriminator_loss", out["discriminator"]),
+                                       ("feature_map_loss", out["feature_map"]), ("grad_norm", out["grad_norm"])):
+                        writer.add_scalar(tag, value, global_step=current_step)
+                    if scheduler is not None:
+                        writer.add_scalar("learning_rate", lrs[0], global_step=current_step)
+
+            if current_step % args.save_step == 0:
+                torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict(),
+                            "discriminator": discriminator.state_dict(),
+                            "discriminator_optimizer": discriminator_optimizer.state_dict()},
+                           os.path.join(current_checkpoint_path, "checkpoint_%d.pth.tar" % current_step))
+                print("save model at step %d ..." % current_step, flush=True)
+
+            step_times.append(time.perf_counter() - step_start)
+            if len(step_times) == hp.clear_time:
+                step_times = [float(np.mean(step_times))]
+
+            if current_step % args.valid_step == 0:
+                value, scored = validate(model, trainer.vocoder_loss, pqmf, valid_buffer, args.valid_num, device, spf)
+                print("valid %d stft=%.8e" % (current_step, value), flush=True)
+                if writer is not None and scored:
+                    writer.add_scalar("valid_stft_loss", value, global_step=current_step)
+
+            done += 1
+            if args.max_steps and done >= args.max_steps:
+                break
+        else:
+            continue
+        break
+    if writer is not None:
+        writer.close()
+    return current_checkpoint_path
+
+
+def run_train(argv=None):
+    return run(check_args(build_parser().parse_args(argv)))
+
+
+if __name__ == "__main__":
+    run_train()

@@ -1,0 +1,87 @@
+"""The training data path of the reference (data/dataset.py): the utterances ``MODE=preprocess`` wrote, held in memory,
+and fixed-length random crops of them in shuffled batches.
+
+``load_data_to_buffer(audio_index, mel_index)`` reads the ``<name>.npy`` / ``<name>.mel.npy`` pairs the two index
+files list (dataset.py:19-53); the mel is stored ``[80, T]`` and kept ``[T, 80]``, as dataset.py:38 transposes it.
+``BatchIterator`` gives the crop of ``BufferDataset.__getitem__`` (dataset.py:63-75) -- the first frame uniform in
+``[0, frames - fixed_length - 1]`` (``random.randint``'s closed range), the waveform slice ``start * hop`` to
+``end * hop`` -- and the epochs of ``DataLoader(shuffle=True, drop_last=True)``, from ONE seeded generator, so that a
+seed fixes the whole run.  Differences, on purpose: utterances too short for a crop are left out and counted in one
+printed line (the reference raises inside ``random.randint``); batches are collated in this process (no DataLoader
+workers: the buffer is in memory and a crop is a slice); the ``features_*.bin`` pickle cache and the sorting into
+``batch_expand_size`` sub-batches by length (all crops have one length) are not reproduced.
+"""
+import numpy as np
+import torch
+
+from . import hparams as hp
+
+
+def parse_path_file(path):
+    with open(path, "r", encoding="utf-8") as f:
+        return [line.rstrip("\n") for line in f if line.strip()]
+
+
+def load_data_to_buffer(audio_index_path_file, mel_index_path_file, size=None):
+    """-> [{"mel": float32 [T, 80], "wav": float32 [n]}] for the first ``size`` (default hparams.test_size, 0 = all)
+    utterances of the index files."""
+    audio_index = parse_path_file(audio_index_path_file)
+    mel_index = parse_path_file(mel_index_path_file)
+    if len(audio_index) != len(mel_index):
+        raise ValueError(f"{audio_index_path_file} lists {len(audio_index)} waveforms, {mel_index_path_file} "
+                         f"{len(mel_index)} mels")
+    n = len(audio_index)
+    size = hp.test_size if size is None else size
+    if size != 0 and size < n:
+        n = size
+    buffer = []
+    for i in range(n):
+        mel = torch.from_numpy(np.ascontiguousarray(np.load(mel_index[i]).T, dtype=np.float32))
+        wav = torch.from_numpy(np.ascontiguousarray(np.load(audio_index[i]), dtype=np.float32))
+        buffer.append({"mel": mel, "wav": wav})
+    return buffer
+
+
+def croppable(item, fixed_length, hop):
+    """Can a crop of ``fixed_length`` frames be cut from this utterance (at every start the reference may draw)?"""
+    frames = item["mel"].shape[0]
+    return frames - fixed_length - 1 >= 0 and item["wav"].shape[0] >= (frames - 1) * hop
+
+
+def crop(item, start, fixed_length, hop):
+    """BufferDataset.__getitem__ at a given first frame -> (mel [fixed_length, 80], wav [fixed_length * hop])."""
+    end = start + fixed_length
+    return item["mel"][start:end, :], item["wav"][start * hop:end * hop]
+
+
+class BatchIterator:
+    """``for mel, wav in BatchIterator(...).epoch()``: mel [B, fixed_length, 80], wav [B, fixed_length * hop], CPU fp32
+    tensors.  ``len()`` is the number of batches of an epoch (``drop_last``)."""
+
+    def __init__(self, buffer, batch_size, fixed_length=None, hop=None, seed=0, name="train"):
+        self.fixed_length = hp.fixed_length if fixed_length is None else int(fixed_length)
+        self.hop = hp.hop_size if hop is None else int(hop)
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1 or self.fixed_length < 1 or self.hop < 1:
+            raise ValueError(f"batch_size {batch_size}, fixed_length {fixed_length} and hop {hop} must be positive")
+        self.items = [it for it in buffer if croppable(it, self.fixed_length, self.hop)]
+        self.skipped = len(buffer) - len(self.items)
+        if self.skipped:
+            print(f"data: {self.skipped} of {len(buffer)} {name} utterances are too short for a crop of "
+                  f"{self.fixed_length} frames and are left out")
+        self.rng = np.random.RandomState(seed)
+
+    def __len__(self):
+        return len(self.items) // self.batch_size
+
+    def epoch(self):
+        order = self.rng.permutation(len(self.items))
+        for b in range(len(self)):
+            mels, wavs = [], []
+            for idx in order[b * self.batch_size:(b + 1) * self.batch_size]:
+                item = self.items[idx]
+                start = int(self.rng.randint(0, item["mel"].shape[0] - self.fixed_length))   # high is exclusive
+                mel, wav = crop(item, start, self.fixed_length, self.hop)
+                mels.append(mel)
+                wavs.append(wav)
+            yield torch.stack(mels), torch.stack(wavs)

@@ -10,9 +10,10 @@ graph (csrc/disc_grad.hip, csrc/stft_mag_grad.hip); ``discriminator_step_terms``
 signal and a detached estimate and returns the terms of its own update on the graph of its parameters
 (csrc/disc_wgrad.hip, csrc/mpd_wgrad.hip): the multi-scale discriminator as it is, the STFT discriminators with
 ``stft_grad=True``, the period discriminators with ``period_grad=True``, Discriminator() with ``stft_grad=True`` and
-Discriminator(use_mpd=True) with both."""
+Discriminator(use_mpd=True) with both.  ``pqmf_synthesis`` is PQMF.synthesis on the graph of the sub-bands (the
+multiband waveform the discriminator sees in training)."""
 from .discriminator_loss import discriminator_step_terms, discriminator_terms, generator_adversarial_terms
-from .loss import Loss
+from .loss import Loss, PqmfSynthesis, pqmf_synthesis
 from .stft_loss import MultiResolutionSTFTLoss, STFTLoss, stft, stft_tables
 
-__all__ = ["Loss", "discriminator_step_terms", "discriminator_terms", "generator_adversarial_terms", "MultiResolutionSTFTLoss", "STFTLoss", "stft", "stft_tables"]
+__all__ = ["Loss", "PqmfSynthesis", "pqmf_synthesis", "discriminator_step_terms", "discriminator_terms", "generator_adversarial_terms", "MultiResolutionSTFTLoss", "STFTLoss", "stft", "stft_tables"]

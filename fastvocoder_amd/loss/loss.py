@@ -8,10 +8,12 @@ from .. import _native
 from .stft_loss import MultiResolutionSTFTLoss, _signal
 
 
-class _PqmfSynthesis(torch.autograd.Function):
+class PqmfSynthesis(torch.autograd.Function):
     """pqmf.synthesis with its adjoint.  synthesis is y[m] = S sum_k sum_t g_k[S t + taps/2 - m] x[k, t] (zero
     stuffing by S, then the zero-padded FIR g_k), so dL/dx[k, t] = sum_m (S g_k[taps - j]) dL/dy[m] at
-    j = m - S t + taps/2: the analysis kernel (a zero-padded FIR decimated by S) with the filter S * flip(g_k)."""
+    j = m - S t + taps/2: the analysis kernel (a zero-padded FIR decimated by S) with the filter S * flip(g_k).
+    ``pqmf_synthesis(x, pqmf)`` is the call: the training loop puts the multiband generator's waveform on the graph
+    with it before the discriminator sees it (bin/train.py:96)."""
 
     @staticmethod
     def forward(ctx, x, pqmf):
@@ -26,6 +28,14 @@ class _PqmfSynthesis(torch.autograd.Function):
         S = ctx.subbands
         adjoint = (S * torch.flip(g[0], dims=(-1,))).reshape(S, 1, -1)
         return _native.pqmf_analysis(gy.contiguous().float(), adjoint), None
+
+
+def pqmf_synthesis(x, pqmf):
+    """pqmf.synthesis(x) [B, 1, S T] of the sub-bands x [B, S, T], on the graph of x when x requires grad."""
+    x = x.contiguous().float()
+    if x.requires_grad and torch.is_grad_enabled():
+        return PqmfSynthesis.apply(x, pqmf)
+    return pqmf.synthesis(x)
 
 
 class Loss(torch.nn.Module):
@@ -56,7 +66,7 @@ class Loss(torch.nn.Module):
             est_source_sub_band = est_source.contiguous().float()
             wav_sub_band = pqmf.analysis(wav_full_band.unsqueeze(1))
             if self.differentiable and est_source_sub_band.requires_grad and torch.is_grad_enabled():
-                est_source_full_band = _PqmfSynthesis.apply(est_source_sub_band, pqmf)[:, 0, :]
+                est_source_full_band = PqmfSynthesis.apply(est_source_sub_band, pqmf)[:, 0, :]
             else:
                 est_source_full_band = pqmf.synthesis(est_source_sub_band)[:, 0, :]
             est_source_sub_band = est_source_sub_band.view(-1, est_source_sub_band.size(2))

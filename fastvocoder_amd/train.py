@@ -1,0 +1,118 @@
+"""One training step of the reference's loop (bin/train.py:48-188, ``trainer``) as a library call.
+
+``Trainer.step(mel, wav, current_step)`` runs, in the reference's order: zero both optimizers' gradients; the
+generator's training forward (``parameter_grad = True``); the composed STFT loss (``Loss``, through the PQMF synthesis
+for a multiband generator); past ``discriminator_train_start_steps`` the adversarial and feature-map terms of the
+discriminator on the estimate (``generator_adversarial_terms``, the multiband waveform being ``pqmf.synthesis`` of the
+sub-bands ON the graph); one backward; clip + Adam in three launches (``optim.Adam.step(max_norm=...)``) and the
+scheduler; then the discriminator's own update on a fresh ``no_grad`` forward of the UPDATED generator
+(train.py:148-155), ``discriminator_step_terms``, backward, clip + Adam, scheduler.
+
+The scalars of a step stay on the device until its end and are read with one copy to the host (the reference reads
+five times, ``.item()`` each).  (The backward of the discriminator terms still reads its incoming coefficient on the
+host, as it does outside this loop: loss/discriminator_loss.py.)
+
+MelGAN, Basis-MelGAN and the ``transposedconv: False`` upsampler have no parameter gradient and are refused where the
+``parameter_grad`` attribute refuses them; mixed precision is not part of this loop.
+"""
+import torch
+
+from .loss import Loss, discriminator_step_terms, generator_adversarial_terms, pqmf_synthesis
+from .optim import Adam
+
+KEYS = ("stft", "total", "adversarial", "feature_map", "discriminator", "grad_norm", "discriminator_grad_norm")
+
+
+def samples_per_frame(model, pqmf=None):
+    """Waveform samples the generator makes of one mel frame: the product of its upsample rates, times the sub-band
+    count when its output goes through a PQMF synthesis."""
+    n = 1
+    for up in model.ups:
+        n *= int(up.stride[0])
+    return n * (int(pqmf.subbands) if pqmf is not None else 1)
+
+
+def fit_estimate(est, n, pqmf=None):
+    """The generator's output cropped to a target of ``n`` samples: a ConvTranspose1d whose kernel is not twice its
+    stride makes a few samples more than frames x rate (the reference's configurations never do).  est (B, T), or the
+    sub-bands (B, S, T / S) with ``pqmf``; a shorter estimate is returned as it is (the loss refuses it)."""
+    if pqmf is not None:
+        n //= int(pqmf.subbands)
+    return est[..., :n].contiguous() if est.shape[-1] > n else est
+
+
+class Trainer:
+    def __init__(self, model, discriminator, optimizer, discriminator_optimizer, scheduler=None,
+                 discriminator_scheduler=None, pqmf=None, *, lambda_stft, use_feature_map_loss,
+                 discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0):
+        for opt, name in ((optimizer, "optimizer"), (discriminator_optimizer, "discriminator_optimizer")):
+            if not isinstance(opt, Adam):
+                raise TypeError(f"{name} must be a fastvocoder_amd.optim.Adam (its step clips and updates in three "
+                                f"launches), got {type(opt).__name__}")
+        model.parameter_grad = True           # raises for the generators that have no parameter gradient
+        self.model, self.discriminator = model, discriminator
+        self.optimizer, self.discriminator_optimizer = optimizer, discriminator_optimizer
+        self.scheduler, self.discriminator_scheduler = scheduler, discriminator_scheduler
+        self.pqmf = pqmf
+        self.lambda_stft, self.lambda_adv, self.lambda_fm = float(lambda_stft), float(lambda_adv), float(lambda_fm)
+        self.use_feature_map_loss = bool(use_feature_map_loss)
+        self.discriminator_train_start_steps = int(discriminator_train_start_steps)
+        self.grad_clip_thresh = float(grad_clip_thresh)
+        self.period_grad = bool(getattr(discriminator, "use_mpd", False))
+        self.vocoder_loss = Loss().to(next(model.parameters()).device)
+        self.vocoder_loss.differentiable = True
+        self.samples_per_frame = samples_per_frame(model, pqmf)
+
+    def _waveform(self, est):
+        """The generator's output as (B, T) full band: the PQMF synthesis of sub-bands, on their graph."""
+        if self.pqmf is None:
+            return est
+        return pqmf_synthesis(est, self.pqmf)[:, 0, :]
+
+    def step(self, mel, wav, current_step):
+        """mel (B, 80, T) and wav (B, T * samples_per_frame), fp32 device tensors -> {key: float for key in KEYS}:
+        the STFT loss (before lambda_stft), the generator's total, its adversarial and feature-map terms, the
+        discriminator's loss (0.0 up to discriminator_train_start_steps) and the two gradient norms before clipping."""
+        if wav.dim() != 2 or mel.dim() != 3 or wav.shape[1] != mel.shape[2] * self.samples_per_frame:
+            raise ValueError(f"mel (B, 80, T) and wav (B, T * {self.samples_per_frame}) expected, got "
+                             f"{tuple(mel.shape)} and {tuple(wav.shape)}")
+        adversarial_phase = current_step > self.discriminator_train_start_steps
+        zero = torch.zeros((), dtype=torch.float32, device=wav.device)
+        self.optimizer.zero_grad()
+        self.discriminator_optimizer.zero_grad()
+
+        est = fit_estimate(self.model(mel), wav.shape[1], self.pqmf)
+        stft_loss, _ = self.vocoder_loss(est, wav, pqmf=self.pqmf)
+        total = self.lambda_stft * stft_loss
+        adv = fm = zero
+        if adversarial_phase:
+            real = wav.unsqueeze(1) if self.use_feature_map_loss else None
+            terms = generator_adversarial_terms(self.discriminator, self._waveform(est).unsqueeze(1), real,
+                                                period_grad=self.period_grad)
+            adv = terms["adversarial"]
+            total = total + self.lambda_adv * adv
+            if self.use_feature_map_loss:
+                fm = terms["feature_map"]
+                total = total + self.lambda_fm * fm
+        total.backward()
+        grad_norm = self.optimizer.step(max_norm=self.grad_clip_thresh)
+        if self.scheduler is not None:
+            self.scheduler.step()
+
+        d_loss = d_norm = zero
+        if adversarial_phase:
+            self.discriminator_optimizer.zero_grad()
+            with torch.no_grad():             # the plain forward, with the weights the step above left
+                est_for_d = self._waveform(fit_estimate(self.model(mel), wav.shape[1], self.pqmf))
+            kw = dict(period_grad=True) if self.period_grad else {}
+            d_loss = discriminator_step_terms(self.discriminator, est_for_d.unsqueeze(1), wav.unsqueeze(1),
+                                              stft_grad=True, **kw)["discriminator"]
+            d_loss.backward()
+            d_norm = self.discriminator_optimizer.step(max_norm=self.grad_clip_thresh)
+            if self.discriminator_scheduler is not None:
+                self.discriminator_scheduler.step()
+
+        scalars = torch.stack([t.detach().float().reshape(()) for t in
+                               (stft_loss, total, adv, fm, d_loss, zero if grad_norm is None else grad_norm,
+                                zero if d_norm is None else d_norm)])
+        return dict(zip(KEYS, scalars.cpu().tolist()))            # the step's one read on the host

@@ -928,6 +928,57 @@ int fv_residual_merge_grad(const float* g_y, const float* d, const float* x, con
                            float slope, void* stream);
 int fv_grad_div(const float* g, float* out, int64_t n, float div, void* stream);
 
+/*
+ * Gradient clipping and the Adam update of a whole parameter set (nn.utils.clip_grad_norm_ + Adam.step() of
+ * bin/train.py:126-136 and 176-186; the reference names the fused form itself, apex.optimizers.FusedAdam,
+ * train.py:338); additions of ABI 18, no existing entry changes.  Three launches for any number of tensors, exact fp32
+ * per element, no atomics, workgroups never wait on each other, identical calls return identical bits.
+ *
+ * Both entries read one table in DEVICE memory (8-byte aligned): n_tensors rows of fv_adam_tensor and n_chunks
+ * entries of fv_adam_chunk that cut every row into pieces of FV_ADAM_CHUNK elements -- row t of n elements owns the
+ * entries (t, 0) .. (t, (n - 1) / FV_ADAM_CHUNK), in any order; one workgroup handles one entry.  An entry whose row
+ * index lies outside the table is skipped.  All tensors are fp32 and contiguous, of n >= 1 elements; 16-byte loads
+ * and stores are used for a row whose pointers are all 16-byte aligned, 4-byte ones otherwise, with the same bits.
+ *
+ * fv_grad_sq_norm: the 2-norm of all the rows' gradients taken together and clip_grad_norm_'s factor,
+ *     out[0] = norm = sqrt(sum_t sum_i g_t[i]^2),     out[1] = coef = min(1, max_norm / (norm + 1e-6))
+ * (a NaN norm gives a NaN coef, as torch.clamp passes it).  Launch 1 writes one partial sum of squares per chunk (a
+ * double) to `workspace`, launch 2 -- one workgroup -- adds them in ascending order (256 consecutive ranges each in
+ * ascending order, then the 256 range sums in ascending order).  workspace: device memory of at
+ * least fv_grad_sq_norm_workspace_bytes(n_chunks) bytes, 8-byte aligned; its contents on entry do not matter.  out: two
+ * floats of device memory.  Only the g and n fields of a row are read.
+ *
+ * fv_adam_step: one launch.  With g' = coef[0] g (coef: ONE float of device memory, e.g. out + 1 of fv_grad_sq_norm,
+ * or NULL for g' = g),
+ *     m = beta1 m + (1 - beta1) g',    v = beta2 v + (1 - beta2) g'^2,
+ *     p = p - step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps))
+ * per element, where step_size = lr / (1 - beta1^step) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^step) are fields of the
+ * row, so that rows may be at different step counts; with a coef, g' is written back to g (the gradient holds the
+ * clipped values afterwards, as after clip_grad_norm_).  Nothing is read on the host.
+ *
+ * A null table, counts below 1, n_chunks >= 2^31, a misaligned table, workspace or result, max_norm < 0 (or NaN), or
+ * betas outside [0, 1) return FV_ERR_INVALID_ARG, a small workspace FV_ERR_WORKSPACE.
+ */
+#define FV_ADAM_CHUNK 4096
+typedef struct fv_adam_tensor {
+    float* p;            /* the parameter */
+    float* g;            /* its gradient */
+    float* m;            /* exp_avg */
+    float* v;            /* exp_avg_sq */
+    int64_t n;           /* elements of each */
+    float step_size;     /* lr / (1 - beta1^step) */
+    float inv_sqrt_bc2;  /* 1 / sqrt(1 - beta2^step) */
+} fv_adam_tensor;        /* 48 bytes */
+typedef struct fv_adam_chunk {
+    int32_t tensor;      /* row of the table */
+    int32_t index;       /* which FV_ADAM_CHUNK elements of it */
+} fv_adam_chunk;
+int64_t fv_grad_sq_norm_workspace_bytes(int64_t n_chunks);
+int fv_grad_sq_norm(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int n_tensors, int64_t n_chunks,
+                    float max_norm, void* workspace, size_t workspace_bytes, float* out, void* stream);
+int fv_adam_step(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int n_tensors, int64_t n_chunks,
+                 const float* coef, double beta1, double beta2, double eps, void* stream);
+
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
  * ------------------------------------------------------------------ */
