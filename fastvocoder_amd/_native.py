@@ -274,6 +274,10 @@ def lib():
     L.fv_conv1d_weight_grad_dilated_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
     L.fv_conv1d_weight_grad_dilated_workspace_bytes.restype = i64
     L.fv_conv1d_weight_grad_dilated.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_conv1d_weight_grad_dilated_mode_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
+    L.fv_conv1d_weight_grad_dilated_mode_workspace_bytes.restype = i64
+    L.fv_conv1d_weight_grad_dilated_mode.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_conv1d_input_grad_reflect.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
     L.fv_conv_transpose1d_input_grad.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, vp]
     L.fv_conv_transpose1d_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
     L.fv_conv_transpose1d_weight_grad_workspace_bytes.restype = i64
@@ -1533,21 +1537,26 @@ def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):
 # the generators' parameter gradient (csrc/gen_grad.hip)
 # ---------------------------------------------------------------------------
 
-def conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil=1, pad=0):
+def conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil=1, pad=0, pad_mode=None):
     """fp32 words of workspace conv1d_weight_grad_dilated needs for these shapes
-    (fv_conv1d_weight_grad_dilated_workspace_bytes); raises for shapes the entry refuses."""
-    need = lib().fv_conv1d_weight_grad_dilated_workspace_bytes(int(B), int(cin), int(cout), int(tin), int(k), int(dil),
-                                                               int(pad))
+    (fv_conv1d_weight_grad_dilated_workspace_bytes; with a ``pad_mode`` fv_conv1d_weight_grad_dilated_mode_workspace_bytes);
+    raises for shapes the entry refuses."""
+    args = (int(B), int(cin), int(cout), int(tin), int(k), int(dil), int(pad))
+    if pad_mode is None:
+        need = lib().fv_conv1d_weight_grad_dilated_workspace_bytes(*args)
+    else:
+        need = lib().fv_conv1d_weight_grad_dilated_mode_workspace_bytes(*args, int(pad_mode))
     if need < 0:
         check(int(need))
     return (need + 3) // 4
 
 
-def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db=False, workspace=None):
+def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db=False, workspace=None, pad_mode=None):
     """The weight (and bias) gradient of a dense stride-1 dilated conv with zero padding
     (fv_conv1d_weight_grad_dilated, two launches): g_pre [B,Cout,Tout], xa [B,Cin,Tin] the conv's input as it saw it
     -> (dw [Cout,Cin,k] or None, db [Cout] or None).  ``workspace``: an fp32 device tensor to use instead of a fresh
-    one (its contents do not matter)."""
+    one (its contents do not matter).  ``pad_mode`` PAD_ZERO or PAD_REFLECT goes through
+    fv_conv1d_weight_grad_dilated_mode: PAD_REFLECT reads xa through ReflectionPad1d(pad) without building it."""
     name = "conv1d_weight_grad_dilated"
     if g_pre.dim() != 3 or xa.dim() != 3 or g_pre.shape[0] != xa.shape[0]:
         raise NativeError(f"{name}: g_pre [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g_pre.shape)} and "
@@ -1561,15 +1570,38 @@ def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db
         raise NativeError(f"{name}: {tout} output times do not belong to an input of {tin} samples")
     dev = g_pre.device
     if workspace is None:
-        workspace = torch.empty(conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad),
+        workspace = torch.empty(conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad, pad_mode),
                                 dtype=torch.float32, device=dev)
     dw = torch.empty((cout, cin, k), dtype=torch.float32, device=dev) if want_dw else None
     db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
     with _on(g_pre, xa, workspace, dw, db) as stream:
-        check(lib().fv_conv1d_weight_grad_dilated(_ptr(g_pre, "g_pre"), _ptr(xa, "xa"), _ptr(dw, "dw", True),
-                                                  _ptr(db, "db", True), B, cin, cout, tin, k, dil, pad,
-                                                  _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
+        head = (_ptr(g_pre, "g_pre"), _ptr(xa, "xa"), _ptr(dw, "dw", True), _ptr(db, "db", True), B, cin, cout, tin, k,
+                dil, pad)
+        tail = (_ptr(workspace, "workspace"), workspace.numel() * 4, stream)
+        if pad_mode is None:
+            check(lib().fv_conv1d_weight_grad_dilated(*head, *tail))
+        else:
+            check(lib().fv_conv1d_weight_grad_dilated_mode(*head, int(pad_mode), *tail))
     return dw, db
+
+
+def conv1d_input_grad_reflect(g, wt, tin, dil=1, pad=0):
+    """The data gradient of conv(ReflectionPad1d(pad)(xa), W, dilation=dil) (fv_conv1d_input_grad_reflect, one launch,
+    no padded tensor): g [B,Cout,Tout], wt [Cin,Cout,k] = W.transpose(0, 1) contiguous -> dxa [B,Cin,tin]."""
+    name = "conv1d_input_grad_reflect"
+    if g.dim() != 3 or wt.dim() != 3 or wt.shape[1] != g.shape[1]:
+        raise NativeError(f"{name}: g [B,Cout,Tout] and wt [Cin,Cout,k] expected, got {tuple(g.shape)} and "
+                          f"{tuple(wt.shape)}")
+    tin, dil, pad = int(tin), int(dil), int(pad)
+    cin, cout, k = wt.shape
+    if dil > 0 and tin + 2 * pad - dil * (k - 1) >= 1 and g.shape[2] != tin + 2 * pad - dil * (k - 1):
+        raise NativeError(f"{name}: {g.shape[2]} output times do not belong to an input of {tin} samples")
+    B = g.shape[0]
+    dxa = torch.empty((B, cin, max(tin, 0)), dtype=torch.float32, device=g.device)
+    with _on(g, wt, dxa) as stream:
+        check(lib().fv_conv1d_input_grad_reflect(_ptr(g, "g"), _ptr(wt, "wt"), _ptr(dxa), B, cin, cout, tin, k, dil, pad,
+                                                 stream))
+    return dxa
 
 
 def _convt_grad_shapes(name, g, cin_tin, w_shape, k, stride, pad, out_pad):

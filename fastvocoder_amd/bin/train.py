@@ -1,12 +1,12 @@
-"""``MODE=train``: the reference's bin/train.py for the generators that have a parameter gradient, HiFi-GAN and
-Multiband-HiFi-GAN, on the MI355X kernels: ``train.Trainer`` runs the step, ``optim.Adam`` clips and updates in three
-launches, ``data.BatchIterator`` cuts the crops.
+"""``MODE=train``: the reference's bin/train.py for the generators that have a parameter gradient, HiFi-GAN,
+Multiband-HiFi-GAN and (opted in with ``--stack_grad 1``) MelGAN, on the MI355X kernels: ``train.Trainer`` runs the
+step, ``optim.Adam`` clips and updates in three launches, ``data.BatchIterator`` cuts the crops.
 
 ``run_train()`` takes the reference's arguments (train.py:478-499) and, for a test or a short run, ``--max_steps``,
 ``--seed``, ``--batch_size``, ``--fixed_length``, ``--discriminator_train_start_steps``, ``--log_step``,
-``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams) and ``--use_mpd``.  ``lamda_stft`` (sic) and
-``use_feature_map_loss`` come from the yaml, as there.  Both optimizers are ``Adam(lr, eps=1e-6)``; ``--use_scheduler 1``
-adds ``CosineAnnealingLR(T_max=2500, eta_min=lr / 10)`` to both.
+``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams), ``--use_mpd`` and ``--stack_grad``.
+``lamda_stft`` (sic) and ``use_feature_map_loss`` come from the yaml, as there.  Both optimizers are
+``Adam(lr, eps=1e-6)``; ``--use_scheduler 1`` adds ``CosineAnnealingLR(T_max=2500, eta_min=lr / 10)`` to both.
 
 Every ``log_step`` steps the reference's log lines are printed and appended to ``<logger_path>/<timestamp>/logger.txt``
 (format_log_lines, format_time_line); ``total_loss.txt`` and ``stft_loss.txt`` get one value per step.  Scalars also
@@ -21,8 +21,10 @@ Deviations from the reference, on purpose: ``--checkpoint_path ""`` starts new, 
 multi-period discriminator is read from its ``mpd.`` keys, as MODE=evaluation does; the validation mean divides by the
 number of utterances scored (the reference scores ``valid_num + 1`` and divides by ``valid_num``) and takes them in
 index order; the samples per frame come from the generator's upsample rates, not from ``hparams.hop_size``.
-``--model_name melgan`` / ``basis-melgan`` and ``--mixprecision 1`` exit: those generators have no parameter gradient
-here, and there is no mixed-precision path.
+``--model_name melgan`` trains with ``--stack_grad 1`` (``MelGANGenerator.stack_grad``: the backward of ResidualStack
+and of the reflection-padded edge convs) and exits without it; the flag is absent from the parsed arguments unless it
+is given.  ``--model_name basis-melgan`` and ``--mixprecision 1`` exit: that generator has no parameter gradient here,
+and there is no mixed-precision path.
 """
 import argparse
 import os
@@ -86,15 +88,22 @@ def build_parser():
     parser.add_argument("--valid_num", type=int, default=hp.valid_num)
     parser.add_argument("--use_mpd", type=int, default=0,
                         help="1: train Discriminator(use_mpd=True), HiFi-GAN's multi-period discriminator included")
+    parser.add_argument("--stack_grad", type=int, default=argparse.SUPPRESS,
+                        help="1: opt in to MelGAN's parameter gradient (--model_name melgan trains only with it)")
     return parser
 
 
 def check_args(args):
     """Exit, with one sentence that names what is missing, for what this loop does not train."""
-    if args.model_name in ("melgan", "basis-melgan"):
+    if args.model_name == "melgan" and getattr(args, "stack_grad", 0):
+        pass                                   # opted in: MelGANGenerator.stack_grad
+    elif args.model_name == "melgan":
+        sys.exit("MODE=train: --model_name melgan has no parameter gradient unless --stack_grad 1 opts in to the "
+                 "backward of ResidualStack; supported without it: " + ", ".join(SUPPORTED))
+    elif args.model_name == "basis-melgan":
         sys.exit(f"MODE=train: --model_name {args.model_name} cannot be trained here: the ResidualStack generators "
                  "(MelGAN, Basis-MelGAN) have no parameter gradient yet; supported: " + ", ".join(SUPPORTED))
-    if args.model_name not in SUPPORTED:
+    elif args.model_name not in SUPPORTED:
         sys.exit(f"MODE=train: --model_name must be one of {', '.join(SUPPORTED)}, got {args.model_name!r}")
     if args.mixprecision:
         sys.exit("MODE=train: --mixprecision 1 is not supported: there is no mixed-precision (apex amp) path, the "
@@ -196,7 +205,8 @@ def run(args):
     trainer = Trainer(model, discriminator, optimizer, discriminator_optimizer, scheduler, discriminator_scheduler,
                       pqmf, lambda_stft=lambda_stft, use_feature_map_loss=use_feature_map_loss,
                       discriminator_train_start_steps=args.discriminator_train_start_steps,
-                      grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm)
+                      grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm,
+                      stack_grad=bool(getattr(args, "stack_grad", 0)))
     spf = samples_per_frame(model, pqmf)
 
     print("Load data to buffer")

@@ -29,6 +29,14 @@
 // gen_dgrad_kernel<MT>: the transposed conv's data gradient as the GEMM [Cin] x [B Tin] over Cout k: the columns are
 // the flat positions q = b Tin + i, A = the forward's weight [Cin][Cout k] as it lies in memory, B the stride-s gather
 // g[b, co, i s + j - p].  One launch; every element one (co, j)-ordered chain, whatever the batch or the grid.
+//
+// The ReflectionPad1d convs of MelGAN (fv_conv1d_weight_grad_dilated_mode, fv_conv1d_input_grad_reflect): the pad is
+// never built.  gen_wgrad_kernel<MT, true> mirrors the staged position (i < 0 -> -i, i >= T -> 2 (T - 1) - i) where
+// the dilated read is resolved anyway; the <MT, false> instantiations are the zero-padding kernels, unchanged.
+// gen_dgrad_reflect_kernel<MT> is the GEMM [Cin] x [B T] over Cout k whose staged B operand of column i is the sum of
+// its one to three gathers g[b, co, p - j dil] over the padded positions p that the pad maps onto i: the straight one
+// p = i + pad, the left mirror p = pad - i (1 <= i <= pad) and the right mirror p = pad + 2 (T - 1) - i
+// (T - 1 - pad <= i <= T - 2), added in that order before the MFMA sees them.  One launch, no [B, C, T + 2 pad] tensor.
 #include <math.h>
 
 #include <type_traits>
@@ -120,8 +128,8 @@ struct GgWArgs {
     int x_tiles;            // column tiles of the GEMM (0: the bias alone); blocks beyond them sum the bias
 };
 
-// grid (x_tiles + (bias ? 1 : 0), ceil(M / MT), S)
-template <int MT>
+// grid (x_tiles + (bias ? 1 : 0), ceil(M / MT), S); REFLECT: the B source is read through a reflection pad (pad < TB)
+template <int MT, bool REFLECT = false>
 __global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
     using T = GgTile<MT>;
     __shared__ float as[MT * T::STR];
@@ -174,7 +182,11 @@ __global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
         }
 #pragma unroll
         for (int i = 0; i < kGgBRows; ++i) {
-            const int64_t pos = tb + b_pos[i];
+            int64_t pos = tb + b_pos[i];
+            if constexpr (REFLECT) {                      // one mirror is enough: pad < TB; a dead column stays outside
+                if (pos < 0) pos = -pos;
+                else if (pos >= a.TB) pos = 2 * ((int64_t)a.TB - 1) - pos;
+            }
             bs[(sr + 8 * i) * T::STR + sc] = (live && pos >= 0 && pos < a.TB) ? bb[(size_t)b_off[i] + pos] : 0.f;
         }
         __syncthreads();
@@ -257,6 +269,78 @@ __global__ __launch_bounds__(kGgThreads) void gen_dgrad_kernel(GgDArgs a) {
     }
 }
 
+struct GgRArgs {
+    const float* w;     // [Cin, Cout k]: the forward's weight [Cout, Cin, k] with its first two axes swapped
+    const float* g;     // [B, Cout, Tout]
+    float* dx;          // [B, Cin, T]
+    int64_t Q;          // B T
+    int Cin, Cout, T, Tout, k, dil, pad;
+};
+
+// grid (ceil(B T / 128), ceil(Cin / MT))
+template <int MT>
+__global__ __launch_bounds__(kGgThreads) void gen_dgrad_reflect_kernel(GgRArgs a) {
+    using T = GgTile<MT>;
+    __shared__ float as[MT * T::STR];
+    __shared__ float bs[kGgNT * T::STR];
+    const int tid = threadIdx.x, sc = tid & 31, sr = tid >> 5;
+    const int K = a.Cout * a.k, m0 = blockIdx.y * MT;
+    const int64_t q0 = (int64_t)blockIdx.x * kGgNT;
+    int64_t c_base[kGgBRows];                             // b Cout Tout
+    int c_pos[kGgBRows];                                  // x + pad: the padded position of the straight gather
+    int c_left[kGgBRows], c_right[kGgBRows];              // the mirrors' padded positions, kGgDead where there is none
+#pragma unroll
+    for (int i = 0; i < kGgBRows; ++i) {
+        const int64_t q = q0 + sr + 8 * i;
+        const int64_t b = q / a.T;
+        const bool in = q < a.Q;
+        const int x = (int)(q - b * a.T);
+        c_base[i] = in ? b * a.Cout * a.Tout : 0;
+        c_pos[i] = in ? x + a.pad : kGgDead;
+        c_left[i] = (in && x >= 1 && x <= a.pad) ? a.pad - x : kGgDead;
+        c_right[i] = (in && x >= a.T - 1 - a.pad && x <= a.T - 2) ? a.pad + 2 * (a.T - 1) - x : kGgDead;
+    }
+    T tile;
+    tile.init();
+    for (int kc = 0; kc < K; kc += kGgTK) {
+        const int kk = kc + sc;
+        const bool live = kk < K;
+        const int co = kk / a.k, jd = (kk - co * a.k) * a.dil;
+        const float* gr = a.g + (size_t)co * a.Tout;
+        __syncthreads();                                  // the previous tile's reads are done
+#pragma unroll
+        for (int i = 0; i < T::ARows; ++i) {
+            const int row = sr + 8 * i, m = m0 + row;
+            as[row * T::STR + sc] = (live && m < a.Cin) ? a.w[(size_t)m * K + kk] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < kGgBRows; ++i) {
+            const float* gb = gr + (size_t)c_base[i];
+            const int ps = c_pos[i] - jd, pl = c_left[i] - jd, pr = c_right[i] - jd;
+            float v = (live && ps >= 0 && ps < a.Tout) ? gb[ps] : 0.f;       // straight, left mirror, right mirror
+            if (live && pl >= 0 && pl < a.Tout) v += gb[pl];
+            if (live && pr >= 0 && pr < a.Tout) v += gb[pr];
+            bs[(sr + 8 * i) * T::STR + sc] = v;
+        }
+        __syncthreads();
+        tile.mma(as, bs);
+    }
+#pragma unroll
+    for (int h = 0; h < T::FN; ++h) {
+        const int64_t q = q0 + tile.col(h);
+        if (q >= a.Q) continue;
+        const int64_t b = q / a.T;
+        float* out = a.dx + (size_t)b * a.Cin * a.T + (q - b * a.T);
+#pragma unroll
+        for (int f = 0; f < T::FM; ++f)
+#pragma unroll
+            for (int e = 0; e < T::NE; ++e) {
+                const int m = m0 + tile.row(f, e);
+                if (m < a.Cin) out[(size_t)m * a.T] = tile.acc[f][h][e];
+            }
+    }
+}
+
 // ---- the elementwise steps of the walk ----
 // the adjoint of y = tanh(z): g (1 - y y)
 __global__ __launch_bounds__(256) void tanh_grad_kernel(const float* __restrict__ g, const float* __restrict__ y,
@@ -302,7 +386,7 @@ static void gg_wgrad_plan(int B, int M, int64_t N, int TR, int Cbias, GgWPlan* p
 }
 
 static int gg_wgrad_run(const GgWPlan& p, GgWArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes,
-                        const char* who, hipStream_t st) {
+                        const char* who, hipStream_t st, bool reflect = false) {
     const size_t need = sizeof(float) * (size_t)p.S * (size_t)p.R;
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
         return fail(FV_ERR_INVALID_ARG, "%s: workspace of %zu bytes, needs %zu (4-byte aligned)", who, workspace_bytes,
@@ -315,11 +399,20 @@ static int gg_wgrad_run(const GgWPlan& p, GgWArgs a, float* dw, float* db, void*
     a.x_tiles = dw ? p.bx : 0;
     if (!db) a.bias_src = nullptr;
     const dim3 grid((unsigned)(a.x_tiles + (db ? 1 : 0)), (unsigned)(dw ? p.by : 1), (unsigned)p.S);
-    switch (p.MT) {
-    case 128: hipLaunchKernelGGL(gen_wgrad_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
-    case 64: hipLaunchKernelGGL(gen_wgrad_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
-    case 32: hipLaunchKernelGGL(gen_wgrad_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(gen_wgrad_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
+    if (reflect) {
+        switch (p.MT) {
+        case 128: hipLaunchKernelGGL((gen_wgrad_kernel<128, true>), grid, dim3(kGgThreads), 0, st, a); break;
+        case 64: hipLaunchKernelGGL((gen_wgrad_kernel<64, true>), grid, dim3(kGgThreads), 0, st, a); break;
+        case 32: hipLaunchKernelGGL((gen_wgrad_kernel<32, true>), grid, dim3(kGgThreads), 0, st, a); break;
+        default: hipLaunchKernelGGL((gen_wgrad_kernel<16, true>), grid, dim3(kGgThreads), 0, st, a); break;
+        }
+    } else {
+        switch (p.MT) {
+        case 128: hipLaunchKernelGGL(gen_wgrad_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
+        case 64: hipLaunchKernelGGL(gen_wgrad_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
+        case 32: hipLaunchKernelGGL(gen_wgrad_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
+        default: hipLaunchKernelGGL(gen_wgrad_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
+        }
     }
     FV_HIP(hipGetLastError());
     return launch_wgrad_combine(a.ws, dw, db, p.R - a.Cbias, a.Cbias, p.R, p.S, st);
@@ -340,6 +433,14 @@ static int dilated_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int dil,
         return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: a map of %lld x %d samples is too long",
                     (long long)big, Tin);
     gg_wgrad_plan(B, Cout, (int64_t)Cin * k, (int)Tout, Cout, p);
+    return 0;
+}
+
+static int dilated_mode_check(const char* who, int Tin, int pad, int pad_mode) {
+    if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
+        return fail(FV_ERR_INVALID_ARG, "%s: pad_mode=%d (FV_PAD_ZERO or FV_PAD_REFLECT)", who, pad_mode);
+    if (pad_mode == FV_PAD_REFLECT && pad >= Tin)
+        return fail(FV_ERR_INVALID_ARG, "%s: a reflection pad of %d needs more than %d samples", who, pad, Tin);
     return 0;
 }
 
@@ -379,11 +480,27 @@ int64_t fv_conv1d_weight_grad_dilated_workspace_bytes(int B, int Cin, int Cout, 
     return (int64_t)sizeof(float) * p.S * p.R;
 }
 
+int64_t fv_conv1d_weight_grad_dilated_mode_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad,
+                                                           int pad_mode) {
+    GgWPlan p;
+    if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
+    if (int rc = dilated_mode_check("conv1d_weight_grad_dilated_mode", Tin, pad, pad_mode)) return rc;
+    return (int64_t)sizeof(float) * p.S * p.R;
+}
+
 int fv_conv1d_weight_grad_dilated(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
                                   int Tin, int k, int dil, int pad, void* workspace, size_t workspace_bytes,
                                   void* stream) {
+    return fv_conv1d_weight_grad_dilated_mode(g_pre, xa, dw, db, B, Cin, Cout, Tin, k, dil, pad, FV_PAD_ZERO, workspace,
+                                              workspace_bytes, stream);
+}
+
+int fv_conv1d_weight_grad_dilated_mode(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin,
+                                       int Cout, int Tin, int k, int dil, int pad, int pad_mode, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
     GgWPlan p;
     if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
+    if (int rc = dilated_mode_check("conv1d_weight_grad_dilated_mode", Tin, pad, pad_mode)) return rc;
     if (!g_pre || !xa || (!dw && !db) || dw == g_pre || dw == xa || db == g_pre || db == xa)
         return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: null tensor, or a result aliases an input");
     const int Tout = Tin + 2 * pad - dil * (k - 1);
@@ -402,7 +519,52 @@ int fv_conv1d_weight_grad_dilated(const float* g_pre, const float* xa, float* dw
     a.Cbias = Cout;
     a.Tbias = Tout;
     a.bias_scale = 1;
-    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, "conv1d_weight_grad_dilated", (hipStream_t)stream);
+    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, "conv1d_weight_grad_dilated", (hipStream_t)stream,
+                        pad_mode == FV_PAD_REFLECT);
+}
+
+int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, int B, int Cin, int Cout, int Tin, int k,
+                                 int dil, int pad, void* stream) {
+    const char* who = "conv1d_input_grad_reflect";
+    if (Cin < 1 || Cout < 1 || k < 1 || dil < 1 || (int64_t)Cin * Cout * k >= (int64_t)1 << 31 ||
+        (int64_t)Cout * k >= (int64_t)1 << 30 || (Cin + 15) / 16 > 65535)
+        return fail(FV_ERR_UNSUPPORTED, "%s: Cin=%d Cout=%d k=%d dil=%d", who, Cin, Cout, k, dil);
+    if (B <= 0 || B > 65535 || Tin < 1 || pad < 0)
+        return fail(FV_ERR_INVALID_ARG, "%s: B=%d, Tin=%d or pad=%d", who, B, Tin, pad);
+    if (pad >= Tin) return fail(FV_ERR_INVALID_ARG, "%s: a reflection pad of %d needs more than %d samples", who, pad, Tin);
+    const int64_t Tout = (int64_t)Tin + 2 * (int64_t)pad - (int64_t)dil * (k - 1);
+    if (Tout < 1)
+        return fail(FV_ERR_INVALID_ARG, "%s: empty output (Tin=%d pad=%d k=%d dil=%d)", who, Tin, pad, k, dil);
+    const int64_t big = Cin > Cout ? Cin : Cout;
+    if (big * ((int64_t)Tin + 2 * (int64_t)pad) >= (int64_t)1 << 30 || (int64_t)dil * (k - 1) >= (int64_t)1 << 30)
+        return fail(FV_ERR_INVALID_ARG, "%s: a map of %lld x %d samples is too long", who, (long long)big, Tin);
+    if (!g || !wt || !dxa || dxa == g || dxa == wt)
+        return fail(FV_ERR_INVALID_ARG, "%s: null tensor, or the result aliases an input", who);
+    GgRArgs a{};
+    a.w = wt;
+    a.g = g;
+    a.dx = dxa;
+    a.Q = (int64_t)B * Tin;
+    a.Cin = Cin;
+    a.Cout = Cout;
+    a.T = Tin;
+    a.Tout = (int)Tout;
+    a.k = k;
+    a.dil = dil;
+    a.pad = pad;
+    const int MT = gg_rows(Cin);
+    const int64_t gx = (a.Q + kGgNT - 1) / kGgNT;
+    if (gx > 0x7fffffff) return fail(FV_ERR_INVALID_ARG, "%s: B Tin = %lld", who, (long long)a.Q);
+    const dim3 grid((unsigned)gx, (unsigned)((Cin + MT - 1) / MT));
+    const hipStream_t st = (hipStream_t)stream;
+    switch (MT) {
+    case 128: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
+    case 64: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
+    case 32: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
+    default: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
+    }
+    FV_HIP(hipGetLastError());
+    return 0;
 }
 
 int fv_conv_transpose1d_input_grad(const float* g, const float* w, float* dxa, int B, int Cin, int Cout, int Tin, int k,

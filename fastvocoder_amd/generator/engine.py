@@ -82,8 +82,9 @@ def param_store(conv, params, need, at, dw, db, out):
 
 
 class NoParameterGrad:
-    """Mix-in of the generators without a parameter gradient (MelGAN, Basis-MelGAN): ``parameter_grad`` reads False,
-    and setting it raises."""
+    """Mix-in of the MelGAN-trunk generators: ``parameter_grad`` reads False, and setting it raises.  Basis-MelGAN keeps
+    it as it is; ``MelGANGenerator`` overrides it with a property that takes True once ``stack_grad = True`` has opted
+    in to the backward of ResidualStack (generator/stack_grad.py)."""
 
     @property
     def parameter_grad(self):

@@ -11,6 +11,7 @@ it is a parameter container only -- calls go through native plans.
 import torch
 
 from .. import _native
+from . import stack_grad as _stack_grad
 from .engine import NativeModule, NoParameterGrad, POST_NONE, POST_RELU, POST_TANH, SLOT_IN, SLOT_OUT, SLOT_OUT2  # noqa: F401
 from .modules import (BasisSignalLayer, LastLayer, LastLinear, ResidualStack, UpsampleLayer,
                       _activation_slope, _pad_mode)
@@ -90,6 +91,41 @@ class _MelGANTrunk(NoParameterGrad, NativeModule):
 class MelGANGenerator(_MelGANTrunk):
     """Drop-in for the reference ``MelGANGenerator``."""
 
+    _stack_grad = False
+    _parameter_grad = False
+
+    @property
+    def stack_grad(self):
+        """Default False: nothing changes, ``parameter_grad = True`` raises as it always did.  True opts in to the
+        backward of ResidualStack and of the two reflection-padded edge convs (generator/stack_grad.py), after which
+        ``parameter_grad`` can be set and read like HiFiGANGenerator's.  Setting True raises NotImplementedError for
+        ``use_causal_conv=True`` and for an activation / pad other than LeakyReLU / ReflectionPad1d."""
+        return self._stack_grad
+
+    @stack_grad.setter
+    def stack_grad(self, value):
+        if value:
+            _stack_grad.check_supported(self)
+        else:
+            self._parameter_grad = False
+        self._stack_grad = bool(value)
+
+    @property
+    def parameter_grad(self):
+        """As ``HiFiGANGenerator.parameter_grad``, once ``stack_grad = True`` has opted in: with True, grad enabled and
+        a conv parameter requiring grad, ``forward`` runs the training forward conv by conv on the exact-fp32 kernels
+        and ``backward`` accumulates into the parameters' ``.grad``.  The mel is a constant."""
+        return self._parameter_grad
+
+    @parameter_grad.setter
+    def parameter_grad(self, value):
+        if value and not self._stack_grad:
+            raise NotImplementedError(
+                f"{type(self).__name__} has no parameter gradient unless it is opted in: the backward of ResidualStack "
+                "and of the reflection-padded edge convs runs only after `stack_grad = True` (set it first, then "
+                "parameter_grad)")
+        self._parameter_grad = bool(value)
+
     def __init__(self, in_channels=80, out_channels=1, kernel_size=7,
                  channels=[512, 256, 128, 64, 32], bias=True, upsample_scales=[10, 6, 2, 2],
                  stack_kernel_size=3, stacks=3, nonlinear_activation="LeakyReLU",
@@ -97,6 +133,7 @@ class MelGANGenerator(_MelGANTrunk):
                  pad_params={}, use_final_nonlinear_activation=True, use_weight_norm=True,
                  use_causal_conv=False):
         super().__init__()
+        self._config = dict(use_causal_conv=bool(use_causal_conv), nonlinear_activation=nonlinear_activation, pad=pad)
         layers = self._build_layers(in_channels, kernel_size, channels, bias, upsample_scales,
                                     stack_kernel_size, stacks, nonlinear_activation,
                                     nonlinear_activation_params, pad, pad_params, use_causal_conv)
@@ -117,6 +154,8 @@ class MelGANGenerator(_MelGANTrunk):
 
     def forward(self, c):
         """c [B,in_channels,T] -> [B, T*prod(upsample_scales)] (channel 0)."""
+        if self._parameter_grad and _stack_grad.wants_param_grad(self):
+            return _stack_grad.run(self, c)[:, 0, :]
         return self._run(self._prepare(c))[:, 0, :]
 
     def _minus_plan(self, T):

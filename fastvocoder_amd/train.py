@@ -12,8 +12,10 @@ The scalars of a step stay on the device until its end and are read with one cop
 five times, ``.item()`` each).  (The backward of the discriminator terms still reads its incoming coefficient on the
 host, as it does outside this loop: loss/discriminator_loss.py.)
 
-MelGAN, Basis-MelGAN and the ``transposedconv: False`` upsampler have no parameter gradient and are refused where the
-``parameter_grad`` attribute refuses them; mixed precision is not part of this loop.
+MelGAN trains with ``Trainer(..., stack_grad=True)``, which sets the generator's ``stack_grad`` opt-in before
+``parameter_grad``; without the keyword it is refused as before.  Basis-MelGAN and the ``transposedconv: False``
+upsampler have no parameter gradient and are refused where the ``parameter_grad`` attribute refuses them; mixed
+precision is not part of this loop.
 """
 import torch
 
@@ -24,10 +26,14 @@ KEYS = ("stft", "total", "adversarial", "feature_map", "discriminator", "grad_no
 
 
 def samples_per_frame(model, pqmf=None):
-    """Waveform samples the generator makes of one mel frame: the product of its upsample rates, times the sub-band
-    count when its output goes through a PQMF synthesis."""
+    """Waveform samples the generator makes of one mel frame: the product of its upsample rates (the strides of
+    ``model.ups``, or of the trunk's ConvTranspose1d layers for a generator without ``ups``), times the sub-band count
+    when its output goes through a PQMF synthesis."""
+    ups = getattr(model, "ups", None)
+    if ups is None:
+        ups = [m for m in model.modules() if isinstance(m, torch.nn.ConvTranspose1d)]
     n = 1
-    for up in model.ups:
+    for up in ups:
         n *= int(up.stride[0])
     return n * (int(pqmf.subbands) if pqmf is not None else 1)
 
@@ -44,11 +50,13 @@ def fit_estimate(est, n, pqmf=None):
 class Trainer:
     def __init__(self, model, discriminator, optimizer, discriminator_optimizer, scheduler=None,
                  discriminator_scheduler=None, pqmf=None, *, lambda_stft, use_feature_map_loss,
-                 discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0):
+                 discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0, stack_grad=False):
         for opt, name in ((optimizer, "optimizer"), (discriminator_optimizer, "discriminator_optimizer")):
             if not isinstance(opt, Adam):
                 raise TypeError(f"{name} must be a fastvocoder_amd.optim.Adam (its step clips and updates in three "
                                 f"launches), got {type(opt).__name__}")
+        if stack_grad and hasattr(type(model), "stack_grad"):
+            model.stack_grad = True           # MelGAN's opt-in; raises for the graphs whose backward is missing
         model.parameter_grad = True           # raises for the generators that have no parameter gradient
         self.model, self.discriminator = model, discriminator
         self.optimizer, self.discriminator_optimizer = optimizer, discriminator_optimizer

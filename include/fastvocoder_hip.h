@@ -31,6 +31,9 @@ extern "C" {
 #endif
 
 #define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad; 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
+/* Entry points are added under one version number: 18 also covers the gradient, optimizer and training entries that
+ * came after fv_stft_distance_grad, the latest being fv_conv1d_weight_grad_dilated_mode and
+ * fv_conv1d_input_grad_reflect (MelGAN's parameter gradient).  No existing entry changed its signature or its result. */
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -927,6 +930,34 @@ int fv_tanh_grad(const float* g, const float* y, float* out, int64_t n, void* st
 int fv_residual_merge_grad(const float* g_y, const float* d, const float* x, const float* acc, float* out, int64_t n,
                            float slope, void* stream);
 int fv_grad_div(const float* g, float* out, int64_t n, float div, void* stream);
+
+/*
+ * The convs behind a ReflectionPad1d (MelGAN's ResidualStack, model/generator/modules.py:320-382, and its two k = 7 edge
+ * convs, melgan.py:61-63 and modules.py:76-89); additions of ABI 18, no existing entry changes.  The padded tensor is
+ * never built.  With r(i) = -i for i < 0, 2 (T - 1) - i for i >= T and i otherwise (T = Tin, pad < Tin):
+ *
+ * fv_conv1d_weight_grad_dilated_mode: fv_conv1d_weight_grad_dilated with a pad_mode, FV_PAD_ZERO (the same kernels, the
+ * same bits as that entry) or FV_PAD_REFLECT:
+ *     dw[co, ci, j] = sum_{b, t} g_pre[b, co, t] * xa[b, ci, r(t + j dil - pad)],   db[co] = sum_{b, t} g_pre[b, co, t]
+ * The mirrored index is resolved while the operand is staged, where the dilated read is resolved.  Error codes as
+ * fv_conv1d_weight_grad_dilated; another pad_mode, or FV_PAD_REFLECT with pad >= Tin, returns FV_ERR_INVALID_ARG.
+ *
+ * fv_conv1d_input_grad_reflect: the data gradient of y = conv(reflection_pad(xa, pad), W, dil) in one launch,
+ *     dxa[b, ci, i] = sum_{p in [0, T + 2 pad), r(p - pad) = i} sum_{co, j} W[co, ci, j] * g[b, co, p - j dil]
+ * (g [B,Cout,Tout], Tout = Tin + 2 pad - dil (k - 1), read as 0 outside [0, Tout)); wt [Cin,Cout,k] is the forward's
+ * folded weight with its first two axes swapped; dxa [B,Cin,Tin], all of it written.  The GEMM [Cin] x [B Tin] over
+ * Cout k whose operand of column i is the sum of its gathers in the fixed order straight (p = i + pad), left mirror
+ * (p = pad - i, 1 <= i <= pad), right mirror (p = pad + 2 (T - 1) - i, T - 1 - pad <= i <= T - 2): each element one
+ * (co, j)-ordered fmaf chain, a row's values do not depend on B or on the grid.  pad >= Tin, Tout < 1, a null pointer
+ * or a result aliasing an input returns FV_ERR_INVALID_ARG.
+ */
+int64_t fv_conv1d_weight_grad_dilated_mode_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad,
+                                                           int pad_mode);
+int fv_conv1d_weight_grad_dilated_mode(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin,
+                                       int Cout, int Tin, int k, int dil, int pad, int pad_mode, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, int B, int Cin, int Cout, int Tin, int k,
+                                 int dil, int pad, void* stream);
 
 /*
  * Gradient clipping and the Adam update of a whole parameter set (nn.utils.clip_grad_norm_ + Adam.step() of
