@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "optim.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "basis_grad.hip", "optim.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -24,7 +24,7 @@ SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_
           [f"conv_inst_s{i}.hip" for i in range(6)]
 HEADERS = ["fv_internal.h", "conv_kernels.hpp", "pair_kernels.hpp", "pair_inst.hpp", "pairh_kernels.hpp",
            "pairh_inst.hpp", "convh_kernels.hpp", "convh_inst.hpp", "convr_kernels.hpp",
-           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp"]
+           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp", "basis_grad_host.hpp"]
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)
@@ -285,6 +285,12 @@ def lib():
     L.fv_tanh_grad.argtypes = [vp, vp, vp, i64, vp]
     L.fv_residual_merge_grad.argtypes = [vp, vp, vp, vp, vp, i64, f, vp]
     L.fv_grad_div.argtypes = [vp, vp, i64, f, vp]
+    L.fv_basis_head_forward.argtypes = [vp, vp, i, i, i, vp]
+    L.fv_basis_head_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
+    L.fv_basis_weight_l1_workspace_bytes.argtypes = [i, i, i]
+    L.fv_basis_weight_l1_workspace_bytes.restype = i64
+    L.fv_basis_weight_l1.argtypes = [vp, vp, vp, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_basis_weight_l1_grad.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     L.fv_grad_sq_norm_workspace_bytes.argtypes = [i64]
     L.fv_grad_sq_norm_workspace_bytes.restype = i64
     L.fv_grad_sq_norm.argtypes = [vp, vp, i, i64, f, vp, ctypes.c_size_t, vp, vp]
@@ -1699,6 +1705,78 @@ def grad_div(g, div):
     with _on(g, out) as stream:
         check(lib().fv_grad_div(_ptr(g, "g"), _ptr(out), g.numel(), float(div), stream))
     return out
+
+
+# ---------------------------------------------------------------------------
+# the head of Basis-MelGAN for training (csrc/basis_grad.hip)
+# ---------------------------------------------------------------------------
+
+def _basis_rows(name, Y):
+    if Y.dim() != 3 or Y.shape[0] < 2:
+        raise NativeError(f"{name}: Y [B+1,C,F] with the zero-mel row last expected, got {tuple(Y.shape)}")
+    return Y.shape[0] - 1, Y.shape[1], Y.shape[2]
+
+
+def basis_head_forward(Y):
+    """Y [B+1,C,F], the trunk's raw output with the zero-mel row last -> D [B,C,F] = relu(Y[b]) - relu(Y[B])
+    (fv_basis_head_forward, one launch)."""
+    B, c, F = _basis_rows("basis_head_forward", Y)
+    D = torch.empty((B, c, F), dtype=torch.float32, device=Y.device)
+    with _on(Y, D) as stream:
+        check(lib().fv_basis_head_forward(_ptr(Y, "Y"), _ptr(D), B, c, F, stream))
+    return D
+
+
+def basis_head_grad(g_est, g_w, Y, basis):
+    """The adjoint of the head in one launch (fv_basis_head_grad): g_est [B, F L/2] or None, g_w [B,C,F] (the cotangent
+    of weight in D's storage) or None, Y [B+1,C,F], basis [L,C] -> g_Y [B+1,C,F]."""
+    B, c, F = _basis_rows("basis_head_grad", Y)
+    if basis.dim() != 2 or basis.shape[1] != c:
+        raise NativeError(f"basis_head_grad: basis [L,{c}] expected, got {tuple(basis.shape)}")
+    L_ = basis.shape[0]
+    if g_est is not None and tuple(g_est.shape) != (B, F * (L_ // 2)):
+        raise NativeError(f"basis_head_grad: g_est {(B, F * (L_ // 2))} expected, got {tuple(g_est.shape)}")
+    if g_w is not None and tuple(g_w.shape) != (B, c, F):
+        raise NativeError(f"basis_head_grad: g_w {(B, c, F)} expected, got {tuple(g_w.shape)}")
+    g_Y = torch.empty_like(Y)
+    with _on(g_est, g_w, Y, basis, g_Y) as stream:
+        check(lib().fv_basis_head_grad(_ptr(g_est, "g_est", True), _ptr(g_w, "g_w", True), _ptr(Y, "Y"),
+                                       _ptr(basis, "basis"), _ptr(g_Y), B, c, F, L_, stream))
+    return g_Y
+
+
+def _basis_l1_shapes(name, D, target):
+    if D.dim() != 3 or target.dim() != 3 or tuple(target.shape) != (D.shape[0], D.shape[2], D.shape[1]):
+        raise NativeError(f"{name}: D [B,C,F] and target [B,F,C] expected, got {tuple(D.shape)} and {tuple(target.shape)}")
+    return D.shape
+
+
+def basis_weight_l1(D, target):
+    """D [B,C,F] against target [B,F,C] -> two device floats, (mean |D^T - target|, mean D) (fv_basis_weight_l1, two
+    launches)."""
+    B, c, F = _basis_l1_shapes("basis_weight_l1", D, target)
+    nbytes = lib().fv_basis_weight_l1_workspace_bytes(B, c, F)
+    if nbytes < 0:
+        check(int(nbytes))
+    workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=D.device)
+    out = torch.empty(2, dtype=torch.float32, device=D.device)
+    with _on(D, target, workspace, out) as stream:
+        check(lib().fv_basis_weight_l1(_ptr(D, "D"), _ptr(target, "target"), _ptr(out), B, c, F, workspace.data_ptr(),
+                                       workspace.numel() * 8, stream))
+    return out
+
+
+def basis_weight_l1_grad(D, target, coef=None):
+    """coef * sign(D^T - target) / (B F C) in D's [B,C,F] storage (fv_basis_weight_l1_grad, one launch); coef: a
+    one-element device tensor, or None for 1."""
+    B, c, F = _basis_l1_shapes("basis_weight_l1_grad", D, target)
+    if coef is not None and coef.numel() != 1:
+        raise NativeError(f"basis_weight_l1_grad: coef of one element expected, got {tuple(coef.shape)}")
+    g = torch.empty_like(D)
+    with _on(D, target, coef, g) as stream:
+        check(lib().fv_basis_weight_l1_grad(_ptr(D, "D"), _ptr(target, "target"), _ptr(coef, "coef", True), _ptr(g), B, c,
+                                            F, stream))
+    return g
 
 
 # ---------------------------------------------------------------------------

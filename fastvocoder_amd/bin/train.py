@@ -1,10 +1,12 @@
 """``MODE=train``: the reference's bin/train.py for the generators that have a parameter gradient, HiFi-GAN,
-Multiband-HiFi-GAN and (opted in with ``--stack_grad 1``) MelGAN, on the MI355X kernels: ``train.Trainer`` runs the
+Multiband-HiFi-GAN and (opted in with ``--stack_grad 1`` / ``--basis_grad 1``) MelGAN and Basis-MelGAN, on the MI355X
+kernels: ``train.Trainer`` runs the
 step, ``optim.Adam`` clips and updates in three launches, ``data.BatchIterator`` cuts the crops.
 
 ``run_train()`` takes the reference's arguments (train.py:478-499) and, for a test or a short run, ``--max_steps``,
 ``--seed``, ``--batch_size``, ``--fixed_length``, ``--discriminator_train_start_steps``, ``--log_step``,
-``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams), ``--use_mpd`` and ``--stack_grad``.
+``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams), ``--use_mpd``, ``--stack_grad``, ``--basis_grad``
+and ``--basis_dataset_path``.
 ``lamda_stft`` (sic) and ``use_feature_map_loss`` come from the yaml, as there.  Both optimizers are
 ``Adam(lr, eps=1e-6)``; ``--use_scheduler 1`` adds ``CosineAnnealingLR(T_max=2500, eta_min=lr / 10)`` to both.
 
@@ -23,8 +25,15 @@ number of utterances scored (the reference scores ``valid_num + 1`` and divides 
 index order; the samples per frame come from the generator's upsample rates, not from ``hparams.hop_size``.
 ``--model_name melgan`` trains with ``--stack_grad 1`` (``MelGANGenerator.stack_grad``: the backward of ResidualStack
 and of the reflection-padded edge convs) and exits without it; the flag is absent from the parsed arguments unless it
-is given.  ``--model_name basis-melgan`` and ``--mixprecision 1`` exit: that generator has no parameter gradient here,
-and there is no mixed-precision path.
+is given.  ``--model_name basis-melgan`` trains with ``--basis_grad 1`` (``BasisMelGANGenerator.basis_grad``) and exits
+without it, ``--stack_grad 1`` or not.  Its flow is the reference's (train.py:297-331, 390-466): the basis comes from
+``<basis_dataset_path>/basis_signal_weight.npy`` [L, C] (``--basis_dataset_path``, ``Basis-MelGAN-dataset`` when absent;
+a resumed checkpoint's ``basis_signal.layer.weight`` wins), the target weights from ``<basis_dataset_path>/weight/``
+(data.load_data_to_buffer), the optimizer covers ``model.melgan.parameters()`` only -- the basis is frozen and gets no
+gradient --, the validation scores ``model(mel)[0]``, the log line's "Weight Loss" is filled and the ``weight_loss`` and
+``weight_average_value`` scalars are written.  A missing basis or weight file ends the run with one sentence that
+names the path.  Both flags are absent from the parsed arguments unless given.  ``--mixprecision 1`` exits: there is no
+mixed-precision path.
 """
 import argparse
 import os
@@ -37,7 +46,7 @@ import torch
 import yaml
 
 from .. import hparams as hp
-from ..data import BatchIterator, load_data_to_buffer
+from ..data import BatchIterator, MissingWeightFile, load_data_to_buffer
 from ..discriminator import Discriminator
 from ..generator import PQMF
 from ..optim import Adam
@@ -90,6 +99,10 @@ def build_parser():
                         help="1: train Discriminator(use_mpd=True), HiFi-GAN's multi-period discriminator included")
     parser.add_argument("--stack_grad", type=int, default=argparse.SUPPRESS,
                         help="1: opt in to MelGAN's parameter gradient (--model_name melgan trains only with it)")
+    parser.add_argument("--basis_grad", type=int, default=argparse.SUPPRESS,
+                        help="1: opt in to Basis-MelGAN's parameter gradient (--model_name basis-melgan trains only with it)")
+    parser.add_argument("--basis_dataset_path", type=str, default=argparse.SUPPRESS,
+                        help="directory of basis_signal_weight.npy and weight/ (default: Basis-MelGAN-dataset)")
     return parser
 
 
@@ -100,6 +113,8 @@ def check_args(args):
     elif args.model_name == "melgan":
         sys.exit("MODE=train: --model_name melgan has no parameter gradient unless --stack_grad 1 opts in to the "
                  "backward of ResidualStack; supported without it: " + ", ".join(SUPPORTED))
+    elif args.model_name == "basis-melgan" and getattr(args, "basis_grad", 0):
+        pass                                   # opted in: BasisMelGANGenerator.basis_grad
     elif args.model_name == "basis-melgan":
         sys.exit(f"MODE=train: --model_name {args.model_name} cannot be trained here: the ResidualStack generators "
                  "(MelGAN, Basis-MelGAN) have no parameter gradient yet; supported: " + ", ".join(SUPPORTED))
@@ -129,6 +144,20 @@ def _summary_writer(path):
     return SummaryWriter(path)
 
 
+def load_basis(model, path):
+    """``basis_signal_weight.npy`` [L, C] into the model's basis layer; exits with the path when it is missing or has
+    another shape."""
+    if not os.path.isfile(path):
+        sys.exit(f"MODE=train: the basis {path} does not exist (--basis_dataset_path names the directory that holds "
+                 "basis_signal_weight.npy and weight/)")
+    value = torch.from_numpy(np.ascontiguousarray(np.load(path), dtype=np.float32))
+    weight = model.basis_signal.layer.weight
+    if value.shape != weight.shape:
+        sys.exit(f"MODE=train: the basis {path} is {tuple(value.shape)}, the model's is {tuple(weight.shape)} (L, C)")
+    with torch.no_grad():
+        weight.copy_(value)
+
+
 def validate(model, vocoder_loss, pqmf, buffer, valid_num, device, spf):
     """(mean STFT loss, utterances scored) over the first ``valid_num`` whole utterances, under no_grad."""
     losses = []
@@ -139,7 +168,9 @@ def validate(model, vocoder_loss, pqmf, buffer, valid_num, device, spf):
                 continue
             mel = item["mel"][:frames].to(device).t().unsqueeze(0).contiguous()
             wav = item["wav"][:frames * spf].to(device).unsqueeze(0).contiguous()
-            losses.append(vocoder_loss(fit_estimate(model(mel), wav.shape[1], pqmf), wav, pqmf=pqmf)[0].reshape(()))
+            est = model(mel)
+            est = est[0] if isinstance(est, tuple) else est          # Basis-MelGAN: (est, weight)
+            losses.append(vocoder_loss(fit_estimate(est, wav.shape[1], pqmf), wav, pqmf=pqmf)[0].reshape(()))
         if not losses:
             return float("nan"), 0
         return float(torch.stack(losses).mean()), len(losses)
@@ -154,6 +185,10 @@ def run(args):
     use_feature_map_loss = config["use_feature_map_loss"]
     print(f"Loading Model of {args.model_name}...")
     model = build_generator(args.model_name, config).to(device)
+    basis = args.model_name == "basis-melgan"
+    basis_dir = getattr(args, "basis_dataset_path", "Basis-MelGAN-dataset")
+    if basis:
+        load_basis(model, os.path.join(basis_dir, "basis_signal_weight.npy"))
     pqmf = PQMF().to(device) if config["multiband"] else None
 
     # the checkpoint first: it decides which discriminator is built
@@ -173,7 +208,9 @@ def run(args):
     discriminator = Discriminator(use_mpd=use_mpd).to(device)
     print(f"Number of Parameters: {sum(p.numel() for p in model.parameters())}")
 
-    optimizer = Adam(model.parameters(), lr=args.learning_rate, eps=1.0e-6, weight_decay=0.0)
+    # Basis-MelGAN: the trunk alone; the basis is frozen (reference train.py:329-331)
+    optimizer = Adam((model.melgan if basis else model).parameters(), lr=args.learning_rate, eps=1.0e-6,
+                     weight_decay=0.0)
     discriminator_optimizer = Adam(discriminator.parameters(), lr=args.learning_rate_discriminator, eps=1.0e-6,
                                    weight_decay=0.0)
     if checkpoint is not None:
@@ -206,12 +243,17 @@ def run(args):
                       pqmf, lambda_stft=lambda_stft, use_feature_map_loss=use_feature_map_loss,
                       discriminator_train_start_steps=args.discriminator_train_start_steps,
                       grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm,
-                      stack_grad=bool(getattr(args, "stack_grad", 0)))
+                      stack_grad=bool(getattr(args, "stack_grad", 0)), basis_grad=bool(getattr(args, "basis_grad", 0)))
     spf = samples_per_frame(model, pqmf)
 
     print("Load data to buffer")
-    batches = BatchIterator(load_data_to_buffer(args.audio_index_path, args.mel_index_path), args.batch_size,
-                            args.fixed_length, spf, seed=args.seed, name="train")
+    try:
+        train_buffer = load_data_to_buffer(args.audio_index_path, args.mel_index_path,
+                                           weight_dir=os.path.join(basis_dir, "weight") if basis else None)
+    except MissingWeightFile as e:                 # Basis-MelGAN's weight/ alone; other missing files raise as before
+        sys.exit(f"MODE=train: {e}")
+    batches = BatchIterator(train_buffer, args.batch_size, args.fixed_length, spf, seed=args.seed, name="train",
+                            basis_L=model.L if basis else None)
     print("Load valid data to buffer")
     valid_buffer = load_data_to_buffer(args.audio_index_valid_path, args.mel_index_valid_path)
     if len(batches) < 1:
@@ -224,12 +266,12 @@ def run(args):
     step_times = []
     done = 0
     for epoch in range(hp.epochs):
-        for i, (mel, wav) in enumerate(batches.epoch()):
+        for i, (mel, wav, *weight) in enumerate(batches.epoch()):
             current_step = i + args.restore_step + epoch * len(batches) + 1
             step_start = time.perf_counter()
             mel = mel.to(device).transpose(1, 2).contiguous()
             wav = wav.to(device)
-            out = trainer.step(mel, wav, current_step)
+            out = trainer.step(mel, wav, current_step, *(w.to(device) for w in weight))
             s_l, t_l = out["stft"], out["total"]
             with open(os.path.join(current_logger_path, "total_loss.txt"), "a") as f:
                 f.write(str(t_l) + "\n")
@@ -243,7 +285,8 @@ def run(args):
                     lrs = scheduler.get_last_lr()[-1], discriminator_scheduler.get_last_lr()[-1]
                 now = time.perf_counter()
                 mean_time = float(np.mean(step_times)) if step_times else now - step_start
-                lines = format_log_lines(epoch, hp.epochs, current_step, total_step, s_l, 0., t_l, out["adversarial"],
+                lines = format_log_lines(epoch, hp.epochs, current_step, total_step, s_l, out.get("weight", 0.), t_l,
+                                         out["adversarial"],
                                          out["discriminator"], out["feature_map"], *lrs)
                 lines.append(format_time_line(now - start, (total_step - current_step) * mean_time))
                 print("\n" + "\n".join(lines), flush=True)
@@ -254,6 +297,10 @@ def run(args):
                                        ("discriminator_loss", out["discriminator"]),
                                        ("feature_map_loss", out["feature_map"]), ("grad_norm", out["grad_norm"])):
                         writer.add_scalar(tag, value, global_step=current_step)
+                    if basis:
+                        writer.add_scalar("weight_loss", out["weight"], global_step=current_step)
+                        writer.add_scalar("weight_average_value", round(out["weight_average"], 6),
+                                          global_step=current_step)
                     if scheduler is not None:
                         writer.add_scalar("learning_rate", lrs[0], global_step=current_step)
 

@@ -82,9 +82,10 @@ def param_store(conv, params, need, at, dw, db, out):
 
 
 class NoParameterGrad:
-    """Mix-in of the MelGAN-trunk generators: ``parameter_grad`` reads False, and setting it raises.  Basis-MelGAN keeps
-    it as it is; ``MelGANGenerator`` overrides it with a property that takes True once ``stack_grad = True`` has opted
-    in to the backward of ResidualStack (generator/stack_grad.py)."""
+    """Mix-in of the MelGAN-trunk generators: ``parameter_grad`` reads False, and setting it raises.  ``MelGANGenerator``
+    overrides it with a property that takes True once ``stack_grad = True`` has opted in to the backward of
+    ResidualStack (generator/stack_grad.py), ``BasisMelGANGenerator`` with one that takes True once ``basis_grad = True``
+    has (generator/basis_grad.py) and raises this message otherwise."""
 
     @property
     def parameter_grad(self):

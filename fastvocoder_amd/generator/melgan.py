@@ -11,6 +11,7 @@ it is a parameter container only -- calls go through native plans.
 import torch
 
 from .. import _native
+from . import basis_grad as _basis_grad
 from . import stack_grad as _stack_grad
 from .engine import NativeModule, NoParameterGrad, POST_NONE, POST_RELU, POST_TANH, SLOT_IN, SLOT_OUT, SLOT_OUT2  # noqa: F401
 from .modules import (BasisSignalLayer, LastLayer, LastLinear, ResidualStack, UpsampleLayer,
@@ -182,6 +183,40 @@ class BasisMelGANGenerator(_MelGANTrunk):
     (``basis_signal_weight [L, out_channels]``); samples = overlap-add of
     ``weight @ basis^T`` with hop L/2."""
 
+    _basis_grad = False
+    _parameter_grad = False
+
+    @property
+    def basis_grad(self):
+        """Default False: nothing changes, ``parameter_grad = True`` raises as it always did.  True opts in to the
+        training forward over B + 1 rows and to the head's adjoint (generator/basis_grad.py), after which
+        ``parameter_grad`` can be set and read like MelGANGenerator's.  Setting True raises NotImplementedError for what
+        ``MelGANGenerator.stack_grad`` refuses and for ``lastlinear=True``, ``transposedconv=False`` and
+        ``use_final_nonlinear_activation=False``."""
+        return self._basis_grad
+
+    @basis_grad.setter
+    def basis_grad(self, value):
+        if value:
+            _basis_grad.check_supported(self)
+        else:
+            self._parameter_grad = False
+        self._basis_grad = bool(value)
+
+    @property
+    def parameter_grad(self):
+        """Once ``basis_grad = True`` has opted in: with True, grad enabled and a trunk parameter requiring grad,
+        ``forward`` returns (est, weight) on the trunk parameters' graph and ``backward`` accumulates into their
+        ``.grad``.  The mel is a constant, and so is the basis (``basis_signal.layer.weight``): the reference never
+        steps it, and it gets no gradient."""
+        return self._parameter_grad
+
+    @parameter_grad.setter
+    def parameter_grad(self, value):
+        if value and not self._basis_grad:
+            NoParameterGrad.parameter_grad.fset(self, value)
+        self._parameter_grad = bool(value)
+
     def __init__(self, basis_signal_weight, L=30, in_channels=80, out_channels=256, kernel_size=7,
                  channels=[256, 256, 256], bias=True, upsample_scales=[4, 4], stack_kernel_size=3,
                  stacks=3, nonlinear_activation="LeakyReLU",
@@ -189,6 +224,9 @@ class BasisMelGANGenerator(_MelGANTrunk):
                  pad_params={}, use_final_nonlinear_activation=True, use_weight_norm=True,
                  use_causal_conv=False, transposedconv=True, lastlinear=False):
         super().__init__()
+        self._config = dict(use_causal_conv=bool(use_causal_conv), nonlinear_activation=nonlinear_activation, pad=pad,
+                            lastlinear=bool(lastlinear), transposedconv=bool(transposedconv),
+                            use_final_nonlinear_activation=bool(use_final_nonlinear_activation))
         layers = self._build_layers(in_channels, kernel_size, channels, bias, upsample_scales,
                                     stack_kernel_size, stacks, nonlinear_activation,
                                     nonlinear_activation_params, pad, pad_params, use_causal_conv,
@@ -242,7 +280,11 @@ class BasisMelGANGenerator(_MelGANTrunk):
     def forward(self, c):
         """Reference semantics (basis_melgan.py:140-162): (est - zero_est [B, F*L/2], weight - zero_weight
         [B,F,C]).  One generator pass: both differences are formed in the epilogues of the trunk's last conv
-        and of the overlap-add, against the cached zero-mel response."""
+        and of the overlap-add, against the cached zero-mel response.  With ``parameter_grad`` on, grad enabled and a
+        trunk parameter requiring grad, the same pair comes from the training forward (generator/basis_grad.py), on
+        the trunk parameters' graph; the cached response has no graph and is not used there."""
+        if self._parameter_grad and _basis_grad.wants_param_grad(self):
+            return _basis_grad.run(self, c)
         c = self._prepare(c)
         hop = self.L // 2
         if c.shape[2] > self.max_frames_per_run:

@@ -42,7 +42,8 @@ def check_supported(gen):
 
 
 def _graph(gen):
-    """The Sequential as (first conv, [(upsampler, [stacks])], LastLayer)."""
+    """The Sequential as (first conv, [(upsampler, [stacks])], LastLayer); None for a trunk that ends at its last
+    ResidualStack (Basis-MelGAN, whose head is generator/basis_grad.py)."""
     mods = list(gen.melgan)
     first = next(m for m in mods if isinstance(m, torch.nn.Conv1d))
     stages = []
@@ -51,7 +52,7 @@ def _graph(gen):
             stages.append((m, []))
         elif isinstance(m, ResidualStack):
             stages[-1][1].append(m)
-    return first, stages, next(m for m in mods if isinstance(m, LastLayer))
+    return first, stages, next((m for m in mods if isinstance(m, LastLayer)), None)
 
 
 def _stack_convs(stack):
@@ -94,7 +95,8 @@ def _twin(x, cout, tout):
 
 
 def train_forward(gen, mel):
-    """mel [B, C, T] fp32 device -> (y [B, out_channels, T'], tape)."""
+    """mel [B, C, T] fp32 device -> (y [B, out_channels, T'], tape).  Without a LastLayer the graph ends at the last
+    ResidualStack's raw output, which is y; its activated twin is not formed."""
     L = _layers(gen)
     slope = gen._slope
     first, stages, last = _graph(gen)
@@ -115,11 +117,12 @@ def train_forward(gen, mel):
             d, pw, sk = _stack_convs(stack)
             ch = stack.channels
             x, xa = y, ya
+            ends = last is None and up is stages[-1][0] and stack is stacks[-1]
             packed, b, _ = L[id(d)]
             ha = _twin(x, ch, x.shape[2])
             _native.conv1d_fused(xa, packed, b, ch, d.kernel_size[0], dil=d.dilation[0], pad=stack._pad,
                                  pad_mode=PAD_REFLECT, out_act=ha, act_slope=slope)
-            ya = _twin(x, ch, x.shape[2])
+            ya = None if ends else _twin(x, ch, x.shape[2])
             if id(stack) in L:
                 packed, b = L[id(stack)]
                 y = _native.conv1d_2src_fused(ha, x, packed, b, ch, out_act=ya, act_slope=slope)
@@ -130,6 +133,8 @@ def train_forward(gen, mel):
         stage["ya"] = ya                               # lrelu of the stage's output: the next conv's input
         tape["stages"].append(stage)
         xa = ya
+    if last is None:
+        return y, tape
     packed, b, _ = L[id(last.conv)]
     out = _native.conv1d_fused(xa, packed, b, last.conv.out_channels, last.conv.kernel_size[0], pad=last._pad,
                                pad_mode=PAD_REFLECT, post=gen._final_post)
@@ -137,7 +142,8 @@ def train_forward(gen, mel):
 
 
 def train_backward(gen, tape, y, params, need, g):
-    """g = dL/dy -> one gradient (or None) per entry of ``params`` (the convs' parameters, train_convs order)."""
+    """g = dL/dy -> one gradient (or None) per entry of ``params`` (the convs' parameters, train_convs order).  Without
+    a LastLayer, y is the last ResidualStack's raw output and the walk starts there."""
     L = _layers(gen)
     slope = gen._slope
     first, stages, last = _graph(gen)
@@ -172,17 +178,20 @@ def train_backward(gen, tape, y, params, need, g):
     def through_pad(conv, g_pre, tin, pad):
         return _native.conv1d_input_grad_reflect(g_pre, L[id(conv)][2], tin, conv.dilation[0], pad)
 
-    g_z = _native.tanh_grad(g, y) if gen._final_post != POST_NONE else g
-    post_in = tape["stages"][-1]["ya"]
-    wgrad(last.conv, g_z, post_in, last._pad, PAD_REFLECT)
-    if not below(last.conv):
-        return out
-    d = through_pad(last.conv, g_z, post_in.shape[2], last._pad)    # the gradient of lrelu(y) of the last stack
-    del g_z
+    if last is None:
+        d = g
+    else:
+        g_z = _native.tanh_grad(g, y) if gen._final_post != POST_NONE else g
+        post_in = tape["stages"][-1]["ya"]
+        wgrad(last.conv, g_z, post_in, last._pad, PAD_REFLECT)
+        if not below(last.conv):
+            return out
+        d = through_pad(last.conv, g_z, post_in.shape[2], last._pad)    # the gradient of lrelu(y) of the last stack
+        del g_z
     for n in range(len(stages) - 1, -1, -1):
         up, stacks = stages[n]
         stage = tape["stages"][n]
-        g_y = _native.disc_map_grad(d, None, stage["ya"], slope)
+        g_y = d if stage["ya"] is None else _native.disc_map_grad(d, None, stage["ya"], slope)
         del d
         for m in range(len(stacks) - 1, -1, -1):
             dil, pw, sk = _stack_convs(stacks[m])

@@ -1,7 +1,8 @@
 """The reference's composed generator loss (model/loss/loss.py): the multi-resolution STFT loss of a full-band
 estimate, or of the sub-bands and their PQMF synthesis for the multiband generators, plus the Basis-MelGAN weight L1
 term.  Forward only by default; ``Loss.differentiable = True`` switches the gradient with respect to the estimate on
-(stft_loss.py), through the PQMF synthesis too on the multiband path."""
+(stft_loss.py), through the PQMF synthesis too on the multiband path, and routes the weight term of an ``est_weight``
+that is on a graph through csrc/basis_grad.hip (``BasisWeightL1``)."""
 import torch
 
 from .. import _native
@@ -38,6 +39,32 @@ def pqmf_synthesis(x, pqmf):
     return pqmf.synthesis(x)
 
 
+class BasisWeightL1(torch.autograd.Function):
+    """L1Loss(est_weight, weight) of Basis-MelGAN's estimated weights [B, F, C] against the targets [B, F, C], with its
+    gradient: -> (mean |est_weight - weight|, mean est_weight), two device scalars from fv_basis_weight_l1; the second
+    is the reference's ``weight_average_value`` and carries no gradient.  ``est_weight`` is the transposed view of the
+    generator's D [B, C, F]; the target keeps the data layout and is transposed on chip.  The backward writes
+    coef sign(est_weight - weight) / (B F C) in D's storage (fv_basis_weight_l1_grad) and returns its transposed view,
+    which the generator's head adjoint reads without a copy."""
+
+    @staticmethod
+    def forward(ctx, est_weight, weight):
+        D = est_weight.transpose(1, 2).contiguous()              # no copy for the generator's own view
+        out = _native.basis_weight_l1(D, weight)
+        ctx.save_for_backward(D, weight)
+        loss, average = out[0], out[1]
+        ctx.mark_non_differentiable(average)
+        return loss, average
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        D, weight = ctx.saved_tensors
+        if g is None:
+            return None, None
+        return _native.basis_weight_l1_grad(D, weight, g.to(torch.float32).reshape(1).contiguous()).transpose(1, 2), None
+
+
 class Loss(torch.nn.Module):
     def __init__(self):
         super().__init__()
@@ -52,12 +79,21 @@ class Loss(torch.nn.Module):
     def differentiable(self, value):
         self.stft_loss.differentiable = value
 
+    def weight_term(self, est_weight, weight):
+        """Basis-MelGAN's weight term -> (L1(est_weight, weight), mean(est_weight) or None).  ``torch.nn.L1Loss`` and
+        None as they stand; when ``differentiable`` and est_weight is a device tensor (B, F, C) on a graph,
+        ``BasisWeightL1``, whose reduction also gives the mean (the reference's ``weight_average_value``)."""
+        if (self.differentiable and est_weight.requires_grad and torch.is_grad_enabled() and est_weight.dim() == 3
+                and est_weight.shape == weight.shape and est_weight.is_cuda):
+            return BasisWeightL1.apply(est_weight, weight.contiguous().float())
+        return self.l1_loss(est_weight, weight), None
+
     def forward(self, est_source, wav, est_weight=None, weight=None, pqmf=None):
         """-> (stft_loss, weight_loss).  Single band: est_source, wav (B, T); stft_loss = sc + mag.
         ``pqmf`` given: est_source (B, subbands, T / subbands) sub-band estimate, wav (B, T) full band;
         stft_loss = ((sc + mag) of the sub-band rows against pqmf.analysis(wav) + (sc + mag) of
         pqmf.synthesis(est_source) against wav) / 2, and weight_loss is None.  Otherwise weight_loss is
-        L1(est_weight, weight) when both are given (Basis-MelGAN), else None."""
+        ``weight_term(est_weight, weight)[0]`` when both are given (Basis-MelGAN), else None."""
         weight_loss = None
         if pqmf is not None:
             if est_source.dim() != 3:
@@ -85,6 +121,6 @@ class Loss(torch.nn.Module):
         stft_loss = sc_loss + mag_loss
 
         if est_weight is not None and weight is not None:
-            weight_loss = self.l1_loss(est_weight, weight)
+            weight_loss = self.weight_term(est_weight, weight)[0]
 
         return stft_loss, weight_loss

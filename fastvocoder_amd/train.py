@@ -13,9 +13,16 @@ five times, ``.item()`` each).  (The backward of the discriminator terms still r
 host, as it does outside this loop: loss/discriminator_loss.py.)
 
 MelGAN trains with ``Trainer(..., stack_grad=True)``, which sets the generator's ``stack_grad`` opt-in before
-``parameter_grad``; without the keyword it is refused as before.  Basis-MelGAN and the ``transposedconv: False``
-upsampler have no parameter gradient and are refused where the ``parameter_grad`` attribute refuses them; mixed
-precision is not part of this loop.
+``parameter_grad``; without the keyword it is refused as before.  Basis-MelGAN trains with
+``Trainer(..., basis_grad=True)`` in the same way (``BasisMelGANGenerator.basis_grad``).  Its step takes the target
+weights, ``step(mel, wav, current_step, weight)``; ``model(mel)`` is the pair (est, est_weight); the L1 weight term
+(loss.BasisWeightL1) is part of the total only up to ``discriminator_train_start_steps`` (reference train.py:87-89);
+the adversarial terms and the discriminator's update see ``est``; the step's dict gains ``"weight"`` and
+``"weight_average"`` (the reference's ``weight_average_value``).  The optimizer should cover ``model.melgan``'s
+parameters only: the basis is a constant of the training graph and gets no gradient (the reference gives it one that
+it never applies, train.py:64, 329-331 -- which its ``clip_grad_norm_`` over ``model.parameters()`` does count; the
+norm here is the trunk's alone).  The ``transposedconv: False`` upsampler has no parameter gradient and is refused
+where the ``parameter_grad`` attribute refuses it; mixed precision is not part of this loop.
 """
 import torch
 
@@ -28,13 +35,16 @@ KEYS = ("stft", "total", "adversarial", "feature_map", "discriminator", "grad_no
 def samples_per_frame(model, pqmf=None):
     """Waveform samples the generator makes of one mel frame: the product of its upsample rates (the strides of
     ``model.ups``, or of the trunk's ConvTranspose1d layers for a generator without ``ups``), times the sub-band count
-    when its output goes through a PQMF synthesis."""
+    when its output goes through a PQMF synthesis, times the basis hop L/2 for Basis-MelGAN (whose trunk makes weight
+    frames, not samples)."""
     ups = getattr(model, "ups", None)
     if ups is None:
         ups = [m for m in model.modules() if isinstance(m, torch.nn.ConvTranspose1d)]
     n = 1
     for up in ups:
         n *= int(up.stride[0])
+    if hasattr(model, "basis_signal"):
+        n *= int(model.L) // 2
     return n * (int(pqmf.subbands) if pqmf is not None else 1)
 
 
@@ -50,13 +60,16 @@ def fit_estimate(est, n, pqmf=None):
 class Trainer:
     def __init__(self, model, discriminator, optimizer, discriminator_optimizer, scheduler=None,
                  discriminator_scheduler=None, pqmf=None, *, lambda_stft, use_feature_map_loss,
-                 discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0, stack_grad=False):
+                 discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0, stack_grad=False,
+                 basis_grad=False):
         for opt, name in ((optimizer, "optimizer"), (discriminator_optimizer, "discriminator_optimizer")):
             if not isinstance(opt, Adam):
                 raise TypeError(f"{name} must be a fastvocoder_amd.optim.Adam (its step clips and updates in three "
                                 f"launches), got {type(opt).__name__}")
         if stack_grad and hasattr(type(model), "stack_grad"):
             model.stack_grad = True           # MelGAN's opt-in; raises for the graphs whose backward is missing
+        if basis_grad and hasattr(type(model), "basis_grad"):
+            model.basis_grad = True           # Basis-MelGAN's
         model.parameter_grad = True           # raises for the generators that have no parameter gradient
         self.model, self.discriminator = model, discriminator
         self.optimizer, self.discriminator_optimizer = optimizer, discriminator_optimizer
@@ -70,6 +83,7 @@ class Trainer:
         self.vocoder_loss = Loss().to(next(model.parameters()).device)
         self.vocoder_loss.differentiable = True
         self.samples_per_frame = samples_per_frame(model, pqmf)
+        self.basis = hasattr(model, "basis_signal")
 
     def _waveform(self, est):
         """The generator's output as (B, T) full band: the PQMF synthesis of sub-bands, on their graph."""
@@ -77,10 +91,14 @@ class Trainer:
             return est
         return pqmf_synthesis(est, self.pqmf)[:, 0, :]
 
-    def step(self, mel, wav, current_step):
+    def step(self, mel, wav, current_step, weight=None):
         """mel (B, 80, T) and wav (B, T * samples_per_frame), fp32 device tensors -> {key: float for key in KEYS}:
         the STFT loss (before lambda_stft), the generator's total, its adversarial and feature-map terms, the
-        discriminator's loss (0.0 up to discriminator_train_start_steps) and the two gradient norms before clipping."""
+        discriminator's loss (0.0 up to discriminator_train_start_steps) and the two gradient norms before clipping.
+        Basis-MelGAN: ``weight`` (B, T * prod(upsample_scales), C), the target weights; the dict also holds "weight"
+        (the L1 weight loss while it is part of the total, else 0.0, as the reference logs it) and "weight_average"."""
+        if weight is not None and not self.basis:
+            raise ValueError("weight is the target of Basis-MelGAN's weight loss; this generator has none")
         if wav.dim() != 2 or mel.dim() != 3 or wav.shape[1] != mel.shape[2] * self.samples_per_frame:
             raise ValueError(f"mel (B, 80, T) and wav (B, T * {self.samples_per_frame}) expected, got "
                              f"{tuple(mel.shape)} and {tuple(wav.shape)}")
@@ -89,9 +107,19 @@ class Trainer:
         self.optimizer.zero_grad()
         self.discriminator_optimizer.zero_grad()
 
-        est = fit_estimate(self.model(mel), wav.shape[1], self.pqmf)
+        est_weight = None
+        if self.basis:
+            est, est_weight = self.model(mel)
+            est = fit_estimate(est, wav.shape[1])
+        else:
+            est = fit_estimate(self.model(mel), wav.shape[1], self.pqmf)
         stft_loss, _ = self.vocoder_loss(est, wav, pqmf=self.pqmf)
+        weight_loss = average = None
+        if est_weight is not None and weight is not None:
+            weight_loss, average = self.vocoder_loss.weight_term(est_weight, weight)
         total = self.lambda_stft * stft_loss
+        if weight_loss is not None and not adversarial_phase:
+            total = total + weight_loss
         adv = fm = zero
         if adversarial_phase:
             real = wav.unsqueeze(1) if self.use_feature_map_loss else None
@@ -111,7 +139,9 @@ class Trainer:
         if adversarial_phase:
             self.discriminator_optimizer.zero_grad()
             with torch.no_grad():             # the plain forward, with the weights the step above left
-                est_for_d = self._waveform(fit_estimate(self.model(mel), wav.shape[1], self.pqmf))
+                est_for_d = self.model(mel)
+                est_for_d = self._waveform(fit_estimate(est_for_d[0] if self.basis else est_for_d, wav.shape[1],
+                                                        self.pqmf))
             kw = dict(period_grad=True) if self.period_grad else {}
             d_loss = discriminator_step_terms(self.discriminator, est_for_d.unsqueeze(1), wav.unsqueeze(1),
                                               stft_grad=True, **kw)["discriminator"]
@@ -120,7 +150,13 @@ class Trainer:
             if self.discriminator_scheduler is not None:
                 self.discriminator_scheduler.step()
 
-        scalars = torch.stack([t.detach().float().reshape(()) for t in
-                               (stft_loss, total, adv, fm, d_loss, zero if grad_norm is None else grad_norm,
-                                zero if d_norm is None else d_norm)])
-        return dict(zip(KEYS, scalars.cpu().tolist()))            # the step's one read on the host
+        values = [stft_loss, total, adv, fm, d_loss, zero if grad_norm is None else grad_norm,
+                  zero if d_norm is None else d_norm]
+        keys = KEYS
+        if self.basis:
+            keys = KEYS + ("weight", "weight_average")
+            average = est_weight.mean() if average is None else average     # no target: the weight term did not run
+            # the reference's w_l: the weight loss while it is part of the total, 0 afterwards (train.py:86-89)
+            values += [zero if weight_loss is None or adversarial_phase else weight_loss, average]
+        scalars = torch.stack([t.detach().float().reshape(()) for t in values])
+        return dict(zip(keys, scalars.cpu().tolist()))            # the step's one read on the host

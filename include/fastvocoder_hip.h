@@ -960,6 +960,41 @@ int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, in
                                  int dil, int pad, void* stream);
 
 /*
+ * The head of Basis-MelGAN for training (model/generator/basis_melgan.py:140-162 under bin/train.py:64-95, and the
+ * weight term of loss.py:39-40); additions of ABI 18, no existing entry changes.  The trunk runs ONCE over B + 1 rows,
+ * the last one the response to the all-zero mel, and ends in the raw Y [B+1, C, F]; the reference's second pass and
+ * its two differences are rows of one tensor.  Exact fp32, no atomics, workgroups never wait on each other, identical
+ * calls return identical bits.  L is the basis length (hop = L/2), basis [L, C] the Linear's weight as it lies in
+ * memory.  Every entry checks its arguments before it touches a pointer: B, C or F < 1, L odd or < 2, a null tensor or
+ * a result aliasing an input return FV_ERR_INVALID_ARG; L > 256, B > 65535 or more than 2^40 elements
+ * FV_ERR_UNSUPPORTED.
+ *
+ * fv_basis_head_forward:  D[b, c, f] = relu(Y[b, c, f]) - relu(Y[B, c, f]),  D [B, C, F].  The module's weight is D
+ *     transposed (a view); its est is fv_basis_ola(D) cut to F hop samples, by linearity of the overlap-add.
+ * fv_basis_head_grad:     the adjoint of the whole head in one launch.  g_est [B, F hop] or NULL, g_w [B, C, F] (the
+ *     cotangent of weight in D's storage) or NULL, not both NULL;
+ *         g_post[b, c, f] = sum_{j < L, f hop + j < F hop} basis[j, c] g_est[b, f hop + j]  +  g_w[b, c, f]
+ *         g_Y[b, c, f]    = [Y[b, c, f] > 0] g_post[b, c, f]                                  (b < B)
+ *         g_Y[B, c, f]    = -[Y[B, c, f] > 0] sum_{b < B} g_post[b, c, f]
+ *     g_Y [B+1, C, F], all of it written.  The taps of the last frame that fall behind the crop get nothing.  An element
+ *     is one j-ordered fmaf chain; the batch sum is formed in ascending b by the one block that owns the element.
+ * fv_basis_weight_l1:     out[0] = mean |D[b, c, f] - target[b, f, c]|, out[1] = mean D (the reference's
+ *     weight_average_value, train.py:73-75); target [B, F, C] in the reference's data layout, out two floats of device
+ *     memory.  One reduction launch (per block two doubles in `workspace`) and a one-block finish that adds them in
+ *     ascending order.  workspace: at least fv_basis_weight_l1_workspace_bytes(B, C, F) bytes, 8-byte aligned.
+ * fv_basis_weight_l1_grad: g[b, c, f] = coef sign(D[b, c, f] - target[b, f, c]) / (B F C), sign(0) = 0, in D's storage
+ *     so that fv_basis_head_grad reads it as g_w.  coef: ONE float of device memory, or NULL for 1.
+ */
+int fv_basis_head_forward(const float* Y, float* D, int B, int C, int F, void* stream);
+int fv_basis_head_grad(const float* g_est, const float* g_w, const float* Y, const float* basis, float* g_Y, int B, int C,
+                       int F, int L, void* stream);
+int64_t fv_basis_weight_l1_workspace_bytes(int B, int C, int F);
+int fv_basis_weight_l1(const float* D, const float* target, float* out, int B, int C, int F, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int fv_basis_weight_l1_grad(const float* D, const float* target, const float* coef, float* g, int B, int C, int F,
+                            void* stream);
+
+/*
  * Gradient clipping and the Adam update of a whole parameter set (nn.utils.clip_grad_norm_ + Adam.step() of
  * bin/train.py:126-136 and 176-186; the reference names the fused form itself, apex.optimizers.FusedAdam,
  * train.py:338); additions of ABI 18, no existing entry changes.  Three launches for any number of tensors, exact fp32
