@@ -295,6 +295,7 @@ def lib():
     L.fv_grad_sq_norm_workspace_bytes.restype = i64
     L.fv_grad_sq_norm.argtypes = [vp, vp, i, i64, f, vp, ctypes.c_size_t, vp, vp]
     L.fv_adam_step.argtypes = [vp, vp, i, i64, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
+    L.fv_grad_bucket_pack.argtypes = [vp, vp, i, i64, vp, f, vp]
     L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
     L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
     L.fv_disc_score_grad.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
@@ -1831,6 +1832,20 @@ def adam_step(table, n_tensors, n_chunks, coef, beta1, beta2, eps, first_chunk=0
     with _on(table, coef) as stream:
         check(lib().fv_adam_step(rows, chunks + ADAM_CHUNK_BYTES * first_chunk, int(n_tensors), chunk_count,
                                  _ptr(coef, "coef", True), float(beta1), float(beta2), float(eps), stream))
+
+
+def grad_bucket_pack(table, n_tensors, n_chunks, scale):
+    """Every gradient into its span of the flat bucket, times ``scale`` (fv_grad_bucket_pack, one launch).  ``table``:
+    the rows and chunks of optim.adam_table, the rows' ``g`` pointing INTO the bucket, followed by the n_tensors source
+    pointers (the parameters' own gradients, 0 for a span of zeros) as uint64 -- one upload carries all three."""
+    rows, chunks = _adam_table(table, n_tensors, n_chunks, "grad_bucket_pack")
+    src = chunks - table.data_ptr() + ADAM_CHUNK_BYTES * int(n_chunks)
+    if table.numel() < src + 8 * int(n_tensors):
+        raise NativeError(f"grad_bucket_pack: a table of {int(n_tensors)} rows and {int(n_chunks)} chunks with its source "
+                          f"pointers needs {src + 8 * int(n_tensors)} bytes, got {table.numel()}")
+    with _on(table) as stream:
+        check(lib().fv_grad_bucket_pack(rows, chunks, int(n_tensors), int(n_chunks), table.data_ptr() + src,
+                                        float(scale), stream))
 
 
 def reflect_pad_fold(gp, pad):

@@ -34,18 +34,36 @@ gradient --, the validation scores ``model(mel)[0]``, the log line's "Weight Los
 ``weight_average_value`` scalars are written.  A missing basis or weight file ends the run with one sentence that
 names the path.  Both flags are absent from the parsed arguments unless given.  ``--mixprecision 1`` exits: there is no
 mixed-precision path.
+
+Several GPUs of one node: ``--gpus N`` (absent from the parsed arguments unless given) with no ``WORLD_SIZE`` in the
+environment starts ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...`` as a child -- the parent
+never touches a GPU -- and returns its exit status; started under ``torch.distributed.run`` directly (``WORLD_SIZE`` in
+the environment) every process is one rank.  The backend is ``nccl`` (RCCL), one GPU per rank by ``LOCAL_RANK``; a world
+larger than the visible devices is refused.  ``FV_TRAIN_BACKEND=gloo`` together with ``FV_TRAIN_ONE_GPU=1`` puts every
+rank on device 0 and moves the collectives through the host: for tests on a one-GPU box.  ``--batch_size`` is PER RANK,
+so a step sees ``batch_size * N`` crops (``BatchIterator(rank=, world_size=)``: the ranks cut one global batch) and an
+epoch has ``utterances // (batch_size * N)`` steps.  The learning rates are NOT rescaled by N.  A fresh start broadcasts
+rank 0's seeded weights (model and discriminator) to every rank; a resume loads the checkpoint on every rank.  The
+gradients are averaged inside the optimizer step (``Trainer(process_group=)``) and the logged scalars are the ranks'
+means.  Only rank 0 prints the log lines, writes the logger files, the tensorboard scalars and the checkpoints, and
+validates.  At every ``save_step``, before saving, all ranks compare one float64 checksum of their parameters (a MIN and
+a MAX all-reduce) and all exit with one sentence when the two differ.  The process group has a finite timeout
+(``COLLECTIVE_TIMEOUT`` seconds): when a rank dies the launcher ends the others, and a rank that merely stops arriving
+at a collective ends the run after that time instead of hanging it.
 """
 import argparse
 import os
+import subprocess
 import sys
 import time
-from datetime import datetime
+from datetime import datetime, timedelta
 
 import numpy as np
 import torch
 import yaml
 
 from .. import hparams as hp
+from .. import parallel
 from ..data import BatchIterator, MissingWeightFile, load_data_to_buffer
 from ..discriminator import Discriminator
 from ..generator import PQMF
@@ -55,6 +73,7 @@ from .evaluation import discriminator_uses_mpd
 from .synthesize import build_generator, default_device, load_checkpoint
 
 SUPPORTED = ("hifigan", "multiband-hifigan")
+COLLECTIVE_TIMEOUT = 600        # seconds a rank waits in a collective before the run ends
 CHECKPOINT_KEYS = ("model", "optimizer", "discriminator", "discriminator_optimizer")
 
 
@@ -103,6 +122,9 @@ def build_parser():
                         help="1: opt in to Basis-MelGAN's parameter gradient (--model_name basis-melgan trains only with it)")
     parser.add_argument("--basis_dataset_path", type=str, default=argparse.SUPPRESS,
                         help="directory of basis_signal_weight.npy and weight/ (default: Basis-MelGAN-dataset)")
+    parser.add_argument("--gpus", type=int, default=argparse.SUPPRESS,
+                        help="data-parallel training over this many GPUs of the node, one rank each (--batch_size is "
+                             "per rank)")
     return parser
 
 
@@ -128,7 +150,98 @@ def check_args(args):
     for name in ("batch_size", "fixed_length", "log_step", "save_step", "valid_step"):
         if getattr(args, name) < 1:
             sys.exit(f"MODE=train: --{name} must be at least 1")
+    if getattr(args, "gpus", 1) < 1:
+        sys.exit("MODE=train: --gpus must be at least 1")
     return args
+
+
+def free_port():
+    import socket
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        return sk.getsockname()[1]
+
+
+def self_launch_argv(gpus, argv, port):
+    """``--gpus N`` started as ONE process: the command of the child that runs the N ranks, one per GPU of this node,
+    rendezvous on 127.0.0.1 (``MODE=train`` and the package's directory travel in the child's environment)."""
+    return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus),
+            "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "fastvocoder_amd.bin.launcher", *argv]
+
+
+def visible_devices_error(world, visible):
+    """The one sentence that refuses a world larger than the node's visible devices, or None."""
+    if world > visible:
+        return (f"MODE=train: --gpus {world} needs {world} visible devices, this node shows {visible} "
+                "(HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES?): refusing to run ranks on shared devices")
+    return None
+
+
+def launch(gpus, argv):
+    """Run the ``gpus`` ranks as a child process -> its exit status.  Nothing here initialises a GPU."""
+    if os.environ.get("FV_TRAIN_ONE_GPU", "0") != "1":
+        err = visible_devices_error(gpus, torch.cuda.device_count())
+        if err:
+            sys.exit(err)
+    root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    path = os.environ.get("PYTHONPATH")
+    env = dict(os.environ, MODE="train", PYTHONPATH=root + (os.pathsep + path if path else ""))
+    sys.stdout.flush()
+    sys.stderr.flush()
+    port = int(os.environ.get("MASTER_PORT") or free_port())        # the rendezvous port: the caller's, or a free one
+    return subprocess.call(self_launch_argv(gpus, list(argv), port), env=env)
+
+
+def init_distributed(args):
+    """(process group or None, rank, world, device) from the launcher's environment; exits with one sentence for a
+    launch that cannot run as asked."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world <= 1:
+        return None, 0, 1, default_device()
+    import torch.distributed as dist
+    rank, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
+    if getattr(args, "gpus", world) != world:
+        sys.exit(f"MODE=train: --gpus {args.gpus} but WORLD_SIZE = {world}: launch exactly one rank per GPU asked for")
+    backend = os.environ.get("FV_TRAIN_BACKEND", "nccl")
+    one_gpu = os.environ.get("FV_TRAIN_ONE_GPU", "0") == "1"
+    if not torch.cuda.is_available():
+        sys.exit("MODE=train: fastvocoder_amd needs a ROCm GPU (MI355X); no CPU training path exists")
+    if one_gpu and backend != "gloo":
+        sys.exit("MODE=train: FV_TRAIN_ONE_GPU=1 (every rank on device 0) needs FV_TRAIN_BACKEND=gloo: RCCL wants one "
+                 "GPU per rank")
+    if one_gpu:
+        local_rank = 0
+    else:
+        err = visible_devices_error(world, torch.cuda.device_count())
+        if err:
+            sys.exit(err)
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    kw = dict(device_id=device) if backend == "nccl" else {}
+    dist.init_process_group(backend, rank=rank, world_size=world, timeout=timedelta(seconds=COLLECTIVE_TIMEOUT), **kw)
+    return dist.group.WORLD, rank, world, device
+
+
+def parameter_checksum(*modules):
+    """One float64 device scalar over every parameter of the modules (the sum of the tensors' float64 sums)."""
+    with torch.no_grad():
+        return torch.stack([p.detach().double().sum() for m in modules for p in m.parameters()]).sum()
+
+
+def check_replicas(group, step, *modules):
+    """All ranks compare their parameter checksum (MIN and MAX over the group); all exit when the two differ."""
+    import torch.distributed as dist
+    value = parameter_checksum(*modules).reshape(1)
+    if dist.get_backend(group) == "gloo":
+        value = value.cpu()
+    lo, hi = value.clone(), value.clone()
+    dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+    lo, hi = float(lo), float(hi)
+    if not lo == hi:
+        sys.exit(f"MODE=train: at step {step} the ranks' parameter checksums differ ({lo!r} to {hi!r}): the replicas "
+                 "have diverged, nothing is saved")
 
 
 def _timestamp():
@@ -177,13 +290,26 @@ def validate(model, vocoder_loss, pqmf, buffer, valid_num, device, spf):
 
 
 def run(args):
-    device = default_device()
+    group, rank, world, device = init_distributed(args)
+    try:
+        return _run(args, group, rank, world, device)
+    finally:
+        if group is not None:
+            torch.distributed.destroy_process_group()
+
+
+def _run(args, group, rank, world, device):
+    main = rank == 0                               # the rank that prints, logs, saves and validates
+
+    def say(*a, **kw):                             # the other ranks run the same lines silently
+        if main:
+            print(*a, **kw)
     torch.manual_seed(args.seed)
     with open(args.config) as f:
         config = yaml.load(f, Loader=yaml.Loader)
     lambda_stft = config["lamda_stft"]
     use_feature_map_loss = config["use_feature_map_loss"]
-    print(f"Loading Model of {args.model_name}...")
+    say(f"Loading Model of {args.model_name}...")
     model = build_generator(args.model_name, config).to(device)
     basis = args.model_name == "basis-melgan"
     basis_dir = getattr(args, "basis_dataset_path", "Basis-MelGAN-dataset")
@@ -206,7 +332,7 @@ def run(args):
     if checkpoint is not None and "discriminator" in checkpoint:
         use_mpd = discriminator_uses_mpd(checkpoint["discriminator"])
     discriminator = Discriminator(use_mpd=use_mpd).to(device)
-    print(f"Number of Parameters: {sum(p.numel() for p in model.parameters())}")
+    say(f"Number of Parameters: {sum(p.numel() for p in model.parameters())}")
 
     # Basis-MelGAN: the trunk alone; the basis is frozen (reference train.py:329-331)
     optimizer = Adam((model.melgan if basis else model).parameters(), lr=args.learning_rate, eps=1.0e-6,
@@ -220,10 +346,13 @@ def run(args):
             discriminator.load_state_dict(checkpoint["discriminator"])
             discriminator_optimizer.load_state_dict(checkpoint["discriminator_optimizer"])
         counts = [int(s["step"]) for s in optimizer.state.values()]
-        print("\n---Model Restored at Step %d---\n" % args.restore_step)
-        print("optimizer state at step count %d" % (max(counts) if counts else 0))
+        say("\n---Model Restored at Step %d---\n" % args.restore_step)
+        say("optimizer state at step count %d" % (max(counts) if counts else 0))
     else:
-        print("\n---Start New Training---\n")
+        if group is not None:                      # every rank starts from rank 0's seeded weights
+            parallel.broadcast_weights(model, src=0, group=group)
+            parallel.broadcast_weights(discriminator, src=0, group=group)
+        say("\n---Start New Training---\n")
     scheduler = discriminator_scheduler = None
     if args.use_scheduler:
         from torch.optim.lr_scheduler import CosineAnnealingLR
@@ -234,32 +363,35 @@ def run(args):
     stamp = _timestamp()
     current_checkpoint_path = os.path.join(hp.checkpoint_path, stamp)
     current_logger_path = os.path.join(hp.logger_path, stamp)
-    os.makedirs(current_checkpoint_path, exist_ok=True)
-    os.makedirs(current_logger_path, exist_ok=True)
-    writer = _summary_writer(os.path.join(hp.tensorboard_path, stamp))
+    writer = None
+    if main:
+        os.makedirs(current_checkpoint_path, exist_ok=True)
+        os.makedirs(current_logger_path, exist_ok=True)
+        writer = _summary_writer(os.path.join(hp.tensorboard_path, stamp))
 
     model.train()
     trainer = Trainer(model, discriminator, optimizer, discriminator_optimizer, scheduler, discriminator_scheduler,
                       pqmf, lambda_stft=lambda_stft, use_feature_map_loss=use_feature_map_loss,
                       discriminator_train_start_steps=args.discriminator_train_start_steps,
                       grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm,
-                      stack_grad=bool(getattr(args, "stack_grad", 0)), basis_grad=bool(getattr(args, "basis_grad", 0)))
+                      stack_grad=bool(getattr(args, "stack_grad", 0)), basis_grad=bool(getattr(args, "basis_grad", 0)),
+                      process_group=group)
     spf = samples_per_frame(model, pqmf)
 
-    print("Load data to buffer")
+    say("Load data to buffer")
     try:
         train_buffer = load_data_to_buffer(args.audio_index_path, args.mel_index_path,
                                            weight_dir=os.path.join(basis_dir, "weight") if basis else None)
     except MissingWeightFile as e:                 # Basis-MelGAN's weight/ alone; other missing files raise as before
         sys.exit(f"MODE=train: {e}")
     batches = BatchIterator(train_buffer, args.batch_size, args.fixed_length, spf, seed=args.seed, name="train",
-                            basis_L=model.L if basis else None)
-    print("Load valid data to buffer")
+                            basis_L=model.L if basis else None, rank=rank, world_size=world)
+    say("Load valid data to buffer")
     valid_buffer = load_data_to_buffer(args.audio_index_valid_path, args.mel_index_valid_path)
     if len(batches) < 1:
         sys.exit(f"MODE=train: {len(batches.items)} usable training utterances do not fill one batch of "
-                 f"{args.batch_size}")
-    print(f"Length of training loader is {len(batches)}")
+                 f"{args.batch_size}" + (f" on each of {world} ranks" if world > 1 else ""))
+    say(f"Length of training loader is {len(batches)}")
     total_step = hp.epochs * len(batches)
 
     start = time.perf_counter()
@@ -273,12 +405,13 @@ def run(args):
             wav = wav.to(device)
             out = trainer.step(mel, wav, current_step, *(w.to(device) for w in weight))
             s_l, t_l = out["stft"], out["total"]
-            with open(os.path.join(current_logger_path, "total_loss.txt"), "a") as f:
-                f.write(str(t_l) + "\n")
-            with open(os.path.join(current_logger_path, "stft_loss.txt"), "a") as f:
-                f.write(str(s_l) + "\n")
+            if main:
+                with open(os.path.join(current_logger_path, "total_loss.txt"), "a") as f:
+                    f.write(str(t_l) + "\n")
+                with open(os.path.join(current_logger_path, "stft_loss.txt"), "a") as f:
+                    f.write(str(s_l) + "\n")
 
-            if current_step % args.log_step == 0:
+            if main and current_step % args.log_step == 0:
                 if scheduler is None:
                     lrs = args.learning_rate, args.learning_rate_discriminator
                 else:
@@ -289,7 +422,7 @@ def run(args):
                                          out["adversarial"],
                                          out["discriminator"], out["feature_map"], *lrs)
                 lines.append(format_time_line(now - start, (total_step - current_step) * mean_time))
-                print("\n" + "\n".join(lines), flush=True)
+                say("\n" + "\n".join(lines), flush=True)
                 with open(os.path.join(current_logger_path, "logger.txt"), "a") as f:
                     f.write("\n".join(lines) + "\n\n")
                 if writer is not None:
@@ -304,20 +437,22 @@ def run(args):
                     if scheduler is not None:
                         writer.add_scalar("learning_rate", lrs[0], global_step=current_step)
 
-            if current_step % args.save_step == 0:
+            if group is not None and current_step % args.save_step == 0:
+                check_replicas(group, current_step, model, discriminator)
+            if main and current_step % args.save_step == 0:
                 torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict(),
                             "discriminator": discriminator.state_dict(),
                             "discriminator_optimizer": discriminator_optimizer.state_dict()},
                            os.path.join(current_checkpoint_path, "checkpoint_%d.pth.tar" % current_step))
-                print("save model at step %d ..." % current_step, flush=True)
+                say("save model at step %d ..." % current_step, flush=True)
 
             step_times.append(time.perf_counter() - step_start)
             if len(step_times) == hp.clear_time:
                 step_times = [float(np.mean(step_times))]
 
-            if current_step % args.valid_step == 0:
+            if main and current_step % args.valid_step == 0:
                 value, scored = validate(model, trainer.vocoder_loss, pqmf, valid_buffer, args.valid_num, device, spf)
-                print("valid %d stft=%.8e" % (current_step, value), flush=True)
+                say("valid %d stft=%.8e" % (current_step, value), flush=True)
                 if writer is not None and scored:
                     writer.add_scalar("valid_stft_loss", value, global_step=current_step)
 
@@ -333,7 +468,11 @@ def run(args):
 
 
 def run_train(argv=None):
-    return run(check_args(build_parser().parse_args(argv)))
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = check_args(build_parser().parse_args(argv))
+    if getattr(args, "gpus", 1) > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(launch(args.gpus, argv))          # the ranks run in a child; this process never opens a GPU
+    return run(args)
 
 
 if __name__ == "__main__":

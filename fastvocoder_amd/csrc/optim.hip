@@ -16,6 +16,10 @@
 //     to at most 1 (a NaN passes, as torch.clamp lets it).
 // adam_step_kernel: g' = coef g (written back to the gradient when there is a coef), m = b1 m + (1 - b1) g',
 //     v = b2 v + (1 - b2) g'^2, p -= step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps)).
+// grad_bucket_pack_kernel (fv_grad_bucket_pack, data-parallel training): row r's span of a flat bucket, row.g, becomes
+//     scale * src[r] -- one rounding per element -- over the same table and the same thread-to-element map; the span is
+//     row.n rounded up to a whole 16-byte group, the words past row.n are written as zeros, a NULL src[r] gives a span of
+//     zeros: every word the collective sends is written by this launch.
 #include <math.h>
 
 #include "fv_internal.h"
@@ -146,6 +150,33 @@ __global__ __launch_bounds__(kOaThreads) void adam_step_kernel(const fv_adam_ten
     }
 }
 
+__global__ __launch_bounds__(kOaThreads) void grad_bucket_pack_kernel(const fv_adam_tensor* __restrict__ rows,
+                                                                      const fv_adam_chunk* __restrict__ chunks,
+                                                                      int n_tensors, const float* const* __restrict__ srcs,
+                                                                      float scale) {
+    const fv_adam_chunk c = chunks[blockIdx.x];
+    if (c.tensor < 0 || c.tensor >= n_tensors || c.index < 0) return;
+    const fv_adam_tensor row = rows[c.tensor];
+    const float* src = srcs[c.tensor];
+    const int64_t base = (int64_t)c.index * kFvAdamChunk;
+    const int64_t padded = (row.n + 3) & ~(int64_t)3;        // the span: whole 16-byte groups
+    const bool vec_src = src != nullptr && oa_aligned(src);
+    const bool vec_dst = oa_aligned(row.g);
+#pragma unroll
+    for (int r = 0; r < kOaRounds; ++r) {
+        const int64_t at = base + 4 * ((int64_t)r * kOaThreads + threadIdx.x);
+        if (at >= row.n) break;
+        oa_f32x4 g = {0.f, 0.f, 0.f, 0.f};
+        if (src != nullptr) {
+            g = oa_load(src, at, row.n, vec_src);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (at + j < row.n) g[j] = scale * g[j];      // the pad words stay +0 whatever the scale
+        }
+        oa_store(row.g, at, padded, vec_dst, g);
+    }
+}
+
 static int oa_table_check(const char* who, const void* rows, const void* chunks, int n_tensors, int64_t n_chunks) {
     if (!rows || !chunks) return fail(FV_ERR_INVALID_ARG, "%s: null table", who);
     if (n_tensors < 1 || n_chunks < 1 || n_chunks > 0x7fffffff)
@@ -194,6 +225,16 @@ int fv_adam_step(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int
     if ((uintptr_t)coef & 3) return fail(FV_ERR_INVALID_ARG, "adam_step: misaligned coef");
     hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, (hipStream_t)stream, tensors,
                        chunks, n_tensors, coef, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int fv_grad_bucket_pack(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int n_tensors, int64_t n_chunks,
+                        const float* const* src, float scale, void* stream) {
+    if (int rc = oa_table_check("grad_bucket_pack", tensors, chunks, n_tensors, n_chunks)) return rc;
+    if (!src || ((uintptr_t)src & 7)) return fail(FV_ERR_INVALID_ARG, "grad_bucket_pack: null or misaligned src array");
+    hipLaunchKernelGGL(grad_bucket_pack_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, (hipStream_t)stream,
+                       tensors, chunks, n_tensors, src, scale);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -82,14 +82,24 @@ class BatchIterator:
     """``for mel, wav in BatchIterator(...).epoch()``: mel [B, fixed_length, 80], wav [B, fixed_length * hop], CPU fp32
     tensors.  ``len()`` is the number of batches of an epoch (``drop_last``).  When the items carry target weights
     (``basis_L``: the basis length L, required then) it yields ``(mel, wav, weight [B, fixed_length * r, C])``,
-    ``r = hop // (L // 2)``."""
+    ``r = hop // (L // 2)``.
 
-    def __init__(self, buffer, batch_size, fixed_length=None, hop=None, seed=0, name="train", basis_L=None):
+    Data-parallel training (``rank``, ``world_size``): ``batch_size`` is per rank.  Every rank draws the same
+    permutation and the same crop starts from the same seeded stream, for a global batch of ``batch_size * world_size``
+    rows, and rank r yields the rows ``[r * batch_size, (r + 1) * batch_size)`` of it: the ranks' batches concatenated
+    in rank order are, bit for bit, the single-process iterator's at batch size ``batch_size * world_size`` with the
+    same seed.  ``len()`` is ``items // (batch_size * world_size)``."""
+
+    def __init__(self, buffer, batch_size, fixed_length=None, hop=None, seed=0, name="train", basis_L=None, rank=0,
+                 world_size=1):
         self.fixed_length = hp.fixed_length if fixed_length is None else int(fixed_length)
         self.hop = hp.hop_size if hop is None else int(hop)
         self.batch_size = int(batch_size)
         if self.batch_size < 1 or self.fixed_length < 1 or self.hop < 1:
             raise ValueError(f"batch_size {batch_size}, fixed_length {fixed_length} and hop {hop} must be positive")
+        self.rank, self.world_size = int(rank), int(world_size)
+        if self.world_size < 1 or not 0 <= self.rank < self.world_size:
+            raise ValueError(f"rank {rank} of world_size {world_size}")
         self.weight_rate = None
         with_weight = sum("weight" in it for it in buffer)
         if with_weight not in (0, len(buffer)):
@@ -108,14 +118,17 @@ class BatchIterator:
         self.rng = np.random.RandomState(seed)
 
     def __len__(self):
-        return len(self.items) // self.batch_size
+        return len(self.items) // (self.batch_size * self.world_size)
 
     def epoch(self):
         order = self.rng.permutation(len(self.items))
+        rows = self.batch_size * self.world_size                 # the global batch; every rank draws all its starts
+        mine = range(self.rank * self.batch_size, (self.rank + 1) * self.batch_size)
         for b in range(len(self)):
             parts = []
-            for idx in order[b * self.batch_size:(b + 1) * self.batch_size]:
+            for row, idx in enumerate(order[b * rows:(b + 1) * rows]):
                 item = self.items[idx]
                 start = int(self.rng.randint(0, item["mel"].shape[0] - self.fixed_length))   # high is exclusive
-                parts.append(crop(item, start, self.fixed_length, self.hop, self.weight_rate))
+                if row in mine:
+                    parts.append(crop(item, start, self.fixed_length, self.hop, self.weight_rate))
             yield tuple(torch.stack(column) for column in zip(*parts))

@@ -17,17 +17,35 @@ The table the kernels walk (pointers, element counts, ``lr / bias_correction1`` 
 tensor, and the chunks) is rebuilt on the host every step -- ``zero_grad(set_to_none=True)`` moves the ``.grad``
 pointers -- and uploaded with one asynchronous copy from pinned memory; a pinned buffer is reused only once the copy
 that read it has completed (an event per buffer, queried, never waited for).
+
+Data-parallel training: ``step(max_norm=None, process_group=<a torch.distributed group>)`` averages the gradients over
+the group's ranks first, with ONE collective.  Every parameter that ``requires_grad``, of every group, in optimizer
+order, owns a span of one flat fp32 bucket (``bucket_layout``: 16-byte-aligned offsets, spans padded to 4 floats; the
+layout is static and the bucket is allocated once per optimizer).  One launch (``fv_grad_bucket_pack``) writes
+``grad / world`` into every span -- and zeros into the padding and into the span of a parameter without a local
+gradient --, ``parallel.all_reduce_sum`` adds the buckets of the ranks in place, and the norm and Adam launches above
+run over rows whose gradient pointer is the span; the source pointers ride in the same pinned upload as the table.
+Afterwards ``p.grad`` IS the parameter's view into the bucket: it holds the averaged (and, with ``max_norm``, clipped)
+gradient, and the next step overwrites it -- clone it to keep it.  Unlike the single-process rule, a parameter that
+requires grad but has no local ``.grad`` is NOT skipped: it contributes zeros, its step count advances and it is
+updated like the rest, so that every rank sends the same number of words and applies the same update whatever its
+shard of the batch touched, and no rank waits for another.  A group of one rank takes the same path.  Learning rates
+are not rescaled by the world size.  Nothing is read on the host (under ``nccl``; a ``gloo`` group stages the bucket
+through pinned host memory, parallel.all_reduce_sum).
 """
 import math
 
 import numpy as np
 import torch
 
-from . import _native
+import torch.distributed
+
+from . import _native, parallel
 
 ROW = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"),
                 ("inv_sqrt_bc2", "<f4")])
 CHUNK = np.dtype([("tensor", "<i4"), ("index", "<i4")])
+BUCKET_ALIGN = 4        # floats: every span of the gradient bucket starts on a 16-byte boundary
 assert ROW.itemsize == _native.ADAM_ROW_BYTES and CHUNK.itemsize == _native.ADAM_CHUNK_BYTES
 
 
@@ -36,9 +54,23 @@ def bias_factors(lr, beta1, beta2, step):
     return lr / (1.0 - beta1 ** step), 1.0 / math.sqrt(1.0 - beta2 ** step)
 
 
-def adam_table(rows):
+def bucket_layout(params):
+    """Where the gradients of ``params`` (in this order; those with ``requires_grad=False`` are left out) live in the
+    flat bucket -> (offset of each in floats, total floats).  Every offset is a multiple of 4 floats (16 bytes) and a
+    span is the element count rounded up to 4 floats, so spans never overlap.  Pure host arithmetic."""
+    offsets, total = [], 0
+    for p in params:
+        if not p.requires_grad:
+            continue
+        offsets.append(total)
+        total += (p.numel() + BUCKET_ALIGN - 1) // BUCKET_ALIGN * BUCKET_ALIGN
+    return offsets, total
+
+
+def adam_table(rows, src=None):
     """rows: [(p_ptr, g_ptr, m_ptr, v_ptr, n, step_size, inv_sqrt_bc2)] -> (bytes of the table as a uint8 ndarray,
-    first chunk of every row + the total).  Layout: the fv_adam_tensor rows, then row 0's chunks, row 1's, ..."""
+    first chunk of every row + the total).  Layout: the fv_adam_tensor rows, then row 0's chunks, row 1's, ...; with
+    ``src`` (one pointer per row: fv_grad_bucket_pack's sources, 0 for none) those follow as uint64."""
     table = np.zeros(len(rows), dtype=ROW)
     for k, name in enumerate(ROW.names):
         table[name] = [r[k] for r in rows]
@@ -47,7 +79,12 @@ def adam_table(rows):
     chunks = np.zeros(int(first[-1]), dtype=CHUNK)
     chunks["tensor"] = np.repeat(np.arange(len(rows), dtype=np.int32), counts)
     chunks["index"] = np.arange(int(first[-1]), dtype=np.int64) - np.repeat(first[:-1], counts)
-    return np.concatenate((table.view(np.uint8), chunks.view(np.uint8))), first
+    parts = (table.view(np.uint8), chunks.view(np.uint8))
+    if src is not None:
+        if len(src) != len(rows):
+            raise ValueError(f"{len(src)} source pointers for {len(rows)} rows")
+        parts += (np.asarray(src, dtype="<u8").view(np.uint8),)
+    return np.concatenate(parts), first
 
 
 def _check_group(group):
@@ -78,6 +115,7 @@ class Adam(torch.optim.Adam):
         super().__init__(params, *args, **kwargs)
         self._pinned = []           # [(pinned uint8 tensor, event of the copy that last read it)]
         self._workspace = None      # fp32 device words: the per-chunk partial sums of the norm
+        self._bucket = None         # (key, flat fp32 device tensor, {parameter: its view}) of the data-parallel step
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -87,6 +125,7 @@ class Adam(torch.optim.Adam):
         super().__setstate__(state)
         self.__dict__.setdefault("_pinned", [])
         self.__dict__.setdefault("_workspace", None)
+        self.__dict__.setdefault("_bucket", None)
         for group in self.param_groups:
             _check_group(group)
         for state in self.state.values():       # a checkpoint loaded with map_location=<device> carries the counts there
@@ -148,6 +187,66 @@ class Adam(torch.optim.Adam):
             touched += [p, g, m, v]
         return rows, touched, spans, device
 
+    def _bucket_views(self):
+        """(the flat bucket, the view of every parameter that requires grad); allocated once, again only when the
+        parameter set or its device changes."""
+        params = [p for group in self.param_groups for p in group["params"] if p.requires_grad]
+        for p in params:
+            if not p.is_cuda:
+                raise _native.NativeError(f"a parameter lives on {p.device}; the HIP kernels need a ROCm device "
+                                          "tensor (there is no CPU path in fastvocoder_amd)")
+        if not params:
+            return None, {}
+        device = params[0].device
+        key = (device, tuple((id(p), p.numel()) for p in params))
+        if self._bucket is None or self._bucket[0] != key:
+            offsets, total = bucket_layout(params)
+            flat = torch.zeros(max(total, BUCKET_ALIGN), dtype=torch.float32, device=device)
+            views = {p: flat[off:off + p.numel()].view(p.shape) for p, off in zip(params, offsets)}
+            self._bucket = (key, flat, views)
+        return self._bucket[1], self._bucket[2]
+
+    def _rows_bucket(self):
+        """``_rows`` for the data-parallel step: a row for EVERY parameter that requires grad, its gradient pointer
+        the parameter's span of the bucket; also the source pointers (0: no local gradient) and the views."""
+        flat, views = self._bucket_views()
+        rows, touched, spans, src = [], [], [], []
+        device = None if flat is None else flat.device
+        at = 0
+        for group in self.param_groups:
+            _check_group(group)
+            beta1, beta2 = group["betas"]
+            lr = float(group["lr"])
+            begin = at
+            for p in group["params"]:
+                if not p.requires_grad:
+                    continue
+                g = p.grad
+                if g is not None and g.is_sparse:
+                    raise RuntimeError("fastvocoder_amd.optim.Adam does not support sparse gradients")
+                state = self._state_of(p)
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                for t, name in ((g, "gradient"), (m, "exp_avg"), (v, "exp_avg_sq")):
+                    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != p.shape
+                                          or t.device != device):
+                        raise _native.NativeError(
+                            f"the {name} of a parameter of shape {tuple(p.shape)} on {device} must be a contiguous "
+                            f"fp32 tensor of that shape there, got {t.dtype} {tuple(t.shape)} on {t.device} "
+                            f"contiguous={t.is_contiguous()}")
+                if p.numel() == 0:
+                    continue
+                rows.append((p, views[p], m, v, state, lr, beta1, beta2))
+                src.append(0 if g is None else g.data_ptr())
+                at += 1
+            spans.append((begin, at, beta1, beta2, group["eps"]))
+        for k, (p, g, m, v, state, lr, beta1, beta2) in enumerate(rows):     # every check has passed: advance
+            state["step"] += 1
+            step = float(state["step"])
+            rows[k] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) \
+                + bias_factors(lr, beta1, beta2, step)
+            touched += [p, g, m, v]
+        return rows, touched, spans, device, src, flat, views
+
     def _upload(self, host, device):
         """The table on ``device``: one asynchronous copy from a pinned buffer no earlier copy may still be reading."""
         slot = None
@@ -169,20 +268,37 @@ class Adam(torch.optim.Adam):
         return table
 
     @torch.no_grad()
-    def step(self, closure=None, *, max_norm=None):
+    def step(self, closure=None, *, max_norm=None, process_group=None):
         """One update of every parameter that has a gradient -> the total gradient norm before clipping as a 0-d device
-        tensor, or None without ``max_norm``.  ``closure`` is not supported (the reference's loop has none)."""
+        tensor, or None without ``max_norm``.  ``closure`` is not supported (the reference's loop has none).
+
+        ``process_group`` (a torch.distributed group, ``torch.distributed.group.WORLD`` for the default one; None:
+        this process alone, the path above): the gradients are averaged over the group's ranks first -- pack with
+        scale 1 / world into the flat bucket, one all-reduce, then the same launches over the bucket.  Every parameter
+        that requires grad is updated, one without a local gradient with the other ranks' mean (it contributes
+        zeros); afterwards ``p.grad`` is the parameter's view into the bucket, holding the averaged, clipped gradient
+        until the next step overwrites it.  The norm returned is that of the averaged gradient."""
         if closure is not None:
             raise ValueError("fastvocoder_amd.optim.Adam.step takes no closure")
         if max_norm is not None and not float(max_norm) >= 0.0:
             raise ValueError(f"max_norm must be a non-negative number, got {max_norm}")
-        rows, touched, spans, device = self._rows()
+        src = flat = views = None
+        if process_group is None:
+            rows, touched, spans, device = self._rows()
+        else:
+            rows, touched, spans, device, src, flat, views = self._rows_bucket()
         if not rows:
             return None
-        host, first = adam_table(rows)
+        host, first = adam_table(rows, src)
         n_tensors, n_chunks = len(rows), int(first[-1])
         with torch.cuda.device(device):
             table = self._upload(host, device)
+            if process_group is not None:
+                world = torch.distributed.get_world_size(process_group)
+                _native.grad_bucket_pack(table, n_tensors, n_chunks, float(np.float32(1.0) / np.float32(world)))
+                parallel.all_reduce_sum(flat, process_group)
+                for p, view in views.items():
+                    p.grad = view
             coef = norm = None
             if max_norm is not None:
                 need = _native.grad_sq_norm_workspace_floats(n_chunks)

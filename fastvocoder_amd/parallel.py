@@ -11,6 +11,9 @@ traffic is
                used concurrently) instead of a ring bound by one link.
 There is no all-reduce and no collective inside the generator.
 
+Data-parallel TRAINING (optim.Adam.step(process_group=), train.Trainer(process_group=)) adds one collective of its
+own, ``all_reduce_sum``: once per optimizer step over the flat gradient bucket, once per step over the scalars.
+
 Backends: "nccl" (RCCL) moves device tensors directly and needs one GPU per rank.  Under "gloo" device tensors are
 staged through the host (gloo's scatter / gather take CPU tensors only): that is how several ranks can share ONE GPU
 in tests (tests/test_gpu_multi.py: world_size 2 through the real generator on a 1-GPU box) and how the CPU tests run.
@@ -47,6 +50,26 @@ def shard_range(n_items, world_size, rank):
 def _staged(group, *tensors):
     """Device tensors have to travel through the host (gloo)?"""
     return dist.get_backend(group) == "gloo" and any(t is not None and t.is_cuda for t in tensors)
+
+
+_PINNED = {}     # (element count, dtype) -> pinned host tensor all_reduce_sum stages through
+
+
+def all_reduce_sum(tensor, group=None):
+    """``tensor`` becomes the sum of the ranks' tensors, in place -> ``tensor``.  One collective: under "nccl" RCCL
+    reduces the device memory itself and nothing touches the host; under "gloo" a device tensor travels through
+    pinned host memory (the rule of ``_staged``: how two ranks share ONE GPU in tests), which waits for the device.  ``tensor`` must be contiguous."""
+    if _staged(group, tensor):
+        key = (tensor.numel(), tensor.dtype)
+        host = _PINNED.get(key)
+        if host is None:
+            host = _PINNED[key] = torch.empty(tensor.numel(), dtype=tensor.dtype).pin_memory()
+        host.copy_(tensor.detach().view(-1))
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        tensor.detach().view(-1).copy_(host)
+    else:
+        dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=group)
+    return tensor
 
 
 def broadcast_weights(model, src=0, group=None):

@@ -23,9 +23,17 @@ parameters only: the basis is a constant of the training graph and gets no gradi
 it never applies, train.py:64, 329-331 -- which its ``clip_grad_norm_`` over ``model.parameters()`` does count; the
 norm here is the trunk's alone).  The ``transposedconv: False`` upsampler has no parameter gradient and is refused
 where the ``parameter_grad`` attribute refuses it; mixed precision is not part of this loop.
+
+Data-parallel training: ``Trainer(..., process_group=<a torch.distributed group>)`` hands the group to both optimizer
+steps (``optim.Adam.step(process_group=...)``: the gradients of the ranks' shards are averaged with one collective over
+one flat bucket per optimizer step) and, at the end of the step, all-reduces the stacked scalar vector once and divides
+it by the world size before the step's one host read: the dict then holds the means over the ranks.  There is no other
+collective; the generators and discriminators have no cross-batch op, so a step over ``world`` shards of ``B`` rows is
+the step over the ``world * B`` rows up to the rounding of the sums.  Learning rates are not rescaled.
 """
 import torch
 
+from . import parallel
 from .loss import Loss, discriminator_step_terms, generator_adversarial_terms, pqmf_synthesis
 from .optim import Adam
 
@@ -61,7 +69,7 @@ class Trainer:
     def __init__(self, model, discriminator, optimizer, discriminator_optimizer, scheduler=None,
                  discriminator_scheduler=None, pqmf=None, *, lambda_stft, use_feature_map_loss,
                  discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0, stack_grad=False,
-                 basis_grad=False):
+                 basis_grad=False, process_group=None):
         for opt, name in ((optimizer, "optimizer"), (discriminator_optimizer, "discriminator_optimizer")):
             if not isinstance(opt, Adam):
                 raise TypeError(f"{name} must be a fastvocoder_amd.optim.Adam (its step clips and updates in three "
@@ -84,6 +92,9 @@ class Trainer:
         self.vocoder_loss.differentiable = True
         self.samples_per_frame = samples_per_frame(model, pqmf)
         self.basis = hasattr(model, "basis_signal")
+        self.process_group = process_group
+        # the keyword is passed only when there is a group: any Adam subclass written against step(max_norm=) still works
+        self._step_kw = {} if process_group is None else {"process_group": process_group}
 
     def _waveform(self, est):
         """The generator's output as (B, T) full band: the PQMF synthesis of sub-bands, on their graph."""
@@ -92,7 +103,8 @@ class Trainer:
         return pqmf_synthesis(est, self.pqmf)[:, 0, :]
 
     def step(self, mel, wav, current_step, weight=None):
-        """mel (B, 80, T) and wav (B, T * samples_per_frame), fp32 device tensors -> {key: float for key in KEYS}:
+        """mel (B, 80, T) and wav (B, T * samples_per_frame), fp32 device tensors -> {key: float for key in KEYS}
+        (with a process group: this rank's shard of the batch, and the means over the ranks):
         the STFT loss (before lambda_stft), the generator's total, its adversarial and feature-map terms, the
         discriminator's loss (0.0 up to discriminator_train_start_steps) and the two gradient norms before clipping.
         Basis-MelGAN: ``weight`` (B, T * prod(upsample_scales), C), the target weights; the dict also holds "weight"
@@ -131,7 +143,7 @@ class Trainer:
                 fm = terms["feature_map"]
                 total = total + self.lambda_fm * fm
         total.backward()
-        grad_norm = self.optimizer.step(max_norm=self.grad_clip_thresh)
+        grad_norm = self.optimizer.step(max_norm=self.grad_clip_thresh, **self._step_kw)
         if self.scheduler is not None:
             self.scheduler.step()
 
@@ -146,7 +158,7 @@ class Trainer:
             d_loss = discriminator_step_terms(self.discriminator, est_for_d.unsqueeze(1), wav.unsqueeze(1),
                                               stft_grad=True, **kw)["discriminator"]
             d_loss.backward()
-            d_norm = self.discriminator_optimizer.step(max_norm=self.grad_clip_thresh)
+            d_norm = self.discriminator_optimizer.step(max_norm=self.grad_clip_thresh, **self._step_kw)
             if self.discriminator_scheduler is not None:
                 self.discriminator_scheduler.step()
 
@@ -159,4 +171,7 @@ class Trainer:
             # the reference's w_l: the weight loss while it is part of the total, 0 afterwards (train.py:86-89)
             values += [zero if weight_loss is None or adversarial_phase else weight_loss, average]
         scalars = torch.stack([t.detach().float().reshape(()) for t in values])
+        if self.process_group is not None:                        # the ranks' means
+            scalars = parallel.all_reduce_sum(scalars, self.process_group) / torch.distributed.get_world_size(
+                self.process_group)
         return dict(zip(keys, scalars.cpu().tolist()))            # the step's one read on the host

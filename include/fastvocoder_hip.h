@@ -1045,6 +1045,22 @@ int fv_grad_sq_norm(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, 
 int fv_adam_step(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int n_tensors, int64_t n_chunks,
                  const float* coef, double beta1, double beta2, double eps, void* stream);
 
+/*
+ * fv_grad_bucket_pack (data-parallel training; an addition under ABI 18, no existing entry changes): one launch over the
+ * same table copies every gradient into its span of a flat fp32 bucket, times `scale` (1 / world size), so that ONE
+ * collective over the bucket averages all gradients and fv_grad_sq_norm / fv_adam_step then read them from the same rows.
+ * tensors[r].g is the DESTINATION, row r's span inside the bucket; src[r] (an array of n_tensors pointers in device
+ * memory, 8-byte aligned) is the parameter's own gradient, n elements, or NULL for a span of zeros.  A span starts on a
+ * 16-byte boundary and is n rounded up to a multiple of 4 floats; the words past n are written as +0, so every word of
+ * a bucket laid out this way is written by the launch, whatever it held before.  Element i becomes scale * src[r][i],
+ * one fp32 rounding.  A source that is 16-byte aligned is read with 16-byte loads, any other with 4-byte loads of the
+ * same elements; the bits do not depend on it.  src[r] == tensors[r].g scales in place.  Only the g and n fields of a
+ * row are read; an entry whose row lies outside the table is skipped; no atomics.  A null or misaligned table or
+ * pointer array returns FV_ERR_INVALID_ARG.
+ */
+int fv_grad_bucket_pack(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int n_tensors, int64_t n_chunks,
+                        const float* const* src, float scale, void* stream);
+
 /* ------------------------------------------------------------------ *
  * whole-generator plans: an op list replayed over a caller-owned arena
  * ------------------------------------------------------------------ */
