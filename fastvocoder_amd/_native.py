@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "basis_grad.hip", "optim.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "basis_grad.hip", "basis_learn.hip", "optim.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -291,6 +291,10 @@ def lib():
     L.fv_basis_weight_l1_workspace_bytes.restype = i64
     L.fv_basis_weight_l1.argtypes = [vp, vp, vp, i, i, i, vp, ctypes.c_size_t, vp]
     L.fv_basis_weight_l1_grad.argtypes = [vp, vp, vp, vp, i, i, i, vp]
+    L.fv_basis_encode.argtypes = [vp, vp, vp, i, i64, i, i, vp]
+    L.fv_basis_learn_grad_workspace_bytes.argtypes = [i, i64, i, i]
+    L.fv_basis_learn_grad_workspace_bytes.restype = i64
+    L.fv_basis_learn_grad.argtypes = [vp, vp, vp, vp, vp, vp, i, i64, i, i, vp, ctypes.c_size_t, vp]
     L.fv_grad_sq_norm_workspace_bytes.argtypes = [i64]
     L.fv_grad_sq_norm_workspace_bytes.restype = i64
     L.fv_grad_sq_norm.argtypes = [vp, vp, i, i64, f, vp, ctypes.c_size_t, vp, vp]
@@ -1778,6 +1782,60 @@ def basis_weight_l1_grad(D, target, coef=None):
         check(lib().fv_basis_weight_l1_grad(_ptr(D, "D"), _ptr(target, "target"), _ptr(coef, "coef", True), _ptr(g), B, c,
                                             F, stream))
     return g
+
+
+# ---------------------------------------------------------------------------
+# learning the basis: the encoder and the whole backward of (encode, decode) (csrc/basis_learn.hip)
+# ---------------------------------------------------------------------------
+
+def _basis_learn_shapes(name, wav, enc):
+    if wav.dim() != 2 or enc.dim() != 2:
+        raise NativeError(f"{name}: wav [B,n] and enc [C,L] expected, got {tuple(wav.shape)} and {tuple(enc.shape)}")
+    return wav.shape[0], wav.shape[1], enc.shape[0], enc.shape[1]
+
+
+def basis_frames(n, L_):
+    """F = ceil(n / hop), hop = L / 2: the weight frames of n samples."""
+    hop = L_ // 2
+    return (n + hop - 1) // hop
+
+
+def basis_encode(wav, enc):
+    """wav [B,n], enc [C,L] -> W [B,C,F] = relu(conv1d(wav, enc, stride=L/2)) over the zero-extended waveform
+    (fv_basis_encode, one launch)."""
+    B, n, c, L_ = _basis_learn_shapes("basis_encode", wav, enc)
+    W = torch.empty((B, c, basis_frames(n, L_) if L_ >= 2 else 0), dtype=torch.float32, device=wav.device)
+    with _on(wav, enc, W) as stream:
+        check(lib().fv_basis_encode(_ptr(wav, "wav"), _ptr(enc, "enc"), _ptr(W), B, n, c, L_, stream))
+    return W
+
+
+def basis_learn_grad(wav, g_est, W, basis, want_enc=True, want_basis=True, workspace=None):
+    """The backward of est = crop(overlap_add(basis W)), W = basis_encode(wav, enc), in one launch and a combine
+    (fv_basis_learn_grad): wav [B,n], g_est [B, F L/2], W [B,C,F], basis [L,C] -> (d_enc [C,L] or None,
+    d_basis [L,C] or None).  ``workspace``: a float32 device tensor of at least the entry's size, for a test."""
+    if W.dim() != 3 or basis.dim() != 2 or wav.dim() != 2 or basis.shape[1] != W.shape[1] or wav.shape[0] != W.shape[0]:
+        raise NativeError(f"basis_learn_grad: wav [B,n], W [B,C,F] and basis [L,C] expected, got {tuple(wav.shape)}, "
+                          f"{tuple(W.shape)} and {tuple(basis.shape)}")
+    (B, n), c, L_ = wav.shape, W.shape[1], basis.shape[0]
+    F = basis_frames(n, L_) if L_ >= 2 else 0
+    if W.shape[2] != F or tuple(g_est.shape) != (B, F * (L_ // 2)):
+        raise NativeError(f"basis_learn_grad: W {(B, c, F)} and g_est {(B, F * (L_ // 2))} expected, got "
+                          f"{tuple(W.shape)} and {tuple(g_est.shape)}")
+    if not (want_enc or want_basis):
+        return None, None
+    nbytes = lib().fv_basis_learn_grad_workspace_bytes(B, n, c, L_)
+    if nbytes < 0:
+        check(int(nbytes))
+    if workspace is None:
+        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=W.device)
+    d_enc = torch.empty((c, L_), dtype=torch.float32, device=W.device) if want_enc else None
+    d_basis = torch.empty((L_, c), dtype=torch.float32, device=W.device) if want_basis else None
+    with _on(wav, g_est, W, basis, d_enc, d_basis, workspace) as stream:
+        check(lib().fv_basis_learn_grad(_ptr(wav, "wav"), _ptr(g_est, "g_est"), _ptr(W, "W"), _ptr(basis, "basis"),
+                                        _ptr(d_enc, "d_enc", True), _ptr(d_basis, "d_basis", True), B, n, c, L_,
+                                        workspace.data_ptr(), workspace.numel() * 4, stream))
+    return d_enc, d_basis
 
 
 # ---------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""``MODE=<train|synthesize|test|publish|preprocess|evaluation> python -m fastvocoder_amd.bin.launcher --flags``
+"""``MODE=<train|basis|synthesize|test|publish|preprocess|evaluation> python -m fastvocoder_amd.bin.launcher --flags``
 -- the reference's $MODE dispatch (bin/launcher.py:7-19): training (HiFi-GAN and
-Multiband-HiFi-GAN), the inference-side modes, the dataset preparation and the evaluation."""
+Multiband-HiFi-GAN), learning Basis-MelGAN's basis and target weights, the inference-side modes, the dataset
+preparation and the evaluation."""
 import os
 import sys
 
@@ -25,8 +26,11 @@ def main():
     elif mode == "train":
         from .train import run_train
         run_train()
+    elif mode == "basis":
+        from .basis import run_basis
+        run_basis()
     else:
-        sys.exit("set MODE=train | synthesize | test | publish | preprocess | evaluation")
+        sys.exit("set MODE=train | basis | synthesize | test | publish | preprocess | evaluation")
 
 
 if __name__ == "__main__":

@@ -995,6 +995,33 @@ int fv_basis_weight_l1_grad(const float* D, const float* target, const float* co
                             void* stream);
 
 /*
+ * Learning the basis itself: Conv-TasNet's encoder / decoder pair with no separator in between, which produces the
+ * basis_signal_weight.npy and weight/ files that Basis-MelGAN trains against; additions of ABI 18, no existing entry
+ * changes.  hop = L / 2, F = ceil(n / hop).  The decoder is fv_pack_basis + fv_basis_ola, cut to F hop samples.  Exact
+ * fp32 on the fp32 matrix instructions, no atomics, workgroups never wait on each other, identical calls return
+ * identical bits.  Every entry checks its arguments before it touches a pointer: B, n or C < 1, L odd or < 2, a null
+ * tensor or a result aliasing an input return FV_ERR_INVALID_ARG; L > 256, B > 65535, F >= 2^31 or more than 2^40
+ * elements FV_ERR_UNSUPPORTED.  All offsets are 64-bit.
+ *
+ * fv_basis_encode:     W[b, c, f] = relu(sum_{j < L} enc[c, j] wav[b, f hop + j]), samples at or beyond n read as 0.
+ *     wav [B, n], enc [C, L] (a Conv1d(1, C, L, stride = hop, bias = False) weight as it lies in memory), W [B, C, F]:
+ *     the trunk's native layout, whose transposed view is the generator's weight [B, F, C].  One launch.
+ * fv_basis_learn_grad: the adjoint of est = crop(overlap_add(basis W)) and of the encoder, from g_est [B, F hop]:
+ *         G[j, f]       = g_est[b, f hop + j], 0 at or beyond F hop (the taps behind the crop get nothing)
+ *         gW[c, f]      = [W[b, c, f] > 0] sum_j basis[j, c] G[j, f]               (registers and LDS only)
+ *         d_basis[j, c] = sum_{b, f} G[j, f] W[b, c, f]                             [L, C]
+ *         d_enc[c, j]   = sum_{b, f} gW[c, f] wav[b, f hop + j]                     [C, L]
+ *     d_enc or d_basis may be NULL (a frozen parameter: its GEMM is not run), not both.  One launch writes S records
+ *     (S a function of the shape alone), a combine launch adds them in ascending order.  workspace: at least
+ *     fv_basis_learn_grad_workspace_bytes(B, n, C, L) bytes, 4-byte aligned; its contents on entry do not matter.
+ */
+int fv_basis_encode(const float* wav, const float* enc, float* W, int B, int64_t n, int C, int L, void* stream);
+int64_t fv_basis_learn_grad_workspace_bytes(int B, int64_t n, int C, int L);
+int fv_basis_learn_grad(const float* wav, const float* g_est, const float* W, const float* basis, float* d_enc,
+                        float* d_basis, int B, int64_t n, int C, int L, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/*
  * Gradient clipping and the Adam update of a whole parameter set (nn.utils.clip_grad_norm_ + Adam.step() of
  * bin/train.py:126-136 and 176-186; the reference names the fused form itself, apex.optimizers.FusedAdam,
  * train.py:338); additions of ABI 18, no existing entry changes.  Three launches for any number of tensors, exact fp32
