@@ -24,7 +24,7 @@ SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_
           [f"conv_inst_s{i}.hip" for i in range(6)]
 HEADERS = ["fv_internal.h", "conv_kernels.hpp", "pair_kernels.hpp", "pair_inst.hpp", "pairh_kernels.hpp",
            "pairh_inst.hpp", "convh_kernels.hpp", "convh_inst.hpp", "convr_kernels.hpp",
-           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp", "basis_grad_host.hpp"]
+           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp", "basis_grad_host.hpp", "wgrad_tile.hpp"]
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)
@@ -1408,14 +1408,35 @@ def grouped_conv1d_input_grad(g_up, g_map, y, w, cin, tin, k, stride, pad, slope
     return dx
 
 
-def conv_weight_grad_workspace_floats(grouped, B, cin, cout, tin, k, stride=1, pad=0, pad_mode=PAD_ZERO):
-    """fp32 words of workspace conv1d_weight_grad (``grouped`` False) or grouped_conv1d_weight_grad needs for these
-    shapes (fv_conv_weight_grad_workspace_bytes); raises for shapes the entries refuse."""
-    need = lib().fv_conv_weight_grad_workspace_bytes(int(bool(grouped)), int(B), int(cin), int(cout), int(tin), int(k),
-                                                     int(stride), int(pad), int(pad_mode))
+def _workspace_floats(need):
+    """fp32 words of a workspace of ``need`` bytes as a *_workspace_bytes entry returns them (negative: its refusal)."""
     if need < 0:
         check(int(need))
     return (need + 3) // 4
+
+
+def _weight_grad_call(name, entry, inputs, want_dw, want_db, dw_shape, db_shape, args, workspace, floats):
+    """What the weight-gradient wrappers share once their shapes are checked: ``inputs`` the (name, tensor) of the
+    gradient and of the layer's input, ``floats()`` the size of the fresh workspace when none is given, and the call
+    ``entry(g, x, dw, db, *args, workspace, bytes, stream)`` -> (dw or None, db or None)."""
+    if not (want_dw or want_db):
+        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
+    dev = inputs[0][1].device
+    if workspace is None:
+        workspace = torch.empty(floats(), dtype=torch.float32, device=dev)
+    dw = torch.empty(dw_shape, dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty(db_shape, dtype=torch.float32, device=dev) if want_db else None
+    with _on(*(t for _, t in inputs), workspace, dw, db) as stream:
+        check(getattr(lib(), entry)(*(_ptr(t, n) for n, t in inputs), _ptr(dw, "dw", True), _ptr(db, "db", True), *args,
+                                    _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
+    return dw, db
+
+
+def conv_weight_grad_workspace_floats(grouped, B, cin, cout, tin, k, stride=1, pad=0, pad_mode=PAD_ZERO):
+    """fp32 words of workspace conv1d_weight_grad (``grouped`` False) or grouped_conv1d_weight_grad needs for these
+    shapes (fv_conv_weight_grad_workspace_bytes); raises for shapes the entries refuse."""
+    return _workspace_floats(lib().fv_conv_weight_grad_workspace_bytes(
+        int(bool(grouped)), int(B), int(cin), int(cout), int(tin), int(k), int(stride), int(pad), int(pad_mode)))
 
 
 def _weight_grad(name, grouped, g_pre, x, k, stride, pad, pad_mode, want_dw, want_db, workspace):
@@ -1423,27 +1444,16 @@ def _weight_grad(name, grouped, g_pre, x, k, stride, pad, pad_mode, want_dw, wan
     if g_pre.dim() != 3 or x.dim() != 3 or g_pre.shape[0] != x.shape[0]:
         raise NativeError(f"{name}: g_pre [B,Cout,Tout] and x [B,Cin,Tin] expected, got {tuple(g_pre.shape)} and "
                           f"{tuple(x.shape)}")
-    if not (want_dw or want_db):
-        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
     B, cout, tout = g_pre.shape
     cin, tin = x.shape[1], x.shape[2]
     k, stride, pad = int(k), int(stride), int(pad)
     if stride > 0 and tin + 2 * pad >= k and tout != (tin + 2 * pad - k) // stride + 1:
         raise NativeError(f"{name}: {tout} output times do not belong to an input of {tin} samples")
-    dev = g_pre.device
-    if workspace is None:
-        workspace = torch.empty(conv_weight_grad_workspace_floats(grouped, B, cin, cout, tin, k, stride, pad, pad_mode),
-                                dtype=torch.float32, device=dev)
-    dw = torch.empty((cout, 4 if grouped else cin, k), dtype=torch.float32, device=dev) if want_dw else None
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
-    with _on(g_pre, x, workspace, dw, db) as stream:
-        ptrs = (_ptr(g_pre, "g_pre"), _ptr(x, "x"), _ptr(dw, "dw", True), _ptr(db, "db", True))
-        ws = (_ptr(workspace, "workspace"), workspace.numel() * 4, stream)
-        if grouped:
-            check(lib().fv_grouped_conv1d_weight_grad(*ptrs, B, cin, cout, tin, k, stride, pad, *ws))
-        else:
-            check(lib().fv_conv1d_weight_grad(*ptrs, B, cin, cout, tin, k, pad, int(pad_mode), *ws))
-    return dw, db
+    return _weight_grad_call(
+        name, "fv_grouped_conv1d_weight_grad" if grouped else "fv_conv1d_weight_grad", (("g_pre", g_pre), ("x", x)),
+        want_dw, want_db, (cout, 4 if grouped else cin, k), (cout,),
+        (B, cin, cout, tin, k, stride, pad) if grouped else (B, cin, cout, tin, k, pad, int(pad_mode)), workspace,
+        lambda: conv_weight_grad_workspace_floats(grouped, B, cin, cout, tin, k, stride, pad, pad_mode))
 
 
 def conv1d_weight_grad(g_pre, x, k, pad=0, pad_mode=PAD_ZERO, want_dw=True, want_db=False, workspace=None):
@@ -1468,11 +1478,8 @@ PERIOD_WGRAD_CHUNK = 1024    # ... of its plain path and of the first layer's ke
 def period_conv_weight_grad_workspace_floats(B, cin, cout, H, period, k, stride):
     """fp32 words of workspace period_conv_weight_grad needs for these shapes
     (fv_period_conv_weight_grad_workspace_bytes); raises for shapes the entry refuses."""
-    need = lib().fv_period_conv_weight_grad_workspace_bytes(int(B), int(cin), int(cout), int(H), int(period), int(k),
-                                                            int(stride))
-    if need < 0:
-        check(int(need))
-    return (need + 3) // 4
+    return _workspace_floats(lib().fv_period_conv_weight_grad_workspace_bytes(
+        int(B), int(cin), int(cout), int(H), int(period), int(k), int(stride)))
 
 
 def period_conv_weight_grad(g_pre, x, k, stride, want_dw=True, want_db=False, workspace=None):
@@ -1483,24 +1490,15 @@ def period_conv_weight_grad(g_pre, x, k, stride, want_dw=True, want_db=False, wo
     if g_pre.dim() != 4 or x.dim() != 4 or g_pre.shape[0] != x.shape[0] or g_pre.shape[3] != x.shape[3]:
         raise NativeError(f"period_conv_weight_grad: g_pre [B,Cout,H',p] and x [B,Cin,H,p] expected, got "
                           f"{tuple(g_pre.shape)} and {tuple(x.shape)}")
-    if not (want_dw or want_db):
-        raise NativeError("period_conv_weight_grad: neither the weight nor the bias gradient is asked for")
     B, cout, hout, p = g_pre.shape
     cin, H = x.shape[1], x.shape[2]
     k, stride = int(k), int(stride)
     if stride > 0 and H > 0 and hout != (H - 1) // stride + 1:
         raise NativeError(f"period_conv_weight_grad: {hout} output rows do not belong to an input of {H} rows")
-    dev = g_pre.device
-    if workspace is None:
-        workspace = torch.empty(period_conv_weight_grad_workspace_floats(B, cin, cout, H, p, k, stride),
-                                dtype=torch.float32, device=dev)
-    dw = torch.empty((cout, cin, k), dtype=torch.float32, device=dev) if want_dw else None
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
-    with _on(g_pre, x, workspace, dw, db) as stream:
-        check(lib().fv_period_conv_weight_grad(_ptr(g_pre, "g_pre"), _ptr(x, "x"), _ptr(dw, "dw", True),
-                                               _ptr(db, "db", True), B, cin, cout, H, p, k, stride,
-                                               _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
-    return dw, db
+    return _weight_grad_call(
+        "period_conv_weight_grad", "fv_period_conv_weight_grad", (("g_pre", g_pre), ("x", x)), want_dw, want_db,
+        (cout, cin, k), (cout,), (B, cin, cout, H, p, k, stride), workspace,
+        lambda: period_conv_weight_grad_workspace_floats(B, cin, cout, H, p, k, stride))
 
 
 def mpd_first_weight_grad(g_pre, x, want_dw=True, want_db=False, workspace=None):
@@ -1509,26 +1507,14 @@ def mpd_first_weight_grad(g_pre, x, want_dw=True, want_db=False, workspace=None)
     if g_pre.dim() != 4 or g_pre.shape[1] != 32 or x.dim() != 3 or x.shape[1] != 1 or x.shape[0] != g_pre.shape[0]:
         raise NativeError(f"mpd_first_weight_grad: g_pre [B,32,H1,p] and x [B,1,T] expected, got "
                           f"{tuple(g_pre.shape)} and {tuple(x.shape)}")
-    if not (want_dw or want_db):
-        raise NativeError("mpd_first_weight_grad: neither the weight nor the bias gradient is asked for")
     B, _, h1, p = g_pre.shape
     T = x.shape[2]
     H = (T + mpd_reflect_tail(T, p)) // p if p > 0 else 0
     if T < 1 or h1 != (H - 1) // 3 + 1:
         raise NativeError(f"mpd_first_weight_grad: {h1} output rows do not belong to a waveform of {T} samples")
-    dev = g_pre.device
-    if workspace is None:
-        need = lib().fv_mpd_first_weight_grad_workspace_bytes(B, T, p)
-        if need < 0:
-            check(int(need))
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
-    dw = torch.empty((32, 5), dtype=torch.float32, device=dev) if want_dw else None
-    db = torch.empty((32,), dtype=torch.float32, device=dev) if want_db else None
-    with _on(g_pre, x, workspace, dw, db) as stream:
-        check(lib().fv_mpd_first_weight_grad(_ptr(g_pre, "g_pre"), _ptr(x, "x"), _ptr(dw, "dw", True),
-                                             _ptr(db, "db", True), B, T, p, _ptr(workspace, "workspace"),
-                                             workspace.numel() * 4, stream))
-    return dw, db
+    return _weight_grad_call(
+        "mpd_first_weight_grad", "fv_mpd_first_weight_grad", (("g_pre", g_pre), ("x", x)), want_dw, want_db, (32, 5),
+        (32,), (B, T, p), workspace, lambda: _workspace_floats(lib().fv_mpd_first_weight_grad_workspace_bytes(B, T, p)))
 
 
 def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):
@@ -1554,12 +1540,8 @@ def conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil=1, pad
     raises for shapes the entry refuses."""
     args = (int(B), int(cin), int(cout), int(tin), int(k), int(dil), int(pad))
     if pad_mode is None:
-        need = lib().fv_conv1d_weight_grad_dilated_workspace_bytes(*args)
-    else:
-        need = lib().fv_conv1d_weight_grad_dilated_mode_workspace_bytes(*args, int(pad_mode))
-    if need < 0:
-        check(int(need))
-    return (need + 3) // 4
+        return _workspace_floats(lib().fv_conv1d_weight_grad_dilated_workspace_bytes(*args))
+    return _workspace_floats(lib().fv_conv1d_weight_grad_dilated_mode_workspace_bytes(*args, int(pad_mode)))
 
 
 def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db=False, workspace=None, pad_mode=None):
@@ -1572,28 +1554,17 @@ def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db
     if g_pre.dim() != 3 or xa.dim() != 3 or g_pre.shape[0] != xa.shape[0]:
         raise NativeError(f"{name}: g_pre [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g_pre.shape)} and "
                           f"{tuple(xa.shape)}")
-    if not (want_dw or want_db):
-        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
     B, cout, tout = g_pre.shape
     cin, tin = xa.shape[1], xa.shape[2]
     k, dil, pad = int(k), int(dil), int(pad)
     if k > 0 and dil > 0 and tin + 2 * pad - dil * (k - 1) >= 1 and tout != tin + 2 * pad - dil * (k - 1):
         raise NativeError(f"{name}: {tout} output times do not belong to an input of {tin} samples")
-    dev = g_pre.device
-    if workspace is None:
-        workspace = torch.empty(conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad, pad_mode),
-                                dtype=torch.float32, device=dev)
-    dw = torch.empty((cout, cin, k), dtype=torch.float32, device=dev) if want_dw else None
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
-    with _on(g_pre, xa, workspace, dw, db) as stream:
-        head = (_ptr(g_pre, "g_pre"), _ptr(xa, "xa"), _ptr(dw, "dw", True), _ptr(db, "db", True), B, cin, cout, tin, k,
-                dil, pad)
-        tail = (_ptr(workspace, "workspace"), workspace.numel() * 4, stream)
-        if pad_mode is None:
-            check(lib().fv_conv1d_weight_grad_dilated(*head, *tail))
-        else:
-            check(lib().fv_conv1d_weight_grad_dilated_mode(*head, int(pad_mode), *tail))
-    return dw, db
+    args = (B, cin, cout, tin, k, dil, pad)
+    return _weight_grad_call(
+        name, "fv_conv1d_weight_grad_dilated" if pad_mode is None else "fv_conv1d_weight_grad_dilated_mode",
+        (("g_pre", g_pre), ("xa", xa)), want_dw, want_db, (cout, cin, k), (cout,),
+        args if pad_mode is None else args + (int(pad_mode),), workspace,
+        lambda: conv1d_weight_grad_dilated_workspace_floats(*args, pad_mode))
 
 
 def conv1d_input_grad_reflect(g, wt, tin, dil=1, pad=0):
@@ -1643,11 +1614,8 @@ def conv_transpose1d_input_grad(g, w, tin, stride, pad, out_pad=0):
 def conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, stride, pad, out_pad=0):
     """fp32 words of workspace conv_transpose1d_weight_grad needs for these shapes
     (fv_conv_transpose1d_weight_grad_workspace_bytes); raises for shapes the entry refuses."""
-    need = lib().fv_conv_transpose1d_weight_grad_workspace_bytes(int(B), int(cin), int(cout), int(tin), int(k),
-                                                                 int(stride), int(pad), int(out_pad))
-    if need < 0:
-        check(int(need))
-    return (need + 3) // 4
+    return _workspace_floats(lib().fv_conv_transpose1d_weight_grad_workspace_bytes(
+        int(B), int(cin), int(cout), int(tin), int(k), int(stride), int(pad), int(out_pad)))
 
 
 def conv_transpose1d_weight_grad(g, xa, k, stride, pad, out_pad=0, want_dw=True, want_db=False, workspace=None):
@@ -1658,22 +1626,13 @@ def conv_transpose1d_weight_grad(g, xa, k, stride, pad, out_pad=0, want_dw=True,
     if xa.dim() != 3 or g.dim() != 3 or g.shape[0] != xa.shape[0]:
         raise NativeError(f"{name}: g [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g.shape)} and "
                           f"{tuple(xa.shape)}")
-    if not (want_dw or want_db):
-        raise NativeError(f"{name}: neither the weight nor the bias gradient is asked for")
     B, cin, tin = xa.shape
     _convt_grad_shapes(name, g, tin, None, k, stride, pad, out_pad)
     cout = g.shape[1]
-    dev = g.device
-    if workspace is None:
-        workspace = torch.empty(conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, stride, pad, out_pad),
-                                dtype=torch.float32, device=dev)
-    dw = torch.empty((cin, cout, k), dtype=torch.float32, device=dev) if want_dw else None
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_db else None
-    with _on(g, xa, workspace, dw, db) as stream:
-        check(lib().fv_conv_transpose1d_weight_grad(_ptr(g, "g"), _ptr(xa, "xa"), _ptr(dw, "dw", True),
-                                                    _ptr(db, "db", True), B, cin, cout, tin, k, stride, pad, out_pad,
-                                                    _ptr(workspace, "workspace"), workspace.numel() * 4, stream))
-    return dw, db
+    args = (B, cin, cout, tin, k, stride, pad, out_pad)
+    return _weight_grad_call(name, "fv_conv_transpose1d_weight_grad", (("g", g), ("xa", xa)), want_dw, want_db,
+                             (cin, cout, k), (cout,), args, workspace,
+                             lambda: conv_transpose1d_weight_grad_workspace_floats(*args))
 
 
 def _same_shape(name, *tensors):

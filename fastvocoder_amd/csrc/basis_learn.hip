@@ -23,13 +23,13 @@
 //     accesses of sw put a group's 32 lanes on 32 consecutive words of one row: all conflict-free; the gW step reads
 //     sg at lane stride hop as the encoder does.  L > 32 recomputes gW once per tap tile.  The two sums stay in the
 //     accumulators over the split's units and leave as one record [d_enc | d_basis]; wgrad_combine_kernel adds the
-//     records in ascending order (disc_wgrad.hip).  Every record word the combine reads is written by this launch.
+//     records in ascending order (wgrad_tile.hpp).  Every record word the combine reads is written by this launch.
 #include <math.h>
 
 #include <type_traits>
 
 #include "basis_grad_host.hpp"
-#include "fv_internal.h"
+#include "wgrad_tile.hpp"
 
 namespace fv {
 
@@ -263,10 +263,9 @@ int fv_basis_learn_grad(const float* wav, const float* g_est, const float* W, co
     if (d_enc == d_basis) return fail(FV_ERR_INVALID_ARG, "basis_learn_grad: d_enc aliases d_basis");
     LgPlan p;
     learn_grad_plan(B, C, F, L, &p);
-    const size_t need = sizeof(float) * (size_t)p.S * (size_t)p.R;
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
-        return fail(FV_ERR_INVALID_ARG, "basis_learn_grad: workspace of %zu bytes, needs %zu (4-byte aligned)",
-                    workspace_bytes, need);
+    if (int rc = wg_workspace_check("basis_learn_grad", workspace, workspace_bytes,
+                                    sizeof(float) * (size_t)p.S * (size_t)p.R))
+        return rc;
     LgArgs a = {wav, g_est, W, basis, static_cast<float*>(workspace), n, (int64_t)F * p.hop, p.U, p.R,
                 C, F, L, p.hop, p.S, p.nft, d_enc != nullptr, d_basis != nullptr};
     hipLaunchKernelGGL(basis_learn_grad_kernel, dim3(p.gx, p.gy, (unsigned)p.S), dim3(kLeThreads), p.lds_bytes,

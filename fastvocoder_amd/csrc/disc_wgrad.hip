@@ -1,19 +1,17 @@
 // Parameter gradient of the multi-scale discriminator (reference: model/discriminator/msd.py; bin/train.py:143-188 the
 // discriminator's update; include/fastvocoder_hip.h fv_conv1d_weight_grad, fv_grouped_conv1d_weight_grad,
-// fv_weight_norm_grad).  Exact fp32, no atomics, no waiting between workgroups: the reduction over (b, t) is cut into
-// UNITS (one row b, one run of output times), the units are dealt to `S` splits in contiguous ranges, every block sums
-// its units in ascending order and writes its partial sums to the workspace record of its split
-//     ws[s][0 .. Cout N)  the weight gradient,   ws[s][Cout N .. Cout N + Cout)  the bias gradient,
-// and a second launch (combine_kernel) adds the S records, s ascending.  S is a function of the shape alone, so
-// identical calls give identical bits.  Every word of a record that the second launch reads is written by the first.
+// fv_weight_norm_grad).  Exact fp32 in the split / record / combine scheme of wgrad_tile.hpp: a UNIT is one row b and
+// one run of output times, and the record of a split is
+//     ws[s][0 .. Cout N)  the weight gradient,   ws[s][Cout N .. Cout N + Cout)  the bias gradient.
+// Every word of a record that the second launch (wgrad_combine_kernel, here) reads is written by the first.
 //
-// dense_wgrad_mfma_kernel (Cout >= 64 and Cin k >= 64): dW as the GEMM [Cout] x [Cin k] over B Tout on
-// v_mfma_f32_32x32x2_f32.  A block owns 128 output channels x 128 columns n = ci k + j; its 4 waves are 2 x 2, each
-// 2 x 2 fragments of 32 x 32.  Per unit (32 output times) the gradient tile gs[128][32 (+1)] and the input rows
-// xs[ci][32 + k - 1 (+1)] of the at most 127 / k + 2 channels the columns touch are staged in LDS -- padding by
-// indexing, never materialised -- and lane l feeds A = gs[co][t + (l >> 5)], B = xs[ci][t + j + (l >> 5)].  The row
-// strides 33 and 32 + k (congruent to k modulo 32) keep both operand reads free of bank conflicts.  Each result is one
-// k-ordered fmaf chain over its units' times.
+// dense_wgrad_mfma_kernel (Cout >= 64 and Cin k >= 64): dW as the GEMM [Cout] x [Cin k] over B Tout on WgTile<128>
+// (wgrad_tile.hpp): a block owns 128 output channels x 128 columns n = ci k + j.  Per unit (32 output times) the
+// gradient tile gs[128][32 (+1)] and the input rows xs[ci][32 + k - 1 (+1)] of the at most 127 / k + 2 channels the
+// columns touch are staged in LDS -- padding by indexing, never materialised -- and lane l feeds
+// A = gs[co][t + (l >> 5)], B = xs[ci][t + j + (l >> 5)]: the B operand is a span read once, not a [column][step]
+// tile, so the kernel sets the tile's off_b itself.  The row strides 33 and 32 + k (congruent to k modulo 32) keep both
+// operand reads free of bank conflicts.  Each result is one k-ordered fmaf chain over its units' times.
 //
 // dense_wgrad_plain_kernel (every other dense shape: the 1-channel first layer, the 1-channel score layer, channel
 // counts below a tile): a block owns one (co, ci) and 8 taps at a time; its 256 threads stride over the times of the
@@ -26,22 +24,26 @@
 // broadcast per 4 outputs) and the 4 input rows as xs[ci][(TT - 1) s + k] (lanes read consecutive words).
 #include <math.h>
 
-#include "fv_internal.h"
+#include "wgrad_tile.hpp"
 
 namespace fv {
 
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kWgThreads = 256;
 constexpr int kWgTaps = 8;          // plain kernel: taps per pass
 constexpr int kWgChunk = 1024;      // plain kernel: output times per unit
-constexpr int kWmTile = 128;        // mfma kernel: output channels and columns per block
-constexpr int kWmTK = 32;           // mfma kernel: output times per unit
-constexpr int kWmGS = kWmTK + 1;    // row stride of gs
+constexpr int kWmGS = WgTile<kWgNT>::STR;   // mfma kernel (128 output channels x 128 columns, units of 32 times): row stride of gs
 constexpr int kWgTT = 64;           // grouped kernel: output times per unit (halved until the tile fits LDS)
 constexpr int kWgBlocks = 1024;     // blocks a launch aims at (512 for the mfma kernel: its blocks are large)
 
 // xpad[q] of a row of Tin samples padded by `pad` on both sides (zeros, or mirrored without the edge sample)
+struct WgArgs {
+    const float* g;       // [B, Cout, Tout]
+    const float* x;       // [B, Cin, Tin]
+    float* ws;            // [S][R], R = Cout N + Cout
+    WgSplit sp;
+    int Cin, Cout, Tin, Tout, k, pad, reflect, stride;
+    int with_bias;
+};
+
 __device__ __forceinline__ float wg_xpad(const float* __restrict__ row, int q, int Tin, int pad, int reflect) {
     if (q < 0 || q >= Tin + 2 * pad) return 0.f;
     int p = q - pad;
@@ -59,8 +61,8 @@ __device__ __forceinline__ float wg_xpad(const float* __restrict__ row, int q, i
 __global__ __launch_bounds__(kWgThreads) void dense_wgrad_plain_kernel(WgArgs a) {
     __shared__ float part[4];
     const int co = blockIdx.x / a.Cin, ci = blockIdx.x % a.Cin, s = blockIdx.z;
-    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
-    float* rec = a.ws + (size_t)s * a.R;
+    const int64_t u0 = (int64_t)s * a.sp.U / a.sp.S, u1 = (int64_t)(s + 1) * a.sp.U / a.sp.S;
+    float* rec = a.ws + (size_t)s * a.sp.R;
     const bool bias = a.with_bias && ci == 0;
     for (int j0 = 0; j0 < a.k; j0 += kWgTaps) {
         float acc[kWgTaps];
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(kWgThreads) void dense_wgrad_plain_kernel(WgArgs a)
         for (int jj = 0; jj < kWgTaps; ++jj) acc[jj] = 0.f;
         float bsum = 0.f;
         for (int64_t u = u0; u < u1; ++u) {
-            const int b = (int)(u / a.nch), c = (int)(u % a.nch);
+            const int b = (int)(u / a.sp.nch), c = (int)(u % a.sp.nch);
             const float* gr = a.g + ((size_t)b * a.Cout + co) * a.Tout;
             const float* xr = a.x + ((size_t)b * a.Cin + ci) * a.Tin;
             const int t1 = a.Tout - c * kWgChunk < kWgChunk ? a.Tout : (c + 1) * kWgChunk;
@@ -97,35 +99,27 @@ __global__ __launch_bounds__(kWgThreads) void dense_wgrad_plain_kernel(WgArgs a)
 __global__ __launch_bounds__(kWgThreads) void dense_wgrad_mfma_kernel(WgArgs a) {
     extern __shared__ float lds[];
     float* gs = lds;
-    float* xs = lds + kWmTile * kWmGS;
-    const int k = a.k, W = kWmTK + k, N = a.Cin * k;
-    const int n0 = blockIdx.x * kWmTile, co0 = blockIdx.y * kWmTile, s = blockIdx.z;
-    const int n_last = n0 + kWmTile - 1 < N - 1 ? n0 + kWmTile - 1 : N - 1;
+    float* xs = lds + kWgNT * kWmGS;
+    const int k = a.k, W = kWgTK + k, N = a.Cin * k;
+    const int n0 = blockIdx.x * kWgNT, co0 = blockIdx.y * kWgNT, s = blockIdx.z;
+    const int n_last = n0 + kWgNT - 1 < N - 1 ? n0 + kWgNT - 1 : N - 1;
     const int ci_lo = n0 / k, nci = n_last / k - ci_lo + 1;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int lm = lane & 31, kq = lane >> 5;
-    int off_a[2], off_b[2];
+    const int tid = threadIdx.x;
+    WgTile<kWgNT> tile;
+    tile.init();
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
-        off_a[f] = (wm * 64 + f * 32 + lm) * kWmGS + kq;
-        int n = n0 + wn * 64 + f * 32 + lm;
+    for (int h = 0; h < 2; ++h) {
+        int n = n0 + tile.col(h);
         if (n > n_last) n = n_last;                       // (a column beyond N: any staged word; never stored)
-        off_b[f] = (n / k - ci_lo) * W + n % k + kq;
+        tile.off_b[h] = (n / k - ci_lo) * W + n % k + tile.kq;
     }
-    wg_f32x16 acc[2][2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[f][h][e] = 0.f;
     float bsum = 0.f;
-    const bool bias = a.with_bias && blockIdx.x == 0 && tid < kWmTile;
-    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
+    const bool bias = a.with_bias && blockIdx.x == 0 && tid < kWgNT;
+    const int64_t u0 = (int64_t)s * a.sp.U / a.sp.S, u1 = (int64_t)(s + 1) * a.sp.U / a.sp.S;
     for (int64_t u = u0; u < u1; ++u) {
-        const int b = (int)(u / a.nch), t0 = (int)(u % a.nch) * kWmTK;
+        const int b = (int)(u / a.sp.nch), t0 = (int)(u % a.sp.nch) * kWgTK;
         __syncthreads();                                  // the previous unit's reads are done
-        for (int i = tid; i < kWmTile * kWmTK; i += kWgThreads) {
+        for (int i = tid; i < kWgNT * kWgTK; i += kWgThreads) {
             const int row = i >> 5, c = i & 31, co = co0 + row, t = t0 + c;
             gs[row * kWmGS + c] = (co < a.Cout && t < a.Tout) ? a.g[((size_t)b * a.Cout + co) * a.Tout + t] : 0.f;
         }
@@ -134,33 +128,13 @@ __global__ __launch_bounds__(kWgThreads) void dense_wgrad_mfma_kernel(WgArgs a) 
             xs[row * W + c] = wg_xpad(a.x + ((size_t)b * a.Cin + ci_lo + row) * a.Tin, t0 + c, a.Tin, a.pad, a.reflect);
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kWmTK; kk += 2) {
-            const float a0 = gs[off_a[0] + kk], a1 = gs[off_a[1] + kk];
-            const float b0 = xs[off_b[0] + kk], b1 = xs[off_b[1] + kk];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        tile.mma(gs, xs);
         if (bias)
 #pragma unroll
-            for (int c = 0; c < kWmTK; ++c) bsum += gs[tid * kWmGS + c];
+            for (int c = 0; c < kWgTK; ++c) bsum += gs[tid * kWmGS + c];
     }
-    float* rec = a.ws + (size_t)s * a.R;
-    // C/D map of the 32x32 fragment: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = co0 + wm * 64 + f * 32 + (e & 3) + 8 * (e >> 2) + 4 * kq;
-            if (co >= a.Cout) continue;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int n = n0 + wn * 64 + h * 32 + lm;
-                if (n < N) rec[(size_t)co * N + n] = acc[f][h][e];
-            }
-        }
+    float* rec = a.ws + (size_t)s * a.sp.R;
+    tile.store(rec, co0, n0, a.Cout, N);
     if (bias && co0 + tid < a.Cout) rec[(size_t)a.Cout * N + co0 + tid] = bsum;
 }
 
@@ -184,9 +158,9 @@ __global__ __launch_bounds__(kWgThreads) void grouped_wgrad_kernel(WgArgs a, int
     for (int o = 0; o < OC; ++o) acc[o] = 0.f;
     float bsum = 0.f;
     const bool bias = a.with_bias && blockIdx.x == 0 && tid < OC;
-    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
+    const int64_t u0 = (int64_t)s * a.sp.U / a.sp.S, u1 = (int64_t)(s + 1) * a.sp.U / a.sp.S;
     for (int64_t u = u0; u < u1; ++u) {
-        const int b = (int)(u / a.nch), t0 = (int)(u % a.nch) * TT;
+        const int b = (int)(u / a.sp.nch), t0 = (int)(u % a.sp.nch) * TT;
         const int nt = a.Tout - t0 < TT ? a.Tout - t0 : TT;
         __syncthreads();                                  // the previous unit's reads are done
         for (int i = tid; i < TT * OC; i += NT) {
@@ -216,7 +190,7 @@ __global__ __launch_bounds__(kWgThreads) void grouped_wgrad_kernel(WgArgs a, int
         if (bias)
             for (int t = 0; t < nt; ++t) bsum += gs[t * GW + tid];
     }
-    float* rec = a.ws + (size_t)s * a.R;
+    float* rec = a.ws + (size_t)s * a.sp.R;
     if (valid)
 #pragma unroll
         for (int o = 0; o < OC; ++o)
@@ -262,7 +236,13 @@ __global__ __launch_bounds__(256) void weight_norm_grad_kernel(const float* __re
 // ---- host side: which kernel, how many splits ----
 enum { kWgPlain = 0, kWgMfma = 1, kWgGrouped16 = 2, kWgGrouped4 = 3 };
 
-static size_t wg_mfma_lds(int k) { return sizeof(float) * ((size_t)kWmTile * kWmGS + (size_t)(127 / k + 2) * (kWmTK + k)); }
+struct WgPlan : WgSplit {
+    int path, TT, threads;
+    size_t lds;
+    dim3 grid;
+};
+
+static size_t wg_mfma_lds(int k) { return sizeof(float) * ((size_t)kWgNT * kWmGS + (size_t)(127 / k + 2) * (kWgTK + k)); }
 
 static int dense_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int pad, int pad_mode, WgPlan* p) {
     if (Cin < 1 || Cout < 1 || k < 1 || (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT) ||
@@ -278,12 +258,12 @@ static int dense_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int pad, i
     p->R = (int64_t)Cout * N + Cout;
     p->TT = 0;
     p->threads = kWgThreads;
-    if (Cout >= 64 && N >= 64 && wg_mfma_lds(k) <= 65536 && (Cout + kWmTile - 1) / kWmTile <= 65535) {
+    if (Cout >= 64 && N >= 64 && wg_mfma_lds(k) <= 65536 && (Cout + kWgNT - 1) / kWgNT <= 65535) {
         p->path = kWgMfma;
-        p->nch = (int)((Tout + kWmTK - 1) / kWmTK);
+        p->nch = (int)((Tout + kWgTK - 1) / kWgTK);
         p->U = (int64_t)B * p->nch;
         p->lds = wg_mfma_lds(k);
-        const int64_t bx = (N + kWmTile - 1) / kWmTile, by = (Cout + kWmTile - 1) / kWmTile;
+        const int64_t bx = (N + kWgNT - 1) / kWgNT, by = (Cout + kWgNT - 1) / kWgNT;
         p->S = wg_splits(bx * by, p->U, kWgBlocks / 2);
         p->grid = dim3((unsigned)bx, (unsigned)by, (unsigned)p->S);
     } else {
@@ -339,17 +319,13 @@ int launch_wgrad_combine(const float* ws, float* dw, float* db, int64_t MN, int 
     return 0;
 }
 
-int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes, const char* who,
-              hipStream_t st) {
-    const size_t need = sizeof(float) * (size_t)p.S * (size_t)p.R;
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
-        return fail(FV_ERR_INVALID_ARG, "%s: workspace of %zu bytes, needs %zu (4-byte aligned)", who, workspace_bytes,
-                    need);
+// the two launches: the kernel p.path names, then the combine
+static int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes,
+                     const char* who, hipStream_t st) {
+    if (int rc = wg_tensor_check(who, a.g, a.x, dw, db)) return rc;
+    if (int rc = wg_workspace_check(who, workspace, workspace_bytes, p.bytes())) return rc;
+    a.sp = p;
     a.ws = static_cast<float*>(workspace);
-    a.R = p.R;
-    a.U = p.U;
-    a.S = p.S;
-    a.nch = p.nch;
     a.with_bias = db != nullptr;
     switch (p.path) {
     case kWgMfma:
@@ -381,15 +357,13 @@ int64_t fv_conv_weight_grad_workspace_bytes(int grouped, int B, int Cin, int Cou
     const int rc = grouped ? grouped_wgrad_plan(B, Cin, Cout, Tin, k, stride, pad, &p)
                            : dense_wgrad_plan(B, Cin, Cout, Tin, k, pad, pad_mode, &p);
     if (rc) return rc;
-    return (int64_t)sizeof(float) * p.S * p.R;
+    return (int64_t)p.bytes();
 }
 
 int fv_conv1d_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout, int Tin,
                           int k, int pad, int pad_mode, void* workspace, size_t workspace_bytes, void* stream) {
     WgPlan p;
     if (int rc = dense_wgrad_plan(B, Cin, Cout, Tin, k, pad, pad_mode, &p)) return rc;
-    if (!g_pre || !x || (!dw && !db) || dw == g_pre || dw == x || db == g_pre || db == x)
-        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad: null tensor, or a result aliases an input");
     WgArgs a{};
     a.g = g_pre;
     a.x = x;
@@ -409,8 +383,6 @@ int fv_grouped_conv1d_weight_grad(const float* g_pre, const float* x, float* dw,
                                   void* stream) {
     WgPlan p;
     if (int rc = grouped_wgrad_plan(B, Cin, Cout, Tin, k, stride, pad, &p)) return rc;
-    if (!g_pre || !x || (!dw && !db) || dw == g_pre || dw == x || db == g_pre || db == x)
-        return fail(FV_ERR_INVALID_ARG, "grouped_conv1d_weight_grad: null tensor, or a result aliases an input");
     WgArgs a{};
     a.g = g_pre;
     a.x = x;

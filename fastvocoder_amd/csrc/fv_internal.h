@@ -508,49 +508,6 @@ int64_t score_grad_chunks(int M, const int64_t* n);   // score-gradient blocks p
 int launch_disc_score_grad(const float* const* e, const float* const* r, float* const* g, const int64_t* n,
                            const float* coef, int M, int B, hipStream_t st);
 
-// ---- the weight-gradient kernels (disc_wgrad.hip, mpd_wgrad.hip): split / record / combine ----
-// sum over the block's 256 threads in a fixed order: the shuffle tree of each wave, then the 4 waves ascending
-__device__ __forceinline__ float wg_block_sum(float v, float* part) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                  // (the previous sum's readers are done)
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-struct WgArgs {
-    const float* g;       // [B, Cout, Tout]
-    const float* x;       // [B, Cin, Tin]
-    float* ws;            // [S][R]
-    int64_t R;            // floats per record: Cout N + Cout
-    int64_t U;            // units
-    int S, nch;           // splits; units per row b
-    int Cin, Cout, Tin, Tout, k, pad, reflect, stride;
-    int with_bias;
-};
-
-struct WgPlan {
-    int path, S, nch, TT, threads;
-    int64_t U, R;
-    size_t lds;
-    dim3 grid;
-};
-
-// splits of a launch of `base` blocks per split that aims at `aim` blocks: a function of the shape alone
-static inline int wg_splits(int64_t base, int64_t U, int aim) {
-    int64_t S = (aim + base - 1) / base;
-    if (S > U) S = U;
-    if (S > 4096) S = 4096;
-    return S < 1 ? 1 : (int)S;
-}
-
-// the two launches of disc_wgrad.hip (the kernel p.path names, then the combine), and the combine launch alone:
-// dw[i] = sum_s ws[s][i] (i < MN), db[c] = sum_s ws[s][MN + c], s ascending; dw or db may be null
-int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes, const char* who,
-              hipStream_t st);
-int launch_wgrad_combine(const float* ws, float* dw, float* db, int64_t MN, int Cout, int64_t R, int S, hipStream_t st);
-
 // self-check of pair_kernels.hpp div_exact against the device's division (fv_div_probe; pair_inst_c16.hip)
 int launch_div_probe(unsigned first, long long n, float d, unsigned long long* mismatches, hipStream_t s);
 

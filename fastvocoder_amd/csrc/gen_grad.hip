@@ -3,17 +3,11 @@
 // fv_conv_transpose1d_weight_grad, fv_tanh_grad, fv_residual_merge_grad, fv_grad_div).  Exact fp32, no atomics, no
 // waiting between workgroups.
 //
-// All three GEMMs run on one tile engine (GgTile<MT>): a block of 4 waves owns MT rows x 128 columns and consumes
-// staged tiles of 32 reduction steps, both operands K-contiguous in LDS -- as[row][step], bs[column][step].
-//     MT = 128: 2 x 2 waves of 2 x 2 fragments of v_mfma_f32_32x32x2_f32        MT = 64: 2 x 2 waves of 1 x 2
-//     MT =  32: 1 x 4 waves of 1 x 1 fragments (32 rows, every one a channel)    MT = 16: 1 x 4 waves of 1 x 2 fragments
-//                                                                                 of v_mfma_f32_16x16x4_f32
-// so 16 and 32 channels fill their fragments.  Row stride 33 words for the 32-wide fragments (a lane group of 32 reads
-// rows 0..31 at one step: banks 33 r + c = 32 different ones), 34 words for the 16-wide ones (a group of 32 lanes reads
-// rows 0..15 at two consecutive steps: banks 2 r + {0, 1}, 32 different ones); the staging writes put the 32 lanes of
-// a group on 32 consecutive words of one row.  Each result is one step-ordered fmaf chain.
+// All three GEMMs run on the tile of wgrad_tile.hpp (WgTile<MT>, MT = 128, 64, 32 or 16 rows by the channel count):
+// both operands K-contiguous in LDS -- as[row][step], bs[column][step]; the staging writes put the 32 lanes of a group
+// on 32 consecutive words of one row.  Each result is one step-ordered fmaf chain.
 //
-// The B operand is an im2col column resolved WHILE STAGING, as period_wgrad_mfma_kernel does: bs[n][t] with
+// The B operand is an im2col column resolved WHILE STAGING: bs[n][t] with
 // n = (channel, tap) reads source[channel][t sB + j dB - pad] (zero outside the row) from per-thread offsets computed
 // before the unit loop -- (sB, dB) = (1, dil) for the dilated conv's weight gradient, (stride, 1) for the transposed
 // conv's.  The MFMA loop's B read is therefore the same conflict-free pattern for every dilation and stride; a staged
@@ -21,10 +15,10 @@
 // dil 3 and 5 at the tap counts 7 and 11.  The price: a source element is loaded once per tap that touches it, from L2
 // after the first (a unit's span is a few KB), not once.
 //
-// gen_wgrad_kernel<MT>: dW[m][n] over (b, t) in the split / record / combine scheme of disc_wgrad.hip (units of 32
-// steps, S a function of the shape alone, wgrad_combine_kernel adds the records in ascending order).  One extra block
-// column sums the bias rows of the split's units (wave w owns channels w, w + 4, ...; lanes stride the unit's
-// positions; one shuffle tree at the end), so every record word the combine reads is written by this launch.
+// gen_wgrad_kernel<MT>: dW[m][n] over (b, t) in the split / record / combine scheme of wgrad_tile.hpp (units of 32
+// steps).  One extra block column sums the bias rows of the split's units (wave w owns channels w, w + 4, ...; lanes
+// stride the unit's positions; one shuffle tree at the end), so every record word the combine reads is written by this
+// launch.
 //
 // gen_dgrad_kernel<MT>: the transposed conv's data gradient as the GEMM [Cin] x [B Tin] over Cout k: the columns are
 // the flat positions q = b Tin + i, A = the forward's weight [Cin][Cout k] as it lies in memory, B the stride-s gather
@@ -39,90 +33,19 @@
 // (T - 1 - pad <= i <= T - 2), added in that order before the MFMA sees them.  One launch, no [B, C, T + 2 pad] tensor.
 #include <math.h>
 
-#include <type_traits>
-
-#include "fv_internal.h"
+#include "wgrad_tile.hpp"
 
 namespace fv {
 
-typedef float gg_f32x16 __attribute__((ext_vector_type(16)));
-typedef float gg_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kGgThreads = 256;
-constexpr int kGgNT = 128;            // columns per block
-constexpr int kGgTK = 32;             // reduction steps per staged tile
-constexpr int kGgBRows = kGgNT / 8;   // rows of the B tile a thread stages (16)
+constexpr int kGgBRows = kWgNT / 8;   // rows of the B tile a thread stages (16)
 constexpr int kGgDead = -(1 << 30);   // position of a column / row beyond the problem: below every source row
-
-template <int MT>
-struct GgTile {
-    static constexpr int F = MT >= 32 ? 32 : 16;            // fragment edge
-    static constexpr int WM = MT >= 64 ? 2 : 1, WN = 4 / WM;
-    static constexpr int FM = MT / (WM * F), FN = kGgNT / (WN * F);
-    static constexpr int STR = F == 32 ? 33 : 34;
-    static constexpr int NE = F == 32 ? 16 : 4;
-    static constexpr int ARows = MT / 8;                    // rows of the A tile a thread stages
-    typedef typename std::conditional<F == 32, gg_f32x16, gg_f32x4>::type acc_t;
-
-    acc_t acc[FM][FN];
-    int off_a[FM], off_b[FN];
-    int row0, col0, lr, kq;
-
-    __device__ __forceinline__ void init() {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave / WN, wn = wave % WN;
-        lr = lane & (F - 1);
-        kq = lane / F;
-        row0 = wm * FM * F;
-        col0 = wn * FN * F;
-#pragma unroll
-        for (int f = 0; f < FM; ++f) off_a[f] = (row0 + f * F + lr) * STR + kq;
-#pragma unroll
-        for (int h = 0; h < FN; ++h) off_b[h] = (col0 + h * F + lr) * STR + kq;
-#pragma unroll
-        for (int f = 0; f < FM; ++f)
-#pragma unroll
-            for (int h = 0; h < FN; ++h)
-#pragma unroll
-                for (int e = 0; e < NE; ++e) acc[f][h][e] = 0.f;
-    }
-
-    // one staged tile of kGgTK steps
-    __device__ __forceinline__ void mma(const float* as, const float* bs) {
-        constexpr int KS = F == 32 ? 2 : 4;
-#pragma unroll
-        for (int kk = 0; kk < kGgTK; kk += KS) {
-            float av[FM], bv[FN];
-#pragma unroll
-            for (int f = 0; f < FM; ++f) av[f] = as[off_a[f] + kk];
-#pragma unroll
-            for (int h = 0; h < FN; ++h) bv[h] = bs[off_b[h] + kk];
-#pragma unroll
-            for (int f = 0; f < FM; ++f)
-#pragma unroll
-                for (int h = 0; h < FN; ++h) {
-                    if constexpr (F == 32)
-                        acc[f][h] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[f], bv[h], acc[f][h], 0, 0, 0);
-                    else
-                        acc[f][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[f], bv[h], acc[f][h], 0, 0, 0);
-                }
-        }
-    }
-
-    // C/D maps: 32 x 32: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5);
-    //           16 x 16: col = lane & 15, row = 4 (lane >> 4) + reg
-    __device__ __forceinline__ int row(int f, int e) const {
-        return row0 + f * F + (F == 32 ? (e & 3) + 8 * (e >> 2) + 4 * kq : 4 * kq + e);
-    }
-    __device__ __forceinline__ int col(int h) const { return col0 + h * F + lr; }
-};
 
 struct GgWArgs {
     const float* a;         // A source [B, M, TR]: row m, step t
     const float* b;         // B source [B, Cb, TB]: column n = cb k + j reads b[., cb, t sB + j dB - pad]
     const float* bias_src;  // [B, Cbias, Tbias], or null
-    float* ws;              // [S][R]
-    int64_t R, U;           // floats per record: M N + Cbias; units
-    int S, nch;             // splits; units per row b
+    float* ws;              // [S][R], R = M N + Cbias
+    WgSplit sp;
     int M, TR, Cb, TB, k, sB, dB, pad;
     int Cbias, Tbias, bias_scale;   // a unit's bias positions: [t0 bias_scale, (t0 + 32) bias_scale), the row's last unit to Tbias
     int x_tiles;            // column tiles of the GEMM (0: the bias alone); blocks beyond them sum the bias
@@ -130,23 +53,23 @@ struct GgWArgs {
 
 // grid (x_tiles + (bias ? 1 : 0), ceil(M / MT), S); REFLECT: the B source is read through a reflection pad (pad < TB)
 template <int MT, bool REFLECT = false>
-__global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
-    using T = GgTile<MT>;
+__global__ __launch_bounds__(kWgThreads) void gen_wgrad_kernel(GgWArgs a) {
+    using T = WgTile<MT>;
     __shared__ float as[MT * T::STR];
-    __shared__ float bs[kGgNT * T::STR];
+    __shared__ float bs[kWgNT * T::STR];
     const int s = blockIdx.z, tid = threadIdx.x;
-    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
+    const int64_t u0 = (int64_t)s * a.sp.U / a.sp.S, u1 = (int64_t)(s + 1) * a.sp.U / a.sp.S;
     const int N = a.Cb * a.k;
-    float* rec = a.ws + (size_t)s * a.R;
+    float* rec = a.ws + (size_t)s * a.sp.R;
     if ((int)blockIdx.x >= a.x_tiles) {                   // the bias column
         if (blockIdx.y != 0) return;
         const int lane = tid & 63, wave = tid >> 6;
         for (int c = wave; c < a.Cbias; c += 4) {
             float v = 0.f;
             for (int64_t u = u0; u < u1; ++u) {
-                const int b = (int)(u / a.nch), ch = (int)(u % a.nch);
-                const int64_t p0 = (int64_t)ch * kGgTK * a.bias_scale;
-                int64_t p1 = ch == a.nch - 1 ? a.Tbias : p0 + (int64_t)kGgTK * a.bias_scale;
+                const int b = (int)(u / a.sp.nch), ch = (int)(u % a.sp.nch);
+                const int64_t p0 = (int64_t)ch * kWgTK * a.bias_scale;
+                int64_t p1 = ch == a.sp.nch - 1 ? a.Tbias : p0 + (int64_t)kWgTK * a.bias_scale;
                 if (p1 > a.Tbias) p1 = a.Tbias;
                 const float* row = a.bias_src + ((size_t)b * a.Cbias + c) * a.Tbias;
                 for (int64_t p = p0 + lane; p < p1; p += 64) v += row[p];
@@ -157,7 +80,7 @@ __global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
         }
         return;
     }
-    const int n0 = blockIdx.x * kGgNT, m0 = blockIdx.y * MT;
+    const int n0 = blockIdx.x * kWgNT, m0 = blockIdx.y * MT;
     const int sc = tid & 31, sr = tid >> 5;
     int b_off[kGgBRows], b_pos[kGgBRows];                 // cb TB, and j dB - pad
 #pragma unroll
@@ -169,7 +92,7 @@ __global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
     T tile;
     tile.init();
     for (int64_t u = u0; u < u1; ++u) {
-        const int b = (int)(u / a.nch), t = (int)(u % a.nch) * kGgTK + sc;
+        const int b = (int)(u / a.sp.nch), t = (int)(u % a.sp.nch) * kWgTK + sc;
         const bool live = t < a.TR;
         const float* ab = a.a + (size_t)b * a.M * a.TR + t;
         const float* bb = a.b + (size_t)b * a.Cb * a.TB;
@@ -192,18 +115,7 @@ __global__ __launch_bounds__(kGgThreads) void gen_wgrad_kernel(GgWArgs a) {
         __syncthreads();
         tile.mma(as, bs);
     }
-#pragma unroll
-    for (int f = 0; f < T::FM; ++f)
-#pragma unroll
-        for (int e = 0; e < T::NE; ++e) {
-            const int m = m0 + tile.row(f, e);
-            if (m >= a.M) continue;
-#pragma unroll
-            for (int h = 0; h < T::FN; ++h) {
-                const int n = n0 + tile.col(h);
-                if (n < N) rec[(size_t)m * N + n] = tile.acc[f][h][e];
-            }
-        }
+    tile.store(rec, m0, n0, a.M, N);
 }
 
 struct GgDArgs {
@@ -216,13 +128,13 @@ struct GgDArgs {
 
 // grid (ceil(B Tin / 128), ceil(Cin / MT))
 template <int MT>
-__global__ __launch_bounds__(kGgThreads) void gen_dgrad_kernel(GgDArgs a) {
-    using T = GgTile<MT>;
+__global__ __launch_bounds__(kWgThreads) void gen_dgrad_kernel(GgDArgs a) {
+    using T = WgTile<MT>;
     __shared__ float as[MT * T::STR];
-    __shared__ float bs[kGgNT * T::STR];
+    __shared__ float bs[kWgNT * T::STR];
     const int tid = threadIdx.x, sc = tid & 31, sr = tid >> 5;
     const int K = a.Cout * a.k, m0 = blockIdx.y * MT;
-    const int64_t q0 = (int64_t)blockIdx.x * kGgNT;
+    const int64_t q0 = (int64_t)blockIdx.x * kWgNT;
     int64_t c_base[kGgBRows];                             // b Cout Tout
     int c_pos[kGgBRows];                                  // i stride - pad
 #pragma unroll
@@ -234,7 +146,7 @@ __global__ __launch_bounds__(kGgThreads) void gen_dgrad_kernel(GgDArgs a) {
     }
     T tile;
     tile.init();
-    for (int kc = 0; kc < K; kc += kGgTK) {
+    for (int kc = 0; kc < K; kc += kWgTK) {
         const int kk = kc + sc;
         const bool live = kk < K;
         const int co = kk / a.k, j = kk - co * a.k;
@@ -279,13 +191,13 @@ struct GgRArgs {
 
 // grid (ceil(B T / 128), ceil(Cin / MT))
 template <int MT>
-__global__ __launch_bounds__(kGgThreads) void gen_dgrad_reflect_kernel(GgRArgs a) {
-    using T = GgTile<MT>;
+__global__ __launch_bounds__(kWgThreads) void gen_dgrad_reflect_kernel(GgRArgs a) {
+    using T = WgTile<MT>;
     __shared__ float as[MT * T::STR];
-    __shared__ float bs[kGgNT * T::STR];
+    __shared__ float bs[kWgNT * T::STR];
     const int tid = threadIdx.x, sc = tid & 31, sr = tid >> 5;
     const int K = a.Cout * a.k, m0 = blockIdx.y * MT;
-    const int64_t q0 = (int64_t)blockIdx.x * kGgNT;
+    const int64_t q0 = (int64_t)blockIdx.x * kWgNT;
     int64_t c_base[kGgBRows];                             // b Cout Tout
     int c_pos[kGgBRows];                                  // x + pad: the padded position of the straight gather
     int c_left[kGgBRows], c_right[kGgBRows];              // the mirrors' padded positions, kGgDead where there is none
@@ -302,7 +214,7 @@ __global__ __launch_bounds__(kGgThreads) void gen_dgrad_reflect_kernel(GgRArgs a
     }
     T tile;
     tile.init();
-    for (int kc = 0; kc < K; kc += kGgTK) {
+    for (int kc = 0; kc < K; kc += kWgTK) {
         const int kk = kc + sc;
         const bool live = kk < K;
         const int co = kk / a.k, jd = (kk - co * a.k) * a.dil;
@@ -369,17 +281,25 @@ __global__ __launch_bounds__(256) void grad_div_kernel(const float* __restrict__
 // ---- host side ----
 static int gg_rows(int M) { return M > 64 ? 128 : M > 32 ? 64 : M > 16 ? 32 : 16; }
 
-struct GgWPlan {
-    int MT, S, nch, bx, by;
-    int64_t U, R;
+// LAUNCH(MT) at the tile height rows = gg_rows(.): 128, 64, 32 or 16
+#define GG_BY_ROWS(rows, LAUNCH)    \
+    switch (rows) {                 \
+    case 128: LAUNCH(128); break;   \
+    case 64: LAUNCH(64); break;     \
+    case 32: LAUNCH(32); break;     \
+    default: LAUNCH(16); break;     \
+    }
+
+struct GgWPlan : WgSplit {
+    int MT, bx, by;
 };
 
 // the plan of a weight-gradient GEMM of M rows x N columns over B rows of TR steps, with Cbias bias words per record
 static void gg_wgrad_plan(int B, int M, int64_t N, int TR, int Cbias, GgWPlan* p) {
     p->MT = gg_rows(M);
-    p->bx = (int)((N + kGgNT - 1) / kGgNT);
+    p->bx = (int)((N + kWgNT - 1) / kWgNT);
     p->by = (M + p->MT - 1) / p->MT;
-    p->nch = (TR + kGgTK - 1) / kGgTK;
+    p->nch = (TR + kWgTK - 1) / kWgTK;
     p->U = (int64_t)B * p->nch;
     p->R = (int64_t)M * N + Cbias;
     p->S = wg_splits((int64_t)p->bx * p->by, p->U, p->MT >= 64 ? 512 : 1024);
@@ -387,33 +307,18 @@ static void gg_wgrad_plan(int B, int M, int64_t N, int TR, int Cbias, GgWPlan* p
 
 static int gg_wgrad_run(const GgWPlan& p, GgWArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes,
                         const char* who, hipStream_t st, bool reflect = false) {
-    const size_t need = sizeof(float) * (size_t)p.S * (size_t)p.R;
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
-        return fail(FV_ERR_INVALID_ARG, "%s: workspace of %zu bytes, needs %zu (4-byte aligned)", who, workspace_bytes,
-                    need);
+    if (int rc = wg_tensor_check(who, a.a, a.b, dw, db)) return rc;
+    if (int rc = wg_workspace_check(who, workspace, workspace_bytes, p.bytes())) return rc;
+    a.sp = p;
     a.ws = static_cast<float*>(workspace);
-    a.R = p.R;
-    a.U = p.U;
-    a.S = p.S;
-    a.nch = p.nch;
     a.x_tiles = dw ? p.bx : 0;
     if (!db) a.bias_src = nullptr;
     const dim3 grid((unsigned)(a.x_tiles + (db ? 1 : 0)), (unsigned)(dw ? p.by : 1), (unsigned)p.S);
-    if (reflect) {
-        switch (p.MT) {
-        case 128: hipLaunchKernelGGL((gen_wgrad_kernel<128, true>), grid, dim3(kGgThreads), 0, st, a); break;
-        case 64: hipLaunchKernelGGL((gen_wgrad_kernel<64, true>), grid, dim3(kGgThreads), 0, st, a); break;
-        case 32: hipLaunchKernelGGL((gen_wgrad_kernel<32, true>), grid, dim3(kGgThreads), 0, st, a); break;
-        default: hipLaunchKernelGGL((gen_wgrad_kernel<16, true>), grid, dim3(kGgThreads), 0, st, a); break;
-        }
-    } else {
-        switch (p.MT) {
-        case 128: hipLaunchKernelGGL(gen_wgrad_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
-        case 64: hipLaunchKernelGGL(gen_wgrad_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
-        case 32: hipLaunchKernelGGL(gen_wgrad_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
-        default: hipLaunchKernelGGL(gen_wgrad_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
-        }
-    }
+#define GG_WGRAD(MT)                                                                                         \
+    if (reflect) hipLaunchKernelGGL((gen_wgrad_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, a);         \
+    else hipLaunchKernelGGL((gen_wgrad_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, a)
+    GG_BY_ROWS(p.MT, GG_WGRAD)
+#undef GG_WGRAD
     FV_HIP(hipGetLastError());
     return launch_wgrad_combine(a.ws, dw, db, p.R - a.Cbias, a.Cbias, p.R, p.S, st);
 }
@@ -477,7 +382,7 @@ extern "C" {
 int64_t fv_conv1d_weight_grad_dilated_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad) {
     GgWPlan p;
     if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
-    return (int64_t)sizeof(float) * p.S * p.R;
+    return (int64_t)p.bytes();
 }
 
 int64_t fv_conv1d_weight_grad_dilated_mode_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad,
@@ -485,7 +390,7 @@ int64_t fv_conv1d_weight_grad_dilated_mode_workspace_bytes(int B, int Cin, int C
     GgWPlan p;
     if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
     if (int rc = dilated_mode_check("conv1d_weight_grad_dilated_mode", Tin, pad, pad_mode)) return rc;
-    return (int64_t)sizeof(float) * p.S * p.R;
+    return (int64_t)p.bytes();
 }
 
 int fv_conv1d_weight_grad_dilated(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
@@ -501,8 +406,6 @@ int fv_conv1d_weight_grad_dilated_mode(const float* g_pre, const float* xa, floa
     GgWPlan p;
     if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
     if (int rc = dilated_mode_check("conv1d_weight_grad_dilated_mode", Tin, pad, pad_mode)) return rc;
-    if (!g_pre || !xa || (!dw && !db) || dw == g_pre || dw == xa || db == g_pre || db == xa)
-        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: null tensor, or a result aliases an input");
     const int Tout = Tin + 2 * pad - dil * (k - 1);
     GgWArgs a{};
     a.a = g_pre;
@@ -553,16 +456,13 @@ int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, in
     a.dil = dil;
     a.pad = pad;
     const int MT = gg_rows(Cin);
-    const int64_t gx = (a.Q + kGgNT - 1) / kGgNT;
+    const int64_t gx = (a.Q + kWgNT - 1) / kWgNT;
     if (gx > 0x7fffffff) return fail(FV_ERR_INVALID_ARG, "%s: B Tin = %lld", who, (long long)a.Q);
     const dim3 grid((unsigned)gx, (unsigned)((Cin + MT - 1) / MT));
     const hipStream_t st = (hipStream_t)stream;
-    switch (MT) {
-    case 128: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
-    case 64: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
-    case 32: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(gen_dgrad_reflect_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
-    }
+#define GG_DGRAD(MT) hipLaunchKernelGGL(gen_dgrad_reflect_kernel<MT>, grid, dim3(kWgThreads), 0, st, a)
+    GG_BY_ROWS(MT, GG_DGRAD)
+#undef GG_DGRAD
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -586,16 +486,13 @@ int fv_conv_transpose1d_input_grad(const float* g, const float* w, float* dxa, i
     a.stride = stride;
     a.pad = pad;
     const int MT = gg_rows(Cin);
-    const int64_t gx = (a.Q + kGgNT - 1) / kGgNT;
+    const int64_t gx = (a.Q + kWgNT - 1) / kWgNT;
     if (gx > 0x7fffffff) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_input_grad: B Tin = %lld", (long long)a.Q);
     const dim3 grid((unsigned)gx, (unsigned)((Cin + MT - 1) / MT));
     const hipStream_t st = (hipStream_t)stream;
-    switch (MT) {
-    case 128: hipLaunchKernelGGL(gen_dgrad_kernel<128>, grid, dim3(kGgThreads), 0, st, a); break;
-    case 64: hipLaunchKernelGGL(gen_dgrad_kernel<64>, grid, dim3(kGgThreads), 0, st, a); break;
-    case 32: hipLaunchKernelGGL(gen_dgrad_kernel<32>, grid, dim3(kGgThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(gen_dgrad_kernel<16>, grid, dim3(kGgThreads), 0, st, a); break;
-    }
+#define GG_DGRAD(MT) hipLaunchKernelGGL(gen_dgrad_kernel<MT>, grid, dim3(kWgThreads), 0, st, a)
+    GG_BY_ROWS(MT, GG_DGRAD)
+#undef GG_DGRAD
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -606,7 +503,7 @@ int64_t fv_conv_transpose1d_weight_grad_workspace_bytes(int B, int Cin, int Cout
     if (Tout < 0) return Tout;
     GgWPlan p;
     gg_wgrad_plan(B, Cin, (int64_t)Cout * k, Tin, Cout, &p);
-    return (int64_t)sizeof(float) * p.S * p.R;
+    return (int64_t)p.bytes();
 }
 
 int fv_conv_transpose1d_weight_grad(const float* g, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
@@ -614,8 +511,6 @@ int fv_conv_transpose1d_weight_grad(const float* g, const float* xa, float* dw, 
                                     size_t workspace_bytes, void* stream) {
     const int64_t Tout = convt_grad_check("conv_transpose1d_weight_grad", B, Cin, Cout, Tin, k, stride, pad, out_pad);
     if (Tout < 0) return (int)Tout;
-    if (!g || !xa || (!dw && !db) || dw == g || dw == xa || db == g || db == xa)
-        return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_weight_grad: null tensor, or a result aliases an input");
     GgWPlan p;
     gg_wgrad_plan(B, Cin, (int64_t)Cout * k, Tin, Cout, &p);
     GgWArgs a{};

@@ -1,17 +1,14 @@
 // Parameter gradient of the multi-period discriminator (reference: model/discriminator/mpd.py:131-164 DiscriminatorP;
 // bin/train.py:143-188 the discriminator's update; include/fastvocoder_hip.h fv_period_conv_weight_grad,
-// fv_mpd_first_weight_grad).  Exact fp32, no atomics, no waiting between workgroups, and the split / record / combine
-// scheme of disc_wgrad.hip: the reduction over (b, h', c) is cut into UNITS (one row b, one run of flat output
-// positions q = h' p + c), the units are dealt to `S` splits in contiguous ranges, every block sums its units in
-// ascending order and writes its partial sums to the workspace record of its split
-//     ws[s][0 .. Cout N)  the weight gradient,   ws[s][Cout N .. Cout N + Cout)  the bias gradient,
-// and wgrad_combine_kernel (disc_wgrad.hip) adds the S records, s ascending.  S is a function of the shape alone, so
-// identical calls give identical bits.  Every word of a record that the second launch reads is written by the first.
+// fv_mpd_first_weight_grad).  Exact fp32 in the split / record / combine scheme of wgrad_tile.hpp: a UNIT is one row b
+// and one run of flat output positions q = h' p + c, and the record of a split is
+//     ws[s][0 .. Cout N)  the weight gradient,   ws[s][Cout N .. Cout N + Cout)  the bias gradient.
+// Every word of a record that the second launch (wgrad_combine_kernel, disc_wgrad.hip) reads is written by the first.
 //
 // period_wgrad_mfma_kernel<P> (Cout >= 64 and Cin k >= 64: the three strided layers and the 1024 -> 1024 layer): dW as
-// the GEMM [Cout] x [Cin k] over B H' p on v_mfma_f32_32x32x2_f32.  A block owns 128 output channels x 128 columns
-// n = ci k + j; its 4 waves are 2 x 2, each 2 x 2 fragments of 32 x 32, as in dense_wgrad_mfma_kernel.  A unit is 32
-// consecutive flat positions q of one b.  Both operands are staged K-contiguous: gs[co][q] (a coalesced flat copy) and
+// the GEMM [Cout] x [Cin k] over B H' p on WgTile<128> (wgrad_tile.hpp): a block owns 128 output channels x 128 columns
+// n = ci k + j.  A unit is 32 consecutive flat positions q of one b.  Both operands are staged as the tile wants them,
+// K-contiguous: gs[co][q] (a coalesced flat copy) and
 // bs[n][q] = x[b, ci, stride h' + j - pad, c], the im2col column of (ci, j) -- the strided (or, at stride 1, dilated)
 // read is resolved once, while staging, from per-thread offsets computed before the unit loop; rows outside [0, H)
 // stage 0, so the padding is never materialised.  A unit therefore need not be a run of whole rows, one kernel serves
@@ -29,16 +26,14 @@
 //
 // mpd_first_wgrad_kernel (1 -> 32, k 5, stride 3, straight from the waveform): a block owns one output channel, its
 // 5 taps and its bias; the reflect tail and the [H, p] view are the address arithmetic of mpd_first_kernel.
-#include "fv_internal.h"
+#include "wgrad_tile.hpp"
 
 namespace fv {
 
-typedef float pw_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kPwThreads = 256;
-constexpr int kPwTile = 128;        // mfma kernel: output channels and columns per block
-constexpr int kPwTK = 32;           // mfma kernel: flat output positions per unit
-constexpr int kPwStr = kPwTK + 1;   // row stride of gs and bs
+constexpr int kPwThreads = kWgThreads;
+constexpr int kPwTile = kWgNT;      // mfma kernel: output channels and columns per block
+constexpr int kPwTK = kWgTK;        // mfma kernel: flat output positions per unit
+constexpr int kPwStr = WgTile<kPwTile>::STR;            // row stride of gs and bs
 constexpr int kPwRows = kPwTile * kPwTK / kPwThreads;   // rows of a tile a thread stages (16)
 constexpr int kPwChunk = 1024;      // plain and first-layer kernels: flat output positions per unit
 constexpr int kPwMaxK = 5;          // taps
@@ -49,8 +44,7 @@ struct PwArgs {
     const float* g;       // [B, Cout, Hout, p]
     const float* x;       // [B, Cin, H, p]
     float* ws;            // [S][R]
-    int64_t R, U;         // floats per record; units
-    int S, nch;           // splits; units per row b
+    WgSplit sp;
     int Cin, Cout, H, Hout, k, stride, pad, p;
     int with_bias;
 };
@@ -62,8 +56,7 @@ __global__ __launch_bounds__(kPwThreads) void period_wgrad_mfma_kernel(PwArgs a)
     __shared__ float bs[kPwTile * kPwStr];
     const int k = a.k, N = a.Cin * k, Nin = a.H * P, Nout = a.Hout * P;
     const int n0 = blockIdx.x * kPwTile, co0 = blockIdx.y * kPwTile, s = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int lm = lane & 31, kq = lane >> 5;
+    const int tid = threadIdx.x;
     // staging: this thread owns position sc of the unit and the rows sr + 8 i of both tiles
     const int sc = tid & 31, sr = tid >> 5;
     int x_off[kPwRows], x_row[kPwRows];                   // ci Nin, and j - pad (far below any row for n >= N)
@@ -74,24 +67,13 @@ __global__ __launch_bounds__(kPwThreads) void period_wgrad_mfma_kernel(PwArgs a)
         x_off[i] = n < N ? ci * Nin : 0;
         x_row[i] = n < N ? n - ci * k - a.pad : -(1 << 29);
     }
-    int off_a[2], off_b[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-        off_a[f] = (wm * 64 + f * 32 + lm) * kPwStr + kq;
-        off_b[f] = (wn * 64 + f * 32 + lm) * kPwStr + kq;
-    }
-    pw_f32x16 acc[2][2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[f][h][e] = 0.f;
+    WgTile<kPwTile> tile;
+    tile.init();
     float bsum = 0.f;
     const bool bias = a.with_bias && blockIdx.x == 0 && tid < kPwTile;
-    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
+    const int64_t u0 = (int64_t)s * a.sp.U / a.sp.S, u1 = (int64_t)(s + 1) * a.sp.U / a.sp.S;
     for (int64_t u = u0; u < u1; ++u) {
-        const int b = (int)(u / a.nch), q = (int)(u % a.nch) * kPwTK + sc;
+        const int b = (int)(u / a.sp.nch), q = (int)(u % a.sp.nch) * kPwTK + sc;
         const bool live = q < Nout;
         const int t = q / P, c = q - t * P;
         const int r0 = a.stride * t;
@@ -109,33 +91,13 @@ __global__ __launch_bounds__(kPwThreads) void period_wgrad_mfma_kernel(PwArgs a)
             bs[row * kPwStr + sc] = (live && r >= 0 && r < a.H) ? xb[(size_t)x_off[i] + (size_t)r * P] : 0.f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kPwTK; kk += 2) {
-            const float a0 = gs[off_a[0] + kk], a1 = gs[off_a[1] + kk];
-            const float b0 = bs[off_b[0] + kk], b1 = bs[off_b[1] + kk];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        tile.mma(gs, bs);
         if (bias)
 #pragma unroll
             for (int cc = 0; cc < kPwTK; ++cc) bsum += gs[tid * kPwStr + cc];
     }
-    float* rec = a.ws + (size_t)s * a.R;
-    // C/D map of the 32x32 fragment: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = co0 + wm * 64 + f * 32 + (e & 3) + 8 * (e >> 2) + 4 * kq;
-            if (co >= a.Cout) continue;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int n = n0 + wn * 64 + h * 32 + lm;
-                if (n < N) rec[(size_t)co * N + n] = acc[f][h][e];
-            }
-        }
+    float* rec = a.ws + (size_t)s * a.sp.R;
+    tile.store(rec, co0, n0, a.Cout, N);
     if (bias && co0 + tid < a.Cout) rec[(size_t)a.Cout * N + co0 + tid] = bsum;
 }
 
@@ -144,14 +106,14 @@ __global__ __launch_bounds__(kPwThreads) void period_wgrad_plain_kernel(PwArgs a
     __shared__ float part[4];
     const int co = blockIdx.x / a.Cin, ci = blockIdx.x % a.Cin, s = blockIdx.z;
     const int p = a.p, Nin = a.H * p, Nout = a.Hout * p;
-    const int64_t u0 = (int64_t)s * a.U / a.S, u1 = (int64_t)(s + 1) * a.U / a.S;
-    float* rec = a.ws + (size_t)s * a.R;
+    const int64_t u0 = (int64_t)s * a.sp.U / a.sp.S, u1 = (int64_t)(s + 1) * a.sp.U / a.sp.S;
+    float* rec = a.ws + (size_t)s * a.sp.R;
     float acc[kPwMaxK];
 #pragma unroll
     for (int j = 0; j < kPwMaxK; ++j) acc[j] = 0.f;
     float bsum = 0.f;
     for (int64_t u = u0; u < u1; ++u) {
-        const int b = (int)(u / a.nch), ch = (int)(u % a.nch);
+        const int b = (int)(u / a.sp.nch), ch = (int)(u % a.sp.nch);
         const float* gr = a.g + ((size_t)b * a.Cout + co) * Nout;
         const float* xr = a.x + ((size_t)b * a.Cin + ci) * Nin;
         const int q1 = Nout - ch * kPwChunk < kPwChunk ? Nout : (ch + 1) * kPwChunk;
@@ -224,10 +186,9 @@ __global__ __launch_bounds__(kPwThreads) void mpd_first_wgrad_kernel(const float
 }
 
 // ---- host side: which kernel, how many splits ----
-struct PwPlan {
+struct PwPlan : WgSplit {
     bool mfma;
-    int S, nch, Hout;
-    int64_t U, R;
+    int Hout;
     dim3 grid;
 };
 
@@ -264,10 +225,8 @@ static int period_wgrad_plan(int B, int Cin, int Cout, int H, int period, int k,
     return 0;
 }
 
-struct PwFirstPlan {
+struct PwFirstPlan : WgSplit {
     MpdView v;
-    int S, nch;
-    int64_t U;
 };
 
 static int first_wgrad_plan(int B, int64_t T, int period, PwFirstPlan* p) {
@@ -283,14 +242,8 @@ static int first_wgrad_plan(int B, int64_t T, int period, PwFirstPlan* p) {
         return fail(FV_ERR_INVALID_ARG, "mpd_first_weight_grad: T=%lld too long", (long long)T);
     p->nch = (int)((p->v.H1 * period + kPwChunk - 1) / kPwChunk);
     p->U = (int64_t)B * p->nch;
+    p->R = kPwFirstC * kPwMaxK + kPwFirstC;
     p->S = wg_splits(kPwFirstC, p->U, kPwBlocks);
-    return 0;
-}
-
-static int pw_workspace(const char* who, void* workspace, size_t workspace_bytes, size_t need) {
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))
-        return fail(FV_ERR_INVALID_ARG, "%s: workspace of %zu bytes, needs %zu (4-byte aligned)", who, workspace_bytes,
-                    need);
     return 0;
 }
 
@@ -303,27 +256,21 @@ extern "C" {
 int64_t fv_period_conv_weight_grad_workspace_bytes(int B, int Cin, int Cout, int H, int period, int k, int stride) {
     PwPlan p;
     if (int rc = period_wgrad_plan(B, Cin, Cout, H, period, k, stride, &p)) return rc;
-    return (int64_t)sizeof(float) * p.S * p.R;
+    return (int64_t)p.bytes();
 }
 
 int fv_period_conv_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout, int H,
                                int period, int k, int stride, void* workspace, size_t workspace_bytes, void* stream) {
     PwPlan p;
     if (int rc = period_wgrad_plan(B, Cin, Cout, H, period, k, stride, &p)) return rc;
-    if (!g_pre || !x || (!dw && !db) || dw == g_pre || dw == x || db == g_pre || db == x)
-        return fail(FV_ERR_INVALID_ARG, "period_conv_weight_grad: null tensor, or a result aliases an input");
-    if (int rc = pw_workspace("period_conv_weight_grad", workspace, workspace_bytes,
-                              sizeof(float) * (size_t)p.S * (size_t)p.R))
-        return rc;
+    if (int rc = wg_tensor_check("period_conv_weight_grad", g_pre, x, dw, db)) return rc;
+    if (int rc = wg_workspace_check("period_conv_weight_grad", workspace, workspace_bytes, p.bytes())) return rc;
     const hipStream_t st = (hipStream_t)stream;
     PwArgs a{};
+    a.sp = p;
     a.g = g_pre;
     a.x = x;
     a.ws = static_cast<float*>(workspace);
-    a.R = p.R;
-    a.U = p.U;
-    a.S = p.S;
-    a.nch = p.nch;
     a.Cin = Cin;
     a.Cout = Cout;
     a.H = H;
@@ -352,24 +299,21 @@ int fv_period_conv_weight_grad(const float* g_pre, const float* x, float* dw, fl
 int64_t fv_mpd_first_weight_grad_workspace_bytes(int B, int64_t T, int period) {
     PwFirstPlan p;
     if (int rc = first_wgrad_plan(B, T, period, &p)) return rc;
-    return (int64_t)sizeof(float) * p.S * (kPwFirstC * kPwMaxK + kPwFirstC);
+    return (int64_t)p.bytes();
 }
 
 int fv_mpd_first_weight_grad(const float* g_pre, const float* x, float* dw, float* db, int B, int64_t T, int period,
                              void* workspace, size_t workspace_bytes, void* stream) {
     PwFirstPlan p;
     if (int rc = first_wgrad_plan(B, T, period, &p)) return rc;
-    if (!g_pre || !x || (!dw && !db) || dw == g_pre || dw == x || db == g_pre || db == x)
-        return fail(FV_ERR_INVALID_ARG, "mpd_first_weight_grad: null tensor, or a result aliases an input");
-    constexpr int R = kPwFirstC * kPwMaxK + kPwFirstC;
-    if (int rc = pw_workspace("mpd_first_weight_grad", workspace, workspace_bytes, sizeof(float) * (size_t)p.S * R))
-        return rc;
+    if (int rc = wg_tensor_check("mpd_first_weight_grad", g_pre, x, dw, db)) return rc;
+    if (int rc = wg_workspace_check("mpd_first_weight_grad", workspace, workspace_bytes, p.bytes())) return rc;
     const hipStream_t st = (hipStream_t)stream;
     float* ws = static_cast<float*>(workspace);
     hipLaunchKernelGGL(mpd_first_wgrad_kernel, dim3(kPwFirstC, 1, (unsigned)p.S), dim3(kPwThreads), 0, st, g_pre, x, ws,
                        T, (int)p.v.H, (int)p.v.H1, period, p.U, p.S, p.nch, db != nullptr ? 1 : 0);
     FV_HIP(hipGetLastError());
-    return launch_wgrad_combine(ws, dw, db, kPwFirstC * kPwMaxK, kPwFirstC, R, p.S, st);
+    return launch_wgrad_combine(ws, dw, db, kPwFirstC * kPwMaxK, kPwFirstC, p.R, p.S, st);
 }
 
 }  // extern "C"

@@ -22,6 +22,8 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fastvocoder_amd import _native  # noqa: E402
+from _ablib import use_lib_from_env  # noqa: E402
+use_lib_from_env(_native)       # FV_AB_LIB=<a library build>: A/B of two builds
 from fastvocoder_amd.generator import HiFiGANGenerator  # noqa: E402
 from fastvocoder_amd.generator.engine import effective_weight  # noqa: E402
 from fastvocoder_amd.synthetic import seeded_mel, seeded_state_dict  # noqa: E402

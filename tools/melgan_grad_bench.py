@@ -29,6 +29,8 @@ import yaml
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from fastvocoder_amd import _native, optim  # noqa: E402
+from _ablib import use_lib_from_env  # noqa: E402
+use_lib_from_env(_native)       # FV_AB_LIB=<a library build>: A/B of two builds
 from fastvocoder_amd.bin.synthesize import build_generator  # noqa: E402
 from fastvocoder_amd.discriminator import Discriminator  # noqa: E402
 from fastvocoder_amd.generator.modules import ResidualStack  # noqa: E402
