@@ -1,5 +1,6 @@
 // C-ABI entry points of libfastvocoder_hip.so (include/fastvocoder_hip.h): the fused operators as direct calls, the op core they
-// share with the plan executor (plan.hip), error text, tuning switches and the measurement hook.  (Weight preparation: pack.hip.)
+// share with the plan executor (plan.hip) -- run_op, the builders of every launch record (pair_params, pair_member, mrf_params)
+// and the one pair dispatch (launch_pair_family) --, error text, tuning switches and the measurement hook.  (Weight preparation: pack.hip.)
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -92,6 +93,22 @@ static int profile_resolve() {
     return 0;
 }
 
+// the events of one measurement call: destroyed on every way out of it
+struct ScopedEvents {
+    std::vector<hipEvent_t> ev;
+    explicit ScopedEvents(size_t n) : ev(n, nullptr) {}
+    ScopedEvents(const ScopedEvents&) = delete;
+    ScopedEvents& operator=(const ScopedEvents&) = delete;
+    ~ScopedEvents() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create() {
+        for (hipEvent_t& e : ev) FV_HIP(hipEventCreate(&e));
+        return 0;
+    }
+};
+
 }  // namespace fv
 
 namespace fv {
@@ -178,66 +195,81 @@ int run_op(const Op& o, const float* x, float* y, float* y2, const float* res, c
                                      sub, sub_batched, s);
     }
     if (o.type == OP_CONVG) {
-        PairParams pp = {};
-        pp.B = B;
-        pp.T = (int)Tin;
-        pp.slope = o.pre_slope;
-        pp.act_slope = o.act_slope;
-        pp.post = o.post;
-        pp.prec = FV_PAIR_SPLIT_F16;
-        pp.guard = guard;
-        pp.sub = sub;
-        pp.sub_batched = sub_batched;
-        pp.m[0].x = x;
-        pp.m[0].x2 = x2;
-        pp.m[0].w1 = o.wp;
-        pp.m[0].b1 = o.bias;
-        pp.m[0].res = res;
-        pp.m[0].y = y;
-        pp.m[0].y_act = y2;
+        PairParams pp = pair_params(o, 1, B, Tin, guard, sub, sub_batched);
+        pp.m[0] = pair_member(x, o.wp, nullptr, o.bias, nullptr, o.k, y, y2, res, nullptr, nullptr, x2);
         return launch_convg(pp, o.Cout, s);
     }
     if (o.type == OP_STACK) {
-        PairParams pp = {};
-        pp.B = B;
-        pp.T = (int)Tin;
-        pp.slope = o.pre_slope;
-        pp.act_slope = o.act_slope;
-        pp.prec = FV_PAIR_SPLIT_F16;
-        pp.guard = guard;
-        pp.reflect = (o.pad_mode & FV_PAD_REFLECT) ? 1 : 0;
-        pp.post = o.post;
-        pp.sub = sub;
-        pp.sub_batched = sub_batched;
-        pp.m[0].x = x;
-        pp.m[0].w1 = o.wp;
-        pp.m[0].b1 = o.bias;
-        pp.m[0].b2 = o.bias2;
-        pp.m[0].y = y;
-        pp.m[0].y_act = y2;
+        PairParams pp = pair_params(o, 1, B, Tin, guard, sub, sub_batched);
+        pp.m[0] = pair_member(x, o.wp, nullptr, o.bias, o.bias2, o.k, y, y2);
         return launch_convk(pp, o.Cout, o.dil, s);
     }
     if (o.type == OP_CONVT && o.prec == FV_PAIR_SPLIT_F16) {
-        PairParams pp = {};
-        pp.B = B;
-        pp.T = (int)Tin;
-        pp.slope = o.pre_slope;
-        pp.act_slope = o.act_slope;
-        pp.prec = FV_PAIR_SPLIT_F16;
-        pp.guard = guard;
-        pp.m[0].x = x;
-        pp.m[0].w1 = o.wp;
-        pp.m[0].b1 = o.bias;
-        pp.m[0].y = y;
-        pp.m[0].y_act = y2;
-        // fv_plan_set_input_merge: the input is ((x + acc) + acc2) / out_div, formed in the kernel's window loader
-        pp.m[0].add1 = acc;
-        pp.m[0].add2 = acc2;
-        pp.out_div = acc ? o.out_div : 1.f;
+        // fv_plan_set_input_merge: the input is ((x + acc) + acc2) / out_div, formed in the kernel's window loader (the
+        // launchers take out_div as 1 without acc)
+        PairParams pp = pair_params(o, 1, B, Tin, guard);
+        pp.m[0] = pair_member(x, o.wp, nullptr, o.bias, nullptr, o.k, y, y2, nullptr, acc, acc2);
         if (convtn_shape(o.Cin, o.Cout, o.k, o.stride)) return launch_convtn(pp, (int)conv_out_len(o, Tin), s);
         return launch_convt(pp, o.Cin, o.Cout, o.stride, o.pad, (int)conv_out_len(o, Tin), s);
     }
     return launch_conv(make_params(o, x, y, y2, res, acc, acc2, B, Tin, x2, sub, sub_batched), s);
+}
+
+PairParams pair_params(const Op& o, int n_members, int B, int64_t T, int* guard, const float* sub, int sub_batched) {
+    PairParams pp = {};
+    pp.n_members = n_members;
+    pp.B = B;
+    pp.T = (int)T;
+    pp.slope = o.pre_slope;
+    pp.act_slope = o.act_slope;
+    pp.out_div = o.out_div;
+    pp.post = o.post;
+    pp.prec = o.prec;
+    pp.guard = guard;
+    pp.reflect = (o.pad_mode & FV_PAD_REFLECT) ? 1 : 0;
+    pp.sub = sub;
+    pp.sub_batched = sub_batched;
+    return pp;
+}
+
+PairMember pair_member(const float* x, const float* w1, const float* w2, const float* b1, const float* b2, int k, float* y,
+                       float* y_act, const float* res, const float* add1, const float* add2, const float* x2) {
+    PairMember mb = {};
+    mb.x = x;
+    mb.x2 = x2;
+    mb.w1 = w1;
+    mb.w2 = w2;
+    mb.b1 = b1;
+    mb.b2 = b2;
+    mb.k = k;
+    mb.y = y;
+    mb.y_act = y_act;
+    mb.res = res;
+    mb.add1 = add1;
+    mb.add2 = add2;
+    return mb;
+}
+
+MrfParams mrf_params(const Op& o, const float* x, float* y, float* y_act, float* fold_y, int B, int64_t T, int* guard) {
+    MrfParams mp = {};
+    mp.x = x;
+    mp.y = y;
+    mp.y_act = y_act;
+    mp.blob = o.wp;
+    for (int j = 0; j < 3; ++j) mp.k[j] = o.pk[j];
+    mp.B = B;
+    mp.T = (int)T;
+    mp.slope = o.pre_slope;
+    mp.out_div = o.out_div;
+    mp.act_slope = o.act_slope;
+    mp.post = o.post;
+    mp.fold_w = o.fold_w;
+    mp.fold_b = o.fold_b;
+    mp.fold_y = fold_y;
+    mp.guard = guard;
+    mp.hist = static_cast<float*>(o.work);
+    mp.hist_bytes = o.work_bytes;
+    return mp;
 }
 
 // CausalConv1d keeps the first Tin outputs of a conv padded on both sides: only a pad of
@@ -929,6 +961,7 @@ int fv_conv1x1_2src_split_f16(const float* x, const float* x2, const float* pack
     if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "conv1x1_2src_split_f16: B=%d T=%d", B, T);
     Op o = {};
     o.type = OP_CONVG;
+    o.prec = FV_PAIR_SPLIT_F16;
     o.wp = packed;
     o.bias = bias;
     o.Cin = 2 * C;
@@ -1021,7 +1054,7 @@ int fv_conv_post_pqmf(const float* x, const float* packed, const float* bias, co
 namespace fv {
 // A pair at C >= 64 (split-f16 arithmetic only): conv1 of every member in one launch, then conv2 + residual
 // (+ the MRF addends); the members' intermediates go through mid[j]
-int launch_wide_pairs(const PairParams& pp, float* const* mid, int C, int dil, hipStream_t s) {
+static int launch_wide_pairs(const PairParams& pp, float* const* mid, int C, int dil, hipStream_t s) {
     PairParams c1 = pp, c2 = pp;
     c1.act_slope = 1.f;
     c1.out_div = 1.f;
@@ -1045,6 +1078,33 @@ int launch_wide_pairs(const PairParams& pp, float* const* mid, int C, int dil, h
     return launch_convh(c2, C, 1, s);
 }
 
+// The kernel family of a launch of fused pairs.  The fused 64- / 128-channel kernels exist in split-f16 arithmetic only;
+// so do pairs of that width at all (check_pair_args, which the direct entry and fv_plan_add_resblock_pair_ex both pass,
+// refuses C >= 64 with FV_PAIR_F32), which is why testing `prec` here accepts exactly what testing C alone did.
+int launch_pair_family(const PairParams& pp, float* const* mid, int C, int dil, int prec, hipStream_t s) {
+    if (C == 64 && prec == FV_PAIR_SPLIT_F16) return launch_convp(pp, dil, s);
+    if (C == 128 && prec == FV_PAIR_SPLIT_F16 && !tuning().pair128_unfused) return launch_convq(pp, dil, s);
+    if (C >= 64) return launch_wide_pairs(pp, mid, C, dil, s);
+    return launch_pairs(pp, C, dil, s);
+}
+
+// The op a direct entry with several members would have added to a plan (what its launch record is built from), and
+// member j of an optional array argument
+static Op pair_op(int type, int C, int dil, int pad_mode, float slope, float out_div, int post, float act_slope, int prec) {
+    Op o = {};
+    o.type = type;
+    o.Cin = o.Cout = C;
+    o.dil = dil;
+    o.pad_mode = pad_mode;
+    o.pre_slope = slope;
+    o.out_div = out_div;
+    o.post = post;
+    o.act_slope = act_slope;
+    o.prec = prec;
+    return o;
+}
+template <class P>
+static P at(P const* a, int j) { return a ? a[j] : nullptr; }
 
 int check_pair_args(int n, int C, const int* k, int dil, int prec) {
     if (n < 1 || n > 3) return fail(FV_ERR_INVALID_ARG, "resblock pair: %d members (1..3)", n);
@@ -1073,38 +1133,18 @@ int fv_resblock1_fused_ex(int n, const float* const* x, const float* const* w1, 
                           int* guard, void* stream) {
     if (!x || !w1 || !w2 || !y || !k) return fail(FV_ERR_INVALID_ARG, "resblock1_fused: null argument");
     if (int rc = check_pair_args(n, C, k, dil, prec)) return rc;
-    PairParams pp = {};
-    pp.n_members = n;
-    pp.B = B;
-    pp.T = T;
-    pp.slope = slope;
-    pp.act_slope = act_slope;
-    pp.out_div = out_div;
-    pp.post = post;
-    pp.prec = prec;
-    pp.guard = prec == FV_PAIR_SPLIT_F16 ? guard : nullptr;
+    const Op o = pair_op(OP_PAIR, C, dil, FV_PAD_ZERO, slope, out_div, post, act_slope, prec);
+    PairParams pp = pair_params(o, n, B, T, prec == FV_PAIR_SPLIT_F16 ? guard : nullptr);
     for (int j = 0; j < n; ++j) {
         if (!x[j] || !y[j] || x[j] == y[j] || (y_act && y_act[j] && (y_act[j] == y[j] || y_act[j] == x[j])))
             return fail(FV_ERR_INVALID_ARG, "resblock1_fused: member %d: null tensor, or y / y_act aliases x or each other", j);
-        PairMember& mb = pp.m[j];
-        mb.add1 = add1 ? add1[j] : nullptr;
-        mb.add2 = add2 ? add2[j] : nullptr;
-        if ((mb.add1 && (mb.add1 == y[j] || (y_act && mb.add1 == y_act[j]))) ||
-            (mb.add2 && (mb.add2 == y[j] || (y_act && mb.add2 == y_act[j]))))
+        const PairMember mb = pair_member(x[j], w1[j], w2[j], at(b1, j), at(b2, j), k[j], y[j], at(y_act, j), nullptr,
+                                          at(add1, j), at(add2, j));
+        if ((mb.add1 && (mb.add1 == mb.y || mb.add1 == mb.y_act)) || (mb.add2 && (mb.add2 == mb.y || mb.add2 == mb.y_act)))
             return fail(FV_ERR_INVALID_ARG, "resblock1_fused: member %d: add1 / add2 alias an output", j);
-        mb.x = x[j];
-        mb.w1 = w1[j];
-        mb.w2 = w2[j];
-        mb.b1 = b1 ? b1[j] : nullptr;
-        mb.b2 = b2 ? b2[j] : nullptr;
-        mb.y = y[j];
-        mb.y_act = y_act ? y_act[j] : nullptr;
-        mb.k = k[j];
+        pp.m[j] = mb;
     }
-    if (C == 64) return launch_convp(pp, dil, (hipStream_t)stream);
-    if (C == 128 && !tuning().pair128_unfused) return launch_convq(pp, dil, (hipStream_t)stream);
-    if (C >= 64) return launch_wide_pairs(pp, mid, C, dil, (hipStream_t)stream);
-    return launch_pairs(pp, C, dil, (hipStream_t)stream);
+    return launch_pair_family(pp, mid, C, dil, prec, (hipStream_t)stream);
 }
 
 int fv_mrf_stage(const float* const* x, const float* const* w1, const float* const* w2, const float* const* b1,
@@ -1112,27 +1152,12 @@ int fv_mrf_stage(const float* const* x, const float* const* w1, const float* con
                  float slope, float out_div, int post, float act_slope, void* stream) {
     if (!x || !w1 || !w2 || !y || !k) return fail(FV_ERR_INVALID_ARG, "mrf_stage: null argument");
     if (int rc = check_pair_args(3, C, k, dil)) return rc;
-    PairParams pp = {};
-    pp.n_members = 3;
+    PairParams pp = pair_params(pair_op(OP_MRFSUM, C, dil, FV_PAD_ZERO, slope, out_div, post, act_slope, FV_PAIR_F32), 3, B, T, nullptr);
     pp.sum = 1;
-    pp.B = B;
-    pp.T = T;
-    pp.slope = slope;
-    pp.act_slope = act_slope;
-    pp.out_div = out_div;
-    pp.post = post;
     for (int j = 0; j < 3; ++j) {
         if (!x[j] || x[j] == y || x[j] == y_act || (y_act && y_act == y))
             return fail(FV_ERR_INVALID_ARG, "mrf_stage: member %d: null input, or y / y_act aliases an input or each other", j);
-        PairMember& mb = pp.m[j];
-        mb.x = x[j];
-        mb.w1 = w1[j];
-        mb.w2 = w2[j];
-        mb.b1 = b1 ? b1[j] : nullptr;
-        mb.b2 = b2 ? b2[j] : nullptr;
-        mb.y = y;
-        mb.y_act = y_act;
-        mb.k = k[j];
+        pp.m[j] = pair_member(x[j], w1[j], w2[j], at(b1, j), at(b2, j), k[j], y, y_act);
     }
     return launch_pairs(pp, C, dil, (hipStream_t)stream);
 }
@@ -1162,25 +1187,14 @@ int fv_mrf_stage_split_f16(const float* x, const float* packed, float* y, float*
                            void* stream) {
     if (int rc = check_stage_args(C, k, dil, slope, act_slope, post)) return rc;
     if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "mrf stage: B=%d T=%d", B, T);
-    MrfParams p = {};
-    p.x = x;
-    p.y = y;
-    p.y_act = y_act;
-    p.blob = packed;
-    for (int j = 0; j < 3; ++j) p.k[j] = k[j];
-    p.B = B;
-    p.T = T;
-    p.slope = slope;
-    p.out_div = out_div;
-    p.act_slope = act_slope;
-    p.post = post;
-    p.fold_w = fold_w;
-    p.fold_b = fold_b;
-    p.fold_y = fold_y;
-    p.hist = static_cast<float*>(workspace);
-    p.hist_bytes = workspace_bytes;
-    p.guard = guard;
-    return launch_mrfh(p, C, dil, (hipStream_t)stream);
+    Op o = pair_op(OP_STAGE, C, dil[0], FV_PAD_ZERO, slope, out_div, post, act_slope, FV_PAIR_SPLIT_F16);
+    o.wp = packed;
+    for (int j = 0; j < 3; ++j) o.pk[j] = k[j];
+    o.fold_w = fold_w;
+    o.fold_b = fold_b;
+    o.work = workspace;
+    o.work_bytes = workspace_bytes;
+    return launch_mrfh(mrf_params(o, x, y, y_act, fold_y, B, T, guard), C, dil, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1209,28 +1223,10 @@ int fv_conv1d_split_f16(int n, const float* const* x, const float* const* packed
                         float out_div, int post, float act_slope, int* guard, void* stream) {
     if (!x || !packed || !y || !k) return fail(FV_ERR_INVALID_ARG, "conv1d_split_f16: null argument");
     if (int rc = check_convh_args(n, C, k, dil, pad_mode)) return rc;
-    PairParams pp = {};
-    pp.n_members = n;
-    pp.B = B;
-    pp.T = T;
-    pp.slope = pre_slope;
-    pp.act_slope = act_slope;
-    pp.out_div = out_div;
-    pp.post = post;
-    pp.prec = FV_PAIR_SPLIT_F16;
-    pp.guard = guard;
-    pp.reflect = pad_mode == FV_PAD_REFLECT;
+    PairParams pp = pair_params(pair_op(OP_CONVH, C, dil, pad_mode, pre_slope, out_div, post, act_slope, FV_PAIR_SPLIT_F16), n, B, T, guard);
     for (int j = 0; j < n; ++j) {
-        PairMember& mb = pp.m[j];
-        mb.x = x[j];
-        mb.w1 = packed[j];
-        mb.b1 = bias ? bias[j] : nullptr;
-        mb.res = res ? res[j] : nullptr;
-        mb.add1 = add1 ? add1[j] : nullptr;
-        mb.add2 = add2 ? add2[j] : nullptr;
-        mb.y = y[j];
-        mb.y_act = y_act ? y_act[j] : nullptr;
-        mb.k = k[j];
+        const PairMember& mb = pp.m[j] = pair_member(x[j], packed[j], nullptr, at(bias, j), nullptr, k[j], y[j], at(y_act, j),
+                                                     at(res, j), at(add1, j), at(add2, j));
         if (!mb.x || !mb.y || mb.x == mb.y || mb.y == mb.res || mb.y == mb.add1 || mb.y == mb.add2 ||
             (mb.y_act && (mb.y_act == mb.y || mb.y_act == mb.x || mb.y_act == mb.res)))
             return fail(FV_ERR_INVALID_ARG, "conv1d_split_f16: member %d: null tensor or an output aliases an input", j);
@@ -1265,7 +1261,9 @@ int fv_debug_pair_schedule(int n_members, const int* n_items, const int* cost, i
     p.n_members = n_members;
     long long n[3] = {0, 0, 0};
     for (int m = 0; m < n_members; ++m) {
-        if (n_items[m] < 0 || cost[m] < 1) return fail(FV_ERR_INVALID_ARG, "debug_pair_schedule: member %d", m);
+        // (the schedulers form block x n_items x cost sums in signed 64 bits: below 3 x 2^31 x 2^16 within these bounds)
+        if (n_items[m] < 0 || n_items[m] >= (1LL << 31) / nblk || cost[m] < 1 || cost[m] > 65535)
+            return fail(FV_ERR_INVALID_ARG, "debug_pair_schedule: member %d", m);
         p.m[m].n_items = n_items[m];
         p.m[m].cost = cost[m];
         n[m] = n_items[m];
@@ -1289,8 +1287,9 @@ __global__ void profile_null_kernel() {}
 int fv_profile_bracket_cost(void* stream, int n, double* ms_per_bracket) {
     if (n <= 0 || !ms_per_bracket) return fail(FV_ERR_INVALID_ARG, "profile_bracket_cost: n=%d", n);
     hipStream_t s = (hipStream_t)stream;
-    std::vector<hipEvent_t> ev((size_t)n + 4);
-    for (hipEvent_t& e : ev) FV_HIP(hipEventCreate(&e));
+    ScopedEvents events((size_t)n + 4);
+    if (int rc = events.create()) return rc;
+    const std::vector<hipEvent_t>& ev = events.ev;
     for (int i = 0; i < 8; ++i) hipLaunchKernelGGL(profile_null_kernel, dim3(1), dim3(64), 0, s);
     FV_HIP(hipEventRecord(ev[n], s));
     for (int i = 0; i < n; ++i) {
@@ -1304,7 +1303,6 @@ int fv_profile_bracket_cost(void* stream, int n, double* ms_per_bracket) {
     float with = 0.f, without = 0.f;
     FV_HIP(hipEventElapsedTime(&with, ev[n], ev[n - 1]));
     FV_HIP(hipEventElapsedTime(&without, ev[n + 1], ev[n + 2]));
-    for (hipEvent_t& e : ev) (void)hipEventDestroy(e);
     const double cost = ((double)with - (double)without) / n;
     *ms_per_bracket = cost > 0 ? cost : 0;
     return 0;
@@ -1349,9 +1347,9 @@ int fv_profile_mfma_f16_rate(float* scratch, long long scratch_floats, int launc
     if (scratch_floats < 512LL * blocks)
         return fail(FV_ERR_INVALID_ARG, "profile_mfma_f16_rate: scratch of %lld floats, %lld needed", scratch_floats, 512LL * blocks);
     hipStream_t s = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    FV_HIP(hipEventCreate(&e0));
-    FV_HIP(hipEventCreate(&e1));
+    ScopedEvents events(2);
+    if (int rc = events.create()) return rc;
+    const hipEvent_t e0 = events.ev[0], e1 = events.ev[1];
     const int first = launches / 2;
     for (int i = 0; i < launches; ++i) {
         if (i == first) FV_HIP(hipEventRecord(e0, s));
@@ -1361,8 +1359,6 @@ int fv_profile_mfma_f16_rate(float* scratch, long long scratch_floats, int launc
     FV_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
     FV_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     const double flop = (double)(launches - first) * blocks * 8.0 * iters * 8.0 * 16384.0;
     *tflops = ms > 0.f ? flop / ((double)ms * 1e-3) / 1e12 : 0.0;
     return 0;

@@ -1,5 +1,6 @@
-// What api.hip (operators, measurement hook, tuning) and plan.hip (the plan executor) share: the op record, the plan, and the
-// argument checks / launch helpers both the direct entry points and their plan ops go through.
+// What api.hip (operators, measurement hook, tuning) and plan.hip (the plan executor) share: the op record, the plan, the
+// argument checks, and what both the direct entry points and their plan ops launch through: run_op, the builders of the
+// launch records (PairParams / PairMember / MrfParams from an Op and resolved pointers) and the pair dispatch.
 #pragma once
 #include <stdint.h>
 
@@ -92,7 +93,22 @@ int run_op(const Op& o, const float* x, float* y, float* y2, const float* res, c
                   const float* sub = nullptr, int sub_batched = 0, int* guard = nullptr);
 int check_pad_mode(int pad_mode, int pad, int k, int dil);
 int check_stack_args(int C, int k, int dil, int pad_mode, float slope, float act_slope, int post = FV_POST_NONE);
-int launch_wide_pairs(const PairParams& pp, float* const* mid, int C, int dil, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// launch records: every PairParams / PairMember / MrfParams of the direct entries and of the plan is built here
+// ---------------------------------------------------------------------------
+// a plan's slot as a pointer
+inline float* ptr(float* const* base, int slot) { return slot == FV_SLOT_NONE ? nullptr : base[slot]; }
+// What a launch takes from its op: B, T, the slopes, out_div, post, the arithmetic, reflection padding; the range guard and the
+// output offset as resolved by the caller.  The members, `sum` and `fold_*` are the caller's.
+PairParams pair_params(const Op& o, int n_members, int B, int64_t T, int* guard, const float* sub = nullptr, int sub_batched = 0);
+PairMember pair_member(const float* x, const float* w1, const float* w2, const float* b1, const float* b2, int k, float* y,
+                       float* y_act, const float* res = nullptr, const float* add1 = nullptr, const float* add2 = nullptr,
+                       const float* x2 = nullptr);
+// an OP_STAGE's launch: blob, taps, slopes, out_div, post, fold_w / fold_b and the history slots from the op
+MrfParams mrf_params(const Op& o, const float* x, float* y, float* y_act, float* fold_y, int B, int64_t T, int* guard);
+// a launch of fused ResBlock pairs, by the kernel family of its channel count (mid: the members' scratch tensors, C >= 64)
+int launch_pair_family(const PairParams& pp, float* const* mid, int C, int dil, int prec, hipStream_t s);
 int check_pair_args(int n, int C, const int* k, int dil, int prec = FV_PAIR_F32);
 int check_stage_args(int C, const int* k, const int* dil, float slope, float act_slope, int post);
 int check_convh_args(int n, int C, const int* k, int dil, int pad_mode);

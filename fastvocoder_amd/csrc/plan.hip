@@ -1,10 +1,12 @@
 // The plan executor of libfastvocoder_hip.so (include/fastvocoder_hip.h, fv_plan_*): a recorded sequence of ops over numbered
-// slots, shape inference, the workspace arena and the run loop that turns groups of ops into single launches.
+// slots; one shape rule (set_shapes) for inference and run, one workspace arena (arena) for fv_plan_workspace_bytes and the
+// run; and the run itself: fv_plan_run_aux dispatches to one function per kind of launch (run_*), groups of ops included.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -15,13 +17,39 @@ using namespace fv;
 
 namespace fv {
 
-// Propagate shapes through the op list; fills per-slot max element counts.
-static int infer(const fv_plan* plan, int B, int T, Shape* sh, int64_t* slot_elems) {
-    for (int i = 0; i < FV_MAX_SLOTS; ++i) {
-        sh[i].set = false;
-        slot_elems[i] = 0;
-    }
+// Channels of an op's result: its residual / running-sum inputs and the activated twin have them, and so has y unless an
+// output conv is folded in (set_shapes).  The PQMF ops write the one full-band channel.
+static int out_channels(const Op& o) { return (o.type == OP_PQMF || o.pq_h) ? 1 : o.Cout; }
+
+static void put_shape(Shape* sh, int64_t* slot_elems, int B, int slot, int C, int64_t T) {
+    sh[slot] = {C, T, true};
+    const int64_t e = (int64_t)B * C * T;
+    if (slot_elems && e > slot_elems[slot]) slot_elems[slot] = e;
+}
+
+// The one shape rule: everything op `o` writes, from its input's shape in sh[] -- the scratch tensors of the two-launch
+// forms (sum3: tmpb / tmpc; a wide pair's intermediate tmpb; a residual stack's hidden tensor alt_mid; each [Cout, Tin]),
+// y and the activated twin y2.  infer() passes slot_elems (the slots' largest uses over B utterances); the run, which
+// walks the ops again because a reused slot changes shape, does not.
+static void set_shapes(const Op& o, Shape* sh, int64_t* slot_elems = nullptr, int B = 0) {
+    const int64_t Tin = sh[o.x].T, Tout = conv_out_len(o, Tin);
+    const int scratch[3] = {o.sum3 || o.type == OP_PAIR ? o.tmpb : FV_SLOT_NONE, o.sum3 ? o.tmpc : FV_SLOT_NONE,
+                            o.type == OP_STACK ? o.alt_mid : FV_SLOT_NONE};
+    for (int t : scratch)
+        if (t != FV_SLOT_NONE) put_shape(sh, slot_elems, B, t, o.Cout, Tin);
+    put_shape(sh, slot_elems, B, o.y, o.fold_w ? 1 : out_channels(o), Tout);
+    if (o.y2 != FV_SLOT_NONE) put_shape(sh, slot_elems, B, o.y2, out_channels(o), Tout);
+}
+
+static void reset_shapes(const fv_plan* plan, int T, Shape* sh) {
+    for (int i = 0; i < FV_MAX_SLOTS; ++i) sh[i].set = false;
     sh[FV_SLOT_IN] = {plan->in_channels, T, true};
+}
+
+// Propagate shapes through the op list: every op's checks, then set_shapes; fills per-slot max element counts.
+static int infer(const fv_plan* plan, int B, int T, Shape* sh, int64_t* slot_elems) {
+    for (int i = 0; i < FV_MAX_SLOTS; ++i) slot_elems[i] = 0;
+    reset_shapes(plan, T, sh);
     for (size_t n = 0; n < plan->ops.size(); ++n) {
         const Op& o = plan->ops[n];
         if (o.x == FV_SLOT_AUX_IN0 || o.x == FV_SLOT_AUX_IN1 || o.y == FV_SLOT_AUX_IN0 || o.y == FV_SLOT_AUX_IN1 ||
@@ -38,11 +66,10 @@ static int infer(const fv_plan* plan, int B, int T, Shape* sh, int64_t* slot_ele
                         o.x2, o.Cin - o.Cin1);
         const int64_t Tout = conv_out_len(o, sh[o.x].T);
         if (Tout <= 0) return fail(FV_ERR_INVALID_ARG, "op %zu: empty output (T=%lld)", n, (long long)sh[o.x].T);
-        const int Cout = (o.type == OP_PQMF || o.pq_h) ? 1 : o.Cout;
         const int aux[3] = {o.res, o.acc, o.acc2};
         for (int a = 0; a < 3; ++a) {
             if (aux[a] == FV_SLOT_NONE) continue;
-            if (!sh[aux[a]].set || sh[aux[a]].C != Cout || sh[aux[a]].T != Tout)
+            if (!sh[aux[a]].set || sh[aux[a]].C != out_channels(o) || sh[aux[a]].T != Tout)
                 return fail(FV_ERR_INVALID_ARG, "op %zu: residual/accumulator slot %d shape mismatch", n, aux[a]);
         }
         if (o.in_merge) {
@@ -71,42 +98,34 @@ static int infer(const fv_plan* plan, int B, int T, Shape* sh, int64_t* slot_ele
         }
         if (o.sum3) {   // the scratch tensors of the two-launch form
             const int t2[2] = {o.tmpb, o.tmpc};
-            for (int e = 0; e < 2; ++e) {
+            for (int e = 0; e < 2; ++e)
                 if (t2[e] == o.x || t2[e] == o.xb || t2[e] == o.xc || t2[e] == o.res || t2[e] == o.resb ||
                     t2[e] == o.resc || t2[e] == o.y || t2[e] == o.y2 || t2[e] == FV_SLOT_IN)
                     return fail(FV_ERR_INVALID_ARG, "op %zu: sum3 scratch slot %d aliases an operand", n, t2[e]);
-                sh[t2[e]] = {o.Cout, sh[o.x].T, true};
-                const int64_t es = (int64_t)B * o.Cout * sh[o.x].T;
-                if (es > slot_elems[t2[e]]) slot_elems[t2[e]] = es;
-            }
         }
-        if (o.type == OP_STACK && o.alt_mid != FV_SLOT_NONE) {   // hidden tensor of the two-launch form
-            if (o.alt_mid == o.x || o.alt_mid == o.y || o.alt_mid == o.y2 || o.alt_mid == FV_SLOT_IN)
-                return fail(FV_ERR_INVALID_ARG, "op %zu: stack scratch slot %d aliases an operand", n, o.alt_mid);
-            sh[o.alt_mid] = {o.Cout, sh[o.x].T, true};
-            const int64_t es = (int64_t)B * o.Cout * sh[o.x].T;
-            if (es > slot_elems[o.alt_mid]) slot_elems[o.alt_mid] = es;
-        }
-        if (o.type == OP_PAIR && o.tmpb != FV_SLOT_NONE) {   // intermediate of a two-launch (C >= 64) pair
-            if (o.tmpb == o.x || o.tmpb == o.y || o.tmpb == o.y2 || o.tmpb == o.acc || o.tmpb == o.acc2 || o.tmpb == FV_SLOT_IN)
-                return fail(FV_ERR_INVALID_ARG, "op %zu: pair scratch slot %d aliases an operand", n, o.tmpb);
-            sh[o.tmpb] = {o.Cout, sh[o.x].T, true};
-            const int64_t es = (int64_t)B * o.Cout * sh[o.x].T;
-            if (es > slot_elems[o.tmpb]) slot_elems[o.tmpb] = es;
-        }
+        if (o.type == OP_STACK && o.alt_mid != FV_SLOT_NONE &&   // hidden tensor of the two-launch form
+            (o.alt_mid == o.x || o.alt_mid == o.y || o.alt_mid == o.y2 || o.alt_mid == FV_SLOT_IN))
+            return fail(FV_ERR_INVALID_ARG, "op %zu: stack scratch slot %d aliases an operand", n, o.alt_mid);
+        if (o.type == OP_PAIR && o.tmpb != FV_SLOT_NONE &&       // intermediate of a two-launch (C >= 64) pair
+            (o.tmpb == o.x || o.tmpb == o.y || o.tmpb == o.y2 || o.tmpb == o.acc || o.tmpb == o.acc2 || o.tmpb == FV_SLOT_IN))
+            return fail(FV_ERR_INVALID_ARG, "op %zu: pair scratch slot %d aliases an operand", n, o.tmpb);
         if (o.y == o.x || o.y == o.x2) return fail(FV_ERR_INVALID_ARG, "op %zu: output aliases input", n);
-        const int Cy = o.fold_w ? 1 : Cout;
-        sh[o.y] = {Cy, Tout, true};
-        const int64_t e = (int64_t)B * Cy * Tout;
-        if (e > slot_elems[o.y]) slot_elems[o.y] = e;
-        if (o.y2 != FV_SLOT_NONE) {
-            if (o.y2 == o.x || o.y2 == o.y || o.y2 == o.x2)
-                return fail(FV_ERR_INVALID_ARG, "op %zu: activated twin aliases another tensor of the op", n);
-            sh[o.y2] = {Cout, Tout, true};
-            if (e > slot_elems[o.y2]) slot_elems[o.y2] = e;
-        }
+        if (o.y2 != FV_SLOT_NONE && (o.y2 == o.x || o.y2 == o.y || o.y2 == o.x2))
+            return fail(FV_ERR_INVALID_ARG, "op %zu: activated twin aliases another tensor of the op", n);
+        set_shapes(o, sh, slot_elems, B);
     }
     return 0;
+}
+
+// The workspace arena: the temporary slots one after the other, each sized by its largest use and 256-byte aligned.
+// Returns the bytes needed; with `base`, also writes the slots' addresses inside `workspace`.
+static int64_t arena(const int64_t* slot_elems, void* workspace = nullptr, float** base = nullptr) {
+    int64_t off = 0;
+    for (int i = FV_SLOT_TMP0; i < FV_SLOT_AUX_IN0; ++i) {
+        if (base) base[i] = reinterpret_cast<float*>(static_cast<char*>(workspace) + off);
+        off += (slot_elems[i] * 4 + 255) / 256 * 256;
+    }
+    return off;
 }
 
 }  // namespace fv
@@ -139,6 +158,18 @@ static int check_slot(int s, bool allow_none) {
     return 0;
 }
 
+// The slot checks the fv_plan_add_* functions share: x and y are slots, y_act and the `optional` ones slots or
+// FV_SLOT_NONE, and no op writes the plan's input
+static int check_op_slots(int x, int y, int y_act, std::initializer_list<int> optional = {}) {
+    if (int rc = check_slot(x, false)) return rc;
+    if (int rc = check_slot(y, false)) return rc;
+    if (int rc = check_slot(y_act, true)) return rc;
+    for (int s : optional)
+        if (int rc = check_slot(s, true)) return rc;
+    if (y == FV_SLOT_IN || y_act == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    return 0;
+}
+
 int fv_plan_add_conv1d(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, int res_slot,
                        int acc_slot, int acc2_slot, const float* packed, const float* bias, int Cin,
                        int Cout, int k, int dil, int pad, int pad_mode, float pre_slope, float out_div,
@@ -146,14 +177,7 @@ int fv_plan_add_conv1d(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, 
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d: null");
     if (int rc = check_conv_args(Cin, Cout, k, dil)) return rc;
     if (int rc = check_pad_mode(pad_mode, pad, k, dil)) return rc;
-    if (int rc = check_slot(x_slot, false)) return rc;
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(res_slot, true)) return rc;
-    if (int rc = check_slot(acc_slot, true)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (int rc = check_slot(acc2_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN)
-        return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {res_slot, acc_slot, acc2_slot})) return rc;
     Op o = {};
     o.type = OP_CONV;
     o.x = x_slot;
@@ -244,26 +268,12 @@ int fv_plan_add_conv1x1_2src_split_f16(fv_plan_t* plan, int x_slot, int x2_slot,
     return 0;
 }
 
-// A residual stack that carries its two-launch form (256 channels): one launch up to Tuning::stack_items tiles per CU (in
-// tenths), else two launches on 128-row x 128-column tiles.  [measured, Basis-MelGAN light, 1000 frames, batch 1 / 4 / 16 /
-// 64, tools/bench_configs.py --only 3 --batch B --tuning stack_items=0 against the default] 0.385 -> 0.304, 1.03 -> 0.94,
-// 3.55 -> 3.35, 13.0 -> 12.45 ms: the one-launch kernel wins at every size, so the default limit is "none"; the switch
-// stays for A/B runs and the bit-identity tests
-static bool stack_two_launch(int C, int B, int64_t T) {
-    const int nm = convk_tile_columns(C);
-    const int64_t items = (int64_t)B * ((T + nm - 1) / nm);
-    return items * 10 > (int64_t)tuning().stack_items * device_cu_count();
-}
-
 int fv_plan_add_residual_stack_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, const float* packed,
                                          const float* bias_dilated, const float* bias_out, int C, int k, int dil, float slope,
                                          int pad_mode, int post, float act_slope) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_residual_stack_split_f16: null");
     if (int rc = check_stack_args(C, k, dil, pad_mode, slope, act_slope, post)) return rc;
-    if (int rc = check_slot(x_slot, false)) return rc;
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot)) return rc;
     Op o = {};
     o.type = OP_STACK;
     o.prec = FV_PAIR_SPLIT_F16;
@@ -312,11 +322,7 @@ int fv_plan_add_conv_transpose1d(fv_plan_t* plan, int x_slot, int y_slot, int y_
     if (int rc = check_conv_args(Cin, Cout, k, 1)) return rc;
     if (stride <= 0 || pad < 0 || out_pad < -stride)
         return fail(FV_ERR_INVALID_ARG, "convT stride=%d pad=%d out_pad=%d", stride, pad, out_pad);
-    if (int rc = check_slot(x_slot, false)) return rc;
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN)
-        return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot)) return rc;
     Op o = {};
     o.type = OP_CONVT;
     o.x = x_slot;
@@ -415,10 +421,7 @@ int fv_plan_add_mrf_stage_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int
     if (workspace_bytes < mrf_workspace_bytes(C) || (mrf_workspace_bytes(C) > 0 && !workspace))
         return fail(FV_ERR_WORKSPACE, "plan_add_mrf_stage: C = %d needs a workspace of %lld bytes (fv_mrf_stage_workspace_bytes)", C,
                     (long long)mrf_workspace_bytes(C));
-    if (int rc = check_slot(x_slot, false)) return rc;
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot)) return rc;
     Op o = {};
     o.type = OP_STAGE;
     o.x = x_slot;
@@ -467,12 +470,7 @@ int fv_plan_add_resblock_pair_ex(fv_plan_t* plan, int x_slot, int y_slot, int y_
     if (prec == FV_PAIR_F32 && (add1_slot != FV_SLOT_NONE || add2_slot != FV_SLOT_NONE || out_div != 1.f || post != FV_POST_NONE))
         return fail(FV_ERR_UNSUPPORTED, "plan_add_resblock_pair: add1 / add2 / out_div / post exist with FV_PAIR_SPLIT_F16 only");
     if (add2_slot != FV_SLOT_NONE && add1_slot == FV_SLOT_NONE) return fail(FV_ERR_INVALID_ARG, "plan_add_resblock_pair: add2 without add1");
-    if (int rc = check_slot(x_slot, false)) return rc;
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (int rc = check_slot(add1_slot, true)) return rc;
-    if (int rc = check_slot(add2_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {add1_slot, add2_slot})) return rc;
     Op o = {};
     o.type = OP_PAIR;
     o.x = x_slot;
@@ -506,13 +504,7 @@ int fv_plan_add_conv1d_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: null");
     if (int rc = check_convh_args(1, C, &k, dil, pad_mode)) return rc;
     if (add2_slot != FV_SLOT_NONE && add1_slot == FV_SLOT_NONE) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: add2 without add1");
-    if (int rc = check_slot(x_slot, false)) return rc;
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (int rc = check_slot(res_slot, true)) return rc;
-    if (int rc = check_slot(add1_slot, true)) return rc;
-    if (int rc = check_slot(add2_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {res_slot, add1_slot, add2_slot})) return rc;
     if (y_slot == res_slot || y_slot == add1_slot || y_slot == add2_slot)
         return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: the output aliases an addend");
     Op o = {};
@@ -551,9 +543,7 @@ int fv_plan_add_mrf_sum(fv_plan_t* plan, const int* x_slots, int y_slot, int y_a
         if (!packed1[j] || !packed2[j]) return fail(FV_ERR_INVALID_ARG, "plan_add_mrf_sum: member %d has no weights", j);
         if (int rc = check_slot(x_slots[j], false)) return rc;
     }
-    if (int rc = check_slot(y_slot, false)) return rc;
-    if (int rc = check_slot(y_act_slot, true)) return rc;
-    if (y_slot == FV_SLOT_IN || y_act_slot == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    if (int rc = check_op_slots(x_slots[0], y_slot, y_act_slot)) return rc;
     Op o = {};
     o.type = OP_MRFSUM;
     o.x = x_slots[0];
@@ -651,10 +641,180 @@ int64_t fv_plan_workspace_bytes(fv_plan_t* plan, int B, int T) {
     Shape sh[FV_MAX_SLOTS];
     int64_t elems[FV_MAX_SLOTS];
     if (int rc = infer(plan, B, T, sh, elems)) return rc < 0 ? rc : -rc;
-    int64_t bytes = 0;
-    for (int i = FV_SLOT_TMP0; i < FV_SLOT_AUX_IN0; ++i) bytes += (elems[i] * 4 + 255) / 256 * 256;
-    return bytes;
+    return arena(elems);
 }
+
+}  // extern "C"
+
+namespace fv {
+
+// ---------------------------------------------------------------------------
+// the run: one function per kind of launch; fv_plan_run_aux checks, lays the arena out and dispatches
+// ---------------------------------------------------------------------------
+// What the branches share.  sh[] holds the shapes in front of the op (or group of ops) being launched.
+struct Run {
+    const fv_plan* plan;
+    int B;
+    float* const* base;      // slot -> tensor
+    const Shape* sh;
+    const int* aux_b;        // auxiliary input 0 / 1 has a batch dimension
+    hipStream_t s;
+    const Op& op(size_t n) const { return plan->ops[n]; }
+    float* at(int slot) const { return ptr(base, slot); }
+    int64_t T(const Op& o) const { return sh[o.x].T; }
+    int* guard() const { return plan->guard_dev; }
+    const float* sub(const Op& o) const { return ptr(base, o.sub); }
+    int sub_batched(const Op& o) const { return o.sub == FV_SLOT_NONE ? 0 : aux_b[o.sub - FV_SLOT_AUX_IN0]; }
+};
+
+// "Same launch": may op b join the group that op a starts?  One predicate per kernel family -- each lists what ITS launch
+// record holds once for all members (the fp32 conv group takes any three convs: every member has a ConvParams of its own).
+static bool same_convh(const Op& a, const Op& b) {
+    return b.type == OP_CONVH && b.group == a.group && b.Cin == a.Cin && b.dil == a.dil && b.pad_mode == a.pad_mode &&
+           b.pre_slope == a.pre_slope && b.act_slope == a.act_slope && b.out_div == a.out_div && b.post == a.post;
+}
+static bool same_pair(const Op& a, const Op& b) {      // (a pair with a folded output conv runs alone)
+    return b.type == OP_PAIR && b.group == a.group && b.Cin == a.Cin && b.dil == a.dil && b.pre_slope == a.pre_slope &&
+           b.act_slope == a.act_slope && !a.fold_w && !b.fold_w && b.prec == a.prec && b.out_div == a.out_div && b.post == a.post;
+}
+static bool same_conv(const Op& a, const Op& b) { return b.type == OP_CONV && b.group == a.group; }
+
+// End of the group that op n starts: up to three consecutive ops with its (non-zero) group id that `same` lets share a launch
+static size_t group_end(const fv_plan* plan, size_t n, bool (*same)(const Op&, const Op&)) {
+    size_t m = n + 1;
+    if (plan->ops[n].group != 0)
+        while (m < plan->ops.size() && m - n < 3 && same(plan->ops[n], plan->ops[m])) ++m;
+    return m;
+}
+
+// split-f16 convs of the wide stages: the members [n, m) of a group in one launch
+static int run_convh_group(const Run& r, size_t n, size_t m) {
+    const Op& o = r.op(n);
+    PairParams pp = pair_params(o, (int)(m - n), r.B, r.T(o), r.guard());
+    for (size_t q = n; q < m; ++q) {
+        const Op& qo = r.op(q);
+        pp.m[q - n] = pair_member(r.base[qo.x], qo.pw1[0], nullptr, qo.pb1[0], nullptr, qo.pk[0], r.base[qo.y], r.at(qo.y2),
+                                  r.at(qo.res), r.at(qo.acc), r.at(qo.acc2));
+    }
+    return launch_convh(pp, o.Cin, o.dil, r.s);
+}
+
+// a whole 16- / 32-channel MRF stage: one launch (with a folded output conv, y is THAT conv's output)
+static int run_stage(const Run& r, const Op& o) {
+    float* const y = r.base[o.y];
+    return launch_mrfh(mrf_params(o, r.base[o.x], o.fold_w ? nullptr : y, o.fold_w ? nullptr : r.at(o.y2), o.fold_w ? y : nullptr,
+                                  r.B, r.T(o), r.guard()),
+                       o.Cin, o.sdil, r.s);
+}
+
+// fused ResBlock pairs: the members [n, m) of a group (the three ResBlocks of an MRF stage) in one launch, or an
+// OP_MRFSUM, which holds its three members itself
+static int run_pair_group(const Run& r, size_t n, size_t m) {
+    const Op& o = r.op(n);
+    const bool sum = o.type == OP_MRFSUM;
+    PairParams pp = pair_params(o, sum ? 3 : (int)(m - n), r.B, r.T(o), r.guard());
+    float* mids[3] = {nullptr, nullptr, nullptr};
+    if (sum) {
+        const int xs3[3] = {o.x, o.xb, o.xc};
+        pp.sum = 1;
+        for (int j = 0; j < 3; ++j)
+            pp.m[j] = pair_member(r.base[xs3[j]], o.pw1[j], o.pw2[j], o.pb1[j], o.pb2[j], o.pk[j], r.base[o.y], r.at(o.y2));
+    } else {
+        for (size_t q = n; q < m; ++q) {
+            const Op& qo = r.op(q);
+            pp.m[q - n] = pair_member(r.base[qo.x], qo.pw1[0], qo.pw2[0], qo.pb1[0], qo.pb2[0], qo.pk[0],
+                                      qo.fold_w ? nullptr : r.base[qo.y], r.at(qo.y2), nullptr, r.at(qo.acc), r.at(qo.acc2));
+            mids[q - n] = r.at(qo.tmpb);
+            if (qo.fold_w) {            // (never grouped: one member)
+                pp.fold_w = qo.fold_w;
+                pp.fold_b = qo.fold_b;
+                pp.fold_y = r.base[qo.y];
+            }
+        }
+    }
+    return launch_pair_family(pp, mids, o.Cin, o.dil, o.prec, r.s);
+}
+
+// a group of mutually independent fp32 convs: one launch when possible
+static int run_conv_group(const Run& r, size_t n, size_t m) {
+    ConvParams gp[3];
+    for (size_t q = n; q < m; ++q) {
+        const Op& qo = r.op(q);
+        gp[q - n] = make_params(qo, r.base[qo.x], r.base[qo.y], r.at(qo.y2), r.at(qo.res), r.at(qo.acc), r.at(qo.acc2), r.B,
+                                r.T(qo), r.at(qo.x2));
+    }
+    return launch_conv_group(gp, (int)(m - n), r.s);
+}
+
+// the last convs of the three ResBlocks of an fp32 MRF stage, summed (fv_plan_add_conv1d_sum3)
+static int run_sum3(const Run& r, const Op& o) {
+    float* const* base = r.base;
+    Op mb = o, mc = o;           // members 1, 2: same layer geometry, their own taps / weights
+    mb.k = o.kb; mb.pad = (o.kb - 1) / 2; mb.wp = o.wpb; mb.bias = nullptr;
+    mc.k = o.kc; mc.pad = (o.kc - 1) / 2; mc.wp = o.wpc; mc.bias = nullptr;
+    float* y2s = r.at(o.y2);
+    // One launch pays when the three K loops in a row still leave enough blocks to fill the
+    // GPU (tiles of 32 x 128, or 16 x 128); otherwise the two-launch form: members 1, 2 as a
+    // grouped launch into scratch, then member 0 with both as running-sum inputs.
+    const int64_t T3 = r.T(o);
+    const int Mp = pad_rows(o.Cout);
+    const int64_t blocks = (int64_t)(Mp == 16 ? 1 : Mp / 32) * ((T3 + 127) / 128);
+    const int min_blocks = tuning().sum3_min;   // 800 -- measured: HiFi-GAN light, B = 1
+    if (blocks >= min_blocks && Mp == o.Cout) {   // (whole row tiles only: the kernel's epilogue is the affine one)
+        ConvParams ps[3] = {
+            make_params(o, base[o.x], base[o.y], y2s, base[o.res], nullptr, nullptr, r.B, T3),
+            make_params(mb, base[o.xb], base[o.y], y2s, base[o.resb], nullptr, nullptr, r.B, T3),
+            make_params(mc, base[o.xc], base[o.y], y2s, base[o.resc], nullptr, nullptr, r.B, T3)};
+        return launch_conv_sum3(ps, r.s);
+    }
+    Op duo_b = mb, duo_c = mc;                 // r_b, r_c: conv + residual, raw, no mean / activation
+    duo_b.out_div = duo_c.out_div = 1.f;
+    duo_b.act_slope = duo_c.act_slope = 1.f;
+    duo_b.post = duo_c.post = FV_POST_NONE;
+    ConvParams duo[2] = {
+        make_params(duo_b, base[o.xb], base[o.tmpb], nullptr, base[o.resb], nullptr, nullptr, r.B, T3),
+        make_params(duo_c, base[o.xc], base[o.tmpc], nullptr, base[o.resc], nullptr, nullptr, r.B, T3)};
+    if (int rc = launch_conv_group(duo, 2, r.s)) return rc;
+    Op car = o;                                // ((own + r_b) + r_c) / out_div, summed bias on this one
+    car.own_first = 1;
+    return launch_conv(make_params(car, base[o.x], base[o.y], y2s, base[o.res], base[o.tmpb], base[o.tmpc], r.B, T3), r.s);
+}
+
+// A residual stack that carries its two-launch form (256 channels): one launch up to Tuning::stack_items tiles per CU (in
+// tenths), else two launches on 128-row x 128-column tiles.  [measured, Basis-MelGAN light, 1000 frames, batch 1 / 4 / 16 /
+// 64, tools/bench_configs.py --only 3 --batch B --tuning stack_items=0 against the default] 0.385 -> 0.304, 1.03 -> 0.94,
+// 3.55 -> 3.35, 13.0 -> 12.45 ms: the one-launch kernel wins at every size, so the default limit is "none"; the switch
+// stays for A/B runs and the bit-identity tests
+static bool stack_two_launch(int C, int B, int64_t T) {
+    const int nm = convk_tile_columns(C);
+    const int64_t items = (int64_t)B * ((T + nm - 1) / nm);
+    return items * 10 > (int64_t)tuning().stack_items * device_cu_count();
+}
+
+// ... its two launches: the dilated conv into the scratch slot, raw (convs_kernel), then the K-concatenated 1x1 pair over
+// the hidden tensor and x (convr_kernel), which carries the op's activation, post op and output offset
+static int run_stack_two_launch(const Run& r, const Op& o) {
+    PairParams pp = pair_params(o, 1, r.B, r.T(o), r.guard());
+    pp.act_slope = 1.f;
+    pp.post = FV_POST_NONE;
+    pp.m[0] = pair_member(r.base[o.x], o.alt_w1, nullptr, o.bias, nullptr, o.k, r.base[o.alt_mid], nullptr);
+    if (int rc = launch_convh(pp, o.Cin, o.dil, r.s)) return rc;
+    PairParams pg = pair_params(o, 1, r.B, r.T(o), r.guard(), r.sub(o), r.sub_batched(o));
+    pg.m[0] = pair_member(r.base[o.alt_mid], o.alt_w2, nullptr, o.bias2, nullptr, 1, r.base[o.y], r.at(o.y2), nullptr, nullptr,
+                          nullptr, r.base[o.x]);
+    return launch_convg(pg, o.Cout, r.s);
+}
+
+// every other op: one launch of its own
+static int run_single(const Run& r, const Op& o) {
+    const bool merge = o.type == OP_CONVT && o.in_merge;   // merged INPUT (fv_plan_set_input_merge): xb, xc travel as acc, acc2
+    return run_op(o, r.base[o.x], r.base[o.y], r.at(o.y2), r.at(o.res), r.at(merge ? o.xb : o.acc), r.at(merge ? o.xc : o.acc2),
+                  r.B, r.T(o), r.s, r.at(o.x2), r.sub(o), r.sub_batched(o), r.guard());
+}
+
+}  // namespace fv
+
+extern "C" {
 
 int fv_plan_run(fv_plan_t* plan, int B, int T, const float* in, float* out, void* workspace,
                 int64_t workspace_bytes, void* stream) {
@@ -670,11 +830,7 @@ int fv_plan_run_aux(fv_plan_t* plan, int B, int T, const float* in, float* out, 
     int64_t elems[FV_MAX_SLOTS];
     if (int rc = infer(plan, B, T, sh, elems)) return rc;
     float* base[FV_MAX_SLOTS] = {};
-    int64_t off = 0;
-    for (int i = FV_SLOT_TMP0; i < FV_SLOT_AUX_IN0; ++i) {
-        base[i] = reinterpret_cast<float*>(static_cast<char*>(workspace) + off);
-        off += (elems[i] * 4 + 255) / 256 * 256;
-    }
+    const int64_t need = arena(elems, workspace, base);
     base[FV_SLOT_AUX_IN0] = aux_in ? const_cast<float*>(aux_in[0]) : nullptr;
     base[FV_SLOT_AUX_IN1] = aux_in ? const_cast<float*>(aux_in[1]) : nullptr;
     base[FV_SLOT_OUT2] = out2;
@@ -683,293 +839,37 @@ int fv_plan_run_aux(fv_plan_t* plan, int B, int T, const float* in, float* out, 
         if (o.sub != FV_SLOT_NONE && !base[o.sub]) return fail(FV_ERR_INVALID_ARG, "plan_run: the plan subtracts auxiliary input %d, which was not given", o.sub - FV_SLOT_AUX_IN0);
         if ((o.y == FV_SLOT_OUT2 || o.y2 == FV_SLOT_OUT2) && !out2) return fail(FV_ERR_INVALID_ARG, "plan_run: the plan writes a second output, which was not given");
     }
-    if (off > workspace_bytes || (off > 0 && !workspace))
-        return fail(FV_ERR_WORKSPACE, "plan needs %lld workspace bytes, got %lld", (long long)off,
+    if (need > workspace_bytes || (need > 0 && !workspace))
+        return fail(FV_ERR_WORKSPACE, "plan needs %lld workspace bytes, got %lld", (long long)need,
                     (long long)workspace_bytes);
     base[FV_SLOT_IN] = const_cast<float*>(in);
     base[FV_SLOT_OUT] = out;
-    hipStream_t const s = (hipStream_t)stream;
-    // shapes again, op by op (a slot may change shape when it is reused)
-    for (int i = 0; i < FV_MAX_SLOTS; ++i) sh[i].set = false;
-    sh[FV_SLOT_IN] = {plan->in_channels, T, true};
-    for (size_t n = 0; n < plan->ops.size(); ++n) {
+    const Run r = {plan, B, base, sh, aux_b, (hipStream_t)stream};
+    reset_shapes(plan, T, sh);      // shapes again, launch by launch (a slot may change shape when it is reused)
+    for (size_t n = 0; n < plan->ops.size();) {
         const Op& o = plan->ops[n];
-        // ---- split-f16 convs of the wide stages: the members of a group in one launch ----
+        size_t m = n + 1;           // the launch runs the ops [n, m)
+        int rc;
         if (o.type == OP_CONVH) {
-            size_t m = n + 1;
-            if (o.group != 0)
-                while (m < plan->ops.size() && m - n < 3 && plan->ops[m].type == OP_CONVH && plan->ops[m].group == o.group &&
-                       plan->ops[m].Cin == o.Cin && plan->ops[m].dil == o.dil &&
-                       plan->ops[m].pad_mode == o.pad_mode &&
-                       plan->ops[m].pre_slope == o.pre_slope && plan->ops[m].act_slope == o.act_slope &&
-                       plan->ops[m].out_div == o.out_div && plan->ops[m].post == o.post)
-                    ++m;
-            PairParams pp = {};
-            pp.B = B;
-            pp.T = (int)sh[o.x].T;
-            pp.slope = o.pre_slope;
-            pp.act_slope = o.act_slope;
-            pp.out_div = o.out_div;
-            pp.post = o.post;
-            pp.prec = FV_PAIR_SPLIT_F16;
-            pp.guard = plan->guard_dev;
-            pp.reflect = o.pad_mode == FV_PAD_REFLECT;
-            pp.n_members = (int)(m - n);
-            for (size_t q = n; q < m; ++q) {
-                const Op& qo = plan->ops[q];
-                PairMember& mb = pp.m[q - n];
-                mb.x = base[qo.x];
-                mb.w1 = qo.pw1[0];
-                mb.b1 = qo.pb1[0];
-                mb.k = qo.pk[0];
-                mb.y = base[qo.y];
-                mb.y_act = qo.y2 == FV_SLOT_NONE ? nullptr : base[qo.y2];
-                mb.res = qo.res == FV_SLOT_NONE ? nullptr : base[qo.res];
-                mb.add1 = qo.acc == FV_SLOT_NONE ? nullptr : base[qo.acc];
-                mb.add2 = qo.acc2 == FV_SLOT_NONE ? nullptr : base[qo.acc2];
-            }
-            if (int rc = launch_convh(pp, o.Cin, o.dil, s)) return rc;
-            for (size_t q = n; q < m; ++q) {
-                const Op& qo = plan->ops[q];
-                sh[qo.y] = {qo.Cout, sh[qo.x].T, true};
-                if (qo.y2 != FV_SLOT_NONE) sh[qo.y2] = sh[qo.y];
-            }
-            n = m - 1;
-            continue;
+            m = group_end(plan, n, same_convh);
+            rc = run_convh_group(r, n, m);
+        } else if (o.type == OP_STAGE) {
+            rc = run_stage(r, o);
+        } else if (o.type == OP_PAIR || o.type == OP_MRFSUM) {
+            m = group_end(plan, n, same_pair);
+            rc = run_pair_group(r, n, m);
+        } else if (o.type == OP_CONV && o.group != 0) {
+            m = group_end(plan, n, same_conv);
+            rc = run_conv_group(r, n, m);
+        } else if (o.sum3) {
+            rc = run_sum3(r, o);
+        } else if (o.type == OP_STACK && o.alt_w1 && stack_two_launch(o.Cout, B, r.T(o))) {
+            rc = run_stack_two_launch(r, o);
+        } else {
+            rc = run_single(r, o);
         }
-        // ---- a whole 16-channel MRF stage: one launch ----
-        if (o.type == OP_STAGE) {
-            MrfParams mp = {};
-            mp.x = base[o.x];
-            mp.blob = o.wp;
-            for (int j = 0; j < 3; ++j) mp.k[j] = o.pk[j];
-            mp.B = B;
-            mp.T = (int)sh[o.x].T;
-            mp.slope = o.pre_slope;
-            mp.out_div = o.out_div;
-            mp.act_slope = o.act_slope;
-            mp.post = o.post;
-            mp.guard = plan->guard_dev;
-            mp.hist = static_cast<float*>(o.work);
-            mp.hist_bytes = o.work_bytes;
-            if (o.fold_w) {
-                mp.fold_w = o.fold_w;
-                mp.fold_b = o.fold_b;
-                mp.fold_y = base[o.y];
-            } else {
-                mp.y = base[o.y];
-                mp.y_act = o.y2 == FV_SLOT_NONE ? nullptr : base[o.y2];
-            }
-            if (int rc = launch_mrfh(mp, o.Cin, o.sdil, s)) return rc;
-            sh[o.y] = {o.fold_w ? 1 : o.Cout, sh[o.x].T, true};
-            if (o.y2 != FV_SLOT_NONE) sh[o.y2] = sh[o.y];
-            continue;
-        }
-        // ---- fused ResBlock pairs: the members of a group (the three ResBlocks of an MRF stage) in one launch ----
-        if (o.type == OP_PAIR || o.type == OP_MRFSUM) {
-            // the launch that starts at op n0: its members [n0, end) and its parameters (Tn: samples per utterance)
-            auto gather = [&](size_t n0, int Tn, PairParams& pp) -> size_t {
-            const Op& o = plan->ops[n0];
-            const size_t n = n0;
-            size_t m = n + 1;
-            if (o.type == OP_PAIR && o.group != 0)
-                while (m < plan->ops.size() && m - n < 3 && plan->ops[m].type == OP_PAIR && plan->ops[m].group == o.group &&
-                       plan->ops[m].Cin == o.Cin && plan->ops[m].dil == o.dil &&
-                       plan->ops[m].pre_slope == o.pre_slope && plan->ops[m].act_slope == o.act_slope && !o.fold_w &&
-                       !plan->ops[m].fold_w &&
-                       plan->ops[m].prec == o.prec && plan->ops[m].out_div == o.out_div && plan->ops[m].post == o.post)
-                    ++m;
-            pp = {};
-            pp.B = B;
-            pp.T = Tn;
-            pp.slope = o.pre_slope;
-            pp.act_slope = o.act_slope;
-            pp.out_div = o.out_div;
-            pp.post = o.post;
-            pp.prec = o.prec;
-            pp.guard = plan->guard_dev;
-            if (o.type == OP_MRFSUM) {
-                const int xs3[3] = {o.x, o.xb, o.xc};
-                pp.sum = 1;
-                pp.n_members = 3;
-                for (int j = 0; j < 3; ++j) {
-                    PairMember& mb = pp.m[j];
-                    mb.x = base[xs3[j]];
-                    mb.w1 = o.pw1[j];
-                    mb.w2 = o.pw2[j];
-                    mb.b1 = o.pb1[j];
-                    mb.b2 = o.pb2[j];
-                    mb.k = o.pk[j];
-                    mb.y = base[o.y];
-                    mb.y_act = o.y2 == FV_SLOT_NONE ? nullptr : base[o.y2];
-                }
-            } else {
-                pp.n_members = (int)(m - n);
-                for (size_t q = n; q < m; ++q) {
-                    const Op& qo = plan->ops[q];
-                    PairMember& mb = pp.m[q - n];
-                    mb.x = base[qo.x];
-                    mb.w1 = qo.pw1[0];
-                    mb.w2 = qo.pw2[0];
-                    mb.b1 = qo.pb1[0];
-                    mb.b2 = qo.pb2[0];
-                    mb.k = qo.pk[0];
-                    mb.y = base[qo.y];
-                    mb.y_act = qo.y2 == FV_SLOT_NONE ? nullptr : base[qo.y2];
-                    mb.add1 = qo.acc == FV_SLOT_NONE ? nullptr : base[qo.acc];
-                    mb.add2 = qo.acc2 == FV_SLOT_NONE ? nullptr : base[qo.acc2];
-                    if (qo.fold_w) {            // (never grouped: one member)
-                        pp.fold_w = qo.fold_w;
-                        pp.fold_b = qo.fold_b;
-                        pp.fold_y = base[qo.y];
-                        mb.y = nullptr;
-                    }
-                }
-            }
-            return m;
-            };
-            auto set_shapes = [&](size_t n0, size_t m0) {
-                for (size_t q = n0; q < m0; ++q) {
-                    const Op& qo = plan->ops[q];
-                    sh[qo.y] = {qo.fold_w ? 1 : qo.Cout, sh[qo.x].T, true};
-                    if (qo.y2 != FV_SLOT_NONE) sh[qo.y2] = sh[qo.y];
-                }
-            };
-            PairParams pp;
-            const size_t m = gather(n, (int)sh[o.x].T, pp);
-            if (o.Cin == 64 && o.prec == FV_PAIR_SPLIT_F16) {
-                if (int rc = launch_convp(pp, o.dil, s)) return rc;
-            } else if (o.Cin == 128 && o.prec == FV_PAIR_SPLIT_F16 && !tuning().pair128_unfused) {
-                if (int rc = launch_convq(pp, o.dil, s)) return rc;
-            } else if (o.Cin >= 64) {
-                float* mids[3] = {nullptr, nullptr, nullptr};
-                for (size_t q = n; q < m; ++q) mids[q - n] = base[plan->ops[q].tmpb];
-                if (int rc = launch_wide_pairs(pp, mids, o.Cin, o.dil, s)) return rc;
-            } else if (int rc = launch_pairs(pp, o.Cin, o.dil, s)) return rc;
-            set_shapes(n, m);
-            n = m - 1;
-            continue;
-        }
-        // ---- a group of mutually independent convs: one launch when possible ----
-        if (o.group != 0 && o.type == OP_CONV) {
-            size_t m = n;
-            ConvParams gp[3];
-            int cnt = 0;
-            while (m < plan->ops.size() && plan->ops[m].group == o.group && plan->ops[m].type == OP_CONV &&
-                   cnt < 3) {
-                const Op& q = plan->ops[m];
-                gp[cnt++] = make_params(q, base[q.x], base[q.y], q.y2 == FV_SLOT_NONE ? nullptr : base[q.y2],
-                                        q.res == FV_SLOT_NONE ? nullptr : base[q.res],
-                                        q.acc == FV_SLOT_NONE ? nullptr : base[q.acc],
-                                        q.acc2 == FV_SLOT_NONE ? nullptr : base[q.acc2], B, sh[q.x].T,
-                                        q.x2 == FV_SLOT_NONE ? nullptr : base[q.x2]);
-                ++m;
-            }
-            if (int rc = launch_conv_group(gp, cnt, s)) return rc;
-            for (size_t q = n; q < m; ++q) {
-                const Op& qo = plan->ops[q];
-                sh[qo.y] = {qo.Cout, conv_out_len(qo, sh[qo.x].T), true};
-                if (qo.y2 != FV_SLOT_NONE) sh[qo.y2] = sh[qo.y];
-            }
-            n = m - 1;
-            continue;
-        }
-        if (o.sum3) {
-            hipStream_t s3 = s;
-            Op mb = o, mc = o;           // members 1, 2: same layer geometry, their own taps / weights
-            mb.k = o.kb; mb.pad = (o.kb - 1) / 2; mb.wp = o.wpb; mb.bias = nullptr;
-            mc.k = o.kc; mc.pad = (o.kc - 1) / 2; mc.wp = o.wpc; mc.bias = nullptr;
-            float* y2s = o.y2 == FV_SLOT_NONE ? nullptr : base[o.y2];
-            // One launch pays when the three K loops in a row still leave enough blocks to fill the
-            // GPU (tiles of 32 x 128, or 16 x 128); otherwise the two-launch form: members 1, 2 as a
-            // grouped launch into scratch, then member 0 with both as running-sum inputs.
-            const int64_t T3 = sh[o.x].T;
-            const int Mp = pad_rows(o.Cout);
-            const int64_t blocks = (int64_t)(Mp == 16 ? 1 : Mp / 32) * ((T3 + 127) / 128);
-            const int min_blocks = tuning().sum3_min;   // 800 -- measured: HiFi-GAN light, B = 1
-            int rc3;
-            if (blocks >= min_blocks && Mp == o.Cout) {   // (whole row tiles only: the kernel's epilogue is the affine one)
-                ConvParams ps[3] = {
-                    make_params(o, base[o.x], base[o.y], y2s, base[o.res], nullptr, nullptr, B, T3),
-                    make_params(mb, base[o.xb], base[o.y], y2s, base[o.resb], nullptr, nullptr, B, T3),
-                    make_params(mc, base[o.xc], base[o.y], y2s, base[o.resc], nullptr, nullptr, B, T3)};
-                rc3 = launch_conv_sum3(ps, s3);
-            } else {
-                Op duo_b = mb, duo_c = mc;                 // r_b, r_c: conv + residual, raw, no mean / activation
-                duo_b.out_div = duo_c.out_div = 1.f;
-                duo_b.act_slope = duo_c.act_slope = 1.f;
-                duo_b.post = duo_c.post = FV_POST_NONE;
-                ConvParams duo[2] = {
-                    make_params(duo_b, base[o.xb], base[o.tmpb], nullptr, base[o.resb], nullptr, nullptr, B, T3),
-                    make_params(duo_c, base[o.xc], base[o.tmpc], nullptr, base[o.resc], nullptr, nullptr, B, T3)};
-                rc3 = launch_conv_group(duo, 2, s3);
-                if (!rc3) {
-                    Op car = o;                            // ((own + r_b) + r_c) / out_div, summed bias on this one
-                    car.own_first = 1;
-                    rc3 = launch_conv(make_params(car, base[o.x], base[o.y], y2s, base[o.res], base[o.tmpb],
-                                                  base[o.tmpc], B, T3), s3);
-                }
-            }
-            if (rc3) return rc3;
-            sh[o.y] = {o.Cout, conv_out_len(o, sh[o.x].T), true};
-            if (o.y2 != FV_SLOT_NONE) sh[o.y2] = sh[o.y];
-            continue;
-        }
-        if (o.type == OP_STACK && o.alt_w1 && stack_two_launch(o.Cout, B, sh[o.x].T)) {
-            // many tiles: dilated conv into the scratch slot (convs_kernel), then the K-concatenated 1x1 pair (convr_kernel)
-            PairParams pp = {};
-            pp.B = B;
-            pp.T = (int)sh[o.x].T;
-            pp.slope = o.pre_slope;
-            pp.act_slope = 1.f;
-            pp.out_div = 1.f;
-            pp.prec = FV_PAIR_SPLIT_F16;
-            pp.guard = plan->guard_dev;
-            pp.reflect = o.pad_mode == FV_PAD_REFLECT;
-            pp.n_members = 1;
-            pp.m[0].x = base[o.x];
-            pp.m[0].w1 = o.alt_w1;
-            pp.m[0].b1 = o.bias;
-            pp.m[0].k = o.k;
-            pp.m[0].y = base[o.alt_mid];
-            if (int rc = launch_convh(pp, o.Cin, o.dil, s)) return rc;
-            PairParams pg = {};
-            pg.B = B;
-            pg.T = (int)sh[o.x].T;
-            pg.slope = o.pre_slope;
-            pg.act_slope = o.act_slope;
-            pg.post = o.post;
-            pg.prec = FV_PAIR_SPLIT_F16;
-            pg.guard = plan->guard_dev;
-            pg.m[0].x = base[o.alt_mid];
-            pg.m[0].x2 = base[o.x];
-            pg.m[0].w1 = o.alt_w2;
-            pg.m[0].b1 = o.bias2;
-            pg.m[0].y = base[o.y];
-            pg.m[0].y_act = o.y2 == FV_SLOT_NONE ? nullptr : base[o.y2];
-            pg.sub = o.sub == FV_SLOT_NONE ? nullptr : base[o.sub];
-            pg.sub_batched = o.sub == FV_SLOT_NONE ? 0 : aux_b[o.sub - FV_SLOT_AUX_IN0];
-            if (int rc = launch_convg(pg, o.Cout, s)) return rc;
-            sh[o.y] = {o.Cout, sh[o.x].T, true};
-            if (o.y2 != FV_SLOT_NONE) sh[o.y2] = sh[o.y];
-            continue;
-        }
-        const int64_t Tin = sh[o.x].T;
-        const int64_t Tout = conv_out_len(o, Tin);
-        const float* res = o.res == FV_SLOT_NONE ? nullptr : base[o.res];
-        const float* acc = o.acc == FV_SLOT_NONE ? nullptr : base[o.acc];
-        const float* acc2 = o.acc2 == FV_SLOT_NONE ? nullptr : base[o.acc2];
-        if (o.type == OP_CONVT && o.in_merge) {        // merged INPUT (fv_plan_set_input_merge): xb, xc travel as acc, acc2
-            acc = base[o.xb];
-            acc2 = o.xc == FV_SLOT_NONE ? nullptr : base[o.xc];
-        }
-        float* y2 = o.y2 == FV_SLOT_NONE ? nullptr : base[o.y2];
-        if (int rc = run_op(o, base[o.x], base[o.y], y2, res, acc, acc2, B, Tin, s,
-                            o.x2 == FV_SLOT_NONE ? nullptr : base[o.x2], o.sub == FV_SLOT_NONE ? nullptr : base[o.sub],
-                            o.sub == FV_SLOT_NONE ? 0 : aux_b[o.sub - FV_SLOT_AUX_IN0], plan->guard_dev))
-            return rc;
-        sh[o.y] = {(o.type == OP_PQMF || o.pq_h) ? 1 : o.Cout, Tout, true};
-        if (o.y2 != FV_SLOT_NONE) sh[o.y2] = sh[o.y];
+        if (rc) return rc;
+        for (; n < m; ++n) set_shapes(plan->ops[n], sh);
     }
     return 0;
 }

@@ -405,6 +405,39 @@ def test_block_schedule_gives_the_same_bits(tuning):
         assert _rel(sched[0], ref) <= 4e-6
 
 
+@pytest.mark.parametrize("C,unfused", [(64, 0), (128, 0), (128, 1)], ids=["fused-64", "fused-128", "two-launch-128"])
+def test_grouped_pairs_in_a_plan_equal_the_direct_entry(C, unfused, tuning):
+    """A plan's pair groups and fv_resblock1_fused_ex build their launches in one place (pair_params / pair_member /
+    launch_pair_family): an MRF stage's shape -- a group of three members (3 / 7 / 11 taps), a group of two, and the
+    carrier pair with the merge of the other two -- through a plan and through the direct entry, in every kernel
+    family of the 64- / 128-channel pairs (pair128_unfused: the two conv launches through the members' scratch slots):
+    the same launches, so the same bits.  333 samples: the last tile of every family is partial."""
+    B, T, dil, ks = 2, 333, 3, (3, 7, 11)
+    rng = np.random.RandomState(C + unfused)
+    tuning("pair128_unfused", unfused)
+    ms = [_member(rng, B, C, T, k, True) for k in ks + ks]          # two positions: six weight sets (x: the first's)
+    x = _t(ms[0][0])
+    h1, h2 = [_native.pack_pair(_t(m[1]), SPLIT) for m in ms], [_native.pack_pair(_t(m[3]), SPLIT) for m in ms]
+    b1, b2 = [_t(m[2]) for m in ms], [_t(m[4]) for m in ms]
+    plan = _native.Plan(C)
+    plan.set_group(1)
+    for j in range(3):                                              # slots 2, 3, 4; scratch 8, 9, 10
+        plan.add_resblock_pair(_native.SLOT_IN, 2 + j, h1[j], h2[j], b1[j], b2[j], C, ks[j], dil, 0.1, prec=SPLIT, mid=8 + j)
+    plan.set_group(2)
+    for j in (1, 2):                                                # slots 6, 7
+        plan.add_resblock_pair(2 + j, 5 + j, h1[3 + j], h2[3 + j], b1[3 + j], b2[3 + j], C, ks[j], dil, 0.1, prec=SPLIT, mid=8 + j)
+    plan.set_group(0)
+    plan.add_resblock_pair(2, _native.SLOT_OUT, h1[3], h2[3], b1[3], b2[3], C, ks[0], dil, 0.1, prec=SPLIT, add1=6, add2=7,
+                           out_div=3.0, act_slope=0.1, mid=8)
+    got = plan.run(x)
+    first = _native.resblock1_fused([x, x, x], h1[:3], h2[:3], b1[:3], b2[:3], list(ks), dil, 0.1, prec=SPLIT)
+    r12 = _native.resblock1_fused(first[1:], h1[4:], h2[4:], b1[4:], b2[4:], list(ks[1:]), dil, 0.1, prec=SPLIT)
+    want, = _native.resblock1_fused([first[0]], [h1[3]], [h2[3]], [b1[3]], [b2[3]], [ks[0]], dil, 0.1, prec=SPLIT,
+                                    add1=[r12[0]], add2=[r12[1]], out_div=3.0, act_slope=0.1)
+    assert torch.equal(got, want)
+    assert bool(torch.isfinite(got).all()) and float(got.abs().max()) > 0
+
+
 @pytest.mark.parametrize("case", [(1, 1000, 3, 5, True), (2, 484, 3, 5, True), (1, 244, 11, 1, False), (3, 8, 7, 3, True),
                                   (1, 2468, 3, 1, False)], ids=lambda c: "x".join(str(v) for v in c))
 def test_pair_with_folded_output_conv_vs_oracle(case):

@@ -328,6 +328,64 @@ def test_plan_shape_inference_without_gpu():
     L.fv_plan_destroy(r)
 
 
+def _arena_bytes(*slot_elems):
+    """The workspace arena: every temporary slot's largest use in fp32, rounded up to 256 bytes."""
+    return sum(-(-e * 4 // 256) * 256 for e in slot_elems)
+
+
+def test_plan_run_and_workspace_bytes_share_one_arena():
+    """fv_plan_run lays out the arena fv_plan_workspace_bytes sized: one byte less is refused -- before any launch, so
+    this runs without a GPU -- and the message names exactly that size.  The three plans carry the scratch slots of the
+    two-launch forms: sum3's two, a 256-channel residual stack's hidden tensor, a 64-channel pair's intermediate."""
+    L = _native.lib()
+    dummy = ctypes.c_void_p(16)     # never dereferenced: the workspace check comes before the first launch
+    B, T = 2, 100
+    ints = lambda *v: (ctypes.c_int * len(v))(*v)
+    s3 = L.fv_plan_create(8)
+    for y in (2, 3, 4):
+        assert L.fv_plan_add_conv1d(s3, 0, y, -1, -1, -1, -1, dummy, None, 8, 8, 3, 1, 1, 0, 1.0, 1.0, 0, 1.0) == 0
+    assert L.fv_plan_add_conv1d_sum3(s3, ints(2, 3, 4), ints(2, 3, 4), ints(5, 6), 1, -1, (ctypes.c_void_p * 3)(16, 16, 16), None,
+                                     8, ints(3, 7, 11), 3.0, 0, 1.0) == 0
+    stack = L.fv_plan_create(256)
+    assert L.fv_plan_add_residual_stack_split_f16(stack, 0, 1, -1, dummy, None, None, 256, 3, 3, 0.2, _native.PAD_REFLECT,
+                                                  _native.POST_RELU, 1.0) == 0
+    assert L.fv_plan_set_stack_two_launch(stack, 2, dummy, dummy) == 0
+    pair = L.fv_plan_create(64)
+    assert L.fv_plan_add_resblock_pair_ex(pair, 0, 1, -1, 2, -1, -1, dummy, dummy, None, None, 64, 3, 3, 0.1, 1.0, 0, 1.0,
+                                          _native.PAIR_SPLIT_F16) == 0
+    for plan, want in ((s3, _arena_bytes(*[B * 8 * T] * 5)), (stack, _arena_bytes(B * 256 * T)), (pair, _arena_bytes(B * 64 * T))):
+        need = L.fv_plan_workspace_bytes(plan, B, T)
+        assert need == want
+        assert L.fv_plan_run(plan, B, T, dummy, dummy, dummy, need - 1, None) == _native.ERR_WORKSPACE
+        assert re.search(rb"needs (\d+) workspace bytes, got (\d+)", L.fv_last_error()).groups() == \
+            (str(need).encode(), str(need - 1).encode())
+        L.fv_plan_destroy(plan)
+
+
+def test_plan_slot_written_twice_is_sized_by_its_larger_use():
+    """A temporary slot written at two lengths: fv_plan_slot_shape reports the last one, the arena holds the larger."""
+    L = _native.lib()
+    dummy = ctypes.c_void_p(16)
+    B, T = 2, 100
+    p = L.fv_plan_create(8)
+    assert L.fv_plan_add_upsample_conv1d(p, 0, 2, -1, dummy, None, 8, 4, 16, 8, 8, 0.1, 0, 1.0) == 0    # 8 T + 1 samples
+    assert L.fv_plan_add_conv1d(p, 2, 3, -1, -1, -1, -1, dummy, None, 4, 4, 3, 1, 1, 0, 1.0, 1.0, 0, 1.0) == 0
+    assert L.fv_plan_add_upsample_conv1d(p, 3, 2, -1, dummy, None, 4, 4, 4, 2, 2, 0.1, 0, 1.0) == 0     # 2 (8 T + 1) + 1
+    c, n = ctypes.c_int(), ctypes.c_int64()
+    assert L.fv_plan_slot_shape(p, T, 2, ctypes.byref(c), ctypes.byref(n)) == 0 and (c.value, n.value) == (4, 16 * T + 3)
+    assert L.fv_plan_slot_shape(p, T, 3, ctypes.byref(c), ctypes.byref(n)) == 0 and (c.value, n.value) == (4, 8 * T + 1)
+    assert L.fv_plan_workspace_bytes(p, B, T) == _arena_bytes(B * 4 * (16 * T + 3), B * 4 * (8 * T + 1))
+    # (the other order: the second use is the smaller one)
+    q = L.fv_plan_create(8)
+    assert L.fv_plan_add_upsample_conv1d(q, 0, 2, -1, dummy, None, 8, 4, 16, 8, 8, 0.1, 0, 1.0) == 0
+    assert L.fv_plan_add_conv1d(q, 2, 3, -1, -1, -1, -1, dummy, None, 4, 4, 3, 1, 1, 0, 1.0, 1.0, 0, 1.0) == 0
+    assert L.fv_plan_add_conv1d(q, 3, 2, -1, -1, -1, -1, dummy, None, 4, 2, 3, 1, 1, 0, 1.0, 1.0, 0, 1.0) == 0
+    assert L.fv_plan_slot_shape(q, T, 2, ctypes.byref(c), ctypes.byref(n)) == 0 and (c.value, n.value) == (2, 8 * T + 1)
+    assert L.fv_plan_workspace_bytes(q, B, T) == _arena_bytes(B * 4 * (8 * T + 1), B * 4 * (8 * T + 1))
+    L.fv_plan_destroy(p)
+    L.fv_plan_destroy(q)
+
+
 def test_encode_16bits_matches_reference_semantics():
     from fastvocoder_amd.audio import encode_16bits
     x = np.array([0.5, -1.0, 0.25], dtype=np.float32)
@@ -489,3 +547,14 @@ def test_block_schedules_cover_every_item_exactly_once():
     assert worst == 70
     with pytest.raises(_native.NativeError):
         _native.debug_pair_schedule([1, 2, 3, 4], [1, 1, 1, 1], 8)
+
+
+def test_schedule_hook_refuses_sizes_whose_cost_sums_could_overflow():
+    """fv_debug_pair_schedule sums n_items * cost in 64 bits: a cost above 65535 or 2^31 / blocks items and more are
+    refused, the largest sizes below that are not."""
+    for items, cost, nblk in (([5], [65536], 4), ([2 ** 31 // 256], [17], 256), ([5, 2 ** 31 // 4], [17, 17], 4)):
+        for mode in (0, 1):
+            with pytest.raises(_native.NativeError):
+                _native.debug_pair_schedule(items, cost, nblk, mode=mode)
+    on, starts = _native.debug_pair_schedule([2 ** 31 // 256 - 1], [65535], 256, mode=1)
+    assert on == 2 and starts[0] == 0 and all(a <= b for a, b in zip(starts, starts[1:]))
