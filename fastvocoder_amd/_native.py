@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 # conv_inst_s*.hip instantiate the conv kernel templates (conv_kernels.hpp) one tile shape each,
 # so that the ~170 kernel variants compile in parallel
-SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "basis_grad.hip", "basis_learn.hip", "optim.hip", "conv_inst_narrow.hip",
+SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_sink.hip", "mel.hip", "resample.hip", "griffin_lim.hip", "stft_loss.hip", "stft_loss_grad.hip", "stft_mag_grad.hip", "disc.hip", "disc_grad.hip", "disc_wgrad.hip", "mpd.hip", "mpd_grad.hip", "mpd_wgrad.hip", "gen_grad.hip", "gen_grad_bf16.hip", "basis_grad.hip", "basis_learn.hip", "optim.hip", "conv_inst_narrow.hip",
            "pair_launch.hip", "pair_inst_c16.hip", "pair_inst_c32.hip", "pairh_inst_c16.hip", "pairh_inst_c32.hip",
            "convh_launch.hip", "convh_inst_c64.hip", "convh_inst_c128.hip", "convt_inst.hip",
            "convg_inst.hip", "convr_inst.hip", "convtn_inst.hip", "convk_inst.hip", "convq2_inst.hip",
@@ -24,7 +24,7 @@ SOURCES = ["conv_mfma.hip", "api.hip", "plan.hip", "pack.hip", "pqmf.hip", "wav_
           [f"conv_inst_s{i}.hip" for i in range(6)]
 HEADERS = ["fv_internal.h", "conv_kernels.hpp", "pair_kernels.hpp", "pair_inst.hpp", "pairh_kernels.hpp",
            "pairh_inst.hpp", "convh_kernels.hpp", "convh_inst.hpp", "convr_kernels.hpp",
-           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp", "basis_grad_host.hpp", "wgrad_tile.hpp"]
+           "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "convq3_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp", "basis_grad_host.hpp", "wgrad_tile.hpp", "gen_grad_host.hpp"]
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)
@@ -282,6 +282,12 @@ def lib():
     L.fv_conv_transpose1d_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
     L.fv_conv_transpose1d_weight_grad_workspace_bytes.restype = i64
     L.fv_conv_transpose1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_conv1d_weight_grad_dilated_bf16_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
+    L.fv_conv1d_weight_grad_dilated_bf16_workspace_bytes.restype = i64
+    L.fv_conv1d_weight_grad_dilated_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_conv_transpose1d_weight_grad_bf16_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
+    L.fv_conv_transpose1d_weight_grad_bf16_workspace_bytes.restype = i64
+    L.fv_conv_transpose1d_weight_grad_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
     L.fv_tanh_grad.argtypes = [vp, vp, vp, i64, vp]
     L.fv_residual_merge_grad.argtypes = [vp, vp, vp, vp, vp, i64, f, vp]
     L.fv_grad_div.argtypes = [vp, vp, i64, f, vp]
@@ -1534,23 +1540,39 @@ def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):
 # the generators' parameter gradient (csrc/gen_grad.hip)
 # ---------------------------------------------------------------------------
 
-def conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil=1, pad=0, pad_mode=None):
+GRAD_PRECISIONS = ("f32", "bf16")   # arithmetic of the generators' weight gradients (csrc/gen_grad.hip, gen_grad_bf16.hip)
+
+
+def _grad_precision(name, precision):
+    if precision not in GRAD_PRECISIONS:
+        raise NativeError(f"{name}: precision {precision!r} ('f32' or 'bf16')")
+    return precision
+
+
+def conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil=1, pad=0, pad_mode=None, precision="f32"):
     """fp32 words of workspace conv1d_weight_grad_dilated needs for these shapes
-    (fv_conv1d_weight_grad_dilated_workspace_bytes; with a ``pad_mode`` fv_conv1d_weight_grad_dilated_mode_workspace_bytes);
-    raises for shapes the entry refuses."""
+    (fv_conv1d_weight_grad_dilated_workspace_bytes; with a ``pad_mode`` fv_conv1d_weight_grad_dilated_mode_workspace_bytes;
+    with ``precision="bf16"`` fv_conv1d_weight_grad_dilated_bf16_workspace_bytes); raises for shapes the entry refuses."""
     args = (int(B), int(cin), int(cout), int(tin), int(k), int(dil), int(pad))
+    if _grad_precision("conv1d_weight_grad_dilated_workspace_floats", precision) == "bf16":
+        return _workspace_floats(lib().fv_conv1d_weight_grad_dilated_bf16_workspace_bytes(
+            *args, PAD_ZERO if pad_mode is None else int(pad_mode)))
     if pad_mode is None:
         return _workspace_floats(lib().fv_conv1d_weight_grad_dilated_workspace_bytes(*args))
     return _workspace_floats(lib().fv_conv1d_weight_grad_dilated_mode_workspace_bytes(*args, int(pad_mode)))
 
 
-def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db=False, workspace=None, pad_mode=None):
+def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db=False, workspace=None, pad_mode=None,
+                               precision="f32"):
     """The weight (and bias) gradient of a dense stride-1 dilated conv with zero padding
     (fv_conv1d_weight_grad_dilated, two launches): g_pre [B,Cout,Tout], xa [B,Cin,Tin] the conv's input as it saw it
     -> (dw [Cout,Cin,k] or None, db [Cout] or None).  ``workspace``: an fp32 device tensor to use instead of a fresh
     one (its contents do not matter).  ``pad_mode`` PAD_ZERO or PAD_REFLECT goes through
-    fv_conv1d_weight_grad_dilated_mode: PAD_REFLECT reads xa through ReflectionPad1d(pad) without building it."""
+    fv_conv1d_weight_grad_dilated_mode: PAD_REFLECT reads xa through ReflectionPad1d(pad) without building it.
+    ``precision="bf16"`` (fv_conv1d_weight_grad_dilated_bf16): dw from the operands rounded to bf16 (nearest even) with
+    fp32 accumulation, db from the un-rounded g_pre."""
     name = "conv1d_weight_grad_dilated"
+    _grad_precision(name, precision)
     if g_pre.dim() != 3 or xa.dim() != 3 or g_pre.shape[0] != xa.shape[0]:
         raise NativeError(f"{name}: g_pre [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g_pre.shape)} and "
                           f"{tuple(xa.shape)}")
@@ -1560,11 +1582,15 @@ def conv1d_weight_grad_dilated(g_pre, xa, k, dil=1, pad=0, want_dw=True, want_db
     if k > 0 and dil > 0 and tin + 2 * pad - dil * (k - 1) >= 1 and tout != tin + 2 * pad - dil * (k - 1):
         raise NativeError(f"{name}: {tout} output times do not belong to an input of {tin} samples")
     args = (B, cin, cout, tin, k, dil, pad)
+    if precision == "bf16":
+        entry, call_args = "fv_conv1d_weight_grad_dilated_bf16", args + (PAD_ZERO if pad_mode is None else int(pad_mode),)
+    elif pad_mode is None:
+        entry, call_args = "fv_conv1d_weight_grad_dilated", args
+    else:
+        entry, call_args = "fv_conv1d_weight_grad_dilated_mode", args + (int(pad_mode),)
     return _weight_grad_call(
-        name, "fv_conv1d_weight_grad_dilated" if pad_mode is None else "fv_conv1d_weight_grad_dilated_mode",
-        (("g_pre", g_pre), ("xa", xa)), want_dw, want_db, (cout, cin, k), (cout,),
-        args if pad_mode is None else args + (int(pad_mode),), workspace,
-        lambda: conv1d_weight_grad_dilated_workspace_floats(*args, pad_mode))
+        name, entry, (("g_pre", g_pre), ("xa", xa)), want_dw, want_db, (cout, cin, k), (cout,), call_args, workspace,
+        lambda: conv1d_weight_grad_dilated_workspace_floats(*args, pad_mode, precision))
 
 
 def conv1d_input_grad_reflect(g, wt, tin, dil=1, pad=0):
@@ -1611,17 +1637,24 @@ def conv_transpose1d_input_grad(g, w, tin, stride, pad, out_pad=0):
     return dxa
 
 
-def conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, stride, pad, out_pad=0):
+def conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, stride, pad, out_pad=0, precision="f32"):
     """fp32 words of workspace conv_transpose1d_weight_grad needs for these shapes
-    (fv_conv_transpose1d_weight_grad_workspace_bytes); raises for shapes the entry refuses."""
-    return _workspace_floats(lib().fv_conv_transpose1d_weight_grad_workspace_bytes(
+    (fv_conv_transpose1d_weight_grad_workspace_bytes; with ``precision="bf16"``
+    fv_conv_transpose1d_weight_grad_bf16_workspace_bytes); raises for shapes the entry refuses."""
+    bf16 = _grad_precision("conv_transpose1d_weight_grad_workspace_floats", precision) == "bf16"
+    entry = "fv_conv_transpose1d_weight_grad_bf16_workspace_bytes" if bf16 else "fv_conv_transpose1d_weight_grad_workspace_bytes"
+    return _workspace_floats(getattr(lib(), entry)(
         int(B), int(cin), int(cout), int(tin), int(k), int(stride), int(pad), int(out_pad)))
 
 
-def conv_transpose1d_weight_grad(g, xa, k, stride, pad, out_pad=0, want_dw=True, want_db=False, workspace=None):
+def conv_transpose1d_weight_grad(g, xa, k, stride, pad, out_pad=0, want_dw=True, want_db=False, workspace=None,
+                                 precision="f32"):
     """The weight (and bias) gradient of ConvTranspose1d (fv_conv_transpose1d_weight_grad, two launches): g
-    [B,Cout,Tout], xa [B,Cin,Tin] the layer's input as it saw it -> (dw [Cin,Cout,k] or None, db [Cout] or None)."""
+    [B,Cout,Tout], xa [B,Cin,Tin] the layer's input as it saw it -> (dw [Cin,Cout,k] or None, db [Cout] or None).
+    ``precision="bf16"`` (fv_conv_transpose1d_weight_grad_bf16): dw from the operands rounded to bf16 (nearest even)
+    with fp32 accumulation, db from the un-rounded g."""
     name = "conv_transpose1d_weight_grad"
+    _grad_precision(name, precision)
     k, stride, pad, out_pad = int(k), int(stride), int(pad), int(out_pad)
     if xa.dim() != 3 or g.dim() != 3 or g.shape[0] != xa.shape[0]:
         raise NativeError(f"{name}: g [B,Cout,Tout] and xa [B,Cin,Tin] expected, got {tuple(g.shape)} and "
@@ -1630,9 +1663,10 @@ def conv_transpose1d_weight_grad(g, xa, k, stride, pad, out_pad=0, want_dw=True,
     _convt_grad_shapes(name, g, tin, None, k, stride, pad, out_pad)
     cout = g.shape[1]
     args = (B, cin, cout, tin, k, stride, pad, out_pad)
-    return _weight_grad_call(name, "fv_conv_transpose1d_weight_grad", (("g", g), ("xa", xa)), want_dw, want_db,
-                             (cin, cout, k), (cout,), args, workspace,
-                             lambda: conv_transpose1d_weight_grad_workspace_floats(*args))
+    return _weight_grad_call(
+        name, "fv_conv_transpose1d_weight_grad_bf16" if precision == "bf16" else "fv_conv_transpose1d_weight_grad",
+        (("g", g), ("xa", xa)), want_dw, want_db, (cin, cout, k), (cout,), args, workspace,
+        lambda: conv_transpose1d_weight_grad_workspace_floats(*args, precision=precision))
 
 
 def _same_shape(name, *tensors):

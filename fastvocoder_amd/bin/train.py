@@ -5,8 +5,8 @@ step, ``optim.Adam`` clips and updates in three launches, ``data.BatchIterator``
 
 ``run_train()`` takes the reference's arguments (train.py:478-499) and, for a test or a short run, ``--max_steps``,
 ``--seed``, ``--batch_size``, ``--fixed_length``, ``--discriminator_train_start_steps``, ``--log_step``,
-``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams), ``--use_mpd``, ``--stack_grad``, ``--basis_grad``
-and ``--basis_dataset_path``.
+``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams), ``--use_mpd``, ``--stack_grad``, ``--basis_grad``,
+``--basis_dataset_path`` and ``--grad_precision``.
 ``lamda_stft`` (sic) and ``use_feature_map_loss`` come from the yaml, as there.  Both optimizers are
 ``Adam(lr, eps=1e-6)``; ``--use_scheduler 1`` adds ``CosineAnnealingLR(T_max=2500, eta_min=lr / 10)`` to both.
 
@@ -33,7 +33,10 @@ a resumed checkpoint's ``basis_signal.layer.weight`` wins), the target weights f
 gradient --, the validation scores ``model(mel)[0]``, the log line's "Weight Loss" is filled and the ``weight_loss`` and
 ``weight_average_value`` scalars are written.  A missing basis or weight file ends the run with one sentence that
 names the path.  Both flags are absent from the parsed arguments unless given.  ``--mixprecision 1`` exits: there is no
-mixed-precision path.
+mixed-precision (apex amp) path.  ``--grad_precision bf16`` (absent from the parsed arguments unless given; every
+trainable ``--model_name``, with or without ``--gpus``) is this hardware's reduced-precision mode,
+``Trainer(grad_precision="bf16")``: the convs' weight gradients on the bf16 matrix cores with fp32 accumulation,
+everything else fp32 -- no loss scale, the same checkpoint and log lines, and a checkpoint resumes under either value.
 
 Several GPUs of one node: ``--gpus N`` (absent from the parsed arguments unless given) with no ``WORLD_SIZE`` in the
 environment starts ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...`` as a child -- the parent
@@ -122,6 +125,9 @@ def build_parser():
                         help="1: opt in to Basis-MelGAN's parameter gradient (--model_name basis-melgan trains only with it)")
     parser.add_argument("--basis_dataset_path", type=str, default=argparse.SUPPRESS,
                         help="directory of basis_signal_weight.npy and weight/ (default: Basis-MelGAN-dataset)")
+    parser.add_argument("--grad_precision", type=str, default=argparse.SUPPRESS,
+                        help="f32 (default) or bf16: the generator's weight gradients on the bf16 matrix cores, fp32 "
+                             "accumulation; everything else stays fp32")
     parser.add_argument("--gpus", type=int, default=argparse.SUPPRESS,
                         help="data-parallel training over this many GPUs of the node, one rank each (--batch_size is "
                              "per rank)")
@@ -143,8 +149,10 @@ def check_args(args):
     elif args.model_name not in SUPPORTED:
         sys.exit(f"MODE=train: --model_name must be one of {', '.join(SUPPORTED)}, got {args.model_name!r}")
     if args.mixprecision:
-        sys.exit("MODE=train: --mixprecision 1 is not supported: there is no mixed-precision (apex amp) path, the "
-                 "kernels train in fp32")
+        sys.exit("MODE=train: --mixprecision 1 is not supported: there is no mixed-precision (apex amp) path; "
+                 "--grad_precision bf16 is the reduced-precision mode (bf16 weight gradients, no loss scaling)")
+    if getattr(args, "grad_precision", "f32") not in ("f32", "bf16"):
+        sys.exit(f"MODE=train: --grad_precision must be f32 or bf16, got {args.grad_precision!r}")
     if not args.config:
         sys.exit("MODE=train: --config (the model's yaml file) is required")
     for name in ("batch_size", "fixed_length", "log_step", "save_step", "valid_step"):
@@ -375,7 +383,7 @@ def _run(args, group, rank, world, device):
                       discriminator_train_start_steps=args.discriminator_train_start_steps,
                       grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm,
                       stack_grad=bool(getattr(args, "stack_grad", 0)), basis_grad=bool(getattr(args, "basis_grad", 0)),
-                      process_group=group)
+                      process_group=group, grad_precision=getattr(args, "grad_precision", "f32"))
     spf = samples_per_frame(model, pqmf)
 
     say("Load data to buffer")

@@ -207,7 +207,15 @@ __global__ __launch_bounds__(256) void wgrad_combine_kernel(const float* __restr
     float* dst = i < MN ? (dw ? dw + i : nullptr) : (db ? db + (i - MN) : nullptr);
     if (!dst) return;
     float v = ws[i];
-    for (int s = 1; s < S; ++s) v += ws[(size_t)s * R + i];
+    int s = 1;
+    for (; s + 8 <= S; s += 8) {                          // 8 loads in flight, added in the same ascending order:
+        float t[8];                                       // the bits of the one-by-one loop, without its latency chain
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] = ws[(size_t)(s + j) * R + i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v += t[j];
+    }
+    for (; s < S; ++s) v += ws[(size_t)s * R + i];
     *dst = v;
 }
 

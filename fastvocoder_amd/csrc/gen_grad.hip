@@ -16,9 +16,9 @@
 // after the first (a unit's span is a few KB), not once.
 //
 // gen_wgrad_kernel<MT>: dW[m][n] over (b, t) in the split / record / combine scheme of wgrad_tile.hpp (units of 32
-// steps).  One extra block column sums the bias rows of the split's units (wave w owns channels w, w + 4, ...; lanes
-// stride the unit's positions; one shuffle tree at the end), so every record word the combine reads is written by this
-// launch.
+// steps).  One extra block column sums the bias rows of the split's units (gen_grad_host.hpp gg_bias_column: wave w
+// owns channels w, w + 4, ...; lanes stride the unit's positions; one shuffle tree at the end), so every record word the
+// combine reads is written by this launch.
 //
 // gen_dgrad_kernel<MT>: the transposed conv's data gradient as the GEMM [Cin] x [B Tin] over Cout k: the columns are
 // the flat positions q = b Tin + i, A = the forward's weight [Cin][Cout k] as it lies in memory, B the stride-s gather
@@ -33,23 +33,9 @@
 // (T - 1 - pad <= i <= T - 2), added in that order before the MFMA sees them.  One launch, no [B, C, T + 2 pad] tensor.
 #include <math.h>
 
-#include "wgrad_tile.hpp"
+#include "gen_grad_host.hpp"
 
 namespace fv {
-
-constexpr int kGgBRows = kWgNT / 8;   // rows of the B tile a thread stages (16)
-constexpr int kGgDead = -(1 << 30);   // position of a column / row beyond the problem: below every source row
-
-struct GgWArgs {
-    const float* a;         // A source [B, M, TR]: row m, step t
-    const float* b;         // B source [B, Cb, TB]: column n = cb k + j reads b[., cb, t sB + j dB - pad]
-    const float* bias_src;  // [B, Cbias, Tbias], or null
-    float* ws;              // [S][R], R = M N + Cbias
-    WgSplit sp;
-    int M, TR, Cb, TB, k, sB, dB, pad;
-    int Cbias, Tbias, bias_scale;   // a unit's bias positions: [t0 bias_scale, (t0 + 32) bias_scale), the row's last unit to Tbias
-    int x_tiles;            // column tiles of the GEMM (0: the bias alone); blocks beyond them sum the bias
-};
 
 // grid (x_tiles + (bias ? 1 : 0), ceil(M / MT), S); REFLECT: the B source is read through a reflection pad (pad < TB)
 template <int MT, bool REFLECT = false>
@@ -62,22 +48,7 @@ __global__ __launch_bounds__(kWgThreads) void gen_wgrad_kernel(GgWArgs a) {
     const int N = a.Cb * a.k;
     float* rec = a.ws + (size_t)s * a.sp.R;
     if ((int)blockIdx.x >= a.x_tiles) {                   // the bias column
-        if (blockIdx.y != 0) return;
-        const int lane = tid & 63, wave = tid >> 6;
-        for (int c = wave; c < a.Cbias; c += 4) {
-            float v = 0.f;
-            for (int64_t u = u0; u < u1; ++u) {
-                const int b = (int)(u / a.sp.nch), ch = (int)(u % a.sp.nch);
-                const int64_t p0 = (int64_t)ch * kWgTK * a.bias_scale;
-                int64_t p1 = ch == a.sp.nch - 1 ? a.Tbias : p0 + (int64_t)kWgTK * a.bias_scale;
-                if (p1 > a.Tbias) p1 = a.Tbias;
-                const float* row = a.bias_src + ((size_t)b * a.Cbias + c) * a.Tbias;
-                for (int64_t p = p0 + lane; p < p1; p += 64) v += row[p];
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if (lane == 0) rec[(size_t)a.M * N + c] = v;
-        }
+        if (blockIdx.y == 0) gg_bias_column<kWgTK>(a, rec, u0, u1, N);
         return;
     }
     const int n0 = blockIdx.x * kWgNT, m0 = blockIdx.y * MT;
@@ -279,92 +250,16 @@ __global__ __launch_bounds__(256) void grad_div_kernel(const float* __restrict__
 }
 
 // ---- host side ----
-static int gg_rows(int M) { return M > 64 ? 128 : M > 32 ? 64 : M > 16 ? 32 : 16; }
-
-// LAUNCH(MT) at the tile height rows = gg_rows(.): 128, 64, 32 or 16
-#define GG_BY_ROWS(rows, LAUNCH)    \
-    switch (rows) {                 \
-    case 128: LAUNCH(128); break;   \
-    case 64: LAUNCH(64); break;     \
-    case 32: LAUNCH(32); break;     \
-    default: LAUNCH(16); break;     \
-    }
-
-struct GgWPlan : WgSplit {
-    int MT, bx, by;
-};
-
-// the plan of a weight-gradient GEMM of M rows x N columns over B rows of TR steps, with Cbias bias words per record
-static void gg_wgrad_plan(int B, int M, int64_t N, int TR, int Cbias, GgWPlan* p) {
-    p->MT = gg_rows(M);
-    p->bx = (int)((N + kWgNT - 1) / kWgNT);
-    p->by = (M + p->MT - 1) / p->MT;
-    p->nch = (TR + kWgTK - 1) / kWgTK;
-    p->U = (int64_t)B * p->nch;
-    p->R = (int64_t)M * N + Cbias;
-    p->S = wg_splits((int64_t)p->bx * p->by, p->U, p->MT >= 64 ? 512 : 1024);
-}
-
-static int gg_wgrad_run(const GgWPlan& p, GgWArgs a, float* dw, float* db, void* workspace, size_t workspace_bytes,
+// the exact-fp32 kernel at the plan's tile height
+static int gg_wgrad_f32(const GgWPlan& p, const GgWArgs& a, float* dw, float* db, void* workspace, size_t workspace_bytes,
                         const char* who, hipStream_t st, bool reflect = false) {
-    if (int rc = wg_tensor_check(who, a.a, a.b, dw, db)) return rc;
-    if (int rc = wg_workspace_check(who, workspace, workspace_bytes, p.bytes())) return rc;
-    a.sp = p;
-    a.ws = static_cast<float*>(workspace);
-    a.x_tiles = dw ? p.bx : 0;
-    if (!db) a.bias_src = nullptr;
-    const dim3 grid((unsigned)(a.x_tiles + (db ? 1 : 0)), (unsigned)(dw ? p.by : 1), (unsigned)p.S);
-#define GG_WGRAD(MT)                                                                                         \
-    if (reflect) hipLaunchKernelGGL((gen_wgrad_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, a);         \
-    else hipLaunchKernelGGL((gen_wgrad_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, a)
-    GG_BY_ROWS(p.MT, GG_WGRAD)
+    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, who, st, 1, [&](int rows, dim3 grid, const GgWArgs& ka) {
+#define GG_WGRAD(MT)                                                                                          \
+    if (reflect) hipLaunchKernelGGL((gen_wgrad_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, ka);         \
+    else hipLaunchKernelGGL((gen_wgrad_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, ka)
+        GG_BY_ROWS(rows, GG_WGRAD)
 #undef GG_WGRAD
-    FV_HIP(hipGetLastError());
-    return launch_wgrad_combine(a.ws, dw, db, p.R - a.Cbias, a.Cbias, p.R, p.S, st);
-}
-
-static int dilated_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int dil, int pad, GgWPlan* p) {
-    if (Cin < 1 || Cout < 1 || k < 1 || dil < 1 || (int64_t)Cin * Cout * k >= (int64_t)1 << 31 ||
-        (int64_t)Cin * k >= (int64_t)1 << 30 || (Cout + 15) / 16 > 65535)
-        return fail(FV_ERR_UNSUPPORTED, "conv1d_weight_grad_dilated: Cin=%d Cout=%d k=%d dil=%d", Cin, Cout, k, dil);
-    if (B <= 0 || B > 65535 || Tin < 1 || pad < 0)
-        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: B=%d, Tin=%d or pad=%d", B, Tin, pad);
-    const int64_t Tout = (int64_t)Tin + 2 * (int64_t)pad - (int64_t)dil * (k - 1);
-    if (Tout < 1)
-        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: empty output (Tin=%d pad=%d k=%d dil=%d)", Tin, pad,
-                    k, dil);
-    const int64_t big = Cin > Cout ? Cin : Cout;
-    if (big * ((int64_t)Tin + 2 * (int64_t)pad) >= (int64_t)1 << 30)
-        return fail(FV_ERR_INVALID_ARG, "conv1d_weight_grad_dilated: a map of %lld x %d samples is too long",
-                    (long long)big, Tin);
-    gg_wgrad_plan(B, Cout, (int64_t)Cin * k, (int)Tout, Cout, p);
-    return 0;
-}
-
-static int dilated_mode_check(const char* who, int Tin, int pad, int pad_mode) {
-    if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
-        return fail(FV_ERR_INVALID_ARG, "%s: pad_mode=%d (FV_PAD_ZERO or FV_PAD_REFLECT)", who, pad_mode);
-    if (pad_mode == FV_PAD_REFLECT && pad >= Tin)
-        return fail(FV_ERR_INVALID_ARG, "%s: a reflection pad of %d needs more than %d samples", who, pad, Tin);
-    return 0;
-}
-
-// Tout, or an error code
-static int64_t convt_grad_check(const char* who, int B, int Cin, int Cout, int Tin, int k, int stride, int pad,
-                                int out_pad) {
-    if (Cin < 1 || Cout < 1 || k < 1 || stride < 1 || (int64_t)Cin * Cout * k >= (int64_t)1 << 31 ||
-        (int64_t)Cout * k >= (int64_t)1 << 30 || (Cin + 15) / 16 > 65535)
-        return fail(FV_ERR_UNSUPPORTED, "%s: Cin=%d Cout=%d k=%d stride=%d", who, Cin, Cout, k, stride);
-    if (B <= 0 || B > 65535 || Tin < 1 || pad < 0)
-        return fail(FV_ERR_INVALID_ARG, "%s: B=%d, Tin=%d or pad=%d", who, B, Tin, pad);
-    const int64_t Tout = ((int64_t)Tin - 1) * stride - 2 * (int64_t)pad + k + out_pad;
-    if (Tout < 1)
-        return fail(FV_ERR_INVALID_ARG, "%s: empty output (Tin=%d k=%d stride=%d pad=%d out_pad=%d)", who, Tin, k, stride,
-                    pad, out_pad);
-    const int64_t span = (int64_t)Tin * stride + k + pad;
-    if ((int64_t)Cout * (Tout > span ? Tout : span) >= (int64_t)1 << 30 || (int64_t)Cin * Tin >= (int64_t)1 << 30)
-        return fail(FV_ERR_INVALID_ARG, "%s: a map of %d x %lld samples is too long", who, Cout, (long long)Tout);
-    return Tout;
+    });
 }
 
 static int gg_elementwise_check(const char* who, const void* a, const void* b, const void* out, int64_t n) {
@@ -406,24 +301,8 @@ int fv_conv1d_weight_grad_dilated_mode(const float* g_pre, const float* xa, floa
     GgWPlan p;
     if (int rc = dilated_wgrad_plan(B, Cin, Cout, Tin, k, dil, pad, &p)) return rc;
     if (int rc = dilated_mode_check("conv1d_weight_grad_dilated_mode", Tin, pad, pad_mode)) return rc;
-    const int Tout = Tin + 2 * pad - dil * (k - 1);
-    GgWArgs a{};
-    a.a = g_pre;
-    a.b = xa;
-    a.bias_src = g_pre;
-    a.M = Cout;
-    a.TR = Tout;
-    a.Cb = Cin;
-    a.TB = Tin;
-    a.k = k;
-    a.sB = 1;
-    a.dB = dil;
-    a.pad = pad;
-    a.Cbias = Cout;
-    a.Tbias = Tout;
-    a.bias_scale = 1;
-    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, "conv1d_weight_grad_dilated", (hipStream_t)stream,
-                        pad_mode == FV_PAD_REFLECT);
+    return gg_wgrad_f32(p, gg_dilated_args(g_pre, xa, Cin, Cout, Tin, k, dil, pad), dw, db, workspace, workspace_bytes,
+                        "conv1d_weight_grad_dilated", (hipStream_t)stream, pad_mode == FV_PAD_REFLECT);
 }
 
 int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, int B, int Cin, int Cout, int Tin, int k,
@@ -513,22 +392,8 @@ int fv_conv_transpose1d_weight_grad(const float* g, const float* xa, float* dw, 
     if (Tout < 0) return (int)Tout;
     GgWPlan p;
     gg_wgrad_plan(B, Cin, (int64_t)Cout * k, Tin, Cout, &p);
-    GgWArgs a{};
-    a.a = xa;
-    a.b = g;
-    a.bias_src = g;
-    a.M = Cin;
-    a.TR = Tin;
-    a.Cb = Cout;
-    a.TB = (int)Tout;
-    a.k = k;
-    a.sB = stride;
-    a.dB = 1;
-    a.pad = pad;
-    a.Cbias = Cout;
-    a.Tbias = (int)Tout;
-    a.bias_scale = stride;
-    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, "conv_transpose1d_weight_grad", (hipStream_t)stream);
+    return gg_wgrad_f32(p, gg_convt_args(g, xa, Cin, Cout, Tin, (int)Tout, k, stride, pad), dw, db, workspace,
+                        workspace_bytes, "conv_transpose1d_weight_grad", (hipStream_t)stream);
 }
 
 int fv_tanh_grad(const float* g, const float* y, float* out, int64_t n, void* stream) {

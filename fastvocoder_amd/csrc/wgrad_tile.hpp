@@ -1,5 +1,6 @@
 // What the training-side weight gradients share (disc_wgrad.hip, mpd_wgrad.hip, gen_grad.hip; basis_learn.hip takes the
-// host part): the exact-fp32 matrix-core tile, and the split / record / combine scheme with its host checks.
+// host part; gen_grad_bf16.hip the wave / fragment split, the accumulators and the epilogue under bf16 operands): the
+// exact-fp32 matrix-core tile, and the split / record / combine scheme with its host checks.
 //
 // WgTile<MT>: a block of 4 waves owns MT rows x 128 columns and consumes staged tiles of 32 reduction steps, both
 // operands K-contiguous in LDS -- as[row][step], bs[column][step].

@@ -100,6 +100,28 @@ class NoParameterGrad:
                 "and MultiBandHiFiGANGenerator")
 
 
+class GradPrecision:
+    """Mix-in of the trainable generators: ``grad_precision``, the arithmetic of the convs' weight gradients under
+    ``parameter_grad``.  "f32" (the default): the exact-fp32 kernels of csrc/gen_grad.hip.  "bf16": both operands of
+    every weight-gradient GEMM are rounded to bf16 (nearest even) while they are staged and multiplied on the bf16
+    matrix cores with fp32 accumulation (csrc/gen_grad_bf16.hip); the forward, the data gradients, the bias gradients,
+    the parameters and the optimizer state stay fp32.  Read at backward time: it invalidates no cached weight or plan,
+    does not touch ``forward``'s bits and does nothing unless ``parameter_grad`` is on.  (Not ``precision``: that
+    attribute is the inference policy.)"""
+
+    _grad_precision = "f32"
+
+    @property
+    def grad_precision(self):
+        return self._grad_precision
+
+    @grad_precision.setter
+    def grad_precision(self, value):
+        if value not in _native.GRAD_PRECISIONS:
+            raise ValueError(f"{type(self).__name__}.grad_precision: {value!r} ('f32' or 'bf16')")
+        self._grad_precision = value
+
+
 def pair_precision(precision, channels):
     """Arithmetic of the ResBlock / ResidualStack / upsampler kernels for a layer of ``channels`` channels under the
     policy ``precision``: "split" = split-f16 operands (csrc/pairh_kernels.hpp, convh_kernels.hpp; fp32-class accuracy,

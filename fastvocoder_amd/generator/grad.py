@@ -114,16 +114,17 @@ def train_forward(gen, mel):
     return y, tape
 
 
-def _wgrad(conv, g_pre, xin, params, need, at, out):
+def _wgrad(conv, g_pre, xin, params, need, at, out, precision="f32"):
     want_dw, want_db = param_wants(conv, need, at)
     if not (want_dw or want_db):
         return
     k = conv.kernel_size[0]
     if isinstance(conv, torch.nn.ConvTranspose1d):
         dw, db = _native.conv_transpose1d_weight_grad(g_pre, xin, k, conv.stride[0], conv.padding[0],
-                                                      conv.output_padding[0], want_dw, want_db)
+                                                      conv.output_padding[0], want_dw, want_db, precision=precision)
     else:
-        dw, db = _native.conv1d_weight_grad_dilated(g_pre, xin, k, conv.dilation[0], conv.padding[0], want_dw, want_db)
+        dw, db = _native.conv1d_weight_grad_dilated(g_pre, xin, k, conv.dilation[0], conv.padding[0], want_dw, want_db,
+                                                    precision=precision)
     param_store(conv, params, need, at, dw, db, out)
 
 
@@ -151,8 +152,10 @@ def train_backward(gen, tape, y, params, need, g):
         seen = seen or any(wanted[id(c)] for j in range(nk) for c in gen.resblocks[i * nk + j].modules() if _is_conv(c))
     out = [None] * len(params)
 
+    precision = gen.grad_precision                      # read here, at backward time
+
     def wgrad(conv, g_pre, xin):
-        _wgrad(conv, g_pre, xin, params, need, first[id(conv)], out)
+        _wgrad(conv, g_pre, xin, params, need, first[id(conv)], out, precision)
 
     g_z = _native.tanh_grad(g, y)
     wgrad(gen.conv_post, g_z, tape["post_in"])

@@ -16,7 +16,7 @@ tanh are epilogue/prologue work of the conv kernels: the whole forward is
 import torch
 
 from .._native import PAIR_SPLIT_F16
-from .engine import (NativeModule, PlanBuilder, POST_TANH, SLOT_IN, SLOT_NONE, SLOT_OUT, pair_precision,  # noqa: F401
+from .engine import (GradPrecision, NativeModule, PlanBuilder, POST_TANH, SLOT_IN, SLOT_NONE, SLOT_OUT, pair_precision,  # noqa: F401
                      weight_norm)
 from . import grad
 from .modules import LRELU_SLOPE, ResBlock1, ResBlock2, UpsampleLayer
@@ -42,7 +42,7 @@ def stage32_windows_fit(cols, cus, fill=0.65):
     return share >= fill * 384 * windows
 
 
-class _HiFiGANBase(NativeModule):
+class _HiFiGANBase(GradPrecision, NativeModule):
     _post_channels = 1
     fuse_pqmf = True      # Multiband: conv_post + tanh + PQMF synthesis as one launch (False: two; A/B and bit-identity tests)
     _parameter_grad = False

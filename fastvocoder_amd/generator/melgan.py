@@ -13,7 +13,7 @@ import torch
 from .. import _native
 from . import basis_grad as _basis_grad
 from . import stack_grad as _stack_grad
-from .engine import NativeModule, NoParameterGrad, POST_NONE, POST_RELU, POST_TANH, SLOT_IN, SLOT_OUT, SLOT_OUT2  # noqa: F401
+from .engine import GradPrecision, NativeModule, NoParameterGrad, POST_NONE, POST_RELU, POST_TANH, SLOT_IN, SLOT_OUT, SLOT_OUT2  # noqa: F401
 from .modules import (BasisSignalLayer, LastLayer, LastLinear, ResidualStack, UpsampleLayer,
                       _activation_slope, _pad_mode)
 
@@ -89,7 +89,7 @@ class _MelGANTrunk(NoParameterGrad, NativeModule):
             cur, pending_slope = nxt, 1.0
 
 
-class MelGANGenerator(_MelGANTrunk):
+class MelGANGenerator(GradPrecision, _MelGANTrunk):
     """Drop-in for the reference ``MelGANGenerator``."""
 
     _stack_grad = False
@@ -177,7 +177,7 @@ class MelGANGenerator(_MelGANTrunk):
         return self._run(c.transpose(1, 0).unsqueeze(0).contiguous(), sync=True).squeeze()
 
 
-class BasisMelGANGenerator(_MelGANTrunk):
+class BasisMelGANGenerator(GradPrecision, _MelGANTrunk):
     """Drop-in for the reference ``BasisMelGANGenerator``: a MelGAN-style trunk
     that ends in ReLU and predicts per-frame weights over a learned basis
     (``basis_signal_weight [L, out_channels]``); samples = overlap-add of

@@ -163,16 +163,19 @@ def train_backward(gen, tape, y, params, need, g):
         """A conv in front of ``conv`` wants a gradient: the walk has to go on past it."""
         return lowest < order[id(conv)]
 
+    precision = gen.grad_precision                      # read here, at backward time
+
     def wgrad(conv, g_pre, xin, pad=0, pad_mode=None):
         want_dw, want_db = param_wants(conv, need, first_at[id(conv)])
         if not (want_dw or want_db):
             return
         if isinstance(conv, torch.nn.ConvTranspose1d):
             dw, db = _native.conv_transpose1d_weight_grad(g_pre, xin, conv.kernel_size[0], conv.stride[0],
-                                                          conv.padding[0], conv.output_padding[0], want_dw, want_db)
+                                                          conv.padding[0], conv.output_padding[0], want_dw, want_db,
+                                                          precision=precision)
         else:
             dw, db = _native.conv1d_weight_grad_dilated(g_pre, xin, conv.kernel_size[0], conv.dilation[0], pad, want_dw,
-                                                        want_db, pad_mode=pad_mode)
+                                                        want_db, pad_mode=pad_mode, precision=precision)
         param_store(conv, params, need, first_at[id(conv)], dw, db, out)
 
     def through_pad(conv, g_pre, tin, pad):

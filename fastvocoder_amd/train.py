@@ -22,7 +22,13 @@ the adversarial terms and the discriminator's update see ``est``; the step's dic
 parameters only: the basis is a constant of the training graph and gets no gradient (the reference gives it one that
 it never applies, train.py:64, 329-331 -- which its ``clip_grad_norm_`` over ``model.parameters()`` does count; the
 norm here is the trunk's alone).  The ``transposedconv: False`` upsampler has no parameter gradient and is refused
-where the ``parameter_grad`` attribute refuses it; mixed precision is not part of this loop.
+where the ``parameter_grad`` attribute refuses it.
+
+Reduced-precision gradients: ``Trainer(..., grad_precision="bf16")`` sets the generator's ``grad_precision``
+(generator/engine.py ``GradPrecision``): the convs' weight gradients round their two operands to bf16 and accumulate
+in fp32 on the bf16 matrix cores; the forward, the data and bias gradients, the parameters and the optimizer state stay
+fp32, so there is no loss scale and no skipped step, and a checkpoint resumes under either value.  The reference's
+mixed-precision flag (apex amp O1: fp16 activations with dynamic loss scaling) is not part of this loop.
 
 Data-parallel training: ``Trainer(..., process_group=<a torch.distributed group>)`` hands the group to both optimizer
 steps (``optim.Adam.step(process_group=...)``: the gradients of the ranks' shards are averaged with one collective over
@@ -69,7 +75,7 @@ class Trainer:
     def __init__(self, model, discriminator, optimizer, discriminator_optimizer, scheduler=None,
                  discriminator_scheduler=None, pqmf=None, *, lambda_stft, use_feature_map_loss,
                  discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0, stack_grad=False,
-                 basis_grad=False, process_group=None):
+                 basis_grad=False, process_group=None, grad_precision="f32"):
         for opt, name in ((optimizer, "optimizer"), (discriminator_optimizer, "discriminator_optimizer")):
             if not isinstance(opt, Adam):
                 raise TypeError(f"{name} must be a fastvocoder_amd.optim.Adam (its step clips and updates in three "
@@ -79,6 +85,11 @@ class Trainer:
         if basis_grad and hasattr(type(model), "basis_grad"):
             model.basis_grad = True           # Basis-MelGAN's
         model.parameter_grad = True           # raises for the generators that have no parameter gradient
+        if hasattr(type(model), "grad_precision"):
+            model.grad_precision = grad_precision     # raises ValueError for anything but "f32" / "bf16"
+        elif grad_precision != "f32":
+            raise NotImplementedError(f"{type(model).__name__} has no grad_precision: its weight gradients are not "
+                                      "the generators' kernels")
         self.model, self.discriminator = model, discriminator
         self.optimizer, self.discriminator_optimizer = optimizer, discriminator_optimizer
         self.scheduler, self.discriminator_scheduler = scheduler, discriminator_scheduler

@@ -32,8 +32,8 @@ extern "C" {
 
 #define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad; 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
 /* Entry points are added under one version number: 18 also covers the gradient, optimizer and training entries that
- * came after fv_stft_distance_grad, the latest being fv_conv1d_weight_grad_dilated_mode and
- * fv_conv1d_input_grad_reflect (MelGAN's parameter gradient).  No existing entry changed its signature or its result. */
+ * came after fv_stft_distance_grad, the latest being fv_conv1d_weight_grad_dilated_bf16 and
+ * fv_conv_transpose1d_weight_grad_bf16 (the generators' bf16 weight gradients).  No existing entry changed its signature or its result. */
 
 #define FV_ERR_INVALID_ARG (-1)
 #define FV_ERR_UNSUPPORTED (-2)
@@ -958,6 +958,34 @@ int fv_conv1d_weight_grad_dilated_mode(const float* g_pre, const float* xa, floa
                                        size_t workspace_bytes, void* stream);
 int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, int B, int Cin, int Cout, int Tin, int k,
                                  int dil, int pad, void* stream);
+
+/*
+ * The generators' weight gradients with bf16 operands (the Python side's grad_precision = "bf16"); additions of ABI 18,
+ * no existing entry changes.  With bf16(.) the round-to-nearest-even of an fp32 value to bfloat16:
+ *
+ * fv_conv1d_weight_grad_dilated_bf16: fv_conv1d_weight_grad_dilated_mode on rounded operands,
+ *     dw[co, ci, j] = sum_{b, t} bf16(g_pre[b, co, t]) * bf16(xa[b, ci, r(t + j dil - pad)])     (fp32 accumulation)
+ *     db[co]        = sum_{b, t} g_pre[b, co, t]                                                 (un-rounded)
+ * fv_conv_transpose1d_weight_grad_bf16: fv_conv_transpose1d_weight_grad in the same way,
+ *     dw[ci, co, j] = sum_{b, i} bf16(xa[b, ci, i]) * bf16(g[b, co, i s + j - p]),    db[co] = sum_{b, n} g[b, co, n]
+ * The rounding is applied to the value the kernel stages: a padded zero stays zero, a reflected sample is the rounded
+ * sample.  The products are exact in fp32 (v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16), so dw differs from the
+ * fp32 sum of the rounded products by the order of the additions alone; bf16 has fp32's exponent range, there is no
+ * scaling.  Shapes, index arithmetic, tensors, error codes and the split / record / combine scheme are those of the
+ * fp32 entries (units of 64 reduction steps instead of 32, so the workspace size and db's last bits may differ from
+ * theirs): S is a function of the shape alone, identical calls return identical bits, the workspace's contents do not
+ * matter, no atomics, no waiting between workgroups.  Two launches.
+ */
+int64_t fv_conv1d_weight_grad_dilated_bf16_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int dil, int pad,
+                                                           int pad_mode);
+int fv_conv1d_weight_grad_dilated_bf16(const float* g_pre, const float* xa, float* dw, float* db, int B, int Cin,
+                                       int Cout, int Tin, int k, int dil, int pad, int pad_mode, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+int64_t fv_conv_transpose1d_weight_grad_bf16_workspace_bytes(int B, int Cin, int Cout, int Tin, int k, int stride,
+                                                             int pad, int out_pad);
+int fv_conv_transpose1d_weight_grad_bf16(const float* g, const float* xa, float* dw, float* db, int B, int Cin, int Cout,
+                                         int Tin, int k, int stride, int pad, int out_pad, void* workspace,
+                                         size_t workspace_bytes, void* stream);
 
 /*
  * The head of Basis-MelGAN for training (model/generator/basis_melgan.py:140-162 under bin/train.py:64-95, and the

@@ -4,12 +4,16 @@
     same chain on the same GPU (F.conv1d / F.conv_transpose1d / F.leaky_relu on the folded weights, written here),
     with the peak device memory of one step of each;
   * each new kernel alone per layer of the model: ms, TFLOP/s of the layer's algorithmic FLOPs and the fraction of the
-    157 TF fp32 matrix peak.
+    157 TF fp32 matrix peak;
+  * with ``--grad-precision bf16``: the forward + backward with ``grad_precision = "bf16"``, and beside every fp32
+    weight-gradient row the row of the bf16 entry (csrc/gen_grad_bf16.hip) with its fraction of the 2517 TF bf16
+    matrix peak.  Eager autograd stays fp32: the two are then not the same arithmetic.
 
 Timing: after a warm-up, ``--reps`` windows of back-to-back calls between device events; the median and the spread
 (min .. max) of the windows are reported.  Prints one JSON line.
 
     python tools/generator_grad_bench.py [--batch 32] [--frames 140] [--reps 7] [--target-s 0.3] [--no-eager]
+                                         [--grad-precision {f32,bf16}]
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ from fastvocoder_amd.generator.engine import effective_weight  # noqa: E402
 from fastvocoder_amd.synthetic import seeded_mel, seeded_state_dict  # noqa: E402
 
 PEAK_TF = 157.3          # fp32 matrix peak of the MI355X
+PEAK_BF16_TF = 2516.8    # its bf16 matrix peak (16 x)
 LIGHT = dict(resblock_kernel_sizes=[3, 7, 11], upsample_rates=[8, 5, 3, 2], upsample_initial_channel=256,
              resblock_type="1", upsample_kernel_sizes=[16, 10, 6, 4],
              resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]], transposedconv=True, bias=True)
@@ -98,18 +103,19 @@ def peak_mb(step):
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
 
 
-def kernel_rows(gen, B, frames, reps, target_s, dev):
-    """Each new kernel alone on every distinct layer shape of the model."""
+def kernel_rows(gen, B, frames, reps, target_s, dev, bf16=False):
+    """Each new kernel alone on every distinct layer shape of the model; ``bf16``: the bf16 weight-gradient entries
+    beside the fp32 ones."""
     rows, rs = [], torch.Generator(device="cpu").manual_seed(0)
 
     def rnd(*shape):
         return torch.randn(*shape, generator=rs).to(dev)
 
-    def row(kind, shape, flops, fn):
+    def row(kind, shape, flops, fn, peak=PEAK_TF):
         med, lo, hi = windows_ms(fn, reps, target_s)
         tf = flops / (med * 1e-3) / 1e12
         rows.append(dict(kernel=kind, shape=shape, ms=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
-                         tflops=round(tf, 2), peak_fraction=round(tf / PEAK_TF, 4)))
+                         tflops=round(tf, 2), peak_fraction=round(tf / peak, 4)))
 
     t, seen = frames, set()
     convs = [(gen.conv_pre, t)]
@@ -135,6 +141,12 @@ def kernel_rows(gen, B, frames, reps, target_s, dev):
                              device=dev)
             row("conv_transpose1d_weight_grad", [cin, cout, k, s, tin], flops,
                 lambda: _native.conv_transpose1d_weight_grad(g, xa, k, s, p, op, True, True, workspace=ws))
+            if bf16:
+                wsb = torch.empty(_native.conv_transpose1d_weight_grad_workspace_floats(B, cin, cout, tin, k, s, p, op,
+                                                                                        "bf16"), device=dev)
+                row("conv_transpose1d_weight_grad_bf16", [cin, cout, k, s, tin], flops,
+                    lambda: _native.conv_transpose1d_weight_grad(g, xa, k, s, p, op, True, True, workspace=wsb,
+                                                                 precision="bf16"), PEAK_BF16_TF)
             row("conv_transpose1d_input_grad", [cin, cout, k, s, tin], flops,
                 lambda: _native.conv_transpose1d_input_grad(g, w, tin, s, p, op))
         else:
@@ -148,6 +160,12 @@ def kernel_rows(gen, B, frames, reps, target_s, dev):
             ws = torch.empty(_native.conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad), device=dev)
             row("conv1d_weight_grad_dilated", [cin, cout, k, dil, tin], 2.0 * B * tout * cin * cout * k,
                 lambda: _native.conv1d_weight_grad_dilated(g, xa, k, dil, pad, True, True, workspace=ws))
+            if bf16:
+                wsb = torch.empty(_native.conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad,
+                                                                                      precision="bf16"), device=dev)
+                row("conv1d_weight_grad_dilated_bf16", [cin, cout, k, dil, tin], 2.0 * B * tout * cin * cout * k,
+                    lambda: _native.conv1d_weight_grad_dilated(g, xa, k, dil, pad, True, True, workspace=wsb,
+                                                               precision="bf16"), PEAK_BF16_TF)
     return rows
 
 
@@ -159,6 +177,7 @@ def main():
     ap.add_argument("--target-s", type=float, default=0.3)
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--grad-precision", choices=["f32", "bf16"], default="f32")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "generator_grad_bench measures on the ROCm device"
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -166,6 +185,7 @@ def main():
     gen.load_state_dict({k: torch.from_numpy(v) for k, v in seeded_state_dict("hifigan", LIGHT, seed=0).items()})
     gen = gen.to(dev)
     gen.parameter_grad = True
+    gen.grad_precision = args.grad_precision
     mel = torch.from_numpy(seeded_mel(args.frames, seed=0, batch=args.batch)).to(dev)
     n = gen(mel).shape[1]
     c = torch.randn(args.batch, n, device=dev)
@@ -175,7 +195,7 @@ def main():
         gen(mel).backward(c)
 
     result = dict(tool="generator_grad_bench", model="hifigan light", batch=args.batch, frames=args.frames, samples=n,
-                  device=torch.cuda.get_device_name(dev))
+                  grad_precision=args.grad_precision, device=torch.cuda.get_device_name(dev))
     med, lo, hi = windows_ms(native_step, args.reps, args.target_s)
     result["native"] = dict(ms=round(med, 3), ms_min=round(lo, 3), ms_max=round(hi, 3), peak_mb=round(peak_mb(native_step), 1))
     if not args.no_eager:
@@ -192,7 +212,8 @@ def main():
                     for k, q in leaves.items())
         result["native_vs_eager_max_rel"] = float(f"{worst:.3e}")
     if not args.no_kernels:
-        result["kernels"] = kernel_rows(gen, args.batch, args.frames, args.reps, min(args.target_s, 0.1), dev)
+        result["kernels"] = kernel_rows(gen, args.batch, args.frames, args.reps, min(args.target_s, 0.1), dev,
+                                        bf16=args.grad_precision == "bf16")
     print(json.dumps(result))
 
 

@@ -9,13 +9,16 @@
     of the layer's algorithmic FLOPs and the fraction of the 157 TF fp32 matrix peak;
   * the pointwise and skip 1x1 weight gradients of a stack as two calls beside ONE call over the concatenated columns
     [lrelu(h) ; x] (what a fused entry would run, timed with the concatenation already made);
-  * ms per whole ``Trainer.step`` in both phases (STFT only, and with the discriminator's terms and update).
+  * ms per whole ``Trainer.step`` in both phases (STFT only, and with the discriminator's terms and update);
+  * with ``--grad-precision bf16``: the forward + backward and the steps with ``grad_precision = "bf16"``, and beside
+    every fp32 weight-gradient row the row of the bf16 entry (csrc/gen_grad_bf16.hip) with its fraction of the bf16
+    matrix peak.  Eager autograd stays fp32: the two are then not the same arithmetic.
 
 Timing: after a warm-up, ``--reps`` windows of back-to-back calls between device events; the median and the spread
 (min .. max) of the windows are reported.  Prints one JSON line.
 
     python tools/melgan_grad_bench.py [--batch 32] [--frames 140] [--reps 7] [--target-s 0.3] [--no-eager] [--no-kernels]
-                                      [--no-steps]
+                                      [--no-steps] [--grad-precision {f32,bf16}]
 """
 import argparse
 import json
@@ -37,21 +40,21 @@ from fastvocoder_amd.generator.modules import ResidualStack  # noqa: E402
 from fastvocoder_amd.synthetic import seeded_mel, seeded_state_dict  # noqa: E402
 from fastvocoder_amd.train import Trainer  # noqa: E402
 from oracle import torch_port  # noqa: E402
-from tools.generator_grad_bench import PEAK_TF, peak_mb, windows_ms  # noqa: E402
+from tools.generator_grad_bench import PEAK_BF16_TF, PEAK_TF, peak_mb, windows_ms  # noqa: E402
 
 
-def kernel_rows(gen, B, frames, reps, target_s, dev):
+def kernel_rows(gen, B, frames, reps, target_s, dev, bf16=False):
     rows, rs = [], torch.Generator(device="cpu").manual_seed(0)
     R = _native.PAD_REFLECT
 
     def rnd(*shape):
         return torch.randn(*shape, generator=rs).to(dev)
 
-    def row(kind, shape, flops, fn):
+    def row(kind, shape, flops, fn, peak=PEAK_TF):
         med, lo, hi = windows_ms(fn, reps, target_s)
         tf = flops / (med * 1e-3) / 1e12
         rows.append(dict(kernel=kind, shape=shape, ms=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
-                         tflops=round(tf, 2), peak_fraction=round(tf / PEAK_TF, 4)))
+                         tflops=round(tf, 2), peak_fraction=round(tf / peak, 4)))
 
     # (conv, pad, input length, has a data gradient) of every conv behind the pad, and the stacks' 1x1 pairs
     t, padded, pairs = frames, [], []
@@ -76,6 +79,12 @@ def kernel_rows(gen, B, frames, reps, target_s, dev):
         ws = torch.empty(_native.conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad, R), device=dev)
         row("conv1d_weight_grad_dilated_mode", [cin, cout, k, dil, tin], flops,
             lambda: _native.conv1d_weight_grad_dilated(g, xa, k, dil, pad, True, True, workspace=ws, pad_mode=R))
+        if bf16:
+            wsb = torch.empty(_native.conv1d_weight_grad_dilated_workspace_floats(B, cin, cout, tin, k, dil, pad, R, "bf16"),
+                              device=dev)
+            row("conv1d_weight_grad_dilated_bf16", [cin, cout, k, dil, tin], flops,
+                lambda: _native.conv1d_weight_grad_dilated(g, xa, k, dil, pad, True, True, workspace=wsb, pad_mode=R,
+                                                           precision="bf16"), PEAK_BF16_TF)
         if not data:
             continue
         wt = w.transpose(0, 1).contiguous()
@@ -102,6 +111,13 @@ def kernel_rows(gen, B, frames, reps, target_s, dev):
         row("pointwise + skip weight grad: two calls", [ch, tin], flops, two)
         row("pointwise + skip weight grad: one call on [lrelu(h) ; x]", [ch, tin], flops,
             lambda: _native.conv1d_weight_grad_dilated(g, both, 1, 1, 0, True, True, workspace=ws))
+        if bf16:
+            wsb = torch.empty(floats(B, ch, ch, tin, 1, 1, 0, precision="bf16"), device=dev)
+
+            def two_bf16():
+                _native.conv1d_weight_grad_dilated(g, ha, 1, 1, 0, True, True, workspace=wsb, precision="bf16")
+                _native.conv1d_weight_grad_dilated(g, x, 1, 1, 0, True, True, workspace=wsb, precision="bf16")
+            row("pointwise + skip weight grad: two bf16 calls", [ch, tin], flops, two_bf16, PEAK_BF16_TF)
     return rows
 
 
@@ -110,7 +126,7 @@ def eager_generator(gen, cfg):
     return (lambda mel: torch.tanh(torch_port.melgan_trunk(mel, leaves, cfg))[:, 0, :]), leaves
 
 
-def step_rows(cfg, sd, mel, dev, reps, target_s):
+def step_rows(cfg, sd, mel, dev, reps, target_s, grad_precision="f32"):
     out = {}
     spf = int(np.prod(cfg["upsample_scales"]))
     wav = 0.3 * torch.randn(mel.shape[0], mel.shape[2] * spf, device=dev)
@@ -123,7 +139,7 @@ def step_rows(cfg, sd, mel, dev, reps, target_s):
         trainer = Trainer(gen, disc, optim.Adam(gen.parameters(), lr=1e-4, eps=1e-6),
                           optim.Adam(disc.parameters(), lr=5e-5, eps=1e-6), lambda_stft=cfg.get("lamda_stft", 1.0),
                           use_feature_map_loss=True, discriminator_train_start_steps=start, grad_clip_thresh=1.0,
-                          stack_grad=True)
+                          stack_grad=True, grad_precision=grad_precision)
         step = [0]
 
         def one():
@@ -143,6 +159,7 @@ def main():
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-steps", action="store_true")
+    ap.add_argument("--grad-precision", choices=["f32", "bf16"], default="f32")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "melgan_grad_bench measures on the ROCm device"
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -154,6 +171,7 @@ def main():
     gen = gen.to(dev)
     gen.stack_grad = True
     gen.parameter_grad = True
+    gen.grad_precision = args.grad_precision
     mel = torch.from_numpy(seeded_mel(args.frames, seed=0, batch=args.batch)).to(dev)
     n = gen(mel).shape[1]
     c = torch.randn(args.batch, n, device=dev)
@@ -163,7 +181,7 @@ def main():
         gen(mel).backward(c)
 
     result = dict(tool="melgan_grad_bench", model="melgan original", batch=args.batch, frames=args.frames, samples=n,
-                  device=torch.cuda.get_device_name(dev))
+                  grad_precision=args.grad_precision, device=torch.cuda.get_device_name(dev))
     med, lo, hi = windows_ms(native_step, args.reps, args.target_s)
     result["native"] = dict(ms=round(med, 3), ms_min=round(lo, 3), ms_max=round(hi, 3), peak_mb=round(peak_mb(native_step), 1))
     if not args.no_eager:
@@ -180,9 +198,10 @@ def main():
                     for k, q in leaves.items())
         result["native_vs_eager_max_rel"] = float(f"{worst:.3e}")
     if not args.no_kernels:
-        result["kernels"] = kernel_rows(gen, args.batch, args.frames, args.reps, min(args.target_s, 0.1), dev)
+        result["kernels"] = kernel_rows(gen, args.batch, args.frames, args.reps, min(args.target_s, 0.1), dev,
+                                        bf16=args.grad_precision == "bf16")
     if not args.no_steps:
-        result["trainer_step"] = step_rows(cfg, sd, mel, dev, args.reps, args.target_s)
+        result["trainer_step"] = step_rows(cfg, sd, mel, dev, args.reps, args.target_s, args.grad_precision)
     print(json.dumps(result))
 
 

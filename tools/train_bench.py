@@ -7,10 +7,14 @@
   * the fused clip + Adam (optim.Adam.step(max_norm), three launches) beside ``clip_grad_norm_`` + ``torch.optim.Adam``
     on the same generator and discriminator parameter sets, gradients in place.
 
+``--grad-precision bf16`` runs all of it with ``Trainer(grad_precision="bf16")``: the generator's weight gradients on
+the bf16 matrix cores (csrc/gen_grad_bf16.hip), everything else fp32.
+
 Timing: after a warm-up, ``--reps`` windows of back-to-back calls between device events; the median and the spread
 (min .. max) of the windows are reported.  Prints one JSON line.
 
     python tools/train_bench.py [--batch 32] [--frames 140] [--reps 5] [--target-s 0.5] [--use-mpd]
+                                [--grad-precision {f32,bf16}]
 """
 import argparse
 import json
@@ -89,6 +93,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--target-s", type=float, default=0.5)
     ap.add_argument("--use-mpd", action="store_true")
+    ap.add_argument("--grad-precision", choices=["f32", "bf16"], default="f32")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -103,9 +108,10 @@ def main():
 
     def trainer(start):
         return Trainer(g, d, optim.Adam(g.parameters(), lr=1e-4, eps=1e-6), optim.Adam(d.parameters(), lr=5e-5, eps=1e-6),
-                       discriminator_train_start_steps=start, **kw)
+                       discriminator_train_start_steps=start, grad_precision=args.grad_precision, **kw)
 
-    out = dict(batch=args.batch, frames=args.frames, use_mpd=args.use_mpd, device=torch.cuda.get_device_name(0))
+    out = dict(batch=args.batch, frames=args.frames, use_mpd=args.use_mpd, grad_precision=args.grad_precision,
+               device=torch.cuda.get_device_name(0))
     t0, t1 = trainer(10 ** 9), trainer(0)
     out["step_stft_only"] = windows_ms(lambda: t0.step(mel, wav, 1), args.reps, args.target_s)
     out["step_adversarial"] = windows_ms(lambda: t1.step(mel, wav, 1), args.reps, args.target_s)
