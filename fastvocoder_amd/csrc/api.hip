@@ -15,6 +15,7 @@
 #include <unistd.h>
 
 #include "api_internal.h"
+#include "launch_host.hpp"
 
 namespace fv {
 
@@ -345,7 +346,7 @@ static const TuningEntry kTuningTable[] = {
     {"sched_switch", &Tuning::sched_switch}, {"convh_skel", &Tuning::convh_skel}, {"convp_skel", &Tuning::convp_skel},
     {"convq_skel", &Tuning::convq_skel},   {"pair128_unfused", &Tuning::pair128_unfused},
     {"convg_rows64", &Tuning::convg_rows64}, {"stack_items", &Tuning::stack_items}, {"stack_wide", &Tuning::stack_wide},
-    {"convp_wide", &Tuning::convp_wide},   {"convq_wide", &Tuning::convq_wide},  {"convp_pp", &Tuning::convp_pp},
+    {"convp_wide", &Tuning::convp_wide},   {"convq_wide", &Tuning::convq_wide},
     {"convh_rows64", &Tuning::convh_rows64},  {"convt_rows64", &Tuning::convt_rows64},
     {"pairh_skel", &Tuning::pairh_skel},   {"pair_skel", &Tuning::pair_skel},    {"convh_blocks", &Tuning::convh_blocks},
     {"pair_blocks", &Tuning::pair_blocks}, {"sum3_min", &Tuning::sum3_min},      {"lds_budget", &Tuning::lds_budget},
@@ -987,9 +988,7 @@ int check_stack_args(int C, int k, int dil, int pad_mode, float slope, float act
                     "dilation 1, 3 or 9)", C, k, dil);
     if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
         return fail(FV_ERR_UNSUPPORTED, "residual_stack_split_f16: pad_mode %d (zero or reflection padding of the 'same' conv)", pad_mode);
-    if (slope < 0.f || slope > 1.f || act_slope < 0.f || act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: activation slope outside [0, 1]");
-    return 0;
+    return check_slopes("residual_stack_split_f16", slope, act_slope);
 }
 }  // namespace fv
 
@@ -1112,7 +1111,7 @@ int check_pair_args(int n, int C, const int* k, int dil, int prec) {
         return fail(FV_ERR_UNSUPPORTED, "resblock pair: C = %d (16 or 32; 64 ... 512 with split-f16 operands); use the conv1d ops", C);
     if (dil != 1 && dil != 3 && dil != 5) return fail(FV_ERR_UNSUPPORTED, "resblock pair: dilation %d (1, 3 or 5)", dil);
     for (int j = 0; j < n; ++j)
-        if (k[j] != 3 && k[j] != 7 && k[j] != 11) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %d taps (3, 7 or 11)", k[j]);
+        if (int rc = check_taps("resblock pair", k[j])) return rc;
     return 0;
 }
 }  // namespace fv
@@ -1170,8 +1169,7 @@ int check_stage_args(int C, const int* k, const int* dil, float slope, float act
     if (!mrf_stage_shape(C, k, dil))
         return fail(FV_ERR_UNSUPPORTED, "mrf stage: C = %d, taps (%d, %d, %d), dilations (%d, %d, %d): built for 16 / 32 channels, "
                     "taps 3 / 7 / 11, dilations (1, 3, 5)", C, k[0], k[1], k[2], dil[0], dil[1], dil[2]);
-    if (slope < 0.f || slope > 1.f || act_slope < 0.f || act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "mrf stage: activation slope outside [0, 1]");
+    if (int rc = check_slopes("mrf stage", slope, act_slope)) return rc;
     if (post != FV_POST_NONE && post != FV_POST_TANH && post != FV_POST_RELU) return fail(FV_ERR_INVALID_ARG, "mrf stage: post %d", post);
     return 0;
 }
@@ -1247,6 +1245,11 @@ int fv_tuning_set(const char* key, int value) {
             g_tuning.*(e.field) = value;
             return 0;
         }
+    // Switches of removed experiments (convp_pp: the two-wave-group pair kernels): "off" is the one state they have left,
+    // so a caller that puts every switch it knows back to its default keeps working; switching one on is an unknown key.
+    static const char* const kRetiredKeys[] = {"convp_pp"};
+    for (const char* retired : kRetiredKeys)
+        if (value == 0 && strcmp(retired, key) == 0) return 0;
     return fail(FV_ERR_INVALID_ARG, "tuning_set: unknown key '%s'", key);
 }
 

@@ -9,7 +9,7 @@
 #include <mutex>
 #include <vector>
 
-#include "fv_internal.h"
+#include "launch_host.hpp"
 
 namespace fv {
 
@@ -162,50 +162,37 @@ ConvHShape convh_shape(int C, int k, int dil) {
 }
 
 int launch_convh(PairParams p, int C, int dil, hipStream_t s) {
+    const char* const fam = "split-f16 conv";
     if (p.B <= 0 || p.T <= 0) return 0;
     if (C != 64 && C != 128 && C != 256 && C != 512)
         return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: C = %d (64, 128, 256 or 512)", C);
     if (dil != 1 && dil != 3 && dil != 5 && dil != 9)
         return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: dilation %d (1, 3, 5; 9 with 3 taps)", dil);
-    if (p.n_members < 1 || p.n_members > 3) return fail(FV_ERR_INVALID_ARG, "split-f16 conv: %d members", p.n_members);
-    if ((double)C * p.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: one utterance's tensor (%d x %d floats) exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance", C, p.T);
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "split-f16 conv: activation slope outside [0, 1]");
+    if (int rc = check_launch(fam, p, C)) return rc;
     int img_bytes = 0;
-    double flops = 0, bytes = 0;
+    Work work = {0, 0};
     long long items = 0;
     const int cus = device_cu_count();
     // 128 channels and more: 128-row tiles (convs_kernel, convr_kernels.hpp -- a chunk's window is converted once for
     // both 64-row tiles) when the launch has items enough for the chip that way (as launch_convg); Tuning::convh_rows64
-    bool wide = false;
-    if (C >= 128) {
-        long long w = 0;
-        for (int i = 0; i < p.n_members; ++i) w += (long long)((p.T + 127) / 128) * p.B * (C / 128);
-        wide = tuning().convh_rows64 < 0 ? w * 10 >= 7LL * cus : !tuning().convh_rows64;
-    }
+    const long long w128 = C >= 128 ? (long long)p.n_members * ((p.T + 127) / 128) * p.B * (C / 128) : 0;     // such items
+    const bool wide = C >= 128 && (tuning().convh_rows64 < 0 ? w128 * 10 >= 7LL * cus : !tuning().convh_rows64);
     // 256 / 512 channels with items enough: the ring-free form (convs2_kernels.hpp: 128 rows x 64 columns, every wave loads the A
     // operands of its own sixteen rows L2 -> registers; no reflection padding, dilations 1 / 3 / 5) -- Tuning::convs_ringfree
     const bool ringfree = wide && C >= 256 && !p.reflect && dil <= 5 && tuning().convs_ringfree != 0;
     int rf_nh = 1;                     // 128-column tiles (32 x 64 wave tiles) when they still give every CU four items
     if (ringfree) {
-        long long w = 0;
-        for (int i = 0; i < p.n_members; ++i) w += (long long)((p.T + 127) / 128) * p.B * (C / 128);
-        rf_nh = tuning().convs_ringfree > 0 ? tuning().convs_ringfree : (w >= 4LL * cus ? 2 : 1);
+        rf_nh = tuning().convs_ringfree > 0 ? tuning().convs_ringfree : (w128 >= 4LL * cus ? 2 : 1);
         if (rf_nh != 1 && rf_nh != 2) rf_nh = 1;
     }
     const int rf_cols = 64 * rf_nh;
     for (int i = 0; i < p.n_members; ++i) {
         PairMember& mb = p.m[i];
-        if (mb.k != 11 && mb.k != 7 && mb.k != 3) return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: %d taps (3, 7 or 11)", mb.k);
+        if (int rc = check_taps(fam, mb.k)) return rc;
         if (dil == 9 && mb.k != 3) return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: dilation 9 with %d taps (3 only)", mb.k);
-        if (p.reflect && (mb.k - 1) / 2 * dil >= p.T)
-            return fail(FV_ERR_INVALID_ARG, "split-f16 conv: reflection padding %d needs more than %d samples", (mb.k - 1) / 2 * dil, p.T);
-        if (!mb.x || !mb.w1 || !mb.y) return fail(FV_ERR_INVALID_ARG, "split-f16 conv: null tensor (member %d)", i);
-        if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "split-f16 conv: add2 without add1 (member %d)", i);
-        if (reinterpret_cast<uintptr_t>(mb.w1) & 15)
-            return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: packed weights must be 16-byte aligned");
+        if (p.reflect)
+            if (int rc = check_reflect(fam, (mb.k - 1) / 2 * dil, p.T)) return rc;
+        if (int rc = check_member(fam, mb, i, kNeedY)) return rc;
         const ConvHShape g = convh_shape(C, mb.k, dil);
         mb.n_tiles = ringfree ? (p.T + rf_cols - 1) / rf_cols : (p.T + g.NTC - 1) / g.NTC;
         mb.n_items = mb.n_tiles * p.B * (wide ? g.NMT / 2 : g.NMT);
@@ -220,40 +207,30 @@ int launch_convh(PairParams p, int C, int dil, hipStream_t s) {
             if (ximg > img_bytes) img_bytes = ximg;
         } else if (g.XIMG > img_bytes) img_bytes = g.XIMG;
         items += mb.n_items;
-        flops += 2.0 * p.B * (double)C * C * mb.k * p.T;
-        bytes += 4.0 * ((double)C * C * mb.k + (double)p.B * C * p.T *
-                        (2 + (mb.res ? 1 : 0) + (mb.add1 ? 1 : 0) + (mb.add2 ? 1 : 0) + (mb.y_act ? 1 : 0)));
+        work.flops += 2.0 * p.B * (double)C * C * mb.k * p.T;
+        work.bytes += 4.0 * ((double)C * C * mb.k + (double)p.B * C * p.T *
+                             (2 + (mb.res ? 1 : 0) + (mb.add1 ? 1 : 0) + (mb.add2 ? 1 : 0) + (mb.y_act ? 1 : 0)));
     }
-    size_t floats = 0;
-    p.x_off = 0;                       // ring of 4 weight stages
-    if (!ringfree) floats += 4 * 16384 / 4;
-    p.img_off = (int)floats;
-    floats += (size_t)img_bytes / 4;
-    p.bias_off = 0;                    // (biases are read from global memory in the epilogue)
-    if (ringfree) floats += 64;        // the low-side guard's scratch
-    const size_t lds = floats * 4;
-    if (lds > 160 * 1024) return fail(FV_ERR_UNSUPPORTED, "split-f16 conv: %zu bytes of LDS", lds);
-    long long nblk = tuning().convh_blocks > 0 ? tuning().convh_blocks : cus;     // one 8-wave block per CU
-    if (nblk > items) nblk = items;
-    p.nblk = (int)nblk;
+    LdsLayout lds;
+    p.x_off = 0;
+    if (!ringfree) lds.add(4 * 16384 / 4);          // ring of 4 weight stages
+    p.img_off = lds.add((size_t)img_bytes / 4);
+    p.bias_off = 0;                                 // (biases are read from global memory in the epilogue)
+    if (ringfree) lds.add(64);                      // the low-side guard's scratch
+    if (int rc = check_lds(fam, lds.bytes())) return rc;
+    p.nblk = (int)persistent_blocks(items, 1, tuning().convh_blocks);       // one 8-wave block per CU
     if (ringfree) p.sched_on = 0;
     else pair_schedule(p, p.nblk);
-    if (!p.sched_on) {                 // no per-block schedule: the kernels' contiguous cut, as a table instead of arithmetic
-        long long n[3] = {0, 0, 0};
-        for (int i = 0; i < p.n_members; ++i) n[i] = p.m[i].n_items;
-        pair_cut_schedule(p, p.nblk, n);
-    }
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-    profile_begin(s);
-    const int rc = ringfree ? launch_convs2_geom(p, dil, rf_nh, lds, s) : wide ? launch_convs_geom(p, dil, lds, s)
-                 : C >= 128 ? launch_convh_geom<4, 2>(p, dil, lds, s) : launch_convh_geom<2, 2>(p, dil, lds, s);
-    profile_end(s, C == 64 ? FV_KERNEL_CONVH64 : FV_KERNEL_CONVH128, flops, bytes);
-    return rc;
+    if (!p.sched_on) cut_table(p, p.nblk);          // no per-block schedule: the kernels' contiguous cut, as a table instead of arithmetic
+    set_debug(p);
+    ProfileScope prof(s, C == 64 ? FV_KERNEL_CONVH64 : FV_KERNEL_CONVH128, work);
+    return ringfree ? launch_convs2_geom(p, dil, rf_nh, lds.bytes(), s) : wide ? launch_convs_geom(p, dil, lds.bytes(), s)
+         : C >= 128 ? launch_convh_geom<4, 2>(p, dil, lds.bytes(), s) : launch_convh_geom<2, 2>(p, dil, lds.bytes(), s);
 }
 
 // ---- ConvTranspose1d, kernel = 2 x stride (convt_kernel) -----------------------------------------------------------
 int launch_convt(PairParams p, int Cin, int Cout, int stride, int pad, int Tout, hipStream_t s) {
+    const char* const fam = "split-f16 transposed conv";
     if (p.B <= 0 || p.T <= 0 || Tout <= 0) return 0;
     if (Cin != 32 && Cin != 64 && Cin != 128 && Cin != 256 && Cin != 512)
         return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv: Cin = %d (32, 64, 128, 256 or 512)", Cin);
@@ -261,15 +238,12 @@ int launch_convt(PairParams p, int Cin, int Cout, int stride, int pad, int Tout,
         return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv: stride %d (2..16), Cout * stride = %d (32 or more)",
                     stride, Cout * stride);
     if (pad < 0 || pad > stride) return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv: padding %d (0..stride)", pad);
-    if ((double)Cin * p.T * 4.0 >= 1073741824.0 || (double)Cout * Tout * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv: one utterance's tensor exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance");
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "split-f16 transposed conv: activation slope outside [0, 1]");
+    if (int rc = check_desc_range(fam, Cin, p.T, false)) return rc;
+    if (int rc = check_desc_range(fam, Cout, Tout, false)) return rc;
+    if (int rc = check_slopes(fam, p.slope, p.act_slope)) return rc;
     PairMember& mb = p.m[0];
-    if (!mb.x || !mb.w1 || !mb.y) return fail(FV_ERR_INVALID_ARG, "split-f16 transposed conv: null tensor");
-    if (reinterpret_cast<uintptr_t>(mb.w1) & 15)
-        return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv: packed weights must be 16-byte aligned");
+    if (int rc = check_tensors(fam, mb, -1, kNeedY)) return rc;
+    if (int rc = check_aligned(fam, mb, 0)) return rc;
     p.n_members = 1;
     p.ctot = Cin;
     const int cc = Cin <= 64 ? 64 : 128;      // input channels per chunk (64 input channels: one chunk of 64, two K steps per tap;
@@ -283,114 +257,70 @@ int launch_convt(PairParams p, int Cin, int Cout, int stride, int pad, int Tout,
     p.reflect = 0;
     const int ncols = (Tout + pad + stride - 1) / stride;          // u = (n + pad) / stride of the last sample, + 1
     mb.k = 2;
-    // Few items: the lean kernel (convtl_kernels.hpp: 64-column tiles, A operands L2 -> registers, no ring) -- a launch of a
-    // handful of tiles per CU is all prologue on the ring pipeline below.  Tuning::convt_lean: (64 x 64 item, chunk) units per CU
-    // (in tenths) up to which it runs; 0: never (A/B, bit-identity tests).  [measured, tools/convt_lean_bench.py, hot loop]
-    // 256 -> 128 x 8 at 1000 frames (2 units per CU): 10.6 against 15.6 us; 512 -> 256 x 8 at 200 frames (2): 15.2 / 23.6;
-    // 64 -> 32 x 3 at 40 000 (4.9): 17.5 / 19.6; 128 -> 64 x 5 at 8000 (2.5): 15.9 / 17.0; at 3.3 units the two are equal, from
-    // ~8 up the ring pipeline wins (batch 16: 74 against 107 us) -- its weights reach all eight waves through LDS once.
-    {
-        const long long lean_items = (long long)((ncols + 63) / 64) * p.B * p.nmt;
-        if (tuning().convt_lean > 0 && lean_items * p.nch * 10 <= (long long)tuning().convt_lean * device_cu_count()) {
-            if (!mb.add1) p.out_div = 1.f;
-            if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "split-f16 transposed conv: add2 without add1");
-            mb.n_tiles = (ncols + 63) / 64;
-            mb.n_items = (int)lean_items;
-            mb.cost = 1;
-            long long nb = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-            if (nb > lean_items) nb = lean_items;
-            p.nblk = (int)nb;
-            p.sched_on = 0;
-            p.dbg = 0;
-            p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-            profile_begin(s);
-            const int rc = launch_convtl_geom(p, cc / 32, s);
-            profile_end(s, FV_KERNEL_CONVT, 2.0 * p.B * (double)p.T * Cin * Cout * 2 * stride,
-                        4.0 * ((double)Cin * Cout * 2 * stride + (double)p.B * ((double)Cin * p.T + (double)Cout * Tout * (mb.y_act ? 2 : 1))));
-            return rc;
-        }
-    }
+    // The form: which kernel, its tiles and items (and, for the ring pipeline, its LDS); one tail launches it.
+    enum { kLean, kResident, kRing } form;
+    const int cus = device_cu_count();
     const int NTC = 128;
-    mb.n_tiles = (ncols + NTC - 1) / NTC;
-    // Many items, 128 / 256 input channels, no merged input: an item is a column tile with ALL its rows on resident images
-    // (convu2_kernels.hpp) -- convu_kernel below converts every window once per PAIR of 64-row tiles.  Tuning::convu_resident
-    {
-        const long long items = (long long)mb.n_tiles * p.B;
-        const int mode = tuning().convu_resident;
-        if (cc == 128 && p.nch <= 2 && p.nmt * 64 <= 1024 && !mb.add1 && mode != 0 && (mode == 2 || items >= 2LL * device_cu_count())) {
-            p.out_div = 1.f;
-            mb.n_items = (int)items;
-            mb.cost = 1;
-            long long nb = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-            if (nb > items) nb = items;
-            p.nblk = (int)nb;
-            p.sched_on = 0;
-            p.dbg = 0;
-            p.trace = nullptr;
-            profile_begin(s);
-            const int rc = launch_convu2_geom(p, p.nch, s);
-            profile_end(s, FV_KERNEL_CONVT, 2.0 * p.B * (double)p.T * Cin * Cout * 2 * stride,
-                        4.0 * ((double)Cin * Cout * 2 * stride + (double)p.B * ((double)Cin * p.T + (double)Cout * Tout * (mb.y_act ? 2 : 1))));
-            return rc;
-        }
+    const int ring_tiles = (ncols + NTC - 1) / NTC;
+    const long long lean_items = (long long)((ncols + 63) / 64) * p.B * p.nmt, column_items = (long long)ring_tiles * p.B;
+    const int resident = tuning().convu_resident;
+    long long items;
+    bool wide = false;
+    LdsLayout lds;
+    if (tuning().convt_lean > 0 && lean_items * p.nch * 10 <= (long long)tuning().convt_lean * cus) {
+        // Few items: the lean kernel (convtl_kernels.hpp: 64-column tiles, A operands L2 -> registers, no ring) -- a launch of a
+        // handful of tiles per CU is all prologue on the ring pipeline below.  Tuning::convt_lean: (64 x 64 item, chunk) units per CU
+        // (in tenths) up to which it runs; 0: never (A/B, bit-identity tests).  [measured, tools/convt_lean_bench.py, hot loop]
+        // 256 -> 128 x 8 at 1000 frames (2 units per CU): 10.6 against 15.6 us; 512 -> 256 x 8 at 200 frames (2): 15.2 / 23.6;
+        // 64 -> 32 x 3 at 40 000 (4.9): 17.5 / 19.6; 128 -> 64 x 5 at 8000 (2.5): 15.9 / 17.0; at 3.3 units the two are equal, from
+        // ~8 up the ring pipeline wins (batch 16: 74 against 107 us) -- its weights reach all eight waves through LDS once.
+        form = kLean;
+        mb.n_tiles = (ncols + 63) / 64;
+        items = lean_items;
+    } else if (cc == 128 && p.nch <= 2 && p.nmt * 64 <= 1024 && !mb.add1 && resident != 0 && (resident == 2 || column_items >= 2LL * cus)) {
+        // Many items, 128 / 256 input channels, no merged input: an item is a column tile with ALL its rows on resident images
+        // (convu2_kernels.hpp) -- convu_kernel below converts every window once per PAIR of 64-row tiles.  Tuning::convu_resident
+        form = kResident;
+        mb.n_tiles = ring_tiles;
+        items = column_items;
+    } else {
+        // The ring pipeline.  128 and more input channels: 128-row tiles (convu_kernel, convr_kernels.hpp) when that still gives
+        // the chip items enough, as launch_convg / launch_convh; Tuning::convt_rows64
+        // (a merged input -- mb.add1: the upsampler behind an MRF stage forms ((x + add1) + add2) / out_div in its window loader --
+        // exists on the 64-row kernel only: the 128-row one has no registers left for the second window)
+        form = kRing;
+        mb.n_tiles = ring_tiles;
+        const long long wide_items = (long long)mb.n_tiles * p.B * ((p.nmt + 1) / 2);
+        wide = cc == 128 && !mb.add1 && (tuning().convt_rows64 < 0 ? wide_items * 10 >= 7LL * cus : !tuning().convt_rows64);
+        items = wide ? wide_items : mb.n_tiles * p.B * p.nmt;
+        const int xrows = (NTC + 1 + 3) / 4 * 4;
+        p.x_off = lds.add(4 * 16384 / 4);          // ring of 4 weight stages
+        p.img_off = lds.add((size_t)(4 * cc * ((xrows + 15) / 16 * 16)) / 4);
     }
-    // 128 and more input channels: 128-row tiles (convu_kernel, convr_kernels.hpp) when that still gives the chip items
-    // enough, as launch_convg / launch_convh; Tuning::convt_rows64
-    const long long wide_items = (long long)mb.n_tiles * p.B * ((p.nmt + 1) / 2);
-    // (a merged input -- mb.add1: the upsampler behind an MRF stage forms ((x + add1) + add2) / out_div in its window loader --
-    // exists on the 64-row kernel only: the 128-row one has no registers left for the second window)
-    const bool wide = cc == 128 && !mb.add1 &&
-                      (tuning().convt_rows64 < 0 ? wide_items * 10 >= 7LL * device_cu_count() : !tuning().convt_rows64);
     if (!mb.add1) p.out_div = 1.f;
-    if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "split-f16 transposed conv: add2 without add1");
-    mb.n_items = wide ? (int)wide_items : mb.n_tiles * p.B * p.nmt;
+    if (form != kResident)             // (the resident kernel has no merged input and reads neither)
+        if (int rc = check_adds(fam, mb.add1, mb.add2)) return rc;
+    mb.n_items = (int)items;
     mb.cost = 1;
-    const int xrows = (NTC + 1 + 3) / 4 * 4;
-    const int img_bytes = 4 * cc * ((xrows + 15) / 16 * 16);
-    p.x_off = 0;                       // ring of 4 weight stages
-    p.img_off = 4 * 16384 / 4;
-    const size_t lds = 4 * 16384 + (size_t)img_bytes;
-    long long nblk = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-    if (nblk > mb.n_items) nblk = mb.n_items;
-    p.nblk = (int)nblk;
+    p.nblk = (int)persistent_blocks(items, 1, tuning().convh_blocks);
     p.sched_on = 0;
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-    profile_begin(s);
-    const int rc = wide ? launch_convu_geom(p, lds, s) : launch_convt_geom(p, cc / 32, lds, s);
-    // MACs of a ConvTranspose1d = Tin * Cin * Cout * k
-    profile_end(s, FV_KERNEL_CONVT, 2.0 * p.B * (double)p.T * Cin * Cout * 2 * stride,
-                4.0 * ((double)Cin * Cout * 2 * stride + (double)p.B * ((double)Cin * p.T + (double)Cout * Tout * (mb.y_act ? 2 : 1))));
-    return rc;
-}
-
-// Long runs of the fused 64- / 128-channel pairs (convp / convq: many tiles per block) are mostly WARM tiles -- NM outputs
-// for the work a cold tile spends on NM - (k - 1) (convq_kernels.hpp) -- so an ITEM (NM - (k - 1) columns) of an 11-tap
-// member costs 84 % of a tile there, one of a 3-tap member 97 %: the members' partition weights follow, or the blocks that
-// walk the 3-tap member finish last [measured, 128 channels, 16 x 64 000 columns, three members: 4.76 ms with equal
-// tile costs whatever the tiling, against 3.50 vs 3.87 ms for the two-member launch]
-#ifndef FV_WARM_TILES
-#define FV_WARM_TILES 1
-#endif
-static void warm_run_costs(PairParams& p, long long items, int nm) {
-    if (!FV_WARM_TILES || items < 8LL * p.nblk) return;
-    for (int i = 0; i < p.n_members; ++i) p.m[i].cost *= nm - (p.m[i].k - 1);
+    set_debug(p, form == kRing, form != kResident);
+    ProfileScope prof(s, FV_KERNEL_CONVT, convt_work(p.B, p.T, Tout, Cin, Cout, 2 * stride, 1, mb.y_act != nullptr));
+    return form == kLean ? launch_convtl_geom(p, cc / 32, s) : form == kResident ? launch_convu2_geom(p, p.nch, s)
+         : wide ? launch_convu_geom(p, lds.bytes(), s) : launch_convt_geom(p, cc / 32, lds.bytes(), s);
 }
 
 // ---- two-source 1x1 conv (convg_kernel) -----------------------------------------------------------------------------
 int launch_convg(PairParams p, int C, hipStream_t s) {
+    const char* const fam = "split-f16 two-source 1x1 conv";
     if (p.B <= 0 || p.T <= 0) return 0;
     if (C != 128 && C != 256 && C != 512)
         return fail(FV_ERR_UNSUPPORTED, "split-f16 two-source 1x1 conv: C = %d (128, 256 or 512)", C);
-    if ((double)C * p.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "split-f16 two-source 1x1 conv: one utterance's tensor (%d x %d floats) exceeds the "
-                    "1 GiB buffer-descriptor range; split the utterance", C, p.T);
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "split-f16 two-source 1x1 conv: activation slope outside [0, 1]");
+    if (int rc = check_desc_range(fam, C, p.T)) return rc;
+    if (int rc = check_slopes(fam, p.slope, p.act_slope)) return rc;
     PairMember& mb = p.m[0];
-    if (!mb.x || !mb.x2 || !mb.w1 || !mb.y) return fail(FV_ERR_INVALID_ARG, "split-f16 two-source 1x1 conv: null tensor");
-    if (reinterpret_cast<uintptr_t>(mb.w1) & 15)
-        return fail(FV_ERR_UNSUPPORTED, "split-f16 two-source 1x1 conv: packed weights must be 16-byte aligned");
+    if (int rc = check_tensors(fam, mb, -1, kNeedX2 | kNeedY)) return rc;
+    if (int rc = check_aligned(fam, mb, 0)) return rc;
     p.n_members = 1;
     p.ctot = C;                                // channels of each input and of the output
     p.nch = 2 * C / 128;                       // chunks of 128 input channels: x's, then x2's
@@ -405,27 +335,22 @@ int launch_convg(PairParams p, int C, hipStream_t s) {
     // [measured, MI355X] Basis-MelGAN light, 64 utterances: 16.3 -> 14.0 ms per step on 128-row tiles; MelGAN, one
     // utterance of 200 frames (13 - 100 column tiles per launch): 0.44 -> 0.47 ms -- with fewer items than CUs the
     // 64-row tiles keep more of the chip busy.  -1: by the item count.
-    const int cus = device_cu_count();
-    const bool wide = tuning().convg_rows64 < 0 ? (long long)mb.n_tiles * p.B * (p.nmt / 2) * 10 >= 7LL * cus : !tuning().convg_rows64;
+    const bool wide = tuning().convg_rows64 < 0 ? (long long)mb.n_tiles * p.B * (p.nmt / 2) * 10 >= 7LL * device_cu_count()
+                                                : !tuning().convg_rows64;
     mb.n_items = mb.n_tiles * p.B * (wide ? p.nmt / 2 : p.nmt);
     mb.cost = 1;
-    p.x_off = 0;                               // ring of 4 weight stages
-    p.img_off = 4 * 16384 / 4;
-    const size_t lds = 4 * 16384 + (size_t)(4 * 128 * 128);      // + image: 128 channels x 128 rows x (2 + 2) bytes
-    long long nblk = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-    if (nblk > mb.n_items) nblk = mb.n_items;
-    p.nblk = (int)nblk;
+    LdsLayout lds;
+    p.x_off = lds.add(4 * 16384 / 4);          // ring of 4 weight stages
+    p.img_off = lds.add(4 * 128 * 128 / 4);    // image: 128 channels x 128 rows x (2 + 2) bytes
+    p.nblk = (int)persistent_blocks(mb.n_items, 1, tuning().convh_blocks);
     p.sched_on = 0;
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-    profile_begin(s);
-    const int rc = wide ? launch_convr_geom(p, lds, s) : launch_convg_geom(p, lds, s);
-    profile_end(s, FV_KERNEL_CONVG, 2.0 * p.B * (double)C * 2 * C * p.T,
-                4.0 * (2.0 * C * C + (double)p.B * C * p.T * (3 + (mb.res ? 1 : 0) + (mb.y_act ? 1 : 0))));
-    return rc;
+    set_debug(p);
+    ProfileScope prof(s, FV_KERNEL_CONVG, Work{2.0 * p.B * (double)C * 2 * C * p.T,
+                                               4.0 * (2.0 * C * C + (double)p.B * C * p.T * (3 + (mb.res ? 1 : 0) + (mb.y_act ? 1 : 0)))});
+    return wide ? launch_convr_geom(p, lds.bytes(), s) : launch_convg_geom(p, lds.bytes(), s);
 }
 
-// ---- fused pair at C = 64 (convq2_kernels.hpp) -------------------------------------------------------------------
+// ---- fused pairs at C = 64 and C = 128 (convq2_kernels.hpp) ----------------------------------------------------------
 constexpr int kPair64Wide = 65, kPair128Wide = 129;     // (convq2_kernels.hpp: the wide forms of the ring-free pair kernel)
 template <int DIL, int C>
 int launch_convq2_dil(const PairParams& p, size_t lds, hipStream_t s);      // convq2_inst.hip: the pairs without the weight ring
@@ -440,185 +365,86 @@ extern template int launch_convq2_dil<3, kPair64Wide>(const PairParams&, size_t,
 extern template int launch_convq2_dil<5, kPair64Wide>(const PairParams&, size_t, hipStream_t);
 extern template int launch_convq2_dil<1, kPair128Wide>(const PairParams&, size_t, hipStream_t);
 extern template int launch_convq2_dil<3, kPair128Wide>(const PairParams&, size_t, hipStream_t);
-template <int DIL>
-int launch_convq3_dil(const PairParams& p, hipStream_t s);                  // convq3_inst.hip: two wave groups one conv phase apart
-extern template int launch_convq3_dil<1>(const PairParams&, hipStream_t);
-extern template int launch_convq3_dil<3>(const PairParams&, hipStream_t);
-extern template int launch_convq3_dil<5>(const PairParams&, hipStream_t);
-template <int DIL>
-int launch_convq4_dil(const PairParams& p, hipStream_t s);                  // ... the same pipelines as blocks of their own, two per CU
-extern template int launch_convq4_dil<1>(const PairParams&, hipStream_t);
-extern template int launch_convq4_dil<3>(const PairParams&, hipStream_t);
-extern template int launch_convq4_dil<5>(const PairParams&, hipStream_t);
 
-// everything launch_convp does in front of the launch: validation, member order, tile counts, LDS layout, block schedule
-// (form: 1 convq2_kernel<DIL, 64> -- 128-column tiles; 2 convq2_kernel<DIL, 65> -- 256-column tiles; 3 convq3_kernel<DIL> -- two
-// wave groups per block, each on 64-column tiles of its own share: 2 nblk shares, LDS laid out by the kernel)
-static int prepare_convp(PairParams& p, int dil, size_t& lds_out, double& flops, double& bytes, int form) {
-    const int C = 64;
-    const int NMc = form == 2 ? 256 : form == 3 ? 64 : 128;           // intermediate columns per tile
+// Long runs of the fused 64- / 128-channel pairs (many tiles per block) are mostly WARM tiles -- NM outputs
+// for the work a cold tile spends on NM - (k - 1) (convq2_kernels.hpp) -- so an ITEM (NM - (k - 1) columns) of an 11-tap
+// member costs 84 % of a tile there, one of a 3-tap member 97 %: the members' partition weights follow, or the blocks that
+// walk the 3-tap member finish last [measured, 128 channels, 16 x 64 000 columns, three members: 4.76 ms with equal
+// tile costs whatever the tiling, against 3.50 vs 3.87 ms for the two-member launch]
+#ifndef FV_WARM_TILES
+#define FV_WARM_TILES 1
+#endif
+static void warm_run_costs(PairParams& p, long long items, int nm) {
+    if (!FV_WARM_TILES || items < 8LL * p.nblk) return;
+    for (int i = 0; i < p.n_members; ++i) p.m[i].cost *= nm - (p.m[i].k - 1);
+}
+
+// What differs between the two channel counts of the fused pair.  Both run convq2_kernel (A operands from L2 into registers) on
+// narrow tiles, and on wide ones (32 x 64 wave tiles) from Tuning::*wide_from tenths of a wide tile per CU up -- at 128 channels
+// only where both images fit without the ring: dilation 1 and 3.
+struct FusedPair {
+    int C;
+    int narrow, wide;              // intermediate columns per tile of the two forms
+    int Tuning::*wide_from;
+    int wide_dil;                  // the largest dilation the wide form exists for
+    int Tuning::*skel;             // the per-tile constant of a tile's cost, in K steps of one conv ...
+    int skel_auto;                 // ... its value when the key is negative (0: the key as it is)
+    bool three_members;            // pair_schedule: three-member launches get the block schedule too
+    int kind;
+};
+static const FusedPair kFusedPair64 = {64, 128, 256, &Tuning::convp_wide, 5, &Tuning::convp_skel, 0, false, FV_KERNEL_CONVH64};
+static const FusedPair kFusedPair128 = {128, 64, 128, &Tuning::convq_wide, 3, &Tuning::convq_skel, 5, true, FV_KERNEL_CONVH128};
+
+static int launch_fused_pair(const FusedPair& f, PairParams& p, int dil, hipStream_t s) {
+    const char* const fam = "resblock pair";
+    const int C = f.C;
+    if (p.B <= 0 || p.T <= 0) return 0;
     if (dil != 1 && dil != 3 && dil != 5) return fail(FV_ERR_UNSUPPORTED, "resblock pair: dilation %d (1, 3 or 5)", dil);
-    if (p.n_members < 1 || p.n_members > 3) return fail(FV_ERR_INVALID_ARG, "resblock pair: %d members", p.n_members);
-    if ((double)C * p.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "resblock pair: one utterance's tensor (%d x %d floats) exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance", C, p.T);
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "resblock pair: activation slope outside [0, 1]");
-    for (int i = 0; i < p.n_members; ++i)        // largest taps first (cost order of the contiguous partition)
-        for (int j = i + 1; j < p.n_members; ++j)
-            if (p.m[j].k > p.m[i].k) { PairMember t = p.m[i]; p.m[i] = p.m[j]; p.m[j] = t; }
+    if (int rc = check_launch(fam, p, C)) return rc;
+    sort_members_by_taps(p);
+    long long wide_items = 0;          // (a wide tile advances by wide - (k - 1) columns)
+    for (int i = 0; i < p.n_members; ++i) wide_items += (long long)p.B * ((p.T + f.wide - p.m[i].k) / (f.wide + 1 - p.m[i].k));
+    const bool wide = dil <= f.wide_dil && wide_items * 10 >= (long long)(tuning().*f.wide_from) * device_cu_count();
+    const int NM = wide ? f.wide : f.narrow;
+    const int skel = f.skel_auto && tuning().*f.skel < 0 ? f.skel_auto : tuning().*f.skel;
     int img_bytes = 0;
-    flops = bytes = 0;
     long long items = 0;
     for (int i = 0; i < p.n_members; ++i) {
         PairMember& mb = p.m[i];
-        if (mb.k != 11 && mb.k != 7 && mb.k != 3) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %d taps (3, 7 or 11)", mb.k);
-        if (!mb.x || !mb.w1 || !mb.w2 || !mb.y) return fail(FV_ERR_INVALID_ARG, "resblock pair: null tensor (member %d)", i);
-        if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "resblock pair: add2 without add1 (member %d)", i);
-        if ((reinterpret_cast<uintptr_t>(mb.w1) | reinterpret_cast<uintptr_t>(mb.w2)) & 15)
-            return fail(FV_ERR_UNSUPPORTED, "resblock pair: packed weights must be 16-byte aligned");
-        const ConvHShape g = convh_shape(C, mb.k, dil);
-        const int nout = NMc - (mb.k - 1);
-        mb.n_tiles = (p.T + nout - 1) / nout;
-        mb.n_items = mb.n_tiles * p.B;
-        mb.cost = 2 * g.NST + tuning().convp_skel;
-        const int xrows = (NMc + (mb.k - 1) * dil + 3) / 4 * 4;
-        const int ximg = form == 2 ? 2 * (C / 8) * ((xrows + 15) / 16 * 16) * 16 : g.XIMG;
-        if (ximg > img_bytes) img_bytes = ximg;
-        items += mb.n_items;
-        flops += 2.0 * 2.0 * p.B * (double)C * C * mb.k * p.T;
-        bytes += 4.0 * (2.0 * C * C * mb.k + (double)p.B * C * p.T * ((mb.y_act ? 3 : 2) + (mb.add1 ? 1 : 0) + (mb.add2 ? 1 : 0)));
-    }
-    size_t floats = 0;
-    p.x_off = 0;
-    p.img_off = (int)floats;
-    floats += (size_t)img_bytes / 4;
-    p.mid_off = (int)floats;
-    floats += (size_t)4 * C * (NMc + 16) / 4;
-    p.bias_off = (int)floats;
-    floats += 4 * (size_t)C + 16;      // [b1 | b2 | inverse row prescales of conv1 | conv2 | scratch of the low-range guard]
-    const size_t lds = floats * 4;
-    if (lds > 160 * 1024) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %zu bytes of LDS", lds);
-    long long nblk = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-    if (form == 3) {
-        // one share per wave group: 2 nblk contiguous, cost-balanced shares of the concatenated items
-        if (nblk > kSchedBlocks) nblk = kSchedBlocks;
-        if (2 * nblk > items) nblk = (items + 1) / 2;
-        p.nblk = (int)nblk;
-        p.sched_on = 0;
-        warm_run_costs(p, items, NMc);
-        long long n[3] = {0, 0, 0};
-        for (int i = 0; i < p.n_members; ++i) n[i] = p.m[i].n_items;
-        pair_cut_schedule(p, 2 * p.nblk, n);
-        if (p.sched_on != 2) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %lld items do not fit the share table", items);
-        p.dbg = tuning().pair_dbg;
-        p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-        lds_out = 0;
-        return 0;
-    }
-    if (nblk > items) nblk = items;
-    p.nblk = (int)nblk;
-    pair_schedule(p, p.nblk);
-    if (!p.sched_on) {                 // no per-block schedule: the kernels' contiguous cut, as a table instead of arithmetic
-        warm_run_costs(p, items, NMc);
-        long long n[3] = {0, 0, 0};
-        for (int i = 0; i < p.n_members; ++i) n[i] = p.m[i].n_items;
-        pair_cut_schedule(p, p.nblk, n);
-    }
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-    lds_out = lds;
-    return 0;
-}
-
-int launch_convp(PairParams p, int dil, hipStream_t s) {
-    if (p.B <= 0 || p.T <= 0) return 0;
-    size_t lds;
-    double flops, bytes;
-    // convq2_kernels.hpp at 64 channels (A operands from L2 into registers) on 128-column tiles, and on 256-column tiles
-    // (32 x 64 wave tiles) from Tuning::convp_wide tenths of such a tile per CU up
-    long long wide_items = 0;
-    for (int i = 0; i < p.n_members; ++i) wide_items += (long long)p.B * ((p.T + 256 - p.m[i].k) / (257 - p.m[i].k));
-    const int form = tuning().convp_pp ? 3 : wide_items * 10 >= (long long)tuning().convp_wide * device_cu_count() ? 2 : 1;
-    if (int rc = prepare_convp(p, dil, lds, flops, bytes, form)) return rc;
-    profile_begin(s);
-    const int rc = form == 3 && tuning().convp_pp == 2 ? (dil == 1 ? launch_convq4_dil<1>(p, s) : dil == 3 ? launch_convq4_dil<3>(p, s) : launch_convq4_dil<5>(p, s))
-                   : form == 3 ? (dil == 1 ? launch_convq3_dil<1>(p, s) : dil == 3 ? launch_convq3_dil<3>(p, s) : launch_convq3_dil<5>(p, s))
-                   : form == 2 ? (dil == 1 ? launch_convq2_dil<1, kPair64Wide>(p, lds, s) : dil == 3 ? launch_convq2_dil<3, kPair64Wide>(p, lds, s) : launch_convq2_dil<5, kPair64Wide>(p, lds, s))
-                             : (dil == 1 ? launch_convq2_dil<1, 64>(p, lds, s) : dil == 3 ? launch_convq2_dil<3, 64>(p, lds, s) : launch_convq2_dil<5, 64>(p, lds, s));
-    profile_end(s, FV_KERNEL_CONVH64, flops, bytes);
-    return rc;
-}
-
-// ---- fused pair at C = 128 (convq2_kernels.hpp) ------------------------------------------------------------------
-
-int launch_convq(PairParams p, int dil, hipStream_t s) {
-    const int C = 128;
-    // 128-column tiles (convq2_kernel<DIL, 129>: 32 x 64 wave tiles) where both images fit without the ring -- dilation 1 and
-    // 3 -- from Tuning::convq_wide tenths of such a tile per CU up
-    long long wide_items = 0;
-    for (int i = 0; i < p.n_members && i < 3; ++i) wide_items += (long long)p.B * ((p.T + 128 - p.m[i].k) / (129 - p.m[i].k));
-    const bool wide = dil <= 3 && wide_items * 10 >= (long long)tuning().convq_wide * device_cu_count();
-    const int NM = wide ? 128 : 64;
-    if (p.B <= 0 || p.T <= 0) return 0;
-    if (dil != 1 && dil != 3 && dil != 5) return fail(FV_ERR_UNSUPPORTED, "resblock pair: dilation %d (1, 3 or 5)", dil);
-    if (p.n_members < 1 || p.n_members > 3) return fail(FV_ERR_INVALID_ARG, "resblock pair: %d members", p.n_members);
-    if ((double)C * p.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "resblock pair: one utterance's tensor (%d x %d floats) exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance", C, p.T);
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "resblock pair: activation slope outside [0, 1]");
-    for (int i = 0; i < p.n_members; ++i)        // largest taps first (cost order of the contiguous partition)
-        for (int j = i + 1; j < p.n_members; ++j)
-            if (p.m[j].k > p.m[i].k) { PairMember t = p.m[i]; p.m[i] = p.m[j]; p.m[j] = t; }
-    int img_bytes = 0;
-    double flops = 0, bytes = 0;
-    long long items = 0;
-    for (int i = 0; i < p.n_members; ++i) {
-        PairMember& mb = p.m[i];
-        if (mb.k != 11 && mb.k != 7 && mb.k != 3) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %d taps (3, 7 or 11)", mb.k);
-        if (!mb.x || !mb.w1 || !mb.w2 || !mb.y) return fail(FV_ERR_INVALID_ARG, "resblock pair: null tensor (member %d)", i);
-        if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "resblock pair: add2 without add1 (member %d)", i);
-        if ((reinterpret_cast<uintptr_t>(mb.w1) | reinterpret_cast<uintptr_t>(mb.w2)) & 15)
-            return fail(FV_ERR_UNSUPPORTED, "resblock pair: packed weights must be 16-byte aligned");
+        if (int rc = check_taps(fam, mb.k)) return rc;
+        if (int rc = check_member(fam, mb, i, kNeedW2 | kNeedY)) return rc;
         const int nout = NM - (mb.k - 1);
         mb.n_tiles = (p.T + nout - 1) / nout;
         mb.n_items = mb.n_tiles * p.B;
-        mb.cost = 4 * mb.k + (tuning().convq_skel >= 0 ? tuning().convq_skel : 5);     // K steps of one conv + per-tile work
+        mb.cost = C / 32 * mb.k + skel;            // K steps of one conv + per-tile work
         const int xrows = (NM + (mb.k - 1) * dil + 3) / 4 * 4;
         const int img = 4 * C * ((xrows + 15) / 16 * 16);
         if (img > img_bytes) img_bytes = img;
         items += mb.n_items;
-        flops += 2.0 * 2.0 * p.B * (double)C * C * mb.k * p.T;
-        bytes += 4.0 * (2.0 * C * C * mb.k + (double)p.B * C * p.T * ((mb.y_act ? 3 : 2) + (mb.add1 ? 1 : 0) + (mb.add2 ? 1 : 0)));
     }
-    size_t floats = 0;
+    LdsLayout lds;
     p.x_off = 0;
-    p.img_off = (int)floats;
-    floats += (size_t)img_bytes / 4;
-    p.mid_off = (int)floats;
-    floats += (size_t)4 * C * (NM + 16) / 4;
-    p.bias_off = (int)floats;
-    floats += 4 * (size_t)C + 16;      // [b1 | b2 | inverse row prescales of conv1 | conv2 | scratch of the low-range guard]
-    const size_t lds = floats * 4;
-    if (lds > 160 * 1024) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %zu bytes of LDS", lds);
-    long long nblk = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-    if (nblk > items) nblk = items;
-    p.nblk = (int)nblk;
-    pair_schedule(p, p.nblk, true);
+    p.img_off = lds.add((size_t)img_bytes / 4);
+    p.mid_off = lds.add((size_t)4 * C * (NM + 16) / 4);
+    p.bias_off = lds.add(4 * (size_t)C + 16);      // [b1 | b2 | inverse row prescales of conv1 | conv2 | scratch of the low-range guard]
+    if (int rc = check_lds(fam, lds.bytes())) return rc;
+    p.nblk = (int)persistent_blocks(items, 1, tuning().convh_blocks);
+    pair_schedule(p, p.nblk, f.three_members);
     if (!p.sched_on) {                 // no per-block schedule: the kernels' contiguous cut, as a table instead of arithmetic
         warm_run_costs(p, items, NM);
-        long long n[3] = {0, 0, 0};
-        for (int i = 0; i < p.n_members; ++i) n[i] = p.m[i].n_items;
-        pair_cut_schedule(p, p.nblk, n);
+        cut_table(p, p.nblk);
     }
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-    profile_begin(s);
-    const int rc = wide ? (dil == 1 ? launch_convq2_dil<1, kPair128Wide>(p, lds, s) : launch_convq2_dil<3, kPair128Wide>(p, lds, s))
-                      : (dil == 1 ? launch_convq2_dil<1, 128>(p, lds, s) : dil == 3 ? launch_convq2_dil<3, 128>(p, lds, s) : launch_convq2_dil<5, 128>(p, lds, s));
-    profile_end(s, FV_KERNEL_CONVH128, flops, bytes);
-    return rc;
+    set_debug(p);
+    ProfileScope prof(s, f.kind, pair_work(p, C));
+    const size_t bytes = lds.bytes();
+    if (C == 64)
+        return wide ? by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, kPair64Wide>(p, bytes, s); })
+                    : by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, 64>(p, bytes, s); });
+    return wide ? by_dilation<1, 3, 3>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, kPair128Wide>(p, bytes, s); })
+                : by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, 128>(p, bytes, s); });
 }
+
+int launch_convp(PairParams p, int dil, hipStream_t s) { return launch_fused_pair(kFusedPair64, p, dil, s); }
+int launch_convq(PairParams p, int dil, hipStream_t s) { return launch_fused_pair(kFusedPair128, p, dil, s); }
 
 }  // namespace fv

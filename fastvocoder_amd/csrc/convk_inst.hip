@@ -1,6 +1,6 @@
 // MelGAN ResidualStack as one split-f16 launch, 32 / 64 / 128 channels: convk_kernel of convk_kernels.hpp
 #include "convk_kernels.hpp"
-#include "fv_internal.h"
+#include "launch_host.hpp"
 
 namespace fv {
 
@@ -82,21 +82,20 @@ static int launch_k2(const ConvKParams& p, hipStream_t s) {
 }
 template <int C, int NM>
 static int launch_k2_dil(const ConvKParams& p, int dil, hipStream_t s) {
-    return dil == 1 ? launch_k2<C, 1, NM>(p, s) : dil == 3 ? launch_k2<C, 3, NM>(p, s) : launch_k2<C, 9, NM>(p, s);
+    return by_dilation<1, 3, 9>(dil, [&](auto d) { return launch_k2<C, decltype(d)::value, NM>(p, s); });
 }
 
 int launch_convk(const PairParams& pp, int C, int dil, hipStream_t s) {
+    const char* const fam = "residual stack";
     const PairMember& mb = pp.m[0];
     if (!convk_shape(C, 3, dil)) return fail(FV_ERR_UNSUPPORTED, "residual stack: C = %d, dilation %d (32 / 64 / 128 / 256 channels, 3 taps, dilation 1, 3 or 9)", C, dil);
-    if (!mb.x || !mb.w1 || !mb.y) return fail(FV_ERR_INVALID_ARG, "residual stack: null tensor");
-    if (reinterpret_cast<uintptr_t>(mb.w1) & 15) return fail(FV_ERR_UNSUPPORTED, "residual stack: packed weights must be 16-byte aligned");
+    if (int rc = check_tensors(fam, mb, -1, kNeedY)) return rc;
+    if (int rc = check_aligned(fam, mb, 0)) return rc;
     if (pp.B <= 0 || pp.T <= 0) return 0;
-    if ((double)C * pp.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "residual stack: one utterance's tensor (%d x %d floats) exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance", C, pp.T);
-    if (pp.reflect && dil >= pp.T) return fail(FV_ERR_INVALID_ARG, "residual stack: reflection padding %d needs more than %d samples", dil, pp.T);
-    if (pp.slope < 0.f || pp.slope > 1.f || pp.act_slope < 0.f || pp.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "residual stack: activation slope outside [0, 1]");
+    if (int rc = check_desc_range(fam, C, pp.T)) return rc;
+    if (pp.reflect)
+        if (int rc = check_reflect(fam, dil, pp.T)) return rc;
+    if (int rc = check_slopes(fam, pp.slope, pp.act_slope)) return rc;
     ConvKParams p = {};
     p.x = mb.x;
     p.w = mb.w1;
@@ -114,9 +113,7 @@ int launch_convk(const PairParams& pp, int C, int dil, hipStream_t s) {
     const long long items = (long long)p.n_tiles * pp.B;
     if (items >= (1LL << 31)) return fail(FV_ERR_UNSUPPORTED, "residual stack: too many tiles");
     p.n_items = (int)items;
-    long long nblk = tuning().convh_blocks > 0 ? tuning().convh_blocks : device_cu_count();
-    if (nblk > items) nblk = items;
-    p.nblk = (int)nblk;
+    p.nblk = (int)persistent_blocks(items, 1, tuning().convh_blocks);
     p.slope = pp.slope;
     p.act_slope = pp.act_slope;
     p.post = pp.post;
@@ -124,13 +121,11 @@ int launch_convk(const PairParams& pp, int C, int dil, hipStream_t s) {
     p.sub_batched = pp.sub_batched;
     p.reflect = pp.reflect;
     p.guard = pp.guard;
-    profile_begin(s);
-    const int rc = C == 256 ? (wide ? launch_k2_dil<256, 64>(p, dil, s) : launch_k2_dil<256, 32>(p, dil, s))
-                 : C == 32 ? launch_k2_dil<32, 256>(p, dil, s) : C == 64 ? launch_k2_dil<64, 128>(p, dil, s) : launch_k2_dil<128, 64>(p, dil, s);
     // conv1 (3 taps) + the two 1x1 convs; x in, y (and its twin) out, the weights once
-    profile_end(s, FV_KERNEL_STACK, 2.0 * pp.B * (double)C * C * 5 * pp.T,
-                4.0 * (5.0 * C * C + (double)pp.B * C * pp.T * (mb.y_act ? 3 : 2)));
-    return rc;
+    ProfileScope prof(s, FV_KERNEL_STACK, Work{2.0 * pp.B * (double)C * C * 5 * pp.T,
+                                               4.0 * (5.0 * C * C + (double)pp.B * C * pp.T * (mb.y_act ? 3 : 2))});
+    return C == 256 ? (wide ? launch_k2_dil<256, 64>(p, dil, s) : launch_k2_dil<256, 32>(p, dil, s))
+         : C == 32 ? launch_k2_dil<32, 256>(p, dil, s) : C == 64 ? launch_k2_dil<64, 128>(p, dil, s) : launch_k2_dil<128, 64>(p, dil, s);
 }
 
 }  // namespace fv

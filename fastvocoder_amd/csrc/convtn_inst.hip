@@ -1,6 +1,6 @@
 // split-f16 ConvTranspose1d 32 -> 16 channels x 2 (HiFi-GAN light's last upsampler): convtn_kernels.hpp
 #include "convtn_kernels.hpp"
-#include "fv_internal.h"
+#include "launch_host.hpp"
 
 namespace fv {
 
@@ -24,13 +24,12 @@ int launch_pack_convtn(const float* w, float* packed, const float* inv, int* ran
 }
 
 int launch_convtn(const PairParams& pp, int Tout, hipStream_t s) {
+    const char* const fam = "split-f16 transposed conv (32 -> 16)";
     const PairMember& mb = pp.m[0];
-    if (!mb.x || !mb.w1 || !mb.y) return fail(FV_ERR_INVALID_ARG, "split-f16 transposed conv (32 -> 16): null tensor");
+    if (int rc = check_tensors(fam, mb, -1, kNeedY)) return rc;
     if (Tout != 2 * pp.T) return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv (32 -> 16): Tout = %d (2 T)", Tout);
-    if ((double)kTnCin * pp.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "split-f16 transposed conv (32 -> 16): one utterance's tensor exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance");
-    if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "split-f16 transposed conv: add2 without add1");
+    if (int rc = check_desc_range(fam, kTnCin, pp.T, false)) return rc;
+    if (int rc = check_adds("split-f16 transposed conv", mb.add1, mb.add2)) return rc;
     ConvTnParams p = {};
     p.x = mb.x;
     p.add1 = mb.add1;
@@ -47,11 +46,10 @@ int launch_convtn(const PairParams& pp, int Tout, hipStream_t s) {
     p.act_slope = pp.act_slope;
     p.out_div = mb.add1 ? pp.out_div : 1.f;
     p.guard = pp.guard;
-    profile_begin(s);
-    hipLaunchKernelGGL(convtn_kernel, dim3((unsigned)(p.n_tiles * p.B)), dim3(256), 0, s, p);
-    profile_end(s, FV_KERNEL_CONVT, 2.0 * pp.B * (double)pp.T * kTnCin * kTnCout * 4,
-                4.0 * ((double)kTnCin * kTnCout * 4 + (double)pp.B * ((double)kTnCin * pp.T * (mb.add1 ? (mb.add2 ? 3 : 2) : 1) +
-                                                                      (double)kTnCout * Tout * (mb.y_act ? 2 : 1))));
+    {
+        ProfileScope prof(s, FV_KERNEL_CONVT, convt_work(pp.B, pp.T, Tout, kTnCin, kTnCout, 4, mb.add1 ? (mb.add2 ? 3 : 2) : 1, mb.y_act != nullptr));
+        hipLaunchKernelGGL(convtn_kernel, dim3((unsigned)(p.n_tiles * p.B)), dim3(256), 0, s, p);
+    }
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,5 @@
 // Host side of the one-launch MRF stage (mrfh_kernels.hpp): validation, blob offsets, window geometry, grid.
-#include "fv_internal.h"
+#include "launch_host.hpp"
 
 namespace fv {
 
@@ -14,6 +14,7 @@ static long long mrfw_max_blocks() {
 long long mrf_workspace_bytes(int C) { return C == 32 ? mrfw_max_blocks() * kMrfwHistBytes : 0; }
 
 int launch_mrfh(MrfParams p, int C, const int* dil, hipStream_t s) {
+    const char* const fam = "mrf stage";
     if (p.B <= 0 || p.T <= 0) return 0;
     if (!mrf_stage_shape(C, p.k, dil))
         return fail(FV_ERR_UNSUPPORTED, "mrf stage: C = %d, taps (%d, %d, %d), dilations (%d, %d, %d): built for 16 / 32 channels, taps "
@@ -26,12 +27,9 @@ int launch_mrfh(MrfParams p, int C, const int* dil, hipStream_t s) {
     if (p.y == p.x || p.y_act == p.x || (p.y_act && p.y_act == p.y) || p.fold_y == p.x)
         return fail(FV_ERR_INVALID_ARG, "mrf stage: an output tensor aliases the input (or y_act aliases y)");
     if ((reinterpret_cast<uintptr_t>(p.blob) & 15) != 0) return fail(FV_ERR_UNSUPPORTED, "mrf stage: the packed stage must be 16-byte aligned");
-    if ((double)C * p.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "mrf stage: one utterance's tensor (%d x %d floats) exceeds the 1 GiB buffer-descriptor "
-                    "range; split the utterance", C, p.T);
+    if (int rc = check_desc_range(fam, C, p.T)) return rc;
     if ((double)p.B * p.T >= 2147483647.0) return fail(FV_ERR_UNSUPPORTED, "mrf stage: B x T = %d x %d columns exceed 2^31", p.B, p.T);
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "mrf stage: activation slope outside [0, 1]");
+    if (int rc = check_slopes(fam, p.slope, p.act_slope)) return rc;
     unsigned off = 0;
     double flops = 0;
     for (int j = 0; j < 3; ++j)
@@ -50,9 +48,7 @@ int launch_mrfh(MrfParams p, int C, const int* dil, hipStream_t s) {
     if (adv < 64) return fail(FV_ERR_UNSUPPORTED, "mrf stage: a %d-column window leaves %d final columns", W, adv);
     // One block per CU (the weight slots, two images and the history are 147 KB of LDS); a share below ~a quarter window
     // is all run-in (a run's first tile starts `halo` columns early).
-    long long nblk = tuning().mrf_blocks > 0 ? tuning().mrf_blocks : device_cu_count();
-    const long long most = (p.total + 127) / 128;
-    if (nblk > most) nblk = most;
+    long long nblk = persistent_blocks((p.total + 127) / 128, 1, tuning().mrf_blocks);
     if (nblk < 1) nblk = 1;
     p.nblk = (int)nblk;
     if (C == 32) {
@@ -63,13 +59,11 @@ int launch_mrfh(MrfParams p, int C, const int* dil, hipStream_t s) {
         p.hist = nullptr;
     }
     p.prio = tuning().mrf_prio;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
+    p.trace = trace_buffer();
     double bytes = 4.0 * ((double)p.B * C * p.T * (fold ? 1.0 : (p.y_act ? 3.0 : 2.0)) + (fold ? (double)p.B * p.T : 0.0)) + off;
     if (fold) flops += 2.0 * p.B * (double)C * 7 * p.T;   // (the folded output conv: C -> 1 channels, 7 taps)
-    profile_begin(s);
-    const int rc = C == 32 ? launch_mrfw_geom(p, s) : shape == 1 ? launch_mrfh_geom<2, 16>(p, s) : launch_mrfh_geom<3, 12>(p, s);
-    profile_end(s, C == 32 ? FV_KERNEL_MRF32 : FV_KERNEL_MRF16, flops, bytes);
-    return rc;
+    ProfileScope prof(s, C == 32 ? FV_KERNEL_MRF32 : FV_KERNEL_MRF16, Work{flops, bytes});
+    return C == 32 ? launch_mrfw_geom(p, s) : shape == 1 ? launch_mrfh_geom<2, 16>(p, s) : launch_mrfh_geom<3, 12>(p, s);
 }
 
 }  // namespace fv

@@ -3,7 +3,7 @@
 // pair_inst_c32.hip (compiled in parallel); this file only sees declarations.
 #include <stdlib.h>
 
-#include "fv_internal.h"
+#include "launch_host.hpp"
 
 namespace fv {
 
@@ -20,18 +20,7 @@ int pair_row_stride(int n) {
     return r;
 }
 
-int num_cus() {
-    static int cus = 0;   // one device model per process: the CU count of the current device
-    if (!cus) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            cus = v;
-        else
-            cus = 256;
-    }
-    return cus;
-}
+const char* const fam = "resblock pair";
 
 }  // namespace
 
@@ -87,18 +76,15 @@ static int launch_pairs_split(PairParams p, int C, int dil, hipStream_t s) {
     if (p.fold_w && (C != 16 || p.n_members != 1 || !p.fold_y || p.m[0].y_act))
         return fail(FV_ERR_UNSUPPORTED, "resblock pair with a folded output conv: one 16-channel member, no activated twin");
     int w_bytes = 0, img_bytes = 0, mid_bytes = 0;
-    double flops = 0, bytes = 0;
     long long items = 0;
     for (int i = 0; i < p.n_members; ++i) {
         PairMember& mb = p.m[i];
-        if (mb.k != 11 && mb.k != 7 && mb.k != 3) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %d taps (3, 7 or 11)", mb.k);
-        if (!mb.x || !mb.w1 || !mb.w2 || (!mb.y && !p.fold_w)) return fail(FV_ERR_INVALID_ARG, "resblock pair: null tensor (member %d)", i);
-        if (mb.add2 && !mb.add1) return fail(FV_ERR_INVALID_ARG, "resblock pair: add2 without add1 (member %d)", i);
-        if ((reinterpret_cast<uintptr_t>(mb.x) | reinterpret_cast<uintptr_t>(mb.w1) | reinterpret_cast<uintptr_t>(mb.w2)) & 15)
-            return fail(FV_ERR_UNSUPPORTED, "resblock pair: x / packed weights must be 16-byte aligned");
+        if (int rc = check_taps(fam, mb.k)) return rc;
+        if (int rc = check_member(fam, mb, i, kNeedW2 | kAlignX | (p.fold_w ? 0 : kNeedY))) return rc;
         const PairHShape g = pairh_shape(C, mb.k, dil);
         const int tstride = p.fold_w ? g.NOUT - 6 : g.NOUT;      // folded 7-tap output conv: 3 samples of halo either side
         mb.n_tiles = (p.T + tstride - 1) / tstride;
+        mb.n_items = mb.n_tiles * p.B;
         // a tile costs its K steps (two convs, LDS-bandwidth bound) plus a part that does not depend on the taps
         // (loads, convert pass, epilogues, stores, barriers): measured per member alone (tools/pair_bench.py)
         // 0.8 us per step + 8 steps' worth at C = 16, 1.6 us per step + 6 steps' worth at C = 32 (240-column tiles)
@@ -108,40 +94,26 @@ static int launch_pairs_split(PairParams p, int C, int dil, hipStream_t s) {
         if (g.XIMG > img_bytes) img_bytes = g.XIMG;
         if (g.MIMG > mid_bytes) mid_bytes = g.MIMG;
         items += (long long)mb.n_tiles * p.B;
-        flops += 2.0 * 2.0 * p.B * (double)C * C * mb.k * p.T;
-        bytes += 4.0 * (2.0 * C * C * mb.k + (double)p.B * C * p.T * ((mb.y_act ? 3 : 2) + (mb.add1 ? 1 : 0) + (mb.add2 ? 1 : 0)));
-        if (p.fold_w) {                // + the 16 -> 1, 7-tap conv; its output instead of the pair's
-            flops += 2.0 * p.B * (double)C * 7 * p.T;
-            bytes += 4.0 * ((double)p.B * p.T - (double)p.B * C * p.T);
-        }
     }
-    size_t floats = 0;
-    p.x_off = 0;                       // [conv1 | conv2] packed weights of the member a block is working on
-    floats += (size_t)w_bytes / 4;
-    p.img_off = (int)floats;
-    floats += (size_t)img_bytes / 4;
-    p.mid_off = (int)floats;
-    floats += (size_t)mid_bytes / 4;
-    p.bias_off = (int)floats;
-    floats += 4 * (size_t)C + 16;      // [b1 | b2 | inverse row prescales of conv1 | conv2 | scratch of the low-range guard]
-    const size_t lds = floats * 4;
-    if (lds > (C == 16 ? 80 : 160) * 1024) return fail(FV_ERR_UNSUPPORTED, "resblock pair, split-f16: %zu bytes of LDS", lds);
+    Work work = pair_work(p, C);
+    if (p.fold_w) {                    // + the 16 -> 1, 7-tap conv; its output instead of the pair's
+        work.flops += 2.0 * p.B * (double)C * 7 * p.T;
+        work.bytes += 4.0 * ((double)p.B * p.T - (double)p.B * C * p.T);
+    }
+    LdsLayout lds;
+    p.x_off = lds.add((size_t)w_bytes / 4);        // [conv1 | conv2] packed weights of the member a block is working on
+    p.img_off = lds.add((size_t)img_bytes / 4);
+    p.mid_off = lds.add((size_t)mid_bytes / 4);
+    p.bias_off = lds.add(4 * (size_t)C + 16);      // [b1 | b2 | inverse row prescales of conv1 | conv2 | scratch of the low-range guard]
+    if (int rc = check_lds("resblock pair, split-f16", lds.bytes(), (C == 16 ? 80 : 160) * 1024)) return rc;
     // 15-16 waves per CU (4 per SIMD): two 8-wave blocks at C = 16, one 15-wave block at C = 32
-    long long nblk = tuning().pair_blocks > 0 ? tuning().pair_blocks : (C == 16 ? 2LL : 1LL) * num_cus();
-    if (nblk > items) nblk = items;
-    p.nblk = (int)nblk;
+    p.nblk = (int)persistent_blocks(items, C == 16 ? 2 : 1, tuning().pair_blocks);
     p.sched_on = 0;
-    {
-        long long n[3] = {0, 0, 0};
-        for (int i = 0; i < p.n_members; ++i) n[i] = (long long)p.m[i].n_tiles * p.B;
-        pair_cut_schedule(p, p.nblk, n);           // the blocks' shares as a table in the kernel arguments
-    }
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-    profile_begin(s);
-    const int rc = C == 16 ? launch_pairh_geom<1, FV_PAIRH16_NF, FV_PAIRH16_NG>(p, dil, lds, s) : launch_pairh_geom<2, 1, FV_PAIRH32_NG>(p, dil, lds, s);
-    profile_end(s, C == 16 ? FV_KERNEL_PAIRH16 : FV_KERNEL_PAIRH32, flops, bytes);
-    return rc;
+    cut_table(p, p.nblk);              // the blocks' shares as a table in the kernel arguments
+    set_debug(p);
+    ProfileScope prof(s, C == 16 ? FV_KERNEL_PAIRH16 : FV_KERNEL_PAIRH32, work);
+    return C == 16 ? launch_pairh_geom<1, FV_PAIRH16_NF, FV_PAIRH16_NG>(p, dil, lds.bytes(), s)
+                   : launch_pairh_geom<2, 1, FV_PAIRH32_NG>(p, dil, lds.bytes(), s);
 }
 
 int launch_pairs(PairParams p, int C, int dil, hipStream_t s) {
@@ -152,11 +124,8 @@ int launch_pairs(PairParams p, int C, int dil, hipStream_t s) {
     if (p.T % 4 != 0)
         return fail(FV_ERR_UNSUPPORTED, "resblock pair: T = %d is not a multiple of 4 (rows must be 16-byte aligned); "
                     "use the conv1d ops", p.T);
-    if ((double)C * p.T * 4.0 >= 1073741824.0)
-        return fail(FV_ERR_UNSUPPORTED, "resblock pair: one utterance's tensor (%d x %d floats) exceeds the 1 GiB "
-                    "buffer-descriptor range; split the utterance", C, p.T);
-    if (p.slope < 0.f || p.slope > 1.f || p.act_slope < 0.f || p.act_slope > 1.f)
-        return fail(FV_ERR_INVALID_ARG, "resblock pair: activation slope outside [0, 1]");
+    if (int rc = check_desc_range(fam, C, p.T)) return rc;
+    if (int rc = check_slopes(fam, p.slope, p.act_slope)) return rc;
     if (p.prec == FV_PAIR_SPLIT_F16) return launch_pairs_split(p, C, dil, s);
     if (p.prec != FV_PAIR_F32) return fail(FV_ERR_INVALID_ARG, "resblock pair: unknown arithmetic %d", p.prec);
     if (p.fold_w) return fail(FV_ERR_UNSUPPORTED, "resblock pair: a folded output conv exists with FV_PAIR_SPLIT_F16 only");
@@ -165,9 +134,7 @@ int launch_pairs(PairParams p, int C, int dil, hipStream_t s) {
             return fail(FV_ERR_UNSUPPORTED, "resblock pair: add1 / add2 exist with FV_PAIR_SPLIT_F16 only (fp32: fv_mrf_stage)");
     if (p.sum) {
         if (p.n_members != 3) return fail(FV_ERR_UNSUPPORTED, "mrf sum: needs the three members");
-        for (int i = 0; i < 3; ++i)          // sort by taps, largest first: the kernel's member order
-            for (int j = i + 1; j < 3; ++j)
-                if (p.m[j].k > p.m[i].k) { PairMember t = p.m[i]; p.m[i] = p.m[j]; p.m[j] = t; }
+        sort_members_by_taps(p);
         if (p.m[0].k != 11 || p.m[1].k != 7 || p.m[2].k != 3)
             return fail(FV_ERR_UNSUPPORTED, "mrf sum: needs the 11 / 7 / 3-tap trio (got %d, %d, %d)", p.m[0].k, p.m[1].k,
                         p.m[2].k);
@@ -175,17 +142,14 @@ int launch_pairs(PairParams p, int C, int dil, hipStream_t s) {
     } else if (p.out_div != 1.f || p.post != FV_POST_NONE) {
         return fail(FV_ERR_INVALID_ARG, "resblock pair: out_div / post only exist in sum mode");
     }
-    size_t floats = 0;
+    LdsLayout lds;
     int xs_floats = 0, mid_floats = 0, wmax = 0;
-    double flops = 0, bytes = 0;
     long long items = 0;
     for (int i = 0; i < p.n_members; ++i) {
         PairMember& mb = p.m[i];
-        if (mb.k != 11 && mb.k != 7 && mb.k != 3) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %d taps (3, 7 or 11)", mb.k);
-        if (!mb.x || !mb.w1 || !mb.w2 || (!p.sum && !mb.y) || (p.sum && i == 0 && !mb.y))
-            return fail(FV_ERR_INVALID_ARG, "resblock pair: null tensor (member %d)", i);
-        if ((reinterpret_cast<uintptr_t>(mb.x) | reinterpret_cast<uintptr_t>(mb.w1) | reinterpret_cast<uintptr_t>(mb.w2)) & 15)
-            return fail(FV_ERR_UNSUPPORTED, "resblock pair: x / packed weights must be 16-byte aligned");
+        if (int rc = check_taps(fam, mb.k)) return rc;
+        // (sum mode: member 0's y is THE output; add1 / add2 were refused above)
+        if (int rc = check_member(fam, mb, i, kNeedW2 | kAlignX | (!p.sum || i == 0 ? kNeedY : 0))) return rc;
         const PairShape g = pair_shape(C, mb.k, dil);
         const int nout = p.sum ? pair_shape(C, 11, dil).NOUT : g.NOUT;
         mb.n_tiles = (p.T + nout - 1) / nout;
@@ -193,9 +157,8 @@ int launch_pairs(PairParams p, int C, int dil, hipStream_t s) {
         // them (staging, activation pass, barriers, epilogue): measured 4.2k + 1.1k * taps cycles at C = 16,
         // 6k + 2.0k * taps at C = 32 (tools/pair_trace.py) -- in units of one tap's time
         mb.cost = mb.k + (tuning().pair_skel >= 0 ? tuning().pair_skel : (C == 16 ? 4 : 3));
-        if (p.sum) {
-            mb.w_off = (int)floats;
-            floats += 2 * (size_t)g.WF;
+        if (p.sum) {                   // all three members' weights stay in LDS, else the one a block is working on
+            mb.w_off = lds.add(2 * (size_t)g.WF);
         } else {
             mb.w_off = 0;
             if (2 * g.WF > wmax) wmax = 2 * g.WF;
@@ -203,43 +166,29 @@ int launch_pairs(PairParams p, int C, int dil, hipStream_t s) {
         if (g.NXI * 256 > xs_floats) xs_floats = g.NXI * 256;
         if (C * g.MS > mid_floats) mid_floats = C * g.MS;
         items += (long long)mb.n_tiles * p.B;
-        flops += 2.0 * 2.0 * p.B * (double)C * C * mb.k * p.T;
-        bytes += 4.0 * (2.0 * C * C * mb.k + (double)p.B * C * p.T * (p.sum ? 1 : (mb.y_act ? 3 : 2)));
     }
+    Work work = pair_work(p, C);
     if (p.sum) {
         p.n_out_sum = pair_shape(C, 11, dil).NOUT;
         items = (long long)p.m[0].n_tiles * p.B;
-        bytes += 4.0 * p.B * (double)C * p.T * (p.m[0].y_act ? 2 : 1);
+        work.bytes += 4.0 * p.B * (double)C * p.T * (p.m[0].y_act ? 2 : 1);
     } else {
-        floats = (size_t)wmax;
+        lds.add((size_t)wmax);
     }
-    p.x_off = (int)floats;
-    floats += (size_t)xs_floats;
-    p.mid_off = (int)floats;
-    floats += (size_t)mid_floats;
-    p.bias_off = (int)floats;
-    floats += (size_t)(p.sum ? 6 : 2) * C;
-
-    const size_t lds = floats * 4;
-    if (lds > 160 * 1024) return fail(FV_ERR_UNSUPPORTED, "resblock pair: %zu bytes of LDS", lds);
+    p.x_off = lds.add((size_t)xs_floats);
+    p.mid_off = lds.add((size_t)mid_floats);
+    p.bias_off = lds.add((size_t)(p.sum ? 6 : 2) * C);
+    if (int rc = check_lds(fam, lds.bytes())) return rc;
     const PairShape g0 = pair_shape(C, 11, dil);
-    int per_cu = (int)(160 * 1024 / lds);
+    int per_cu = (int)(160 * 1024 / lds.bytes());
     if (per_cu * g0.NW > 16) per_cu = 16 / g0.NW;      // <= 128 VGPRs: 4 waves per SIMD
     if (per_cu < 1) per_cu = 1;
-    long long nblk = tuning().pair_blocks > 0 ? tuning().pair_blocks : (long long)per_cu * num_cus();
-    if (nblk > items) nblk = items;
-    p.nblk = (int)nblk;
+    p.nblk = (int)persistent_blocks(items, per_cu, tuning().pair_blocks);
     p.sched_on = 0;
     p.guard = nullptr;                 // (exact fp32 products: no operand range to guard)
-    p.dbg = tuning().pair_dbg;
-    p.trace = reinterpret_cast<unsigned long long*>(tuning().trace_ptr);
-
-    profile_begin(s);
-    int rc;
-    if (C == 16) rc = launch_pair_geom<1, 2, 8>(p, dil, lds, s);
-    else rc = launch_pair_geom<2, 1, 8>(p, dil, lds, s);
-    profile_end(s, C == 16 ? FV_KERNEL_PAIR16 : FV_KERNEL_PAIR32, flops, bytes);
-    return rc;
+    set_debug(p);
+    ProfileScope prof(s, C == 16 ? FV_KERNEL_PAIR16 : FV_KERNEL_PAIR32, work);
+    return C == 16 ? launch_pair_geom<1, 2, 8>(p, dil, lds.bytes(), s) : launch_pair_geom<2, 1, 8>(p, dil, lds.bytes(), s);
 }
 
 }  // namespace fv

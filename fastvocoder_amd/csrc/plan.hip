@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "launch_host.hpp"
 
 using namespace fv;
 
@@ -469,7 +470,7 @@ int fv_plan_add_resblock_pair_ex(fv_plan_t* plan, int x_slot, int y_slot, int y_
         return fail(FV_ERR_INVALID_ARG, "plan_add_resblock_pair: unknown arithmetic %d", prec);
     if (prec == FV_PAIR_F32 && (add1_slot != FV_SLOT_NONE || add2_slot != FV_SLOT_NONE || out_div != 1.f || post != FV_POST_NONE))
         return fail(FV_ERR_UNSUPPORTED, "plan_add_resblock_pair: add1 / add2 / out_div / post exist with FV_PAIR_SPLIT_F16 only");
-    if (add2_slot != FV_SLOT_NONE && add1_slot == FV_SLOT_NONE) return fail(FV_ERR_INVALID_ARG, "plan_add_resblock_pair: add2 without add1");
+    if (int rc = check_adds("plan_add_resblock_pair", add1_slot != FV_SLOT_NONE, add2_slot != FV_SLOT_NONE)) return rc;
     if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {add1_slot, add2_slot})) return rc;
     Op o = {};
     o.type = OP_PAIR;
@@ -503,7 +504,7 @@ int fv_plan_add_conv1d_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_
                                  int pad_mode, float pre_slope, float out_div, int post, float act_slope) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: null");
     if (int rc = check_convh_args(1, C, &k, dil, pad_mode)) return rc;
-    if (add2_slot != FV_SLOT_NONE && add1_slot == FV_SLOT_NONE) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: add2 without add1");
+    if (int rc = check_adds("plan_add_conv1d_split_f16", add1_slot != FV_SLOT_NONE, add2_slot != FV_SLOT_NONE)) return rc;
     if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {res_slot, add1_slot, add2_slot})) return rc;
     if (y_slot == res_slot || y_slot == add1_slot || y_slot == add2_slot)
         return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: the output aliases an addend");

@@ -374,7 +374,7 @@ def test_conv1d_split_f16_reflection_rejects():
 def tuning():
     """fv_tuning_set for the duration of a test (process-wide switches of the launchers: restored afterwards)."""
     defaults = {"sched": 1, "sched_switch": 4, "convh_blocks": 0, "pair_blocks": 0, "pair128_unfused": 0, "convg_rows64": -1,
-                "convh_rows64": -1, "convt_rows64": -1, "convp_wide": 20, "convq_wide": 20, "convt_lean": 50, "convs_ringfree": -1, "convu_resident": 1, "convp_pp": 0}
+                "convh_rows64": -1, "convt_rows64": -1, "convp_wide": 20, "convq_wide": 20, "convt_lean": 50, "convs_ringfree": -1, "convu_resident": 1}
     yield _native.tuning_set
     for k, v in defaults.items():
         _native.tuning_set(k, v)
@@ -607,7 +607,8 @@ def test_pair_tile_forms_give_the_same_bits(tuning):
     dilation 1 / 3), on full and three-block grids (long runs of warm tiles), two utterances, every tap count, with the MRF sum:
     the same MFMA order per output, so identical bits -- and the bits of the two conv launches (convh_kernel) a fused pair
     replaces.  (Until round 4 this test also ran the LDS-ring forms convq_kernel / convp_kernel, which gave the same bits and
-    were removed in round 5.)"""
+    were removed in round 5.  Likewise it ran convq3_kernel / convq4_kernel -- the 64-channel pair as two wave groups one conv
+    phase apart, its "pp" / "pp2" arms: the same bits, 5-15 % slower -- until they were removed with Tuning::convp_pp.)"""
     rng = np.random.RandomState(123)
     ks = (11, 3, 7)
     # (the last four: shorter than a tile / than the halo, exactly one cold tile, one column into the first warm tile)
@@ -619,17 +620,11 @@ def test_pair_tile_forms_give_the_same_bits(tuning):
         b1s, b2s = [_t(m[2]) for m in ms], [_t(m[4]) for m in ms]
         refs = [_pair_ref(x, w1, b1, w2, b2, dil, 0.1) for x, w1, b1, w2, b2 in ms]
         outs = {}
-        # (wide: narrow tiles only / wide tiles wherever they exist; 64 channels, "pp": convq3_kernel -- two wave groups one
-        # conv phase apart, each on 64-column tiles of its own share -- on full, three- and one-block grids)
-        # ("pp2": convq4_kernel -- the same group pipeline as four-wave blocks of their own, two per CU)
-        for wide in (1 << 20, 0, "pp", "pp2"):
-            if wide in ("pp", "pp2") and C != 64:
-                continue
-            tuning("convp_pp", 1 if wide == "pp" else 2 if wide == "pp2" else 0)
-            if wide not in ("pp", "pp2"):
-                tuning("convp_wide", wide)
-                tuning("convq_wide", wide)
-            for blocks in (0, 3, 1) if wide in ("pp", "pp2") else (0, 3):
+        # (wide: narrow tiles only / wide tiles wherever they exist)
+        for wide in (1 << 20, 0):
+            tuning("convp_wide", wide)
+            tuning("convq_wide", wide)
+            for blocks in (0, 3):
                 tuning("convh_blocks", blocks)
                 ys = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
                 merged = torch.empty_like(xs[0])
@@ -639,7 +634,6 @@ def test_pair_tile_forms_give_the_same_bits(tuning):
         tuning("convh_blocks", 0)
         tuning("convp_wide", 20)
         tuning("convq_wide", 20)
-        tuning("convp_pp", 0)
         base = outs[(1 << 20, 0)]
         for y, ref in zip(base[:3], refs):
             assert _rel(y, ref) <= 4e-6
@@ -650,6 +644,44 @@ def test_pair_tile_forms_give_the_same_bits(tuning):
         two = _native.conv1d_split_f16(mids, h2, b2s, list(ks), 1, pre_slope=0.1, res=xs)
         for yf, yt in zip(base[:3], two):
             assert torch.equal(yf, yt)
+
+
+PAIR_REJECTIONS = [
+    # what is wrong with the call, the message at 16 / 32 channels (pair_launch.hip) and at 64 / 128 (convh_launch.hip); taps
+    # and dilation are refused by the entry itself.  Every one is refused before anything is launched.
+    ("taps", "resblock pair: 5 taps (3, 7 or 11)", "resblock pair: 5 taps (3, 7 or 11)"),
+    ("dilation", "resblock pair: dilation 2 (1, 3 or 5)", "resblock pair: dilation 2 (1, 3 or 5)"),
+    ("add2", "resblock pair: add2 without add1 (member 0)", "resblock pair: add2 without add1 (member 0)"),
+    ("slope", "resblock pair: activation slope outside [0, 1]", "resblock pair: activation slope outside [0, 1]"),
+    ("weights", "resblock pair: x / packed weights must be 16-byte aligned", "resblock pair: packed weights must be 16-byte aligned"),
+]
+
+
+def test_pair_launchers_share_their_rejections():
+    """The argument checks the launchers of the four channel counts share (csrc/launch_host.hpp), through the one entry
+    fv_resblock1_fused_ex with FV_PAIR_SPLIT_F16: the same bad call is refused with the same words whichever kernel family
+    it was on its way to -- and the entry still computes the pair afterwards."""
+    import re
+    rng = np.random.RandomState(2024)
+    for C in (16, 32, 64, 128):
+        x, w1, b1, w2, b2 = _member(rng, 1, C, 64, 3, True)
+        xs, b1s, b2s = [_t(x)], [_t(b1)], [_t(b2)]
+        h1, h2 = [_native.pack_pair(_t(w1), SPLIT)], [_native.pack_pair(_t(w2), SPLIT)]
+        shifted = torch.empty(h1[0].numel() + 1, dtype=torch.float32, device=_dev())[1:]      # a view 4 bytes into a larger buffer
+        shifted.copy_(h1[0])
+        other = torch.zeros_like(xs[0])
+        calls = {
+            "taps": lambda: _native.resblock1_fused(xs, h1, h2, b1s, b2s, [5], 1, 0.1, prec=SPLIT),
+            "dilation": lambda: _native.resblock1_fused(xs, h1, h2, b1s, b2s, [3], 2, 0.1, prec=SPLIT),
+            "add2": lambda: _native.resblock1_fused(xs, h1, h2, b1s, b2s, [3], 1, 0.1, prec=SPLIT, add2=[other]),
+            "slope": lambda: _native.resblock1_fused(xs, h1, h2, b1s, b2s, [3], 1, 1.5, prec=SPLIT),
+            "weights": lambda: _native.resblock1_fused(xs, [shifted], h2, b1s, b2s, [3], 1, 0.1, prec=SPLIT),
+        }
+        for what, narrow, wide in PAIR_REJECTIONS:
+            with pytest.raises(_native.NativeError, match=re.escape(narrow if C <= 32 else wide)):
+                calls[what]()
+        y, = _native.resblock1_fused(xs, h1, h2, b1s, b2s, [3], 1, 0.1, prec=SPLIT)
+        assert _rel(y, _pair_ref(x, w1, b1, w2, b2, 1, 0.1)) <= 4e-6, C
 
 
 def test_pair_results_do_not_depend_on_the_batch():

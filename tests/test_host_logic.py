@@ -558,3 +558,17 @@ def test_schedule_hook_refuses_sizes_whose_cost_sums_could_overflow():
                 _native.debug_pair_schedule(items, cost, nblk, mode=mode)
     on, starts = _native.debug_pair_schedule([2 ** 31 // 256 - 1], [65535], 256, mode=1)
     assert on == 2 and starts[0] == 0 and all(a <= b for a, b in zip(starts, starts[1:]))
+
+
+def test_tuning_keys_of_removed_kernels_are_unknown():
+    """fv_tuning_set knows the launchers' switches only: the key of the removed two-wave-group pair kernels (convp_pp) is
+    refused by name, a key that stays (convp_wide, at its default) is accepted.  Putting the removed switch back to "off",
+    the one state it has left, is still accepted: callers that reset every switch they know (the tuning fixture of
+    test_gpu_pairs.py did) keep working."""
+    lib = _native.lib()
+    for value in (1, 2, -1):
+        assert lib.fv_tuning_set(b"convp_pp", value) != 0
+        assert "unknown key" in lib.fv_last_error().decode()
+    assert lib.fv_tuning_set(b"convp_wide", 20) == 0
+    assert lib.fv_tuning_set(b"convp_pp", 0) == 0
+    assert lib.fv_tuning_set(b"no_such_key", 0) != 0
