@@ -362,6 +362,10 @@ def lib():
     L.fv_plan_check_range.argtypes = [vp, vp]
     L.fv_tuning_set.argtypes = [ctypes.c_char_p, i]
     L.fv_debug_pair_schedule.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), i, i, i, ctypes.POINTER(ctypes.c_uint)]
+    L.fv_debug_mrf_class_schedule.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint)]
+    L.fv_debug_mrf_stage_class_f16.argtypes = [vp, vp, vp, i, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp]
+    L.fv_mrf_stage_classes_f16.argtypes = [vp, vp, vp, vp, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp, vp]
+    L.fv_plan_add_mrf_stage_classes_f16.argtypes = [vp, i, i, i, vp, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64]
     L.fv_plan_set_group.argtypes = [vp, i]
     L.fv_plan_output_shape.argtypes = [vp, i, ctypes.POINTER(i), ctypes.POINTER(i64)]
     L.fv_plan_workspace_bytes.argtypes = [vp, i, i]
@@ -469,6 +473,23 @@ def debug_pair_schedule(n_items, cost, nblk, mode=0, three_members=False):
     if rc == 2:
         return 2, [int(table[i]) for i in range(nblk)]
     return 0, None
+
+
+def mrf_class_schedule(batch, t, nblk, force=False):
+    """Test and policy hook (fv_debug_mrf_class_schedule, host only): what the 32-channel MRF stage's launchers do with
+    ``batch`` utterances of ``t`` columns on at most ``nblk`` blocks.  Returns a dict: ``split`` (two block classes, or the
+    all-in-one form where that is not slower by the window arithmetic -- ``force``: the split whenever nblk >= 2 batch),
+    ``n_a`` / ``n_b`` blocks per class, ``makespan`` / ``makespan_one`` (hundreds of cycles), ``reach_a`` / ``reach_b``,
+    ``window``, ``cost_a`` / ``cost_b`` / ``cost_one`` and ``ranges``: block i (class A first) owns the global columns
+    [lo, hi) of the utterances concatenated."""
+    info = (ctypes.c_int64 * 12)()
+    table = (ctypes.c_uint * 512)()
+    check(lib().fv_debug_mrf_class_schedule(int(batch), int(t), int(nblk), 1 if force else 0, info, table))
+    keys = ("split", "n_a", "n_b", "makespan", "makespan_one", "reach_a", "reach_b", "window", "cost_a", "cost_b", "cost_one")
+    out = {k: int(info[i]) for i, k in enumerate(keys)}
+    out["split"] = bool(out["split"])
+    out["ranges"] = [(int(table[2 * i]), int(table[2 * i + 1])) for i in range(out["n_a"] + out["n_b"])]
+    return out
 
 
 def _flag_ptr(flag):
@@ -792,6 +813,35 @@ def mrf_stage_split_f16(x, packed, ks, dils=MRF_STAGE_DILATIONS, slope=0.1, out_
                                            B, C, T, karr, darr, float(slope), float(out_div), post, float(act_slope), None,
                                            None, None, *_work_args(work), _guard_ptr(guard), stream))
     return out
+
+
+def mrf_stage_classes_f16(x, packed, ks, dils=MRF_STAGE_DILATIONS, slope=0.1, guard=None, work=None):
+    """The 32-channel MRF stage as one launch of two block classes (fv_mrf_stage_classes_f16): returns
+    (r_0 + r_1, r_2), un-divided, r_j = ResBlock1_j(x); taps (3, 7, 11) in this order.  ``work``: the scratch
+    (mrf_stage_workspace; allocated here when None)."""
+    B, C, T = x.shape
+    karr, darr = (ctypes.c_int * 3)(*ks), (ctypes.c_int * 3)(*dils)
+    if work is None:
+        work = mrf_stage_workspace(C, x.device)
+    y_s, y_r2 = torch.empty_like(x), torch.empty_like(x)
+    with _on(x, packed, y_s, y_r2, work) as stream:
+        check(lib().fv_mrf_stage_classes_f16(_ptr(x, "x"), _ptr(packed, "packed"), _ptr(y_s, "y_s"), _ptr(y_r2, "y_r2"), B, C, T,
+                                             karr, darr, float(slope), *_work_args(work), _guard_ptr(guard), stream))
+    return y_s, y_r2
+
+
+def mrf_stage_one_class_f16(x, packed, ks, cls, dils=MRF_STAGE_DILATIONS, slope=0.1, work=None):
+    """Timing hook (fv_debug_mrf_stage_class_f16): mrf_stage_classes_f16's launch with the blocks of one class alone --
+    ``cls`` "a": returns r_2, "b": r_0 + r_1."""
+    B, C, T = x.shape
+    karr, darr = (ctypes.c_int * 3)(*ks), (ctypes.c_int * 3)(*dils)
+    if work is None:
+        work = mrf_stage_workspace(C, x.device)
+    y = torch.empty_like(x)
+    with _on(x, packed, y, work) as stream:
+        check(lib().fv_debug_mrf_stage_class_f16(_ptr(x, "x"), _ptr(packed, "packed"), _ptr(y, "y"), {"a": 1, "b": 2}[cls], B, C, T,
+                                                 karr, darr, float(slope), *_work_args(work), stream))
+    return y
 
 
 def mrf_stage(xs, w1s, w2s, b1s, b2s, ks, dil, slope, out_div=3.0, post=POST_NONE, act_slope=1.0, out=None,
@@ -2120,6 +2170,17 @@ class Plan:
         check(lib().fv_plan_add_mrf_stage_split_f16(self._h, x, y, y_act, _ptr(packed, "packed"), channels,
                                                     (ctypes.c_int * 3)(*ks), (ctypes.c_int * 3)(*dils), float(slope),
                                                     float(out_div), post, float(act_slope), *_work_args(work)))
+
+    def add_mrf_stage_classes(self, x, y_s, y_r2, packed, channels, ks, dils, slope):
+        """The 32-channel MRF stage as one launch of two block classes (fv_plan_add_mrf_stage_classes_f16): slot ``y_s``
+        receives r_0 + r_1, ``y_r2`` r_2; the op owns its scratch."""
+        self.keep(packed)
+        work = mrf_stage_workspace(channels, packed.device)
+        if work is not None:
+            self.keep(work)
+        check(lib().fv_plan_add_mrf_stage_classes_f16(self._h, x, y_s, y_r2, _ptr(packed, "packed"), channels,
+                                                      (ctypes.c_int * 3)(*ks), (ctypes.c_int * 3)(*dils), float(slope),
+                                                      *_work_args(work)))
 
     def set_pair_output_conv(self, w, bias, y, act_slope, post=POST_NONE):
         """Fold a 16 -> 1 channel, 7-tap conv into the resblock pair appended last (fv_plan_set_pair_output_conv):

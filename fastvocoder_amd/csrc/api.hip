@@ -273,6 +273,13 @@ MrfParams mrf_params(const Op& o, const float* x, float* y, float* y_act, float*
     return mp;
 }
 
+MrfSplitParams mrf_split_params(const Op& o, const float* x, float* y_s, float* y_r2, int B, int64_t T, int* guard) {
+    MrfSplitParams sp = {};
+    static_cast<MrfParams&>(sp) = mrf_params(o, x, y_s, nullptr, nullptr, B, T, guard);
+    sp.y2 = y_r2;
+    return sp;
+}
+
 // CausalConv1d keeps the first Tin outputs of a conv padded on both sides: only a pad of
 // at least (k-1)*dil - which makes that many outputs exist - is meaningful.
 int check_pad_mode(int pad_mode, int pad, int k, int dil) {
@@ -354,6 +361,7 @@ static const TuningEntry kTuningTable[] = {
     {"shape64", &Tuning::shape64},         {"krows", &Tuning::krows},            {"grid_cap", &Tuning::grid_cap},
     {"no_group", &Tuning::no_group},       {"mrf_blocks", &Tuning::mrf_blocks},  {"mrf_shape", &Tuning::mrf_shape},
     {"mrf_prio", &Tuning::mrf_prio},       {"convt_lean", &Tuning::convt_lean},
+    {"mrf_cost_a", &Tuning::mrf_cost_a},   {"mrf_cost_b", &Tuning::mrf_cost_b},  {"mrf_cost_one", &Tuning::mrf_cost_one},
     {"convs_ringfree", &Tuning::convs_ringfree}, {"convu_resident", &Tuning::convu_resident},
 };
 static void tuning_from_env() {
@@ -1193,6 +1201,46 @@ int fv_mrf_stage_split_f16(const float* x, const float* packed, float* y, float*
     o.work = workspace;
     o.work_bytes = workspace_bytes;
     return launch_mrfh(mrf_params(o, x, y, y_act, fold_y, B, T, guard), C, dil, (hipStream_t)stream);
+}
+
+int fv_mrf_stage_classes_f16(const float* x, const float* packed, float* y_s, float* y_r2, int B, int C, int T, const int* k,
+                             const int* dil, float slope, void* workspace, int64_t workspace_bytes, int* guard, void* stream) {
+    if (int rc = check_stage_args(C, k, dil, slope, 1.f, FV_POST_NONE)) return rc;
+    if (C != 32) return fail(FV_ERR_UNSUPPORTED, "mrf stage (two classes): C = %d (32)", C);
+    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "mrf stage (two classes): B=%d T=%d", B, T);
+    Op o = pair_op(OP_STAGE, C, dil[0], FV_PAD_ZERO, slope, 1.f, FV_POST_NONE, 1.f, FV_PAIR_SPLIT_F16);
+    o.wp = packed;
+    for (int j = 0; j < 3; ++j) o.pk[j] = k[j];
+    o.work = workspace;
+    o.work_bytes = workspace_bytes;
+    return launch_mrfw_split(mrf_split_params(o, x, y_s, y_r2, B, T, guard), dil, (hipStream_t)stream);
+}
+
+int fv_debug_mrf_stage_class_f16(const float* x, const float* packed, float* y, int cls, int B, int C, int T, const int* k,
+                                 const int* dil, float slope, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (cls != 1 && cls != 2) return fail(FV_ERR_INVALID_ARG, "debug_mrf_stage_class: class %d (1: A, 2: B)", cls);
+    if (int rc = check_stage_args(C, k, dil, slope, 1.f, FV_POST_NONE)) return rc;
+    if (C != 32) return fail(FV_ERR_UNSUPPORTED, "debug_mrf_stage_class: C = %d (32)", C);
+    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "debug_mrf_stage_class: B=%d T=%d", B, T);
+    Op o = pair_op(OP_STAGE, C, dil[0], FV_PAD_ZERO, slope, 1.f, FV_POST_NONE, 1.f, FV_PAIR_SPLIT_F16);
+    o.wp = packed;
+    for (int j = 0; j < 3; ++j) o.pk[j] = k[j];
+    o.work = workspace;
+    o.work_bytes = workspace_bytes;
+    return launch_mrfw_split(mrf_split_params(o, x, y, nullptr, B, T, nullptr), dil, (hipStream_t)stream, cls);
+}
+
+int fv_debug_mrf_class_schedule(int B, int T, int nblk, int force, int64_t* info, unsigned* table) {
+    if (!info || !table) return fail(FV_ERR_INVALID_ARG, "debug_mrf_class_schedule: null argument");
+    fv::MrfClassPlan pl;
+    if (!fv::mrf_class_plan(B, T, nblk, force != 0, pl))
+        return fail(FV_ERR_INVALID_ARG, "debug_mrf_class_schedule: B=%d T=%d on %d blocks (1 .. %d blocks, B x T < 2^31)", B, T, nblk, fv::kSchedBlocks);
+    const fv::Tuning& tn = fv::tuning();
+    const int64_t v[12] = {pl.split, pl.n_a, pl.n_b, pl.makespan, pl.makespan_one, pl.reach_a, pl.reach_b, 384,
+                           tn.mrf_cost_a, tn.mrf_cost_b, tn.mrf_cost_one, 0};
+    memcpy(info, v, sizeof(v));
+    memcpy(table, pl.range, sizeof(pl.range));
+    return 0;
 }
 
 }  // extern "C"

@@ -50,6 +50,7 @@ struct Op {
     int pk[3] = {0, 0, 0};
     int sdil[3] = {0, 0, 0};  // OP_STAGE: dilations of the three pair positions (pk: taps of the three ResBlocks; wp: the packed stage)
     void* work = nullptr;     // OP_STAGE, 32 channels: the launch's history slots (caller-owned)
+    bool classes = false;     // OP_STAGE: fv_plan_add_mrf_stage_classes_f16 (y: r_0 + r_1, y2: r_2)
     int64_t work_bytes = 0;
     int prec = 0;             // FV_PAIR_F32 / FV_PAIR_SPLIT_F16
     bool in_merge = false;    // fv_plan_set_input_merge (split-f16 transposed conv): the input is ((x + xb) + xc) / out_div
@@ -107,6 +108,8 @@ PairMember pair_member(const float* x, const float* w1, const float* w2, const f
                        const float* x2 = nullptr);
 // an OP_STAGE's launch: blob, taps, slopes, out_div, post, fold_w / fold_b and the history slots from the op
 MrfParams mrf_params(const Op& o, const float* x, float* y, float* y_act, float* fold_y, int B, int64_t T, int* guard);
+// ... in two block classes (Op::classes): y_s = r_0 + r_1, y_r2 = r_2
+MrfSplitParams mrf_split_params(const Op& o, const float* x, float* y_s, float* y_r2, int B, int64_t T, int* guard);
 // a launch of fused ResBlock pairs, by the kernel family of its channel count (mid: the members' scratch tensors, C >= 64)
 int launch_pair_family(const PairParams& pp, float* const* mid, int C, int dil, int prec, hipStream_t s);
 int check_pair_args(int n, int C, const int* k, int dil, int prec = FV_PAIR_F32);

@@ -3,7 +3,8 @@
 // split-f16 operands (pairh_kernels.hpp: v = h1 + h2 / 2048, three v_mfma_f32_16x16x32_f16 terms per product):
 //
 //     x   = lrelu( ((r0 + r1) + r2) / div, slope )           (r1, r2 optional: the MRF merge of the stage in front,
-//                                                              hifigan.py:99-103, formed here -- convh_kernels.hpp merge_window)
+//                                                              hifigan.py:99-103, formed here -- convh_kernels.hpp merge_window;
+//                                                              r1 alone: (s + r2) / div behind the two-class stage, s = r0 + r1)
 //     y[co][2 u + ph - 1] = bias[co] + sum_ci  w[ci][co][2 + ph] x[ci][u - 1]  +  w[ci][co][ph] x[ci][u]
 //
 // The layer is 30 MB of traffic and 0.5 GFLOP: HBM-bound, and at batch 1 latency-bound.  The general split-f16 transposed conv
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- window: task = (row, block of 8 channels); 1040 tasks on 256 threads: four full rounds + 16 left over ----
     constexpr int TASKS = kTnRows * (kTnCin / 8), NR = (TASKS + 255) / 256;
     float v[NR][8], a1[NR][8], a2[NR][8];
-    const bool merge = p.add1 != nullptr;
+    const bool merge = p.add1 != nullptr, merge3 = p.add2 != nullptr;   // two tensors: (x + add1) / div, e.g. (r_0 + r_1) + r_2
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
         const int idx = tid + q * 256;
@@ -62,8 +63,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (merge) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) a1[q][j] = buffer_load1s(r1, voff, (unsigned)j * t4);
+            if (merge3) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) a2[q][j] = buffer_load1s(r2, voff, (unsigned)j * t4);
+                for (int j = 0; j < 8; ++j) a2[q][j] = buffer_load1s(r2, voff, (unsigned)j * t4);
+            }
         }
     }
     pair_wait_vm0();
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int j = 0; j < 4; ++j) {
                 f32x2 raw = {v[q][2 * j], v[q][2 * j + 1]};
                 if (merge) {
-                    raw = (raw + f32x2{a1[q][2 * j], a1[q][2 * j + 1]}) + f32x2{a2[q][2 * j], a2[q][2 * j + 1]};
+                    raw = raw + f32x2{a1[q][2 * j], a1[q][2 * j + 1]};
+                    if (merge3) raw = raw + f32x2{a2[q][2 * j], a2[q][2 * j + 1]};
                     if (p.out_div != 1.f) {
                         raw.x = rcp != 0.f ? div_exact(raw.x, p.out_div, rcp) : raw.x / p.out_div;
                         raw.y = rcp != 0.f ? div_exact(raw.y, p.out_div, rcp) : raw.y / p.out_div;

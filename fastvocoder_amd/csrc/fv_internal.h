@@ -170,6 +170,13 @@ struct Tuning {
     int pair_blocks = 0;     // > 0: ... of the pair launches
     int mrf_blocks = 0;      // > 0: ... of the one-launch MRF stage (mrfh_kernel)
     int mrf_shape = 0;       // one-launch MRF stage: 0 -- 12 waves x 3 fragments (576-column windows), 1 -- 16 waves x 2 (512)
+    // 32-channel stage in two block classes (mrf_class_plan): cost of a class-A window (the 11-tap ResBlock), of a class-B window
+    // (the 3- and 7-tap ResBlocks) and of an all-in-one window, in hundreds of cycles at the sustained clock.  Measured
+    // (tools/stage32_bench.py, either class's blocks alone, 2 against 3 and 11 / 12 windows per block): 27.7 / 31.3 / 70.5 us a
+    // window; splitting the all-in-one window's 149 k cycles by taps, pairs and pieces had given 706 / 784.
+    int mrf_cost_a = 585;
+    int mrf_cost_b = 661;
+    int mrf_cost_one = 1490;
     int mrf_prio = 1;        // ... s_setprio inside the K loops (0: none; 1: level 1; 2 / 3: later waves higher -- mrfh_kernels.hpp)
     int sum3_min = 800;      // fewest tiles for which the three last convs of an MRF stage run as ONE fp32 launch
     int lds_budget = 39;     // fp32 conv kernels: KiB of LDS per block
@@ -407,6 +414,33 @@ int launch_mrfh_geom(const MrfParams& p, hipStream_t s);
 constexpr int kMrfwHistBytes = 9 * 30 * 128;
 long long mrf_workspace_bytes(int C);
 int launch_mrfw_geom(const MrfParams& p, hipStream_t s);
+
+// ---- the 32-channel stage as ONE launch of two block classes (mrfw_kernels.hpp, SPLIT) --------------------------------------
+// Class A blocks run the last (11-tap) ResBlock alone and store r_2 in y2; class B blocks run ResBlocks 0 and 1 and store
+// r_0 + r_1 in y: the three ResBlocks are independent until the sum, a class's windows overlap by its OWN reach (60 / 36
+// columns) and cost roughly half a whole window each.  Blocks [0, n_a) are class A, [n_a, nblk) class B; block i owns the
+// global columns [range[2 i], range[2 i + 1]) (utterances concatenated), inside ONE utterance.  The table is part of the
+// kernel arguments, as PairParams::sched is: no device table, no copy, legal under stream capture.
+struct MrfSplitParams : MrfParams {   // halo: class A's; y: r_0 + r_1; out_div / post / act_slope / fold_*: unused
+    float* y2;               // [B, 32, T] r_2
+    int n_a;
+    int halo_b;              // columns a class-B run's first window starts early
+    unsigned range[2 * kSchedBlocks];
+};
+// What the launcher does with B utterances of T columns on at most nblk blocks (mrf_class_plan).  Costs: Tuning's.
+struct MrfClassPlan {
+    int split;               // 1: two classes; 0: the all-in-one form is not slower by the window arithmetic, or nblk < 2 B
+    int n_a, n_b;            // blocks per class (split = 0: n_a = 0, n_b = the all-in-one launch's blocks)
+    long long makespan;      // the longest block's windows x window cost, of the form chosen
+    long long makespan_one;  // ... of the all-in-one form
+    int reach_a, reach_b;    // a class's one-sided reach (split = 0: reach_b = the stage's)
+    unsigned range[2 * kSchedBlocks];
+};
+// false: the shape is outside the table (nblk > kSchedBlocks, B x T >= 2^31).  force: split whenever nblk >= 2 B.
+bool mrf_class_plan(int B, int T, int nblk, bool force, MrfClassPlan& out);
+// one_class (fv_debug_mrf_stage_class_f16 only): 1 / 2 -- the blocks of class A / class B alone, whose sum goes to p.y; p.y2 unused
+int launch_mrfw_split(MrfSplitParams p, const int* dil, hipStream_t stream, int one_class = 0);
+int launch_mrfw_split_geom(const MrfSplitParams& p, hipStream_t s);
 
 // Shared between the host launcher (conv_mfma.hip) and the kernels (conv_kernels.hpp):
 #ifndef FV_RING

@@ -13,4 +13,14 @@ int launch_mrfw_geom(const MrfParams& p, hipStream_t s) {
     return 0;
 }
 
+// ... in two block classes: the same tile, one block per table entry
+int launch_mrfw_split_geom(const MrfSplitParams& p, hipStream_t s) {
+    typedef MrfwTile<3, 8> TL;
+    auto kern = mrfw_kernel<3, 8, 1, 3, 5, false, true>;
+    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kern), TL::LDS)) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(TL::NT), TL::LDS, s, p);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace fv

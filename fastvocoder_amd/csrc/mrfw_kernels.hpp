@@ -20,7 +20,16 @@
 //     saves nothing -- at batch 1 the history is never touched.
 // Arithmetic: pairh_mma's sums in pairh_mma's order per accumulator, split_mid4 / combine4 / div_exact epilogues: bit-identical
 // to the stage as four launches of fused pairs (tests/test_gpu_stage.py).
+//
+// SPLIT (MrfSplitParams, launch_mrfw_split): the three ResBlocks of a window are independent until the sum, and a block whose
+// share is 1.45 windows of work runs two whole windows.  So the launch's blocks come in two CLASSES -- A runs the 11-tap
+// ResBlock alone (reach 60: 264 final columns in a run's first window, 324 in the others), B the 3- and 7-tap ones (reach 36:
+// 312 / 348) -- each on the column range a host table names (inside one utterance), each cycling through its own class's
+// weight pieces and history slots.  A class stores its un-divided sum (r_2; r_0 + r_1) and the upsampler behind the stage
+// forms ((r_0 + r_1) + r_2) / 3 from two tensors.  The K loops, epilogues and guards are the same code
+// (tests/test_gpu_stage_classes.py: bit-identical to the pair launches).
 #pragma once
+#include <type_traits>
 #include "mrfh_kernels.hpp"
 
 namespace fv {
@@ -316,16 +325,18 @@ __device__ __forceinline__ void mrfw_pair(const MrfParams& p, const MrfwLane<TL>
 }
 
 // ---- one ResBlock: three pairs on xr (= x0 on entry).  The pair that runs after the block: conv1 reach pnext, blob offset
-// next_off, piece 0 of next_kb KB.  zero_after: what MrfwWhen::zero_next is for the block's last pair.
+// next_off, piece 0 of next_kb KB.  zero_after: what MrfwWhen::zero_next is for the block's last pair.  [j_first, j_last]: the
+// ResBlocks the thread block cycles through (SPLIT: its class's).
 template <class TL, int KT, int D0, int D1, int D2>
 __device__ __forceinline__ void mrfw_block_run(const MrfParams& p, const MrfwLane<TL>& L, float* wbuf, int& par, int j, int pnext,
                                                float (&xr)[2][TL::NF][4], const float (&x0)[2][TL::NF][4], bool write_next,
                                                MrfwWhen wh, bool zero_after, LowGuard& low, __amdgpu_buffer_rsrc_t rb,
-                                               __amdgpu_buffer_rsrc_t rh, unsigned next_off, int next_kb, int tile_no) {
+                                               __amdgpu_buffer_rsrc_t rh, unsigned next_off, int next_kb, int tile_no,
+                                               int j_first = 0, int j_last = 2) {
     constexpr int KB0 = 4 * mrfw_piece_taps(KT, 0);
     const int q0 = 3 * j;
     const float* const bl = reinterpret_cast<const float*>(L.sm + TL::OFF_B) + q0 * (TL::TAIL / 4);
-    const int h0 = q0 * TL::HSLOT, hn = (j == 2 ? 0 : q0 + 3) * TL::HSLOT;
+    const int h0 = q0 * TL::HSLOT, hn = (j == j_last ? 3 * j_first : q0 + 3) * TL::HSLOT;
     const unsigned o0 = p.blk_off[q0], o1 = p.blk_off[q0 + 1], o2 = p.blk_off[q0 + 2];
     mrfw_pair<TL, KT, D0, 0>(p, L, wbuf, par, bl, xr, x0, true, wh, h0, h0 + TL::HSLOT, (KT - 1) * D1 / 2, low, rb, rh, o0, o1, KB0,
                              tile_no, q0);
@@ -336,8 +347,14 @@ __device__ __forceinline__ void mrfw_block_run(const MrfParams& p, const MrfwLan
                              rh, o2, next_off, next_kb, tile_no, q0 + 2);
 }
 
-template <int NF, int NG, int D0, int D1, int D2, bool FOLD>
-__global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3) / 4, (NG + 3) / 4))) void mrfw_kernel(MrfParams p) {
+// SPLIT (MrfSplitParams, no FOLD): the block runs the ResBlocks [j_lo, j_hi) of its class only -- halo, vcols and adv from that
+// class's reach, the weight pieces, history slots and the piece asked for one ahead cycling through the class's pairs -- over
+// the column range its table entry names, and stores the class's un-divided sum.  Everything SPLIT adds is behind
+// `if constexpr`: the kernels without it are, instruction for instruction, what they were before there were classes.
+template <int NF, int NG, int D0, int D1, int D2, bool FOLD, bool SPLIT = false>
+__global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3) / 4, (NG + 3) / 4)))
+void mrfw_kernel(std::conditional_t<SPLIT, MrfSplitParams, MrfParams> p) {
+    static_assert(!(SPLIT && FOLD), "a class stores its sum: nothing to fold an output conv into");
     typedef MrfwTile<NF, NG> TL;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* const sm = reinterpret_cast<char*>(smem);
@@ -360,7 +377,15 @@ __global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3
     char* const mimg0 = sm + TL::OFF_M;
     float* const wbuf = smem + TL::OFF_W / 4;
     float* const scratch = smem + TL::OFF_S / 4;
-    const int T = p.T, halo = p.halo, ol = p.ol;
+    // SPLIT: blocks [0, n_a) are class A (the last ResBlock alone), the others class B (ResBlocks 0 and 1)
+    int j_lo = 0, j_hi = 3, halo_c = p.halo;
+    if constexpr (SPLIT) {
+        const bool class_a = (int)blockIdx.x < p.n_a;
+        j_lo = class_a ? 2 : 0;
+        j_hi = class_a ? 3 : 2;
+        halo_c = class_a ? p.halo : p.halo_b;
+    }
+    const int T = p.T, halo = halo_c, ol = p.ol;
     const int vcols = TL::W - halo;                      // columns of a window that are final for the pairs (given history)
     const int adv = vcols - 2 * ol;                      // window advance inside a run (FOLD: the output conv's reach either side)
     const int k0 = p.k[0], k1 = p.k[1], k2 = p.k[2];
@@ -369,8 +394,15 @@ __global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3
     const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.blob, p.blob_bytes);
     const __amdgpu_buffer_rsrc_t rh = make_rsrc(p.hist + (size_t)blockIdx.x * (9 * TL::HSLOT / 4), p.hist ? 9 * TL::HSLOT : 0);
 
-    const int share = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const long long g_lo = p.total * share / p.nblk, g_hi = p.total * (share + 1) / p.nblk;
+    long long g_lo, g_hi;
+    if constexpr (SPLIT) {
+        g_lo = p.range[2 * blockIdx.x];
+        g_hi = p.range[2 * blockIdx.x + 1];
+    } else {
+        const int share = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+        g_lo = p.total * share / p.nblk;
+        g_hi = p.total * (share + 1) / p.nblk;
+    }
     if (g_lo >= g_hi) return;
     MrfIter it;
     mrf_first(it, g_lo, g_hi, T, halo, ol, vcols);
@@ -378,6 +410,14 @@ __global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3
     const unsigned t4 = (unsigned)T * 4u, ubytes = (unsigned)TL::C * (unsigned)T * 4u;
     const size_t ustride = (size_t)TL::C * (size_t)T;
     float x0[2][NF][4], xr[2][NF][4], sum[2][NF][4];
+    if constexpr (SPLIT) {                               // (class A never forms a sum: keep the select below off undefined registers)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sum[h][f][i] = 0.f;
+    }
     auto load_x0 = [&](const MrfIter& at) {
         const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + at.b * ustride, ubytes);
 #pragma unroll
@@ -411,7 +451,12 @@ __global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3
         }
     }
     load_x0(it);
-    mrfw_dma<NG>(rb, wbuf, off0, 4 * (k0 < 4 ? k0 : 4), L.wave, L.lane);
+    if constexpr (SPLIT) {
+        const int kf = j_lo == 0 ? k0 : k2;
+        mrfw_dma<NG>(rb, wbuf, j_lo == 0 ? off0 : off6, 4 * (kf < 4 ? kf : 4), L.wave, L.lane);
+    } else {
+        mrfw_dma<NG>(rb, wbuf, off0, 4 * (k0 < 4 ? k0 : 4), L.wave, L.lane);
+    }
     for (int idx = L.tid; idx < 2 * 8 * 2 * TL::FM * 4; idx += TL::NT) {
         // (image, part, front / back, row, dword)
         const int dw = idx & 3, row = (idx >> 2) % TL::FM, fb = (idx >> 2) / TL::FM % 2, part = (idx >> 2) / (2 * TL::FM) % 8,
@@ -455,24 +500,30 @@ __global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3
         wh.save = more && !it.cold;
         wh.zero_mid = wh.zero_next = cur.cold;
 #pragma unroll 1
-        for (int j = 0; j < 3; ++j) {
-            const int kj = j == 0 ? k0 : j == 1 ? k1 : k2, kn = j == 0 ? k1 : j == 1 ? k2 : k0;
-            const unsigned offn = j == 0 ? off3 : j == 1 ? off6 : off0;
-            const int kbn = (j < 2 || more) ? 4 * (kn < 4 ? kn : 4) : 0;
+        for (int j = SPLIT ? j_lo : 0; j < (SPLIT ? j_hi : 3); ++j) {
+            // the class's last ResBlock / one in front of it; (SPLIT) the ResBlock that runs next
+            auto last_j = [&] { return SPLIT ? j == j_hi - 1 : j == 2; };
+            auto inner_j = [&] { return SPLIT ? j < j_hi - 1 : j < 2; };
+            const int jn = SPLIT ? (j == j_hi - 1 ? j_lo : j + 1) : 0;
+            const int kj = j == 0 ? k0 : j == 1 ? k1 : k2;
+            const int kn = SPLIT ? (jn == 0 ? k0 : jn == 1 ? k1 : k2) : (j == 0 ? k1 : j == 1 ? k2 : k0);
+            const unsigned offn = SPLIT ? (jn == 0 ? off0 : jn == 1 ? off3 : off6) : (j == 0 ? off3 : j == 1 ? off6 : off0);
+            const int kbn = (inner_j() || more) ? 4 * (kn < 4 ? kn : 4) : 0;
             const int pnext = (kn - 1) * D0 / 2;
-            const bool zero_after = j == 2 ? !wh.save : cur.cold;
+            const bool zero_after = last_j() ? !wh.save : cur.cold;
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int f = 0; f < NF; ++f)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) xr[h][f][i] = x0[h][f][i];
-            if (j == 2 && more) load_x0(it);
-            const bool wn = j < 2 || more;
-            if (kj == 11) mrfw_block_run<TL, 11, D0, D1, D2>(p, L, wbuf, par, j, pnext, xr, x0, wn, wh, zero_after, low, rb, rh, offn, kbn, tile_no);
-            else if (kj == 7) mrfw_block_run<TL, 7, D0, D1, D2>(p, L, wbuf, par, j, pnext, xr, x0, wn, wh, zero_after, low, rb, rh, offn, kbn, tile_no);
-            else mrfw_block_run<TL, 3, D0, D1, D2>(p, L, wbuf, par, j, pnext, xr, x0, wn, wh, zero_after, low, rb, rh, offn, kbn, tile_no);
-            if (j < 2) {
+            if (last_j() && more) load_x0(it);
+            const bool wn = inner_j() || more;
+            const int jf = SPLIT ? j_lo : 0, jl = SPLIT ? j_hi - 1 : 2;
+            if (kj == 11) mrfw_block_run<TL, 11, D0, D1, D2>(p, L, wbuf, par, j, pnext, xr, x0, wn, wh, zero_after, low, rb, rh, offn, kbn, tile_no, jf, jl);
+            else if (kj == 7) mrfw_block_run<TL, 7, D0, D1, D2>(p, L, wbuf, par, j, pnext, xr, x0, wn, wh, zero_after, low, rb, rh, offn, kbn, tile_no, jf, jl);
+            else mrfw_block_run<TL, 3, D0, D1, D2>(p, L, wbuf, par, j, pnext, xr, x0, wn, wh, zero_after, low, rb, rh, offn, kbn, tile_no, jf, jl);
+            if (inner_j()) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -483,7 +534,26 @@ __global__ __launch_bounds__(64 * NG) __attribute__((amdgpu_waves_per_eu((NG + 3
         }
         // ---- ((r0 + r1) + r2) / 3 and the stores (behind the tile's last barrier: they drain under the next tile) ----
         if (tile_no == 0) mrf_stamp(p, NG, L.wave, L.lane, 2, 2);
-        if constexpr (FOLD) {
+        if constexpr (SPLIT) {
+            // the class's sum as it stands in the D fragments -- r_0 + r_1 (class B: y) or r_2 (class A: y2); the upsampler
+            // behind the stage forms ((r_0 + r_1) + r_2) / 3.  The range guard of the store path below.
+            const bool two = j_hi - j_lo > 1;
+            const __amdgpu_buffer_rsrc_t ry = make_rsrc((j_lo == 0 ? p.y : p.y2) + cur.b * ustride, ubytes);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    float out[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) out[i] = two ? sum[h][f][i] + xr[h][f][i] : xr[h][f][i];
+                    const int t = cur.tw + L.colw + f * 16;
+                    const bool ok = t >= cur.lo && t < cur.hi;
+                    range_note4(bad, out[0], out[1], out[2], out[3], ok);
+                    const unsigned voff = ok ? (unsigned)((L.row0 + 16 * h) * T + t) * 4u : kOutOfRange;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) buffer_store1s(ry, voff, (unsigned)i * t4, out[i]);
+                }
+        } else if constexpr (FOLD) {
             // mrfh_kernel's fold at 32 channels.  The activated tile -> LDS over the intermediate image (free since the last
             // barrier), zero outside [0, T), as [column][32 channels]: the four channels of a D fragment are ONE 16-byte entry
             // (entry e = channels 4 e ...: e = 4 h + g), a column's eight entries rotated by column / 2 -- sixteen consecutive

@@ -449,6 +449,23 @@ int fv_plan_add_mrf_stage_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int
     return 0;
 }
 
+int fv_plan_add_mrf_stage_classes_f16(fv_plan_t* plan, int x_slot, int ys_slot, int yr2_slot, const float* packed, int C,
+                                      const int* k, const int* dil, float slope, void* workspace, int64_t workspace_bytes) {
+    if (C != 32 || yr2_slot == FV_SLOT_NONE || yr2_slot == ys_slot)
+        return fail(FV_ERR_UNSUPPORTED, "plan_add_mrf_stage_classes: 32 channels and two distinct output slots");
+    // the op is an OP_STAGE whose second output slot (Op::y2: elsewhere the activated twin) holds r_2 -- the all-in-one entry's
+    // checks of slots, shape and workspace apply as they are, with yr2_slot in its y_act_slot argument; Op::classes tells run_stage
+    if (int rc = fv_plan_add_mrf_stage_split_f16(plan, x_slot, ys_slot, yr2_slot, packed, C, k, dil, slope, 1.f, FV_POST_NONE, 1.f,
+                                                 workspace, workspace_bytes))
+        return rc;
+    if (k[0] != 3 || k[1] != 7 || k[2] != 11) {
+        plan->ops.pop_back();
+        return fail(FV_ERR_UNSUPPORTED, "plan_add_mrf_stage_classes: taps (3, 7, 11) in this order");
+    }
+    plan->ops.back().classes = true;
+    return 0;
+}
+
 int fv_plan_add_resblock_pair(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, const float* packed1,
                               const float* packed2, const float* bias1, const float* bias2, int C, int k, int dil,
                               float slope, float act_slope) {
@@ -703,6 +720,8 @@ static int run_convh_group(const Run& r, size_t n, size_t m) {
 // a whole 16- / 32-channel MRF stage: one launch (with a folded output conv, y is THAT conv's output)
 static int run_stage(const Run& r, const Op& o) {
     float* const y = r.base[o.y];
+    if (o.classes)
+        return launch_mrfw_split(mrf_split_params(o, r.base[o.x], y, r.at(o.y2), r.B, r.T(o), r.guard()), o.sdil, r.s);
     return launch_mrfh(mrf_params(o, r.base[o.x], o.fold_w ? nullptr : y, o.fold_w ? nullptr : r.at(o.y2), o.fold_w ? y : nullptr,
                                   r.B, r.T(o), r.guard()),
                        o.Cin, o.sdil, r.s);

@@ -318,12 +318,22 @@ class PlanBuilder:
                 and all([c.dilation[0] for c in b.convs1] == dils for b in blocks)
                 and all(self.pair_fusable(c1, c2, _native.PAIR_SPLIT_F16) for b in blocks for c1, c2 in zip(b.convs1, b.convs2)))
 
-    def mrf_stage(self, blocks, src, dst, slope, out_div, fold=None):
+    def mrf_stage_classes_supported(self, blocks):
+        """Can these three ResBlock1s run as one launch of two block classes (fv_mrf_stage_classes_f16)?  What
+        mrf_stage_supported asks, at 32 channels, with 3, 7 and 11 taps in this order (r_0 + r_1 is the reference's first sum)."""
+        return (self.mrf_stage_supported(blocks) and blocks[0].channels == 32
+                and [b.convs1[0].kernel_size[0] for b in blocks] == [3, 7, 11])
+
+    def mrf_stage(self, blocks, src, dst, slope, out_div, fold=None, classes_r2=SLOT_NONE):
         """dst = ((r0 + r1) + r2) / out_div, r_j = blocks[j](src): a whole MRF stage (hifigan.py:97-103) as ONE op.
         ``fold`` = (out_conv, slope, post): the stage's result is not stored; dst = post(out_conv(lrelu(result, slope))),
-        a [B, 1, T] tensor (pair_fold_supported)."""
+        a [B, 1, T] tensor (pair_fold_supported).  ``classes_r2`` (a slot; mrf_stage_classes_supported): the launch's blocks
+        split into two classes -- dst = r0 + r1 and classes_r2 = r2, un-divided, for a consumer that merges them
+        (conv_transpose(merge=(classes_r2, SLOT_NONE, out_div)))."""
         if not self.mrf_stage_supported(blocks):
             raise _native.NativeError("mrf stage: shape not built into the one-launch kernel")
+        if classes_r2 != SLOT_NONE and (fold is not None or not self.mrf_stage_classes_supported(blocks)):
+            raise _native.NativeError("mrf stage: two block classes exist at 32 channels, taps (3, 7, 11), without a folded conv")
         ks = [b.convs1[0].kernel_size[0] for b in blocks]
         dils = [c.dilation[0] for c in blocks[0].convs1]
         c1s = [c for b in blocks for c in b.convs1]
@@ -339,6 +349,8 @@ class PlanBuilder:
                 raise _native.NativeError("mrf stage: this output conv cannot be folded into the stage")
             op.update(fold_w=effective_weight(out_conv).detach().float().reshape(blocks[0].channels, 7).contiguous(),
                       fold_b=self._bias(out_conv), fold_post=fpost, act_slope=float(fslope))
+        if classes_r2 != SLOT_NONE:
+            op.update(out_div=1.0, y2=classes_r2, tmps=[classes_r2])   # (tmps: a slot the op writes, for _hoist_activations)
         self.ops.append(op)
 
     def conv_split_supported(self, conv, pad, pad_mode=PAD_ZERO):
@@ -417,15 +429,21 @@ class PlanBuilder:
         """Can this upsampler form its own input from the three ResBlock results of the stage in front of it
         (``conv_transpose(..., merge=...)``)?  The split-f16 transposed-conv kernel can (csrc/convh_kernels.hpp
         merge_window); the fp32 polyphase kernel and UpsampleLayer cannot."""
+        return self.conv_transpose_merges(convt, self.precision)
+
+    @classmethod
+    def conv_transpose_merges(cls, convt, precision):
+        """conv_transpose_takes_merge under the policy ``precision``, for callers without a builder (the generators' per-call
+        choice of a stage's form)."""
         if not isinstance(convt, torch.nn.ConvTranspose1d) or convt.groups != 1 or convt.dilation[0] != 1:
             return False
         k, s = convt.kernel_size[0], convt.stride[0]
         # (up to 128 input channels: with 256 / 512 the merging kernel -- 64-row tiles only -- converts every chunk's window once
         # per 64 rows where the 128-row kernel converts it once per 128: HiFi-GAN large, 64 utterances, 118.7 -> 121.8 ms
         # with the merge in its 256-channel upsampler [measured, tools/bench_configs.py --no-merge])
-        return ((self.SPLIT_CONVT_MIN_CIN <= convt.in_channels <= 128
+        return ((cls.SPLIT_CONVT_MIN_CIN <= convt.in_channels <= 128
                  or _native.conv_transpose_small(convt.in_channels, convt.out_channels, k, s))
-                and self.pair_precision(convt.in_channels) == _native.PAIR_SPLIT_F16
+                and pair_precision(precision, convt.in_channels) == _native.PAIR_SPLIT_F16
                 and _native.conv_transpose_split_supported(convt.in_channels, convt.out_channels, k, s, convt.padding[0],
                                                            convt.output_padding[0]))
 
@@ -577,7 +595,7 @@ class PlanBuilder:
         ceil(k/stride)+1 taps)."""
         need = {}
         for op in reversed(self.ops):
-            h_out = max(need.pop(op["y"], 0), need.pop(op.get("y_act", SLOT_NONE), 0))
+            h_out = max(need.pop(op["y"], 0), need.pop(op.get("y_act", SLOT_NONE), 0), need.pop(op.get("y2", SLOT_NONE), 0))
             if op["kind"] == "conv":
                 reach = op["dil"] * (op["k"] - 1)
                 own, rate = max(op["pad"], reach - op["pad"]), 1
@@ -642,6 +660,11 @@ class PlanBuilder:
                                             post=op["post"], mid=op["mid"])
                 if "fold_w" in op:
                     self.plan.set_pair_output_conv(op["fold_w"], op["fold_b"], op["y"], op["act_slope"], op["fold_post"])
+            elif op["kind"] == "stage" and "y2" in op:
+                if op["y_act"] != SLOT_NONE or op["act_slope"] != 1.0:
+                    raise _native.NativeError("mrf stage in two classes: its sums are stored raw")
+                self.plan.add_mrf_stage_classes(op["x"], op["y"], op["y2"], op["packed"], op["channels"], op["ks"], op["dils"],
+                                                op["slope"])
             elif op["kind"] == "stage":
                 self.plan.add_mrf_stage(op["x"], op["y"], op["packed"], op["channels"], op["ks"], op["dils"], op["slope"],
                                         out_div=op["out_div"], y_act=op["y_act"], act_slope=op["act_slope"])
@@ -759,6 +782,8 @@ class NativeModule(torch.nn.Module):
                      (csrc/mrfh_kernels.hpp, mrfw_kernels.hpp) or as fused-pair launches.  True (default): 16 channels always,
                      32 channels where one window per block covers the batch (hifigan._stage_one_launch); a tuple of channel
                      counts -- e.g. (16,) or (16, 32) -- fuses exactly those stages; False: none (A/B runs, identical bits).
+                     "32c" in a tuple -- (16, "32c") -- forces the 32-channel stage as one launch of two block classes in
+                     front of a merging upsampler (mrfw_kernels.hpp SPLIT; identical bits again).
     ``fold_post``    HiFi-GAN's conv_post inside the last pair's / the last stage's launch (default) or as a launch of its own.
     ``merge_in_upsampler``  the MRF merge ((r0 + r1) + r2) / 3 of a fused stage inside the split-f16 upsampler behind it
                      (default: the stage ends in one three-member launch) or in the stage's own last launch (A/B runs;
@@ -792,7 +817,7 @@ class NativeModule(torch.nn.Module):
         prec = "f32" if (self.precision == "f32" or self._fv_overflow or getattr(self, "_fv_force_f32", False)) else "split"
         # (the guard is part of the key: a plan built under range_guard = "off" carries no guard word)
         return (prec, bool(self.fuse_pairs), bool(self.fold_post), self.range_guard != "off", bool(self.merge_in_upsampler),
-                self.fuse_stage if isinstance(self.fuse_stage, tuple) else bool(self.fuse_stage))
+                tuple(self.fuse_stage) if isinstance(self.fuse_stage, (tuple, list)) else bool(self.fuse_stage))
 
     def _fv_state(self):
         """(identity + in-place version of every tensor the plans bake in, policy in force).  The tensor list is

@@ -15,6 +15,7 @@ tanh are epilogue/prologue work of the conv kernels: the whole forward is
 """
 import torch
 
+from .. import _native
 from .._native import PAIR_SPLIT_F16
 from .engine import (GradPrecision, NativeModule, PlanBuilder, POST_TANH, SLOT_IN, SLOT_NONE, SLOT_OUT, pair_precision,  # noqa: F401
                      weight_norm)
@@ -40,6 +41,38 @@ def stage32_windows_fit(cols, cus, fill=0.65):
     share = -(-cols // nblk)
     windows = 1 if share <= 264 else 1 + -(-(share - 264) // 324)
     return share >= fill * 384 * windows
+
+
+# The 32-channel stage in microseconds, from the launchers' window arithmetic (_native.mrf_class_schedule: makespans in
+# hundreds of cycles) and what tools/stage32_bench.py measured on 256 CUs: a window is 70.5 us all-in-one (1490
+# units), a launch's prologue and tail 10 us (8 us in two classes); the two classes' blocks running side by side take 1.17 x
+# the slower class alone (116.9 us against 100.5 at 120 000 columns, 76.3 / 69.4 at 61 440, 416.9 / 355.2 at 4 x 120 000);
+# the three pair launches take 24 us + 0.97 us per 1000 columns.
+_STAGE32_US_PER_UNIT = 70.5 / 1490
+_STAGE32_ONE_FIXED_US, _STAGE32_CLASSES_FIXED_US, _STAGE32_CLASSES_SHARING = 10.0, 8.0, 1.17
+_STAGE32_PAIRS_FIXED_US, _STAGE32_PAIRS_US_PER_COLUMN_CU = 24.0, 0.97e-3 * 256
+
+
+def stage32_form(batch, t, cus):
+    """How the 32-channel MRF stage of ``batch`` utterances of ``t`` samples runs on ``cus`` CUs: "pairs" (three launches of
+    fused pairs, tiles cut to the share), "s" (ONE launch, every block all three ResBlocks) or "c" (ONE launch of two block
+    classes, csrc/mrfw_kernels.hpp SPLIT).  Pairs against "s" is stage32_windows_fit, as before there were classes; "c"
+    replaces that choice where the launcher's own table (csrc/mrfh_launch.hip mrf_class_plan, through its host-only hook)
+    gives the classes fewer cycles than the all-in-one windows AND the estimate above puts it below the form it replaces."""
+    cols = int(batch) * int(t)
+    base = "s" if stage32_windows_fit(cols, cus) else "pairs"
+    nblk = max(1, min(int(cus), 256, -(-cols // 128)))
+    if cols <= 0 or nblk < 2 * int(batch):
+        return base
+    plan = _native.mrf_class_schedule(batch, t, nblk)
+    if not plan["split"]:
+        return base
+    classes_us = _STAGE32_CLASSES_FIXED_US + _STAGE32_CLASSES_SHARING * plan["makespan"] * _STAGE32_US_PER_UNIT
+    if base == "s":
+        base_us = _STAGE32_ONE_FIXED_US + plan["makespan_one"] * _STAGE32_US_PER_UNIT
+    else:
+        base_us = _STAGE32_PAIRS_FIXED_US + _STAGE32_PAIRS_US_PER_COLUMN_CU * cols / int(cus)
+    return "c" if classes_us < base_us else base
 
 
 class _HiFiGANBase(GradPrecision, NativeModule):
@@ -130,30 +163,61 @@ class _HiFiGANBase(GradPrecision, NativeModule):
                 t = (t - 1) * up.stride[0] - 2 * up.padding[0] + up.kernel_size[0] + up.output_padding[0]
             fusable = t > 0 and t % 4 == 0 and self._stage_fusable(i, precision)
             ch = self.resblocks[i * self.num_kernels].channels
-            flags.append("s" if fusable and self._stage_one_launch(ch, t) else bool(fusable))
+            # False / "s" / "c" -- "c" only for a stage that can run in two classes: the flag says what is emitted
+            form = self._stage_one_launch(ch, t, classes=self._stage_classes_possible(i, precision)) if fusable else False
+            flags.append(form or bool(fusable))
         return tuple(flags)
 
-    def _stage_one_launch(self, channels, t):
+    def _stage_classes_possible(self, i, precision):
+        """Can the fusable stage i run as one launch of two block classes (PlanBuilder.mrf_stage(classes_r2=...))?  32
+        channels, taps 3, 7, 11 in this order, pair dilations (1, 3, 5), split-f16 arithmetic -- and an upsampler behind
+        it that merges r_0 + r_1 and r_2 (merge_in_upsampler).  A LAST stage (HiFi-GAN large, V1) cannot: its one-launch
+        form is the all-in-one kernel, which folds conv_post."""
+        nk = self.num_kernels
+        if not (self.merge_in_upsampler and nk == 3 and i + 1 < self.num_upsamples):
+            return False
+        blocks = [self.resblocks[i * nk + j] for j in range(nk)]
+        ks = [b.convs1[0].kernel_size[0] for b in blocks]
+        dils = [c.dilation[0] for c in blocks[0].convs1]
+        return (blocks[0].channels == 32 and ks == [3, 7, 11] and _native.mrf_stage_supported(32, ks, dils)
+                and pair_precision(precision, 32) == PAIR_SPLIT_F16
+                and PlanBuilder.conv_transpose_merges(self.ups[i + 1], precision))
+
+    def _stage_one_launch(self, channels, t, classes=False):
         """A fused stage of ``t`` samples as ONE launch (csrc/mrfh_kernels.hpp, mrfw_kernels.hpp) rather than as pair
-        launches?  ``fuse_stage`` = a tuple of widths: exactly those; False: none; True (default): 16 channels always; 32
-        channels when the kernel's fixed 384-column windows fit the work -- a block's share of the batch's columns takes
-        one run-in window (264 final columns) plus whole windows of 324, and the pair launches, whose tiles are cut to the
-        share, win when much of the last window is empty.  Measured on whole forwards (tools/stage_policy_bench.py, us,
-        pairs / one launch): batch 1, 560 frames (share 263 of one window: 0.68) 457 / 440; 1000 frames (469 of two: 0.61)
-        603 / 619; 700 frames (0.43) 494 / 537; batch 4, 1000 frames (1875 of six: 0.81) 1938 / 1850; 500 frames (0.61)
-        1093 / 1120; 700 frames (0.68) 1407 / 1403 -- one launch from 0.65 up."""
+        launches?  Returns False (pair launches), "s" (one launch, every block the whole stage) or "c" (32 channels: one
+        launch of two block classes -- only with ``classes``: the stage can run so, _stage_classes_possible).  ``fuse_stage`` =
+        a tuple of widths: exactly those as "s", and "32c" in it: "c" where the stage can, else what the tuple says
+        without it (no other string is accepted); False: none; True (default): 16 channels always; 32 channels by stage32_form -- "s"
+        when the kernel's fixed 384-column windows fit the work: a block's share of the batch's columns takes one run-in
+        window (264 final columns) plus whole windows of 324, and the pair launches, whose tiles are cut to the share, win
+        when much of the last window is empty; "c" where the classes' own windows (912 / 1008 columns of three) beat
+        whichever of the two that rule picks.  Measured on whole forwards (tools/stage_policy_bench.py, us, pairs / one
+        launch / two classes): batch 1, 500 frames 443.8 / 434.2 / 433.8; 560 frames (share 263 of one window: 0.68)
+        472.5 / 456.2 / 454.8; 700 frames (0.43) 508.0 / 553.4 / 499.0; 1000 frames (469 of two: 0.61) 624.3 / 637.6 /
+        604.3; batch 4, 500 frames (0.61) 1138.9 / 1175.7 / 1100.0; 560 frames 1257.8 / 1265.7 / 1214.4; 700 frames (0.68)
+        1482.6 / 1463.9 / 1404.7; 1000 frames (1875 of six: 0.81) 2030.3 / 1932.4 / 1915.2 -- one launch from 0.65 up, and
+        the classes wherever stage32_form's estimate says so (every row but 560 frames at batch 1, a tie).  (These rows
+        time the three FORMS, each forced; what the default policy as it stands picks was timed in a second session on
+        another box -- profiles/r07_ab.txt: 125 ... 700 frames at batch 1 and 4 -- where its choice is the fastest form or
+        within 2 us of it.)"""
         fs = self.fuse_stage
         if isinstance(fs, (tuple, list)):
-            return channels in fs
+            if any(isinstance(v, str) and v != "32c" for v in fs):
+                raise _native.NativeError(f"fuse_stage = {fs!r}: channel counts, and \"32c\" for the 32-channel stage in two classes")
+            return "c" if channels == 32 and classes and "32c" in fs else "s" if channels in fs else False
         if not fs or channels == 16:
-            return bool(fs)
+            return "s" if fs else False
         if channels != 32:
             return False
         dev = self._device()
         cus = _CU_COUNT.get(dev)
         if cus is None:
             cus = _CU_COUNT[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
-        return stage32_windows_fit(getattr(self, "_fv_batch", 1) * int(t), cus)
+        if not classes:
+            return "s" if stage32_windows_fit(getattr(self, "_fv_batch", 1) * int(t), cus) else False
+        form = stage32_form(getattr(self, "_fv_batch", 1), int(t), cus)
+        return False if form == "pairs" else form
 
     def _emit_fused_stage(self, pb, blocks, up, x, scratch, parts, fold=None, merge_next=False, one_launch=False):
         """The three ResBlocks of a stage as fused pair launches: every pair position is ONE launch of
@@ -285,7 +349,7 @@ class _HiFiGANBase(GradPrecision, NativeModule):
                 pb.upsample_conv(self.ups[i], x, up, pre_slope=LRELU_SLOPE)
             else:
                 pb.conv_transpose(self.ups[i], x, up, pre_slope=LRELU_SLOPE,
-                                  merge=(parts[0], parts[1], float(nk)) if merged else None)
+                                  merge=(parts[0], SLOT_NONE if merged == "two" else parts[1], float(nk)) if merged else None)
             merged = False
             blocks = [self.resblocks[i * nk + j] for j in range(nk)]
             if fused is not None and fused[i]:
@@ -298,6 +362,14 @@ class _HiFiGANBase(GradPrecision, NativeModule):
                           and pb.pair_precision(blocks[0].channels) == PAIR_SPLIT_F16
                           and pb.conv_transpose_takes_merge(self.ups[i + 1])
                           and not (fused[i] == "s" and pb.mrf_stage_supported(blocks)))
+                if fused[i] == "c":
+                    # ONE launch of two block classes: r_0 + r_1 in x, r_2 in parts[0]; the upsampler merges two tensors
+                    # (_fused_flags says "c" only where _stage_classes_possible holds: anything else here is a bug)
+                    if not (merged and pb.mrf_stage_classes_supported(blocks)):
+                        raise _native.NativeError("stage flagged for two block classes cannot run so")
+                    pb.mrf_stage(blocks, up, x, LRELU_SLOPE, float(nk), classes_r2=parts[0])
+                    merged = "two"
+                    continue
                 self._emit_fused_stage(pb, blocks, up, x, scratch, parts, merge_next=merged, one_launch=fused[i] == "s")
                 continue
             if nk <= 3:
@@ -345,12 +417,18 @@ class _HiFiGANBase(GradPrecision, NativeModule):
             pb.conv(self.conv_post, x, dst, pre_slope=DEFAULT_LRELU_SLOPE, post=POST_TANH)
 
     def _flag_tag(self, T):
+        """Per stage: "-" conv by conv, "s" the stage stores its mean from ONE launch, "f" fused otherwise -- the ResBlocks'
+        results stay apart (pair launches, or the 32-channel stage's launch of two block classes)."""
         return "".join("s" if f == "s" else "f" if f else "-" for f in self._fused_flags(T))
+
+    def _plan_tag(self, T):
+        """What the plan cache keys on: _flag_tag with the two-class form of a stage told apart from the pair launches ("c")."""
+        return "".join(f if f in ("s", "c") else "f" if f else "-" for f in self._fused_flags(T))
 
     # (which stages run fused depends on the policy in force -- after a range overflow the fp32 pair kernels exist at 16 /
     # 32 channels only -- so plan names and emit functions evaluate _fused_flags when they are used, not here)
     def _trunk_plan(self, T):
-        return self._plan(lambda: "trunk" + self._flag_tag(T),
+        return self._plan(lambda: "trunk" + self._plan_tag(T),
                           lambda pb: self._emit_trunk(pb, SLOT_OUT, self._fused_flags(T), fold_post=True), 80)
 
     def _emit_inference(self, pb, fused):
@@ -361,7 +439,7 @@ class _HiFiGANBase(GradPrecision, NativeModule):
         def emit(pb):
             self._emit_inference(pb, self._fused_flags(T))
             pb.subtract_output(0, second=True)
-        return self._plan(lambda: "minus" + self._flag_tag(T), emit, 80)
+        return self._plan(lambda: "minus" + self._plan_tag(T), emit, 80)
 
     def inference_minus(self, x, bias):
         """x [T,80], bias [n] (e.g. the response to an all-zero mel) -> (waveform, waveform - bias), both 1-D,
@@ -430,7 +508,7 @@ class MultiBandHiFiGANGenerator(_HiFiGANBase):
         self._emit_full(pb, fused)
 
     def _full_plan(self, T):
-        return self._plan(lambda: "inference" + self._flag_tag(T),
+        return self._plan(lambda: "inference" + self._plan_tag(T),
                           lambda pb: self._emit_full(pb, self._fused_flags(T)), 80)
 
     def inference(self, x):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad; 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
+#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad (entries added since -- the latest: fv_mrf_stage_classes_f16 -- change no existing one); 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
 /* Entry points are added under one version number: 18 also covers the gradient, optimizer and training entries that
  * came after fv_stft_distance_grad, the latest being fv_conv1d_weight_grad_dilated_bf16 and
  * fv_conv_transpose1d_weight_grad_bf16 (the generators' bf16 weight gradients).  No existing entry changed its signature or its result. */
@@ -240,6 +240,20 @@ int fv_mrf_stage_split_f16(const float* x, const float* packed, float* y, float*
                            const int* dil, float slope, float out_div, int post, float act_slope, const float* fold_w,
                            const float* fold_b, float* fold_y, void* workspace, int64_t workspace_bytes, int* guard,
                            void* stream);
+/*
+ * The 32-channel stage as ONE launch of two block classes (csrc/mrfw_kernels.hpp, SPLIT): the three ResBlocks are
+ * independent until the sum, so class A blocks run the 11-tap ResBlock alone and class B blocks the 3- and 7-tap ones, each
+ * class on windows that overlap by its OWN reach (60 / 36 columns instead of 60 for all) and cost about half a window:
+ *     y_s = r_0 + r_1,   y_r2 = r_2        (un-divided; the consumer forms ((r_0 + r_1) + r_2) / 3, e.g. the merged
+ *                                           input of fv_plan_set_input_merge(add1 = y_r2, add2 = none, div = 3))
+ * -- bit-identical to the pair launches' r_0, r_1, r_2 summed in that order.  C = 32, k = {3, 7, 11} in this order,
+ * dil = {1, 3, 5}; anything else: FV_ERR_UNSUPPORTED.  x, y_s, y_r2 [B, 32, T], no aliasing; packed, workspace, guard: as
+ * fv_mrf_stage_split_f16.  The launcher gives class A n_A and class B n_B of its blocks (n_A + n_B <= one per CU, at most
+ * one per 128 columns, at most 256) so that the slower class's whole windows x window cost is smallest; a block's columns
+ * lie inside one utterance, so fewer than 2 B blocks is FV_ERR_UNSUPPORTED (one block: use fv_mrf_stage_split_f16).
+ */
+int fv_mrf_stage_classes_f16(const float* x, const float* packed, float* y_s, float* y_r2, int B, int C, int T, const int* k,
+                             const int* dil, float slope, void* workspace, int64_t workspace_bytes, int* guard, void* stream);
 
 /*
  * Conv1d of the wide ResBlock stages with split-f16 operands (arithmetic: FV_PAIR_SPLIT_F16 above), n = 1..3
@@ -1205,6 +1219,9 @@ int fv_plan_set_pair_output_conv(fv_plan_t* plan, const float* w, const float* b
 int fv_plan_add_mrf_stage_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, const float* packed, int C,
                                     const int* k, const int* dil, float slope, float out_div, int post, float act_slope,
                                     void* workspace, int64_t workspace_bytes);
+/* fv_mrf_stage_classes_f16 as a plan op: ys_slot receives r_0 + r_1, yr2_slot r_2 (workspace: as above). */
+int fv_plan_add_mrf_stage_classes_f16(fv_plan_t* plan, int x_slot, int ys_slot, int yr2_slot, const float* packed, int C,
+                                      const int* k, const int* dil, float slope, void* workspace, int64_t workspace_bytes);
 /* fv_conv1d_split_f16 as a plan op; consecutive ops under one non-zero group id with equal C, dilation, padding
  * mode, slopes, out_div and post run as ONE launch */
 int fv_plan_add_conv1d_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, int res_slot, int add1_slot,
@@ -1324,6 +1341,25 @@ int fv_tuning_set(const char* key, int value);
  */
 int fv_debug_pair_schedule(int n_members, const int* n_items, const int* cost, int nblk, int mode, int three_members,
                            unsigned* table);
+/*
+ * Test and policy hook, host only: what the 32-channel stage's launchers do with B utterances of T columns on at most nblk
+ * (1 .. 256) blocks (csrc/mrfh_launch.hip mrf_class_plan) -- the table the two-class kernel indexes with blockIdx.
+ *   force != 0: the split whenever it exists (nblk >= 2 B: what fv_mrf_stage_classes_f16 launches); 0: the split only where
+ *   its makespan is below the all-in-one form's (what the generators' policy asks).
+ * info[12] = {split (1 / 0: all-in-one), n_A, n_B, makespan, makespan of the all-in-one form, reach of class A, of class B,
+ * window columns W, cost of a class-A window, of a class-B window, of an all-in-one window (fv_tuning_set mrf_cost_a /
+ * mrf_cost_b / mrf_cost_one, hundreds of cycles; makespans in the same unit), 0}; table[512]: block i (class A first) owns
+ * the global columns [table[2 i], table[2 i + 1]) of the B utterances concatenated.  A run's first window is final for
+ * W - 2 reach columns, every further one for W - reach.  split = 0: n_A = 0, n_B = nblk, reach of class B = the stage's,
+ * the table holds the all-in-one kernel's equal shares.  Returns 0 or a negative FV_ERR_* code.
+ */
+int fv_debug_mrf_class_schedule(int B, int T, int nblk, int force, int64_t* info, unsigned* table);
+/*
+ * Timing hook (tools/stage32_bench.py: what a window of one class costs): fv_mrf_stage_classes_f16's launch with the blocks
+ * of ONE class of the same table alone -- cls = 1: class A, y = r_2; cls = 2: class B, y = r_0 + r_1.  No guard word.
+ */
+int fv_debug_mrf_stage_class_f16(const float* x, const float* packed, float* y, int cls, int B, int C, int T, const int* k,
+                                 const int* dil, float slope, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
  * measurement hook (bench.py): per-launch timing of the dominant kernel

@@ -1,5 +1,7 @@
 """Time the 32-channel MRF stage of HiFi-GAN light on the GPU: ONE launch (fv_mrf_stage_split_f16, csrc/mrfw_kernels.hpp)
-against the three pair launches it replaces (the merge then rides in the next upsampler).
+and ONE launch of two block classes (fv_mrf_stage_classes_f16; also either class's blocks alone, fv_debug_mrf_stage_class_f16: what a class-A / class-B
+window costs, Tuning::mrf_cost_a / mrf_cost_b) against the three pair launches they replace (the merge then rides in the
+next upsampler).
 usage: python tools/stage32_bench.py [T [B ...]]"""
 import sys
 
@@ -42,19 +44,30 @@ def main():
                                         [b2[i] for i in idx], list(KS), DILS[p], 0.1, prec=SPLIT, outs=outs)
                 cur = outs
 
-        variants = {"three pair launches": (None, pairs)}
+        work = _native.mrf_stage_workspace(C, dev)
+        variants = {"three pair launches": ({}, pairs)}
         for prio in (0, 1):
-            variants[f"one launch, prio {prio}"] = (prio, lambda: _native.mrf_stage_split_f16(x, P, KS, out=y))
+            variants[f"one launch, prio {prio}"] = ({"mrf_prio": prio}, lambda: _native.mrf_stage_split_f16(x, P, KS, out=y))
+        plan = _native.mrf_class_schedule(B, T, min(256, -(-B * T // 128)), force=True)
+        if plan["split"]:
+            variants["two classes"] = ({}, lambda: _native.mrf_stage_classes_f16(x, P, KS, work=work))
+            variants["class A blocks alone"] = ({}, lambda: _native.mrf_stage_one_class_f16(x, P, KS, "a", work=work))
+            variants["class B blocks alone"] = ({}, lambda: _native.mrf_stage_one_class_f16(x, P, KS, "b", work=work))
         best = {k: [] for k in variants}
         for rnd in range(5):
-            for name, (prio, fn) in variants.items():
-                if prio is not None:
-                    _native.tuning_set("mrf_prio", prio)
+            for name, (switches, fn) in variants.items():
+                for k, v in switches.items():
+                    _native.tuning_set(k, v)
                 best[name].append(timed(fn, reps=20, warm=3))
-        _native.tuning_set("mrf_prio", 1)
+                _native.tuning_set("mrf_prio", 1)
         print(f"B={B} T={T}  (us per call: min / median of 5 interleaved rounds)")
         for name, ts in best.items():
             print(f"  {name:28s} {min(ts):8.1f} {sorted(ts)[2]:8.1f}")
+        if plan["split"]:
+            wa = max(-(-max(0, hi - lo - 264) // 324) + 1 for lo, hi in plan["ranges"][:plan["n_a"]])
+            wb = max(-(-max(0, hi - lo - 312) // 348) + 1 for lo, hi in plan["ranges"][plan["n_a"]:])
+            print(f"  classes: {plan['n_a']} blocks x {wa} windows (A), {plan['n_b']} x {wb} (B); all-in-one makespan "
+                  f"{plan['makespan_one']}, two classes {plan['makespan']} (hundreds of cycles, Tuning costs)")
 
 
 if __name__ == "__main__":

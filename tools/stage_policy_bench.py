@@ -1,5 +1,6 @@
-"""Whole HiFi-GAN-light forwards with the 32-channel MRF stage as ONE launch (fuse_stage = (16, 32)) against pair launches
-(fuse_stage = (16,)), over utterance lengths and batch sizes: where does the one-launch kernel pay?  (The default policy,
+"""Whole HiFi-GAN-light forwards with the 32-channel MRF stage as ONE launch (fuse_stage = (16, 32)) and as one launch of two
+block classes (fuse_stage = (16, "32c")) against pair launches (fuse_stage = (16,)), over utterance lengths and batch sizes:
+where do the one-launch kernels pay?  (The default policy,
 fuse_stage = True, picks per call: hifigan._stage_one_launch.)  Interleaved rounds, min / median.
 usage: python tools/stage_policy_bench.py [frames ...]"""
 import sys
@@ -31,7 +32,7 @@ def main():
     dev = torch.device("cuda:0")
     cfg = cases.load_conf("conf/hifigan/light.yaml")
     models = {}
-    for name, fs in (("pairs", (16,)), ("one launch", (16, 32)), ("default", True)):
+    for name, fs in (("pairs", (16,)), ("one launch", (16, 32)), ("two classes", (16, "32c")), ("default", True)):
         m = build_generator("hifigan", cfg)
         sd = seeded_state_dict("hifigan", cfg, seed=0)
         m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
@@ -49,7 +50,7 @@ def main():
                     for name, m in models.items():
                         best[name].append(timed(lambda: m(x)))
             print(f"B={B} frames={T}: " + "  ".join(f"{k} {min(v):7.1f}/{sorted(v)[2]:7.1f}" for k, v in best.items())
-                  + f"   tag {models['default']._flag_tag(T)}")
+                  + f"   tag {models['default']._plan_tag(T)}")
     for m in models.values():
         assert not m.check_range()
 

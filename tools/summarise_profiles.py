@@ -28,6 +28,7 @@ with open(f"{dst}/{tag}_mfma_counters.txt", "w") as f:
             "# MI355X, HiFi-GAN light B=1 T=1000; per-dispatch averages; GRBM_GUI_ACTIVE is summed over the 8 XCDs\n")
     fams = {"split-f16 convs / fused pairs at 64+ channels (convh_kernel, convs_kernel, convq2_kernel)": ("convh_kernel", "convs_kernel", "convq2_kernel"),
             "split-f16 fused pairs at 32 channels (pairh_kernel)": ("pairh_kernel",),
+            "split-f16 one-launch 32-channel MRF stage (mrfw_kernel)": ("mrfw_kernel",),
             "split-f16 one-launch 16-channel MRF stage (mrfh_kernel)": ("mrfh_kernel",),
             "split-f16 transposed convs (convt_kernel)": ("convt_kernel",),
             "fp32-MFMA convs (conv_mfma_kernel + conv_group3_kernel + conv_sum3_kernel + pair_kernel + pair_sum_kernel)":
@@ -58,6 +59,8 @@ print(open(f"{dst}/{tag}_mfma_counters.txt").read()[-1200:])
 # ---- the other BASELINE configs: kernel-time shares from rocprofv3 --stats ----
 names = {0: "config 1: MelGAN original, T=200, B=1", 2: "config 3: MB-HiFi-GAN light + PQMF, T=1000, B=32",
          3: "config 4: Basis-MelGAN light, T=1000, B=64", 4: "config 5 (one GPU's share): HiFi-GAN large, T=1000, B=64"}
+if not any(os.path.exists(f"{src}/cfg{i}/cfg_kernel_stats.csv") for i in names):      # (collect_profiles.sh <tag> headline)
+    sys.exit(0)
 with open(f"{dst}/{tag}_configs.md", "w") as f:
     f.write(f"# {tag}: the other BASELINE configs on one MI355X (tools/collect_profiles.sh)\n\n")
     if os.path.exists(f"{src}/configs.log"):
