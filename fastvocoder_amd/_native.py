@@ -362,6 +362,7 @@ def lib():
     L.fv_plan_check_range.argtypes = [vp, vp]
     L.fv_tuning_set.argtypes = [ctypes.c_char_p, i]
     L.fv_debug_pair_schedule.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), i, i, i, ctypes.POINTER(ctypes.c_uint)]
+    L.fv_debug_pair_widths.argtypes = [i, i, i, i, i, ctypes.POINTER(i), i, ctypes.POINTER(ctypes.c_int64)]
     L.fv_debug_mrf_class_schedule.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint)]
     L.fv_debug_mrf_stage_class_f16.argtypes = [vp, vp, vp, i, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp]
     L.fv_mrf_stage_classes_f16.argtypes = [vp, vp, vp, vp, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp, vp]
@@ -473,6 +474,19 @@ def debug_pair_schedule(n_items, cost, nblk, mode=0, three_members=False):
     if rc == 2:
         return 2, [int(table[i]) for i in range(nblk)]
     return 0, None
+
+
+def debug_pair_widths(channels, batch, t, dil, taps, blocks):
+    """Test and policy hook (fv_debug_pair_widths, host only): the tile widths the fused 128-channel pair launcher picks for
+    ``batch`` utterances of ``t`` columns, members of ``taps`` taps (largest first), at most ``blocks`` persistent blocks.
+    Returns a dict: ``widths`` / ``items`` / ``costs`` per member, ``makespan`` (the block schedule's model, -1: no block
+    schedule for this shape) and ``nblk``.  ``tuning_set("convq_nm11", 64 | 80)`` forces the 11-tap member's width."""
+    n = len(taps)
+    info = (ctypes.c_int64 * 12)()
+    check(lib().fv_debug_pair_widths(int(channels), int(batch), int(t), int(dil), n, (ctypes.c_int * n)(*[int(k) for k in taps]),
+                                     int(blocks), info))
+    return {"widths": [int(info[m]) for m in range(n)], "items": [int(info[3 + m]) for m in range(n)],
+            "costs": [int(info[6 + m]) for m in range(n)], "makespan": int(info[9]), "nblk": int(info[10])}
 
 
 def mrf_class_schedule(batch, t, nblk, force=False):

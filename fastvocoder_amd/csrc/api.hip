@@ -354,6 +354,7 @@ static const TuningEntry kTuningTable[] = {
     {"convq_skel", &Tuning::convq_skel},   {"pair128_unfused", &Tuning::pair128_unfused},
     {"convg_rows64", &Tuning::convg_rows64}, {"stack_items", &Tuning::stack_items}, {"stack_wide", &Tuning::stack_wide},
     {"convp_wide", &Tuning::convp_wide},   {"convq_wide", &Tuning::convq_wide},
+    {"convq_nm11", &Tuning::convq_nm11},   {"convq_cost80", &Tuning::convq_cost80},
     {"convh_rows64", &Tuning::convh_rows64},  {"convt_rows64", &Tuning::convt_rows64},
     {"pairh_skel", &Tuning::pairh_skel},   {"pair_skel", &Tuning::pair_skel},    {"convh_blocks", &Tuning::convh_blocks},
     {"pair_blocks", &Tuning::pair_blocks}, {"sum3_min", &Tuning::sum3_min},      {"lds_budget", &Tuning::lds_budget},
@@ -1323,6 +1324,28 @@ int fv_debug_pair_schedule(int n_members, const int* n_items, const int* cost, i
     else fv::pair_cut_schedule(p, nblk, n);
     memcpy(table, p.sched, sizeof(p.sched));
     return p.sched_on;
+}
+
+int fv_debug_pair_widths(int C, int B, int T, int dil, int n_members, const int* taps, int blocks, int64_t* info) {
+    if (!taps || !info) return fail(FV_ERR_INVALID_ARG, "debug_pair_widths: null argument");
+    if (C != 128) return fail(FV_ERR_UNSUPPORTED, "debug_pair_widths: C = %d (128: the other launchers have one width)", C);
+    if (dil != 1 && dil != 3 && dil != 5) return fail(FV_ERR_UNSUPPORTED, "debug_pair_widths: dilation %d (1, 3 or 5)", dil);
+    if (n_members < 1 || n_members > 3) return fail(FV_ERR_INVALID_ARG, "debug_pair_widths: %d members", n_members);
+    if (B < 1 || T < 1 || blocks < 1 || (double)B * T >= 2147483647.0)
+        return fail(FV_ERR_INVALID_ARG, "debug_pair_widths: B=%d T=%d on %d blocks (B x T < 2^31)", B, T, blocks);
+    for (int m = 0; m < n_members; ++m)
+        if ((taps[m] != 3 && taps[m] != 7 && taps[m] != 11) || (m > 0 && taps[m] > taps[m - 1]))
+            return fail(FV_ERR_INVALID_ARG, "debug_pair_widths: member %d: %d taps (3, 7 or 11, largest first)", m, taps[m]);
+    const fv::PairWidthPlan pl = fv::pair_width_plan(B, T, n_members, taps, blocks);
+    for (int m = 0; m < 3; ++m) {
+        info[m] = m < n_members ? pl.nm[m] : 0;
+        info[3 + m] = m < n_members ? pl.n_items[m] : 0;
+        info[6 + m] = m < n_members ? pl.cost[m] : 0;
+    }
+    info[9] = pl.makespan;
+    info[10] = pl.nblk;
+    info[11] = 0;
+    return 0;
 }
 
 int fv_profile_enable(int on) {

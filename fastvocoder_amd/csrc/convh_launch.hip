@@ -352,6 +352,7 @@ int launch_convg(PairParams p, int C, hipStream_t s) {
 
 // ---- fused pairs at C = 64 and C = 128 (convq2_kernels.hpp) ----------------------------------------------------------
 constexpr int kPair64Wide = 65, kPair128Wide = 129;     // (convq2_kernels.hpp: the wide forms of the ring-free pair kernel)
+constexpr int kPair128Col80 = 130;                      // (... the 11-tap member on 80-column tiles)
 template <int DIL, int C>
 int launch_convq2_dil(const PairParams& p, size_t lds, hipStream_t s);      // convq2_inst.hip: the pairs without the weight ring
 extern template int launch_convq2_dil<1, 128>(const PairParams&, size_t, hipStream_t);
@@ -365,6 +366,9 @@ extern template int launch_convq2_dil<3, kPair64Wide>(const PairParams&, size_t,
 extern template int launch_convq2_dil<5, kPair64Wide>(const PairParams&, size_t, hipStream_t);
 extern template int launch_convq2_dil<1, kPair128Wide>(const PairParams&, size_t, hipStream_t);
 extern template int launch_convq2_dil<3, kPair128Wide>(const PairParams&, size_t, hipStream_t);
+extern template int launch_convq2_dil<1, kPair128Col80>(const PairParams&, size_t, hipStream_t);
+extern template int launch_convq2_dil<3, kPair128Col80>(const PairParams&, size_t, hipStream_t);
+extern template int launch_convq2_dil<5, kPair128Col80>(const PairParams&, size_t, hipStream_t);
 
 // Long runs of the fused 64- / 128-channel pairs (many tiles per block) are mostly WARM tiles -- NM outputs
 // for the work a cold tile spends on NM - (k - 1) (convq2_kernels.hpp) -- so an ITEM (NM - (k - 1) columns) of an 11-tap
@@ -374,9 +378,11 @@ extern template int launch_convq2_dil<3, kPair128Wide>(const PairParams&, size_t
 #ifndef FV_WARM_TILES
 #define FV_WARM_TILES 1
 #endif
-static void warm_run_costs(PairParams& p, long long items, int nm) {
+// (mixed: the members' tiles differ in width -- an item's share of a warm tile is nout / nm of it: in 1 / 320, 64 and 80 both
+// divide it)
+static void warm_run_costs(PairParams& p, long long items, const int* nm, bool mixed) {
     if (!FV_WARM_TILES || items < 8LL * p.nblk) return;
-    for (int i = 0; i < p.n_members; ++i) p.m[i].cost *= nm - (p.m[i].k - 1);
+    for (int i = 0; i < p.n_members; ++i) p.m[i].cost *= (nm[i] - (p.m[i].k - 1)) * (mixed ? 320 / nm[i] : 1);
 }
 
 // What differs between the two channel counts of the fused pair.  Both run convq2_kernel (A operands from L2 into registers) on
@@ -395,6 +401,66 @@ struct FusedPair {
 static const FusedPair kFusedPair64 = {64, 128, 256, &Tuning::convp_wide, 5, &Tuning::convp_skel, 0, false, FV_KERNEL_CONVH64};
 static const FusedPair kFusedPair128 = {128, 64, 128, &Tuning::convq_wide, 3, &Tuning::convq_skel, 5, true, FV_KERNEL_CONVH128};
 
+static int fused_pair_skel(const FusedPair& f) { return f.skel_auto && tuning().*f.skel < 0 ? f.skel_auto : tuning().*f.skel; }
+
+// items, costs and pair_schedule's makespan of a 128-channel launch whose 11-tap member runs on nm11 columns
+static PairWidthPlan pair_width_candidate(int B, int T, int n_members, const int* taps, int blocks, int nm11) {
+    const Tuning& tn = tuning();
+    PairWidthPlan pl = {};
+    PairParams p = {};
+    p.n_members = n_members;
+    long long items = 0;
+    for (int m = 0; m < n_members; ++m) {
+        const int nm = taps[m] == 11 ? nm11 : 64, nout = nm - (taps[m] - 1);
+        pl.nm[m] = nm;
+        pl.n_tiles[m] = (T + nout - 1) / nout;
+        pl.n_items[m] = pl.n_tiles[m] * B;
+        pl.cost[m] = nm == 80 && tn.convq_cost80 > 0 ? tn.convq_cost80 : 128 / 32 * taps[m] * nm / 64 + fused_pair_skel(kFusedPair128);
+        p.m[m].n_items = pl.n_items[m];
+        p.m[m].cost = pl.cost[m];
+        items += pl.n_items[m];
+    }
+    pl.nblk = (int)std::min<long long>(blocks, items);
+    pl.makespan = -1;
+    pair_schedule(p, pl.nblk, kFusedPair128.three_members);
+    if (p.sched_on != 1) return pl;
+    for (int b = 0; b < pl.nblk; ++b) {
+        const int cnt[3] = {(int)((p.sched[2 * b] >> 11) & 31u), (int)(p.sched[2 * b] >> 27), (int)((p.sched[2 * b + 1] >> 11) & 31u)};
+        long long load = 0;
+        for (int m = 0; m < n_members; ++m)
+            if (cnt[m]) load += (long long)cnt[m] * pl.cost[m] + (load > 0 ? tn.sched_switch : 0);
+        pl.makespan = std::max(pl.makespan, load);
+    }
+    return pl;
+}
+
+PairWidthPlan pair_width_plan(int B, int T, int n_members, const int* taps, int blocks) {
+    const Tuning& tn = tuning();
+    typedef std::array<int, 13> Key;
+    static std::mutex mu;
+    static std::map<Key, PairWidthPlan> cache;
+    Key key = {B, T, n_members, 0, 0, 0, blocks, tn.convq_nm11, tn.convq_cost80, fused_pair_skel(kFusedPair128), tn.sched, tn.sched_switch, 0};
+    bool has11 = false;
+    for (int m = 0; m < n_members; ++m) {
+        key[3 + m] = taps[m];
+        has11 = has11 || taps[m] == 11;
+    }
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = cache.find(key);
+        if (it != cache.end()) return it->second;
+    }
+    PairWidthPlan pl = pair_width_candidate(B, T, n_members, taps, blocks, has11 && tn.convq_nm11 == 80 ? 80 : 64);
+    if (has11 && tn.convq_nm11 != 64 && tn.convq_nm11 != 80 && pl.makespan >= 0) {
+        const PairWidthPlan w = pair_width_candidate(B, T, n_members, taps, blocks, 80);
+        if (w.makespan >= 0 && w.makespan < pl.makespan) pl = w;
+    }
+    std::lock_guard<std::mutex> lock(mu);
+    if (cache.size() >= 512) cache.clear();
+    cache.emplace(key, pl);
+    return pl;
+}
+
 static int launch_fused_pair(const FusedPair& f, PairParams& p, int dil, hipStream_t s) {
     const char* const fam = "resblock pair";
     const int C = f.C;
@@ -405,33 +471,51 @@ static int launch_fused_pair(const FusedPair& f, PairParams& p, int dil, hipStre
     long long wide_items = 0;          // (a wide tile advances by wide - (k - 1) columns)
     for (int i = 0; i < p.n_members; ++i) wide_items += (long long)p.B * ((p.T + f.wide - p.m[i].k) / (f.wide + 1 - p.m[i].k));
     const bool wide = dil <= f.wide_dil && wide_items * 10 >= (long long)(tuning().*f.wide_from) * device_cu_count();
-    const int NM = wide ? f.wide : f.narrow;
-    const int skel = f.skel_auto && tuning().*f.skel < 0 ? f.skel_auto : tuning().*f.skel;
-    int img_bytes = 0;
+    const int skel = fused_pair_skel(f);
+    for (int i = 0; i < p.n_members; ++i)
+        if (int rc = check_taps(fam, p.m[i].k)) return rc;
+    // columns per tile and cost of a tile, per member: one width for all, but for the 11-tap member of a 128-channel launch on
+    // narrow tiles (pair_width_plan)
+    int nm[3], cost[3];
+    for (int i = 0; i < p.n_members; ++i) {
+        nm[i] = wide ? f.wide : f.narrow;
+        cost[i] = C / 32 * p.m[i].k + skel;        // K steps of one conv + per-tile work
+    }
+    if (C == 128 && !wide) {
+        int taps[3] = {0, 0, 0};
+        for (int i = 0; i < p.n_members; ++i) taps[i] = p.m[i].k;
+        const PairWidthPlan pl = pair_width_plan(p.B, p.T, p.n_members, taps, (int)persistent_blocks(1LL << 40, 1, tuning().convh_blocks));
+        for (int i = 0; i < p.n_members; ++i) {
+            nm[i] = pl.nm[i];
+            cost[i] = pl.cost[i];
+        }
+    }
+    const bool col80 = nm[0] == 80;
+    int img_bytes = 0, nm_max = 0;
     long long items = 0;
     for (int i = 0; i < p.n_members; ++i) {
         PairMember& mb = p.m[i];
-        if (int rc = check_taps(fam, mb.k)) return rc;
         if (int rc = check_member(fam, mb, i, kNeedW2 | kNeedY)) return rc;
-        const int nout = NM - (mb.k - 1);
+        const int nout = nm[i] - (mb.k - 1);
         mb.n_tiles = (p.T + nout - 1) / nout;
         mb.n_items = mb.n_tiles * p.B;
-        mb.cost = C / 32 * mb.k + skel;            // K steps of one conv + per-tile work
-        const int xrows = (NM + (mb.k - 1) * dil + 3) / 4 * 4;
+        mb.cost = cost[i];
+        const int xrows = (nm[i] + (mb.k - 1) * dil + 3) / 4 * 4;
         const int img = 4 * C * ((xrows + 15) / 16 * 16);
-        if (img > img_bytes) img_bytes = img;
+        if (img > img_bytes) img_bytes = img;      // both images: sized for the largest member
+        if (nm[i] > nm_max) nm_max = nm[i];
         items += mb.n_items;
     }
     LdsLayout lds;
     p.x_off = 0;
     p.img_off = lds.add((size_t)img_bytes / 4);
-    p.mid_off = lds.add((size_t)4 * C * (NM + 16) / 4);
+    p.mid_off = lds.add((size_t)4 * C * (nm_max + 16) / 4);
     p.bias_off = lds.add(4 * (size_t)C + 16);      // [b1 | b2 | inverse row prescales of conv1 | conv2 | scratch of the low-range guard]
     if (int rc = check_lds(fam, lds.bytes())) return rc;
     p.nblk = (int)persistent_blocks(items, 1, tuning().convh_blocks);
     pair_schedule(p, p.nblk, f.three_members);
     if (!p.sched_on) {                 // no per-block schedule: the kernels' contiguous cut, as a table instead of arithmetic
-        warm_run_costs(p, items, NM);
+        warm_run_costs(p, items, nm, col80);
         cut_table(p, p.nblk);
     }
     set_debug(p);
@@ -440,6 +524,7 @@ static int launch_fused_pair(const FusedPair& f, PairParams& p, int dil, hipStre
     if (C == 64)
         return wide ? by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, kPair64Wide>(p, bytes, s); })
                     : by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, 64>(p, bytes, s); });
+    if (col80) return by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, kPair128Col80>(p, bytes, s); });
     return wide ? by_dilation<1, 3, 3>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, kPair128Wide>(p, bytes, s); })
                 : by_dilation<1, 3, 5>(dil, [&](auto d) { return launch_convq2_dil<decltype(d)::value, 128>(p, bytes, s); });
 }

@@ -19,4 +19,7 @@ template int launch_convq2_dil<3, kPair64Wide>(const PairParams&, size_t, hipStr
 template int launch_convq2_dil<5, kPair64Wide>(const PairParams&, size_t, hipStream_t);
 template int launch_convq2_dil<1, kPair128Wide>(const PairParams&, size_t, hipStream_t);
 template int launch_convq2_dil<3, kPair128Wide>(const PairParams&, size_t, hipStream_t);
+template int launch_convq2_dil<1, kPair128Col80>(const PairParams&, size_t, hipStream_t);
+template int launch_convq2_dil<3, kPair128Col80>(const PairParams&, size_t, hipStream_t);
+template int launch_convq2_dil<5, kPair128Col80>(const PairParams&, size_t, hipStream_t);
 }  // namespace fv

@@ -22,11 +22,12 @@
 namespace fv {
 
 // ---- tile geometry at 128 channels: a block owns ALL 128 rows of a 64-column tile (conv2 needs every channel of the
-// intermediate); x image 64 + (KT - 1) DIL columns, intermediate 64 + 16 columns
-template <int KT_, int DIL_>
+// intermediate); x image 64 + (KT - 1) DIL columns, intermediate 64 + 16 columns.  NF_: fragments of 16 columns per tile (4;
+// 5 -- an 80-column tile -- for the 11-tap member of kPair128Col80 below)
+template <int KT_, int DIL_, int NF_ = 4>
 struct ConvQGeom {
     static constexpr int KT = KT_, DIL = DIL_, C = 128, CG = 4, CB = 16, NFW = 2, NT = 512;
-    static constexpr int NM = 64;                        // intermediate columns per tile
+    static constexpr int NM = 16 * NF_;                  // intermediate columns per tile
     static constexpr int NOUT = NM - (KT - 1);           // output columns per tile
     static constexpr int P1 = (KT - 1) * DIL / 2, P2 = (KT - 1) / 2;
     static constexpr int NSTEP = KT * CG;                // K steps of 32 per conv = weight stages per conv
@@ -49,7 +50,8 @@ struct ConvQGeom {
     static constexpr int BD = FV_CONVQ_BDEPTH;           // B operands BD - 1 steps ahead of their MFMAs (register budget)
     static constexpr int NRAW = XRM * 8;
     static_assert(KT - 1 <= 16 && NSTEP >= 8, "taps");
-    static_assert(((CG - 1) * 4 * XRP + (KT - 1) * DIL + 16 * (NFW - 1)) * 16 + 16 < 65536, "ds_read immediate range");
+    static_assert(((CG - 1) * 4 * XRP + (KT - 1) * DIL + 16 * (NF_ - 1)) * 16 + 16 < 65536, "ds_read immediate range");
+    static_assert(2 * XHALF + 2 * MHALF + (4 * C + 16) * 4 <= 160 * 1024, "LDS");
 };
 
 // ---- tile geometry at 64 channels: 128 intermediate columns per tile, the image / wave layout of convh_kernel<2, 2>
@@ -76,6 +78,7 @@ struct ConvPGeom {
 // The kernel's second template argument: a channel count on its ordinary tile (128 / 64), or one of the wide forms below
 constexpr int kPair64Wide = 65;      // 64 channels on 256-column tiles
 constexpr int kPair128Wide = 129;    // 128 channels on 128-column tiles (dilation 1 and 3)
+constexpr int kPair128Col80 = 130;   // 128 channels, the 11-tap member on 80-column tiles (7 and 3 taps: the ordinary 64)
 template <int KT_, int DIL_, int C_>
 struct ConvQ2Geom;
 template <int KT_, int DIL_>
@@ -141,13 +144,26 @@ struct ConvQ2Geom<KT_, DIL_, kPair128Wide> {
     static_assert(((CG - 1) * 4 * XRP + (KT - 1) * DIL + 16 * 3) * 16 + 16 < 65536, "ds_read immediate range");
     static_assert(2 * XHALF + 2 * MHALF + (4 * C + 16) * 4 <= 160 * 1024, "LDS: dilation 1 and 3 only");
 };
+// kPair128Col80: the 16 x 64 wave tile of the ordinary form grown to 16 x 80 for the 11-tap member -- one column group of
+// FIVE fragments, 70 output columns for 80 computed (14 % halo instead of 18.5 %).  Not for speed per column: a batch-1
+// launch has fewer, longer 11-tap tiles that way, which the block schedule packs better (the launcher decides:
+// convh_launch.hip pair_width_plan).  Same MFMA order per output, same epilogues: the same bits.  LDS at dilation 5:
+// 72 KB of x image + 48 KB of intermediate.
+template <int KT_, int DIL_>
+struct ConvQ2Geom<KT_, DIL_, kPair128Col80> : ConvQ2Geom<KT_, DIL_, 128> {};
+template <int DIL_>
+struct ConvQ2Geom<11, DIL_, kPair128Col80> : ConvQGeom<11, DIL_, 5> {
+    typedef ConvQGeom<11, DIL_, 5> IMG;
+    static constexpr int WN = 1;
+    static constexpr int WBYTES = 2 * IMG::WTILE;
+};
 #ifndef FV_Q2_ILV
 #define FV_Q2_ILV 1
 #endif
 template <int KT_, int DIL_, int C_>
 struct ConvQ2Run : ConvQ2Geom<KT_, DIL_, C_> {
     typedef ConvQ2Geom<KT_, DIL_, C_> B;
-    static constexpr int NFW = 4;                        // fragments per wave: 64 columns
+    static constexpr int NFW = B::NM / (16 * B::WN);     // fragments per wave: 64 columns (kPair128Col80, 11 taps: 80)
     static constexpr int NH = C_ == kPair64Wide || C_ == kPair128Wide ? 2 : 1;     // row sixteenths per wave
     static constexpr int NSLAB = B::C / (16 * NH);       // row slabs = waves per column group
 #ifndef FV_Q2_DEEP
@@ -174,7 +190,8 @@ struct ConvQ2Run : ConvQ2Geom<KT_, DIL_, C_> {
     static constexpr int RAWK = NSEQ - QD;               // K step at which the next tile's window is requested: no A operand of
                                                          // THIS tile is issued after it, so nothing here waits for it
     static_assert(NSEQ % (QD + 1) == 0, "the A queue runs on from tile to tile: slot = K step % (QD + 1)");
-    static_assert(B::NM == 64 * B::WN && NSLAB * B::WN == 8, "8 waves: row slabs x column groups of 64");
+    static_assert(B::NM == 16 * NFW * B::WN && NSLAB * B::WN == 8 && (NFW == 4 || B::WN == 1),
+                  "8 waves: row slabs x column groups of 64 (one group: of 16 NFW)");
 };
 
 template <class G>
@@ -462,7 +479,7 @@ __device__ __forceinline__ void convq2_run_member(const PairParams& p, const Pai
 }
 
 // one 8-wave block per CU, 2 waves per SIMD
-// C: 128, 64, kPair64Wide or kPair128Wide
+// C: 128, 64, kPair64Wide, kPair128Wide or kPair128Col80
 template <int DIL, int C>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void convq2_kernel(PairParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

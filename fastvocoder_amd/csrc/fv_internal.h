@@ -158,6 +158,9 @@ struct Tuning {
     int convt_lean = 50;      // ... on the lean kernel (convtl_kernels.hpp) up to this many (64 x 64 item, chunk) units per CU, in tenths; 0: never
     int convq_wide = 20;         // fused 128-channel pairs, dilation 1 / 3: 128-column tiles per CU (in tenths) from which the wide form runs
     int convp_wide = 20;         // fused 64-channel pairs: 256-column tiles per CU (in tenths) from which the wide no-ring form runs
+    int convq_nm11 = -1;         // fused 128-channel pairs on narrow tiles: intermediate columns of the 11-tap member's tile -- 64, 80, or
+                                 // -1: whichever the block schedule's model finishes earlier (pair_width_plan; 64 on a tie)
+    int convq_cost80 = -1;       // ... cost of an 80-column 11-tap tile in the schedule's units (-1: K steps x 80 / 64 + convq_skel = 60)
     int stack_wide = 10;         // residual stacks of 256 channels: tiles of 64 columns per CU (in tenths) from which the wide tile runs
                                  // (Basis-MelGAN, 1000 frames: batch 1 -- 250 such tiles in its second stage -- 0.238 narrow / 0.248 wide,
                                  // batch 2 0.384 / 0.359, batch 3 0.624 / 0.534)
@@ -299,6 +302,18 @@ int launch_convh(PairParams p, int C, int dil, hipStream_t stream);
 // assignment instead of the contiguous cut, written into p.sched (host cache per shape); p.sched_on = 0 when every block
 // has many items anyway
 void pair_schedule(PairParams& p, int nblk, bool three_members = false);
+// Tile widths of a fused 128-channel pair launch on narrow tiles (launch_convq): the 11-tap member's tile has 64 or 80
+// intermediate columns, the others 64.  Fewer, longer 11-tap tiles can pack better into the blocks (HiFi-GAN light, one
+// utterance of 8000 columns on 256 blocks: 149 tiles of cost 49 end at a makespan of 70, 115 of cost 60 at 60), so both
+// widths go through pair_schedule's model and the smaller makespan wins; 64 on a tie and wherever pair_schedule leaves the
+// launch to the contiguous cut.  Tuning::convq_nm11 forces a width.  taps: largest first.  blocks: the grid's upper bound
+// (one per CU, or Tuning::convh_blocks).  Host only; kept per shape.
+struct PairWidthPlan {
+    int nm[3], n_tiles[3], n_items[3], cost[3];
+    int nblk;                // persistent blocks: min(blocks, items)
+    long long makespan;      // of pair_schedule's assignment, member switches included; -1: no block schedule for this shape
+};
+PairWidthPlan pair_width_plan(int B, int T, int n_members, const int* taps, int blocks);
 // The kernels' own contiguous, cost-balanced cut (pair_share) computed on the host: p.sched[i] = the global item number
 // (members concatenated) share i starts at, i = 0 .. nblk - 1 (nblk <= 2 kSchedBlocks entries), p.sched_on = 2; n[m]: items
 // of member m.  Left alone (sched_on unchanged) when the table does not fit.

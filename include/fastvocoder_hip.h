@@ -1342,6 +1342,17 @@ int fv_tuning_set(const char* key, int value);
 int fv_debug_pair_schedule(int n_members, const int* n_items, const int* cost, int nblk, int mode, int three_members,
                            unsigned* table);
 /*
+ * Test and policy hook, host only: the tile widths the fused 128-channel pair launcher (csrc/convh_launch.hip
+ * pair_width_plan) picks on its narrow tiles for B utterances of T columns, n_members (1 .. 3) members of taps[m] taps
+ * (3, 7 or 11, largest first) and at most `blocks` persistent blocks -- the 11-tap member on 64 or 80 intermediate columns,
+ * whichever the block schedule's model finishes earlier (fv_tuning_set "convq_nm11": 64 / 80 force one, -1 chooses).
+ * C: 128; dil: 1, 3 or 5 (the choice does not depend on it).
+ * info: 12 words -- [0..2] intermediate columns per tile of each member, [3..5] its items, [6..8] the cost of one of its
+ * tiles in the schedule's units, [9] the modelled makespan (member switches included; -1: this shape has no block
+ * schedule and keeps 64), [10] persistent blocks, [11] 0.  Returns 0 or a negative FV_ERR_* code.
+ */
+int fv_debug_pair_widths(int C, int B, int T, int dil, int n_members, const int* taps, int blocks, int64_t* info);
+/*
  * Test and policy hook, host only: what the 32-channel stage's launchers do with B utterances of T columns on at most nblk
  * (1 .. 256) blocks (csrc/mrfh_launch.hip mrf_class_plan) -- the table the two-class kernel indexes with blockIdx.
  *   force != 0: the split whenever it exists (nblk >= 2 B: what fv_mrf_stage_classes_f16 launches); 0: the split only where
