@@ -798,23 +798,21 @@ class NativeModule(torch.nn.Module):
     fold_post = True
     merge_in_upsampler = True
 
+    # (class-level defaults: a module pickled before one of these existed reads the default)
+    _fv_guard = None
+    _fv_overflow = _fv_force_f32 = False    # the exact-fp32 kernels: until the weights change / for the one call _exec repeats
+    _fv_low_hits = 0
+    _fv_last_batch = 1     # of the most recent call (_resolve): a plan getter called WITHOUT a batch answers for it; no policy reads it
+
     def __init__(self):
         super().__init__()
-        self._fv_plans = {}
-        self._fv_fast = {}         # (plan getter, batch, frames) -> (state, plan): the per-call route to a plan (_exec)
-        self._fv_tensors = None
-        self._fv_ids = ()
-        self._fv_epoch = -1
-        self._fv_key = None
-        self._fv_guard = None
-        self._fv_overflow = False
-        self._fv_low_hits = 0
-        self._fv_force_f32 = False
+        self._fv_plans, self._fv_fast = {}, {}      # the two cache levels: _resolve
+        self._fv_tensors, self._fv_ids, self._fv_epoch = None, (), -1
 
     # -- cache bookkeeping -------------------------------------------------
     def _fv_policy(self):
         """The policy a plan is built under (part of every plan's cache key)."""
-        prec = "f32" if (self.precision == "f32" or self._fv_overflow or getattr(self, "_fv_force_f32", False)) else "split"
+        prec = "f32" if (self.precision == "f32" or self._fv_overflow or self._fv_force_f32) else "split"
         # (the guard is part of the key: a plan built under range_guard = "off" carries no guard word)
         return (prec, bool(self.fuse_pairs), bool(self.fold_post), self.range_guard != "off", bool(self.merge_in_upsampler),
                 tuple(self.fuse_stage) if isinstance(self.fuse_stage, (tuple, list)) else bool(self.fuse_stage))
@@ -832,11 +830,7 @@ class NativeModule(torch.nn.Module):
     # unpickled module must not share it (double free, stale device pointers) -- it rebuilds its own.
     def __getstate__(self):
         state = self.__dict__.copy()
-        state["_fv_plans"] = {}
-        state["_fv_fast"] = {}
-        state["_fv_tensors"] = None
-        state["_fv_epoch"] = -1
-        state["_fv_guard"] = None
+        state.update(_fv_plans={}, _fv_fast={}, _fv_tensors=None, _fv_epoch=-1, _fv_guard=None)
         state.pop("_fv_zero", None)       # cached device waveforms (zero-mel responses) are not part of a model
         state.pop("_zero_cache", None)
         return state
@@ -845,10 +839,9 @@ class NativeModule(torch.nn.Module):
         """Drop cached native plans (packed weights) and everything derived from the weights.  Called automatically on
         load_state_dict / .to() / weight-norm changes / in-place parameter updates; call it by hand after writing
         through ``param.data``."""
-        self._fv_plans = {}
-        self._fv_fast = {}
+        self._fv_plans, self._fv_fast = {}, {}
         self._fv_tensors = None
-        self._fv_overflow = False         # new weights: the split-f16 path gets its chance again
+        self._fv_overflow = False        # new weights: the split-f16 path gets its chance again
         self._fv_low_hits = 0
         self.__dict__.pop("_fv_zero", None)
         self.__dict__.pop("_zero_cache", None)
@@ -896,21 +889,23 @@ class NativeModule(torch.nn.Module):
                       "tensor that is smaller than 2^-10 as a whole); this model now runs on the exact-fp32 kernels "
                       "(precision = 'f32')", RuntimeWarning, stacklevel=3)
 
-    def _plan(self, name, emit, in_channels):
-        """Return the cached plan ``name`` or build it with ``emit(builder)``.  A split-f16 plan whose pack kernels
-        meet a weight beyond the f16 range is discarded and rebuilt with fp32 arithmetic.  ``name`` may be a callable
-        (and ``emit`` should then consult the same things): graphs whose shape depends on the policy -- which stages
-        run fused -- are named and emitted under the policy in force at that moment."""
+    def _plan(self, kind, emit, in_channels, variant=None):
+        """The cached plan of the graph ``kind``, built when missing.  ``variant``: what the graph's shape depends on besides the
+        weights and the policy (which stages run fused at this length and batch) -- a hashable value, or a zero-argument
+        callable evaluated under the policy in force, ONCE per build attempt: that one value names the plan in the cache
+        (``kind`` + its ``str()``) and is what ``emit(builder, value)`` receives (``emit(builder)`` without a variant).  A plan
+        whose pack kernels meet a weight beyond the f16 range is rebuilt with fp32 arithmetic: a new attempt, a new value."""
         state = self._fv_state()
-        name_of, name = name, (name() if callable(name) else name)
-        hit = self._fv_plans.get((name, state[1]))
+        value = variant() if callable(variant) else variant
+        key = (kind if value is None else f"{kind}{value}", state[1])
+        hit = self._fv_plans.get(key)
         if hit is not None and hit[0] == state:
             return hit[1]
         prec, _, fold, guarded = state[1][:4]
         guard = self._guard_word() if (prec == "split" and guarded) else None
         with torch.no_grad():
             pb = PlanBuilder(in_channels, precision=prec, fold_post=fold, guard=guard)
-            emit(pb)
+            emit(pb) if value is None else emit(pb, value)
             plan = pb.finalize()
             if guard is not None and plan.guarded:
                 # one-off, at plan build: the pack kernels' verdict (they ran on the MODULE's device, under _on())
@@ -918,14 +913,37 @@ class NativeModule(torch.nn.Module):
                 if guard.peek(1):
                     guard.clear(1)
                     self._went_out_of_range("a weight lies")
-                    return self._plan(name_of, emit, in_channels)
-        self._fv_plans[(name, state[1])] = (state, plan)
+                    return self._plan(kind, emit, in_channels, variant)
+        self._fv_plans[key] = (state, plan)
+        return plan
+
+    def _resolve(self, plan_for, B, T):
+        """The plan a call of ``B`` utterances of ``T`` frames runs on: the one way from a call to its plan (_exec, _run_chunked,
+        _run_minus).  ``plan_for``: a plan spec ``(kind, emit, in_channels[, variant])`` -- _plan's arguments, for a graph
+        private to one call site -- or a plan getter, a bound method ``getter(T, B)`` of this module that ends in _plan.
+        Two cache levels (__init__, invalidate_plans, __getstate__); an entry serves while ``_fv_state()`` is what it was stored with:
+        ``_fv_plans``  (plan name, policy) -> (state, plan): every plan built (_plan; ``cached`` keeps its values here too);
+        ``_fv_fast``   (getter, B, T, policy) -> (state, plan): the per-call route past a getter's policy evaluation (which
+                       stages fuse at this length and batch: ~100 us of Python in front of the first launch); emptied at 512.
+        A getter must be a pure function of ``(T, B, self._fv_state())``: whatever else it consulted (an attribute outside
+        _fv_policy, an earlier call's batch, a process-wide switch), _fv_fast would go on serving the first answer."""
+        self._fv_last_batch = B
+        if isinstance(plan_for, tuple):
+            return self._plan(*plan_for)
+        state = self._fv_state()
+        hit = self._fv_fast.get((plan_for.__func__, B, T, state[1]))
+        if hit is not None and hit[0] == state:
+            return hit[1]
+        plan = plan_for(T, B)
+        state = self._fv_state()          # (AFTER the build: a weight beyond the f16 range moves the policy to fp32)
+        if len(self._fv_fast) >= 512:
+            self._fv_fast.clear()
+        self._fv_fast[(plan_for.__func__, B, T, state[1])] = (state, plan)
         return plan
 
     def _exec(self, plan_for, x, sync=False, **run_kw):
-        """``plan_for(T).run(x, **run_kw)`` under the module's range guard (class docstring); ``sync``: the result is
-        bound for the host (informational since round 5: "auto" checks every call before returning).  ``plan_for`` must resolve the plan through
-        :meth:`_plan` every time it is called: after an overflow it returns the fp32 plan."""
+        """Run x [B,C,T] on its plan (``plan_for``: _resolve) under the module's range guard (class docstring); ``sync``:
+        the result is bound for the host (informational since round 5: "auto" checks every call before returning)."""
         mode = self.range_guard
         if mode == "auto":              # safe by default: every call is checked before it returns (class docstring)
             mode = "sync"
@@ -935,40 +953,23 @@ class NativeModule(torch.nn.Module):
             self._fv_guard.clear(0)
             self._went_out_of_range("an EARLIER call met an activation (its output holds non-finite values)")
         B, T = int(x.shape[0]), int(x.shape[2])
-        self._fv_batch = B                # (graphs whose shape depends on the batch: hifigan._stage_one_launch)
-        # The per-call route to the plan: resolving it through plan_for costs the whole policy evaluation (which stages
-        # fuse at this length and batch, ~100 us of Python in front of the first launch -- exposed in full when every call
-        # is checked before it returns); what the answer depends on is (getter, batch, frames) + the state _plan keys on.
-        getter = getattr(plan_for, "__func__", None) if getattr(plan_for, "__self__", None) is self else None
-        plan = None
-        if getter is not None:
-            state = self._fv_state()
-            hit = self.__dict__.setdefault("_fv_fast", {}).get((getter, B, T))
-            if hit is not None and hit[0] == state:
-                plan = hit[1]
-        if plan is None:
-            plan = plan_for(T)
-            if getter is not None:
-                if len(self._fv_fast) >= 512:
-                    self._fv_fast.clear()
-                self._fv_fast[(getter, B, T)] = (self._fv_state(), plan)    # (the state AFTER the build: a weight beyond
-                                                                           # the f16 range moves the policy to fp32)
+        plan = self._resolve(plan_for, B, T)
         out = plan.run(x, **run_kw)
         if mode == "sync" and plan.guarded:
             seen = plan.check_range()
-            if seen == "low" and getattr(self, "_fv_low_hits", 0) < self.low_range_patience:
+            if seen == "low" and self._fv_low_hits < self.low_range_patience:
                 # The LOW side alone: some block's share of a tensor was small as a whole -- a property of THIS input (a quiet
                 # stretch), not of the model.  This call is repeated on the exact-fp32 kernels; the module stays on the split
                 # kernels (until it has happened `low_range_patience` times in a row: then it is the model).
-                self._fv_low_hits = getattr(self, "_fv_low_hits", 0) + 1
+                self._fv_low_hits += 1
                 self._fv_force_f32 = True
                 try:
-                    out = plan_for(x.shape[2]).run(x, **run_kw)
+                    out = self._resolve(plan_for, B, T).run(x, **run_kw)
                 finally:
                     self._fv_force_f32 = False
             elif seen:
                 self._went_out_of_range("an activation lies")
-                out = plan_for(x.shape[2]).run(x, **run_kw)
+                out = self._resolve(plan_for, B, T).run(x, **run_kw)
             else:
                 self._fv_low_hits = 0
         return out
@@ -987,44 +988,44 @@ class NativeModule(torch.nn.Module):
             self._went_out_of_range("an activation lay")
         return True
 
-    # Longest input (frames) handed to one plan run; longer inputs are cut into chunks with
-    # receptive-field halos.  One launch addresses < 1 GiB per
-    # tensor row (csrc/conv_mfma.hip kOutOfRange), which the widest shipped layer
-    # (MelGAN 256 ch x 10T) reaches near T = 100k frames; 16384 frames (~3 min of audio)
-    # keeps the workspace bounded and costs < 1 % in halo recomputation.
+    # Longest input (frames) handed to one plan run; longer inputs are cut into chunks with receptive-field halos (SURVEY.md
+    # section 8 f-4).  One launch addresses < 1 GiB per tensor row (csrc/conv_mfma.hip kOutOfRange), which the widest
+    # shipped layer (MelGAN 256 ch x 10T) reaches near T = 100k frames; 16384 frames (~3 min of audio) keeps the workspace
+    # bounded and costs < 1 % in halo recomputation.
     max_frames_per_run = 16384
 
-    def _run_plan(self, plan, x, chunk_frames=None, sync=False):
-        """plan.run(x), time-chunked when x is longer than ``chunk_frames``
-        (default ``max_frames_per_run``).  ``plan`` is a native plan or a callable ``T -> plan``
-        (variants of one graph whose fused ops depend on the length, all with the same
-        receptive field and output-length law)."""
-        plan_for = plan if callable(plan) else (lambda T: plan)
+    def _run_plan(self, plan_for, x, chunk_frames=None, sync=False):
+        """x on its plan (_resolve), time-chunked when longer than ``chunk_frames`` (default ``max_frames_per_run``)."""
         chunk = self.max_frames_per_run if chunk_frames is None else int(chunk_frames)
         if chunk <= 0 or x.shape[2] <= chunk:
             return self._exec(plan_for, x, sync=sync)
         return self._run_chunked(plan_for, x, chunk, sync)
 
+    @staticmethod
+    def _length_law(plan):
+        """(halo frames, output channels, hop, c) of a plan: T frames in, hop * T + c samples out."""
+        (_, n1), (cout, n2) = (plan.output_shape(plan.halo_frames + k) for k in (64, 65))
+        return plan.halo_frames, cout, n2 - n1, n1 - (n2 - n1) * (plan.halo_frames + 64)
+
     def _run_chunked(self, plan_for, x, chunk, sync=False):
-        """Exact chunked evaluation: each chunk of ``chunk`` frames is run with ``halo`` extra
-        frames of real input on both sides (clipped at the utterance ends, where the layers'
-        own zero / reflection padding applies as in a whole run) and only its interior is
-        kept.  Output length law out = hop*T + c is read from the plan: c < 0 is a symmetric
-        crop (MB-large), c > 0 a tail (Basis overlap-add); either way a chunk that starts at
-        frame ``lo`` produces final samples [lo*hop, lo*hop + len)."""
-        B, _, T = x.shape
-        self._fv_batch = int(B)           # (plan_for below: graphs whose shape depends on the batch are chosen for THIS batch,
-                                          # not for the last call's -- ADVICE r5)
-        plan = plan_for(min(T, chunk))            # any length's variant has the same receptive field and output-length law: ask
-                                                  # for one of the size the chunks will run at, not for a whole-length plan
-        halo = plan.halo_frames
-        (_, n1), (cout, n2) = plan.output_shape(halo + 64), plan.output_shape(halo + 65)
-        hop = n2 - n1
+        """Exact chunked evaluation: each chunk of ``chunk`` frames is run with ``halo`` extra frames of real input on both
+        sides (clipped at the utterance ends, where the layers' own zero / reflection padding applies as in a whole run)
+        and only its interior is kept.  Output length law out = hop*T + c is read from the plan: c < 0 is a symmetric crop
+        (MB-large), c > 0 a tail (Basis overlap-add); either way a chunk that starts at frame ``lo`` produces final samples
+        [lo*hop, lo*hop + len).  A graph may have another variant at each length the chunks run at (chunk + halo ... chunk +
+        2 halo frames): the law is read from the plan of the FIRST chunk's length (a first query, at ``chunk`` frames, tells
+        the halo), and every plan a chunk runs on must have that halo and law."""
+        B, T = int(x.shape[0]), int(x.shape[2])
+        halo = self._resolve(plan_for, B, min(T, chunk)).halo_frames
+        plan = self._resolve(plan_for, B, min(T, chunk + halo))
+        law = halo, cout, hop, _ = self._length_law(plan)
         total = plan.output_shape(T)[1]
         out = torch.empty((B, cout, total), dtype=torch.float32, device=x.device)
         for a in range(0, T, chunk):
             b = min(T, a + chunk)
             lo, hi = max(0, a - halo), min(T, b + halo)
+            ran = self._resolve(plan_for, B, hi - lo)
+            assert ran is plan or self._length_law(ran) == law, (hi - lo, self._length_law(ran), law)
             y = self._exec(plan_for, x[:, :, lo:hi].contiguous(), sync=sync)
             first = a * hop if a > 0 else 0
             last = b * hop if b < T else total
@@ -1032,17 +1033,17 @@ class NativeModule(torch.nn.Module):
         return out
 
     def _run_minus(self, plan_for, x, bias):
-        """Run ``plan_for(T)`` -- a graph whose last op carries ``PlanBuilder.subtract_output(0, True)`` --
-        on x [B,C,T] with ``bias`` (any shape with the output's element count per utterance, or one row
-        per utterance) as the offset: returns (out, out - bias), both [B,Cout,Tout], from ONE pass; the
-        subtraction happens in the last kernel's epilogue.  Inputs longer than ``max_frames_per_run`` take
-        the chunked route and one elementwise subtraction."""
+        """Run x [B,C,T] on its plan (``plan_for``: _resolve) -- a graph whose last op carries
+        ``PlanBuilder.subtract_output(0, True)`` -- with ``bias`` (any shape with the output's element count per utterance, or
+        one row per utterance) as the offset: returns (out, out - bias), both [B,Cout,Tout], from ONE pass; the subtraction
+        happens in the last kernel's epilogue.  Longer than ``max_frames_per_run``: the chunked route and one subtraction."""
         bias = bias.detach().to(device=x.device, dtype=torch.float32)
-        if x.shape[2] > self.max_frames_per_run:
+        B, T = int(x.shape[0]), int(x.shape[2])
+        if T > self.max_frames_per_run:
             out = self._run_plan(plan_for, x, sync=True)
             return out, out - bias.reshape((-1,) + tuple(out.shape[1:]))
-        c, n = plan_for(x.shape[2]).output_shape(x.shape[2])
-        if bias.numel() not in (c * n, x.shape[0] * c * n):
+        c, n = self._resolve(plan_for, B, T).output_shape(T)
+        if bias.numel() not in (c * n, B * c * n):
             raise _native.NativeError(f"bias has {bias.numel()} elements, the output {c} x {n} per utterance")
         return self._exec(plan_for, x, sync=True, aux=(bias.reshape(-1, c, n).contiguous(),), out2=True)
 

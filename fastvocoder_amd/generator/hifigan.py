@@ -75,6 +75,13 @@ def stage32_form(batch, t, cus):
     return "c" if classes_us < base_us else base
 
 
+class StageFlags(tuple):
+    """Per stage how it runs (_HiFiGANBase._fused_flags): False conv by conv, True fused pair launches, "s" ONE launch, "c" ONE
+    launch of two block classes.  The variant of the generators' plans (NativeModule._plan); ``str()``: the tag ("ffcs")."""
+    def __str__(self):
+        return "".join(f if f in ("s", "c") else "f" if f else "-" for f in self)
+
+
 class _HiFiGANBase(GradPrecision, NativeModule):
     _post_channels = 1
     fuse_pqmf = True      # Multiband: conv_post + tanh + PQMF synthesis as one launch (False: two; A/B and bit-identity tests)
@@ -148,12 +155,12 @@ class _HiFiGANBase(GradPrecision, NativeModule):
         prec = pair_precision(precision, blocks[0].channels)
         return all(PlanBuilder.pair_fusable(c1, c2, prec) for b in blocks for c1, c2 in zip(b.convs1, b.convs2))
 
-    def _fused_flags(self, T):
-        """Per stage: run it fused for a mel of T frames?  The pair kernels need 16-byte aligned rows
+    def _fused_flags(self, T, B):
+        """Per stage: run it fused for B mels of T frames?  The pair kernels need 16-byte aligned rows
         (stage length % 4 == 0); ``fuse_pairs = False`` keeps every stage on the conv-by-conv path (A/B runs)."""
         precision, fuse = self._fv_policy()[:2]
         if not fuse:
-            return (False,) * self.num_upsamples
+            return StageFlags((False,) * self.num_upsamples)
         flags, t = [], int(T)
         for i in range(self.num_upsamples):
             up = self.ups[i]
@@ -164,9 +171,9 @@ class _HiFiGANBase(GradPrecision, NativeModule):
             fusable = t > 0 and t % 4 == 0 and self._stage_fusable(i, precision)
             ch = self.resblocks[i * self.num_kernels].channels
             # False / "s" / "c" -- "c" only for a stage that can run in two classes: the flag says what is emitted
-            form = self._stage_one_launch(ch, t, classes=self._stage_classes_possible(i, precision)) if fusable else False
+            form = self._stage_one_launch(ch, t, B, classes=self._stage_classes_possible(i, precision)) if fusable else False
             flags.append(form or bool(fusable))
-        return tuple(flags)
+        return StageFlags(flags)
 
     def _stage_classes_possible(self, i, precision):
         """Can the fusable stage i run as one launch of two block classes (PlanBuilder.mrf_stage(classes_r2=...))?  32
@@ -183,8 +190,8 @@ class _HiFiGANBase(GradPrecision, NativeModule):
                 and pair_precision(precision, 32) == PAIR_SPLIT_F16
                 and PlanBuilder.conv_transpose_merges(self.ups[i + 1], precision))
 
-    def _stage_one_launch(self, channels, t, classes=False):
-        """A fused stage of ``t`` samples as ONE launch (csrc/mrfh_kernels.hpp, mrfw_kernels.hpp) rather than as pair
+    def _stage_one_launch(self, channels, t, batch, classes=False):
+        """A fused stage of ``batch`` x ``t`` samples as ONE launch (csrc/mrfh_kernels.hpp, mrfw_kernels.hpp) rather than as pair
         launches?  Returns False (pair launches), "s" (one launch, every block the whole stage) or "c" (32 channels: one
         launch of two block classes -- only with ``classes``: the stage can run so, _stage_classes_possible).  ``fuse_stage`` =
         a tuple of widths: exactly those as "s", and "32c" in it: "c" where the stage can, else what the tuple says
@@ -215,8 +222,8 @@ class _HiFiGANBase(GradPrecision, NativeModule):
         if cus is None:
             cus = _CU_COUNT[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
         if not classes:
-            return "s" if stage32_windows_fit(getattr(self, "_fv_batch", 1) * int(t), cus) else False
-        form = stage32_form(getattr(self, "_fv_batch", 1), int(t), cus)
+            return "s" if stage32_windows_fit(int(batch) * int(t), cus) else False
+        form = stage32_form(batch, int(t), cus)
         return False if form == "pairs" else form
 
     def _emit_fused_stage(self, pb, blocks, up, x, scratch, parts, fold=None, merge_next=False, one_launch=False):
@@ -416,30 +423,33 @@ class _HiFiGANBase(GradPrecision, NativeModule):
         else:
             pb.conv(self.conv_post, x, dst, pre_slope=DEFAULT_LRELU_SLOPE, post=POST_TANH)
 
-    def _flag_tag(self, T):
+    def _flag_tag(self, T, B=None):
         """Per stage: "-" conv by conv, "s" the stage stores its mean from ONE launch, "f" fused otherwise -- the ResBlocks'
         results stay apart (pair launches, or the 32-channel stage's launch of two block classes)."""
-        return "".join("s" if f == "s" else "f" if f else "-" for f in self._fused_flags(T))
+        return self._plan_tag(T, B).replace("c", "f")
 
-    def _plan_tag(self, T):
+    def _plan_tag(self, T, B=None):
         """What the plan cache keys on: _flag_tag with the two-class form of a stage told apart from the pair launches ("c")."""
-        return "".join(f if f in ("s", "c") else "f" if f else "-" for f in self._fused_flags(T))
+        return str(self._fused_flags(T, self._fv_last_batch if B is None else B))
 
-    # (which stages run fused depends on the policy in force -- after a range overflow the fp32 pair kernels exist at 16 /
-    # 32 channels only -- so plan names and emit functions evaluate _fused_flags when they are used, not here)
-    def _trunk_plan(self, T):
-        return self._plan(lambda: "trunk" + self._plan_tag(T),
-                          lambda pb: self._emit_trunk(pb, SLOT_OUT, self._fused_flags(T), fold_post=True), 80)
+    # The plan getters (NativeModule._resolve; without B: the module's most recent call's).  Which stages run fused depends on the
+    # policy in force (after a range overflow: fp32 pair kernels at 16 / 32 channels only): the flags are _plan's VARIANT.
+    def _flags_plan(self, kind, emit, T, B):
+        B = self._fv_last_batch if B is None else B
+        return self._plan(kind, emit, 80, lambda: self._fused_flags(T, B))
+
+    def _trunk_plan(self, T, B=None):
+        return self._flags_plan("trunk", lambda pb, fused: self._emit_trunk(pb, SLOT_OUT, fused, fold_post=True), T, B)
 
     def _emit_inference(self, pb, fused):
         self._emit_trunk(pb, SLOT_OUT, fused)
 
-    def _minus_plan(self, T):
+    def _minus_plan(self, T, B=None):
         """The inference graph whose last op also writes (output - auxiliary input) to the second output."""
-        def emit(pb):
-            self._emit_inference(pb, self._fused_flags(T))
+        def emit(pb, fused):
+            self._emit_inference(pb, fused)
             pb.subtract_output(0, second=True)
-        return self._plan(lambda: "minus" + self._plan_tag(T), emit, 80)
+        return self._flags_plan("minus", emit, T, B)
 
     def inference_minus(self, x, bias):
         """x [T,80], bias [n] (e.g. the response to an all-zero mel) -> (waveform, waveform - bias), both 1-D,
@@ -507,9 +517,8 @@ class MultiBandHiFiGANGenerator(_HiFiGANBase):
     def _emit_inference(self, pb, fused):
         self._emit_full(pb, fused)
 
-    def _full_plan(self, T):
-        return self._plan(lambda: "inference" + self._plan_tag(T),
-                          lambda pb: self._emit_full(pb, self._fused_flags(T)), 80)
+    def _full_plan(self, T, B=None):
+        return self._flags_plan("inference", self._emit_full, T, B)
 
     def inference(self, x):
         """x [T,80] -> 1-D full-band waveform (trunk + PQMF synthesis, one plan)."""

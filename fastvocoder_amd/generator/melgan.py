@@ -150,8 +150,7 @@ class MelGANGenerator(GradPrecision, _MelGANTrunk):
         self.pqmf = None  # attribute kept for parity with the reference (melgan.py:123)
 
     def _run(self, x, sync=False):
-        return self._run_plan(lambda T: self._plan("trunk", lambda pb: self._emit_layers(pb, SLOT_OUT, self._final_post),
-                                                   self._in_channels), x, sync=sync)
+        return self._run_plan(("trunk", lambda pb: self._emit_layers(pb, SLOT_OUT, self._final_post), self._in_channels), x, sync=sync)
 
     def forward(self, c):
         """c [B,in_channels,T] -> [B, T*prod(upsample_scales)] (channel 0)."""
@@ -159,7 +158,7 @@ class MelGANGenerator(GradPrecision, _MelGANTrunk):
             return _stack_grad.run(self, c)[:, 0, :]
         return self._run(self._prepare(c))[:, 0, :]
 
-    def _minus_plan(self, T):
+    def _minus_plan(self, T, B=None):
         def emit(pb):
             self._emit_layers(pb, SLOT_OUT, self._final_post)
             pb.subtract_output(0, second=True)
@@ -246,8 +245,7 @@ class BasisMelGANGenerator(GradPrecision, _MelGANTrunk):
 
     def _weights(self, x):
         """Trunk + ReLU in its native layout [B, C, F]."""
-        return self._run_plan(lambda T: self._plan("trunk", lambda pb: self._emit_layers(pb, SLOT_OUT, self._final_post),
-                                                   self._in_channels), x)
+        return self._run_plan(("trunk", lambda pb: self._emit_layers(pb, SLOT_OUT, self._final_post), self._in_channels), x)
 
     def _emit_full(self, pb):
         w = pb.tmp()
@@ -257,7 +255,7 @@ class BasisMelGANGenerator(GradPrecision, _MelGANTrunk):
     def _samples(self, x, sync=False):
         """mel [B,C,T] -> [B, (F-1)*L/2 + L] in one plan (weights stay on chip/HBM
         scratch, no [B,F,L] frame tensor)."""
-        return self._run_plan(lambda T: self._plan("full", self._emit_full, self._in_channels), x, sync=sync)[:, 0, :]
+        return self._run_plan(("full", self._emit_full, self._in_channels), x, sync=sync)[:, 0, :]
 
     def _zero_response(self, T):
         """(zero_weight [1,C,F], zero_est [1,1,n]): the generator's response to an all-zero mel of T frames.
@@ -273,7 +271,7 @@ class BasisMelGANGenerator(GradPrecision, _MelGANTrunk):
                 cache.pop(next(iter(cache)))
             dev = self._device()
             zero = torch.zeros((1, self._in_channels, int(T)), dtype=torch.float32, device=dev)
-            est, w = self._exec(lambda T: self._plan("zero", emit, self._in_channels), zero, out2=True)
+            est, w = self._exec(("zero", emit, self._in_channels), zero, out2=True)
             cache[key] = (w, est)
         return cache[key]
 
@@ -293,8 +291,7 @@ class BasisMelGANGenerator(GradPrecision, _MelGANTrunk):
             outs = []
             for inp in (torch.zeros_like(c[:1]), c):
                 w = self._weights(inp)                                   # [B,C,F]
-                src = self._exec(lambda T: self._plan("ola", lambda pb: self.basis_signal.emit(pb, SLOT_IN, SLOT_OUT),
-                                                      w.shape[1]), w)[:, 0, :]
+                src = self._exec(("ola", lambda pb: self.basis_signal.emit(pb, SLOT_IN, SLOT_OUT), w.shape[1]), w)[:, 0, :]
                 outs.append((src[:, : w.shape[2] * hop], w.transpose(1, 2)))
             (zs, zw), (s, w) = outs
             return s - zs, w - zw
@@ -306,10 +303,10 @@ class BasisMelGANGenerator(GradPrecision, _MelGANTrunk):
             pb.subtract_output(0, second=True)                       # SLOT_OUT2 = weight - zero_weight
             self.basis_signal.emit(pb, w, SLOT_OUT)
             pb.subtract_output(1, second=False)                      # SLOT_OUT  = est - zero_est
-        s, w = self._exec(lambda T: self._plan("forward", emit, self._in_channels), c, aux=(zw, zs), out2=True)
+        s, w = self._exec(("forward", emit, self._in_channels), c, aux=(zw, zs), out2=True)
         return s[:, 0, : w.shape[2] * hop], w.transpose(1, 2)
 
-    def _minus_plan(self, T):
+    def _minus_plan(self, T, B=None):
         def emit(pb):
             self._emit_full(pb)
             pb.subtract_output(0, second=True)

@@ -43,11 +43,9 @@ class _Block(NativeModule):
         return 0
 
     def forward(self, x):
-        x = self._prepare(x)
-
         def build(pb):
             self.emit(pb, SLOT_IN, SLOT_OUT, [pb.tmp() for _ in range(self.scratch_slots())])
-        return self._exec(lambda T: self._plan("forward", build, self.channels), x)
+        return self._exec(("forward", build, self.channels), self._prepare(x))
 
 
 class ResBlock1(_Block):
@@ -117,12 +115,12 @@ class ResBlock1(_Block):
     def forward(self, x):
         x = self._prepare(x)
 
-        def fused():     # (evaluated under the policy in force: after a range overflow the fp32 pair kernels exist at 16 / 32 channels only)
-            return x.shape[2] % 4 == 0 and self.fuse_pairs and self.pairs_fusable(self._fv_policy()[0])
+        def variant():   # (evaluated under the policy in force: after a range overflow the fp32 pair kernels exist at 16 / 32 channels only)
+            return "_fused" if x.shape[2] % 4 == 0 and self.fuse_pairs and self.pairs_fusable(self._fv_policy()[0]) else ""
 
-        def build(pb):
-            (self.emit_fused if fused() else self.emit)(pb, SLOT_IN, SLOT_OUT, [pb.tmp() for _ in range(3)])
-        return self._exec(lambda T: self._plan(lambda: "forward_fused" if fused() else "forward", build, self.channels), x)
+        def build(pb, fused):
+            (self.emit_fused if fused else self.emit)(pb, SLOT_IN, SLOT_OUT, [pb.tmp() for _ in range(3)])
+        return self._exec(("forward", build, self.channels, variant), x)
 
 
 class ResBlock2(_Block):
@@ -298,8 +296,7 @@ class LastLinear(NativeModule):
 
     def forward(self, x):
         x = self._prepare(x)
-        return self._exec(lambda T: self._plan("forward", lambda pb: self.emit(pb, SLOT_IN, SLOT_OUT, [pb.tmp()]),
-                                               self.hidden_channel), x)
+        return self._exec(("forward", lambda pb: self.emit(pb, SLOT_IN, SLOT_OUT, [pb.tmp()]), self.hidden_channel), x)
 
 
 class LastLayer(NativeModule):
@@ -322,8 +319,7 @@ class LastLayer(NativeModule):
 
     def forward(self, x):
         x = self._prepare(x)
-        return self._exec(lambda T: self._plan("forward", lambda pb: self.emit(pb, SLOT_IN, SLOT_OUT),
-                                               self.in_channels), x)
+        return self._exec(("forward", lambda pb: self.emit(pb, SLOT_IN, SLOT_OUT), self.in_channels), x)
 
 
 class BasisSignalLayer(NativeModule):
@@ -345,8 +341,7 @@ class BasisSignalLayer(NativeModule):
     def forward(self, weight):
         """weight [B,F,C] (the reference's layout) -> [B,(F-1)*L/2+L]."""
         w = self._prepare(weight).transpose(1, 2).contiguous()
-        out = self._exec(lambda T: self._plan("forward", lambda pb: self.emit(pb, SLOT_IN, SLOT_OUT),
-                                              self.layer.weight.shape[1]), w)
+        out = self._exec(("forward", lambda pb: self.emit(pb, SLOT_IN, SLOT_OUT), self.layer.weight.shape[1]), w)
         return out[:, 0, :]
 
 
@@ -364,9 +359,8 @@ class CausalConvTranspose1d(NativeModule):
 
     def forward(self, x):
         x = self._prepare(x)
-        return self._exec(lambda T: self._plan("forward", lambda pb: pb.conv_transpose(self.deconv, SLOT_IN, SLOT_OUT,
-                                                                                        trim=self.stride),
-                                               self.in_channels), x)
+        return self._exec(("forward", lambda pb: pb.conv_transpose(self.deconv, SLOT_IN, SLOT_OUT, trim=self.stride),
+                           self.in_channels), x)
 
 
 class UpsampleLayer(NativeModule):
@@ -386,5 +380,4 @@ class UpsampleLayer(NativeModule):
 
     def forward(self, x):
         x = self._prepare(x)
-        return self._exec(lambda T: self._plan("forward", lambda pb: pb.upsample_conv(self, SLOT_IN, SLOT_OUT),
-                                               self.in_channel), x)
+        return self._exec(("forward", lambda pb: pb.upsample_conv(self, SLOT_IN, SLOT_OUT), self.in_channel), x)

@@ -676,8 +676,7 @@ def test_one_launch_stage_gives_the_same_bits():
             assert torch.equal(a, b) and torch.equal(last(x), a) and torch.equal(auto(x), a), (T, batch)
             assert torch.equal(one(x[:1].contiguous())[0], a[0])
         # 560 frames are 67 200 columns at 32 channels: one window per block -> one launch; 1000 frames: two -> pair launches
-        auto._fv_batch = 1
-        assert auto._flag_tag(560) == "ffss" and auto._flag_tag(1000) == "fffs" and one._flag_tag(1000) == "ffss"
+        assert auto._flag_tag(560, 1) == "ffss" and auto._flag_tag(1000, 1) == "fffs" and one._flag_tag(1000, 1) == "ffss"
         mel = seeded_mel(123, seed=16)
         assert torch.equal(one.inference(mel), four.inference(mel))
         bias = four.inference(np.zeros_like(mel))
@@ -1007,7 +1006,7 @@ def test_saturated_kernel_forms_vs_aten_port(name, path, B, T):
 
 
 def test_policy_flips_between_same_shape_calls_on_one_module():
-    """The per-call plan route (engine.NativeModule._exec) is keyed on (getter, batch, frames) plus the module state:
+    """The per-call plan route (engine.NativeModule._resolve) is keyed on (getter, batch, frames, policy) plus the module state:
     flipping a policy between two calls of the SAME shape on ONE module must reach a plan built under the new policy,
     and flipping it back must reach the old one again.  HiFi-GAN light, one policy at a time and back; the launch count
     changes wherever the policy changes the graph (range_guard only drops the guard word: same launches), the first

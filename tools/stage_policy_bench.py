@@ -50,7 +50,7 @@ def main():
                     for name, m in models.items():
                         best[name].append(timed(lambda: m(x)))
             print(f"B={B} frames={T}: " + "  ".join(f"{k} {min(v):7.1f}/{sorted(v)[2]:7.1f}" for k, v in best.items())
-                  + f"   tag {models['default']._plan_tag(T)}")
+                  + f"   tag {models['default']._plan_tag(T, B)}")
     for m in models.values():
         assert not m.check_range()
 
