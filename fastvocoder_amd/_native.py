@@ -267,6 +267,9 @@ def lib():
     L.fv_period_conv_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
     L.fv_period_conv_weight_grad_workspace_bytes.restype = i64
     L.fv_period_conv_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
+    L.fv_period_conv_weight_grad_bf16_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.fv_period_conv_weight_grad_bf16_workspace_bytes.restype = i64
+    L.fv_period_conv_weight_grad_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
     L.fv_mpd_first_weight_grad_workspace_bytes.argtypes = [i, i64, i]
     L.fv_mpd_first_weight_grad_workspace_bytes.restype = i64
     L.fv_mpd_first_weight_grad.argtypes = [vp, vp, vp, vp, i, i64, i, vp, ctypes.c_size_t, vp]
@@ -1545,18 +1548,24 @@ PERIOD_WGRAD_UNIT = 32       # flat positions h' p + c per unit of period_wgrad_
 PERIOD_WGRAD_CHUNK = 1024    # ... of its plain path and of the first layer's kernel (kPwChunk)
 
 
-def period_conv_weight_grad_workspace_floats(B, cin, cout, H, period, k, stride):
+def period_conv_weight_grad_workspace_floats(B, cin, cout, H, period, k, stride, precision="f32"):
     """fp32 words of workspace period_conv_weight_grad needs for these shapes
-    (fv_period_conv_weight_grad_workspace_bytes); raises for shapes the entry refuses."""
-    return _workspace_floats(lib().fv_period_conv_weight_grad_workspace_bytes(
+    (fv_period_conv_weight_grad_workspace_bytes; with ``precision="bf16"``
+    fv_period_conv_weight_grad_bf16_workspace_bytes); raises for shapes the entry refuses."""
+    bf16 = _grad_precision("period_conv_weight_grad_workspace_floats", precision) == "bf16"
+    entry = "fv_period_conv_weight_grad_bf16_workspace_bytes" if bf16 else "fv_period_conv_weight_grad_workspace_bytes"
+    return _workspace_floats(getattr(lib(), entry)(
         int(B), int(cin), int(cout), int(H), int(period), int(k), int(stride)))
 
 
-def period_conv_weight_grad(g_pre, x, k, stride, want_dw=True, want_db=False, workspace=None):
+def period_conv_weight_grad(g_pre, x, k, stride, want_dw=True, want_db=False, workspace=None, precision="f32"):
     """The weight (and bias) gradient of a (k, 1) conv along H with zero padding (k - 1) // 2
     (fv_period_conv_weight_grad, two launches): g_pre [B,Cout,(H-1)//stride+1,p] the gradient in front of the
     LeakyReLU, x [B,Cin,H,p] the layer's input -> (dw [Cout,Cin,k] or None, db [Cout] or None).  ``workspace``: an
-    fp32 device tensor to use instead of a fresh one (its contents do not matter)."""
+    fp32 device tensor to use instead of a fresh one (its contents do not matter).  ``precision="bf16"``
+    (fv_period_conv_weight_grad_bf16): dw from the operands rounded to bf16 (nearest even) with fp32 accumulation, db
+    from the un-rounded g_pre; stride 1 for every shape, stride 2 and 3 for Cout >= 64 with Cin k >= 64."""
+    _grad_precision("period_conv_weight_grad", precision)
     if g_pre.dim() != 4 or x.dim() != 4 or g_pre.shape[0] != x.shape[0] or g_pre.shape[3] != x.shape[3]:
         raise NativeError(f"period_conv_weight_grad: g_pre [B,Cout,H',p] and x [B,Cin,H,p] expected, got "
                           f"{tuple(g_pre.shape)} and {tuple(x.shape)}")
@@ -1566,9 +1575,10 @@ def period_conv_weight_grad(g_pre, x, k, stride, want_dw=True, want_db=False, wo
     if stride > 0 and H > 0 and hout != (H - 1) // stride + 1:
         raise NativeError(f"period_conv_weight_grad: {hout} output rows do not belong to an input of {H} rows")
     return _weight_grad_call(
-        "period_conv_weight_grad", "fv_period_conv_weight_grad", (("g_pre", g_pre), ("x", x)), want_dw, want_db,
-        (cout, cin, k), (cout,), (B, cin, cout, H, p, k, stride), workspace,
-        lambda: period_conv_weight_grad_workspace_floats(B, cin, cout, H, p, k, stride))
+        "period_conv_weight_grad",
+        "fv_period_conv_weight_grad_bf16" if precision == "bf16" else "fv_period_conv_weight_grad",
+        (("g_pre", g_pre), ("x", x)), want_dw, want_db, (cout, cin, k), (cout,), (B, cin, cout, H, p, k, stride),
+        workspace, lambda: period_conv_weight_grad_workspace_floats(B, cin, cout, H, p, k, stride, precision))
 
 
 def mpd_first_weight_grad(g_pre, x, want_dw=True, want_db=False, workspace=None):
@@ -1604,7 +1614,7 @@ def weight_norm_grad(dw, v, g, want_dv=True, want_dg=True):
 # the generators' parameter gradient (csrc/gen_grad.hip)
 # ---------------------------------------------------------------------------
 
-GRAD_PRECISIONS = ("f32", "bf16")   # arithmetic of the generators' weight gradients (csrc/gen_grad.hip, gen_grad_bf16.hip)
+GRAD_PRECISIONS = ("f32", "bf16")   # arithmetic of the generators' and the MPD's weight gradients (csrc/gen_grad_bf16.hip)
 
 
 def _grad_precision(name, precision):

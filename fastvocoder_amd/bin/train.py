@@ -6,7 +6,7 @@ step, ``optim.Adam`` clips and updates in three launches, ``data.BatchIterator``
 ``run_train()`` takes the reference's arguments (train.py:478-499) and, for a test or a short run, ``--max_steps``,
 ``--seed``, ``--batch_size``, ``--fixed_length``, ``--discriminator_train_start_steps``, ``--log_step``,
 ``--save_step``, ``--valid_step``, ``--valid_num`` (defaults: hparams), ``--use_mpd``, ``--stack_grad``, ``--basis_grad``,
-``--basis_dataset_path`` and ``--grad_precision``.
+``--basis_dataset_path``, ``--grad_precision`` and ``--discriminator_grad_precision``.
 ``lamda_stft`` (sic) and ``use_feature_map_loss`` come from the yaml, as there.  Both optimizers are
 ``Adam(lr, eps=1e-6)``; ``--use_scheduler 1`` adds ``CosineAnnealingLR(T_max=2500, eta_min=lr / 10)`` to both.
 
@@ -37,6 +37,9 @@ mixed-precision (apex amp) path.  ``--grad_precision bf16`` (absent from the par
 trainable ``--model_name``, with or without ``--gpus``) is this hardware's reduced-precision mode,
 ``Trainer(grad_precision="bf16")``: the convs' weight gradients on the bf16 matrix cores with fp32 accumulation,
 everything else fp32 -- no loss scale, the same checkpoint and log lines, and a checkpoint resumes under either value.
+``--discriminator_grad_precision bf16`` (absent unless given; needs ``--use_mpd 1``) is
+``Trainer(discriminator_grad_precision="bf16")``: the multi-period discriminator's weight gradients in the same
+arithmetic, the MSD and MFD untouched.  It is not stored in the checkpoint either.
 
 Several GPUs of one node: ``--gpus N`` (absent from the parsed arguments unless given) with no ``WORLD_SIZE`` in the
 environment starts ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...`` as a child -- the parent
@@ -128,6 +131,9 @@ def build_parser():
     parser.add_argument("--grad_precision", type=str, default=argparse.SUPPRESS,
                         help="f32 (default) or bf16: the generator's weight gradients on the bf16 matrix cores, fp32 "
                              "accumulation; everything else stays fp32")
+    parser.add_argument("--discriminator_grad_precision", type=str, default=argparse.SUPPRESS,
+                        help="f32 (default) or bf16: the multi-period discriminator's weight gradients on the bf16 "
+                             "matrix cores (needs --use_mpd 1); the MSD and MFD stay fp32")
     parser.add_argument("--gpus", type=int, default=argparse.SUPPRESS,
                         help="data-parallel training over this many GPUs of the node, one rank each (--batch_size is "
                              "per rank)")
@@ -153,6 +159,12 @@ def check_args(args):
                  "--grad_precision bf16 is the reduced-precision mode (bf16 weight gradients, no loss scaling)")
     if getattr(args, "grad_precision", "f32") not in ("f32", "bf16"):
         sys.exit(f"MODE=train: --grad_precision must be f32 or bf16, got {args.grad_precision!r}")
+    if getattr(args, "discriminator_grad_precision", "f32") not in ("f32", "bf16"):
+        sys.exit("MODE=train: --discriminator_grad_precision must be f32 or bf16, got "
+                 f"{args.discriminator_grad_precision!r}")
+    if getattr(args, "discriminator_grad_precision", "f32") == "bf16" and not args.use_mpd:
+        sys.exit("MODE=train: --discriminator_grad_precision bf16 needs --use_mpd 1: only the multi-period "
+                 "discriminator's weight gradients have bf16 kernels")
     if not args.config:
         sys.exit("MODE=train: --config (the model's yaml file) is required")
     for name in ("batch_size", "fixed_length", "log_step", "save_step", "valid_step"):
@@ -339,6 +351,9 @@ def _run(args, group, rank, world, device):
     use_mpd = bool(args.use_mpd)
     if checkpoint is not None and "discriminator" in checkpoint:
         use_mpd = discriminator_uses_mpd(checkpoint["discriminator"])
+        if not use_mpd and getattr(args, "discriminator_grad_precision", "f32") == "bf16":
+            sys.exit(f"MODE=train: --discriminator_grad_precision bf16 needs the multi-period discriminator, and "
+                     f"--checkpoint_path {args.checkpoint_path} was trained without it")
     discriminator = Discriminator(use_mpd=use_mpd).to(device)
     say(f"Number of Parameters: {sum(p.numel() for p in model.parameters())}")
 
@@ -383,7 +398,9 @@ def _run(args, group, rank, world, device):
                       discriminator_train_start_steps=args.discriminator_train_start_steps,
                       grad_clip_thresh=hp.grad_clip_thresh, lambda_adv=hp.lambda_adv, lambda_fm=hp.lambda_fm,
                       stack_grad=bool(getattr(args, "stack_grad", 0)), basis_grad=bool(getattr(args, "basis_grad", 0)),
-                      process_group=group, grad_precision=getattr(args, "grad_precision", "f32"))
+                      process_group=group,
+                      discriminator_grad_precision=getattr(args, "discriminator_grad_precision", "f32"),
+                      grad_precision=getattr(args, "grad_precision", "f32"))
     spf = samples_per_frame(model, pqmf)
 
     say("Load data to buffer")

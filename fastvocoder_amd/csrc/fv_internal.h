@@ -359,6 +359,12 @@ inline MpdView mpd_view(int64_t T, int period) {
     const int64_t H = (T + n_pad) / period;
     return MpdView{n_pad, H, period_conv_rows(H)};
 }
+// fv_period_conv_weight_grad's argument checks (mpd_wgrad.hip; 0 or the error code, the message set) and the shapes it
+// runs as a GEMM on the matrix cores; its bf16 twin (gen_grad_bf16.hip) refuses and routes by the same two
+int period_wgrad_check(int B, int Cin, int Cout, int H, int period, int k, int stride);
+inline bool period_wgrad_gemm_shape(int Cin, int Cout, int k) {
+    return Cout >= 64 && (int64_t)Cin * k >= 64 && (Cout + 127) / 128 <= 65535;
+}
 int launch_pack_convk(const float* w1, const float* w2, const float* ws, float* packed, int C, int* range_flag, hipStream_t s);
 // y = post(W1 lrelu(x, slope) + W2 x2 + bias + res), 1-tap convs C -> C with split-f16 operands (convg_kernel): member 0
 // uses x, x2, w1 (fv_pack_conv1x1_2src_split_f16 image), b1, res, y, y_act; C = 128, 256 or 512

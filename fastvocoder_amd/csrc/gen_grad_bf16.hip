@@ -7,7 +7,15 @@
 // arguments (GgWArgs), the checks and the split / record / combine scheme are those of gen_grad.hip; no atomics, no
 // waiting between workgroups, the split count a function of the shape alone.
 //
-// gen_wgrad_bf16_kernel<MT, REFLECT>: 4 waves own MT rows x 128 columns (the wave / fragment split of WgTile<MT>) and
+// The multi-period discriminator's (k, 1) convs take the same kernel (fv_period_conv_weight_grad_bf16): on the flat axis
+// q = h' p + c of a [B, C, H, p] map a period conv is a 1-D conv whose column (ci, j) reads
+//     x_flat[b, ci, pos],   pos = stride (q - q mod p) + q mod p + (j - pad) p,   zero unless 0 <= pos < H p
+// (pos = (stride h' + j - pad) p + c: inside the map exactly when the row is).  At stride 1 that is the dilated conv
+// with dil = p and zero padding pad p, as it stands; at stride 2 and 3 it is GgWArgs' pos = t sB + j dB - pad with
+// dB = p, pad = pad p and one more term, -(sB - 1)(t mod p), which the template period P > 0 adds (P = 0: none, the
+// generators' code unchanged).
+//
+// gen_wgrad_bf16_kernel<MT, REFLECT, P>: 4 waves own MT rows x 128 columns (the wave / fragment split of WgTile<MT>) and
 // consume units of 64 reduction steps on v_mfma_f32_32x32x16_bf16 (MT >= 32) or v_mfma_f32_16x16x32_bf16 (MT = 16).
 //
 // LDS image: as[row][32 words], bs[column][32 words], a word = two bf16.  Which step of the unit sits at which k of
@@ -88,8 +96,9 @@ struct BfTile : WgTile<MT> {
     }
 };
 
-// grid (x_tiles + bias blocks, ceil(M / MT), S); REFLECT: the B source is read through a reflection pad (pad < TB)
-template <int MT, bool REFLECT>
+// grid (x_tiles + bias blocks, ceil(M / MT), S); REFLECT: the B source is read through a reflection pad (pad < TB);
+// P > 0: step t reads from t sB - (sB - 1)(t mod P), the flat axis of a period-P map under a row stride of sB
+template <int MT, bool REFLECT, int P = 0>
 __global__ __launch_bounds__(kWgThreads) void gen_wgrad_bf16_kernel(GgWArgs a) {
     using T = BfTile<MT>;
     constexpr int ARows = MT / 8;
@@ -126,7 +135,8 @@ __global__ __launch_bounds__(kWgThreads) void gen_wgrad_bf16_kernel(GgWArgs a) {
             const int t = t0 + e * kBfW;
             const bool live = t < a.TR;
             const int tc = live ? t : a.TR - 1;           // (tc sB stays inside the source row: no overflow)
-            const int tb = tc * a.sB;
+            int tb = tc * a.sB;
+            if constexpr (P > 0) tb -= (a.sB - 1) * (tc % P);
             ok_a[e] = ok_b[e] = 0;
 #pragma unroll
             for (int i = 0; i < ARows; ++i) {
@@ -187,6 +197,63 @@ static int gg_wgrad_bf16(const GgWPlan& p, const GgWArgs& a, float* dw, float* d
     });
 }
 
+// the periodic variant: the strided layers of DiscriminatorP, 64 output channels and more (gg_rows: 64 or 128)
+static int gg_wgrad_bf16_period(const GgWPlan& p, const GgWArgs& a, float* dw, float* db, void* workspace,
+                                size_t workspace_bytes, const char* who, hipStream_t st, int period) {
+    return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, who, st, kBfBiasBlocks,
+                        [&](int rows, dim3 grid, const GgWArgs& ka) {
+#define GG_PERIOD(P)                                                                                               \
+    case P:                                                                                                        \
+        if (rows == 128) hipLaunchKernelGGL((gen_wgrad_bf16_kernel<128, false, P>), grid, dim3(kWgThreads), 0, st, ka); \
+        else hipLaunchKernelGGL((gen_wgrad_bf16_kernel<64, false, P>), grid, dim3(kWgThreads), 0, st, ka);         \
+        break;
+        switch (period) {
+            GG_PERIOD(2) GG_PERIOD(3) GG_PERIOD(5) GG_PERIOD(7) GG_PERIOD(11)
+        }
+#undef GG_PERIOD
+    });
+}
+
+// the plan and the arguments of a period conv's weight gradient on the flat axis; `strided`: the periodic variant
+struct PbPlan : GgWPlan {
+    bool strided;
+    GgWArgs a;
+};
+
+static int period_wgrad_bf16_plan(int B, int Cin, int Cout, int H, int period, int k, int stride, PbPlan* p) {
+    const char* who = "period_conv_weight_grad_bf16";
+    if (int rc = period_wgrad_check(B, Cin, Cout, H, period, k, stride)) return rc;
+    const int pad = (k - 1) / 2 * period;
+    p->strided = stride > 1;
+    if (!p->strided) {                                    // a dilated conv1d on [B, C, H p]
+        if (int rc = dilated_wgrad_plan(B, Cin, Cout, H * period, k, period, pad, p, kBfTK)) return rc;
+        p->a = gg_dilated_args(nullptr, nullptr, Cin, Cout, H * period, k, period, pad);
+        return 0;
+    }
+    if (!period_wgrad_gemm_shape(Cin, Cout, k))
+        return fail(FV_ERR_UNSUPPORTED, "%s: stride %d needs Cout >= 64 and Cin k >= 64 (Cin=%d Cout=%d k=%d); the fp32 "
+                    "entry takes every shape", who, stride, Cin, Cout, k);
+    const int64_t big = Cin > Cout ? Cin : Cout;
+    if (big * ((int64_t)H + k) * period >= (int64_t)1 << 30)
+        return fail(FV_ERR_INVALID_ARG, "%s: a map of %lld x %d x %d words is too long", who, (long long)big, H, period);
+    const int Hout = (H - 1) / stride + 1;
+    gg_wgrad_plan(B, Cout, (int64_t)Cin * k, Hout * period, Cout, p, kBfTK);
+    GgWArgs a{};
+    a.M = Cout;
+    a.TR = Hout * period;
+    a.Cb = Cin;
+    a.TB = H * period;
+    a.k = k;
+    a.sB = stride;
+    a.dB = period;
+    a.pad = pad;
+    a.Cbias = Cout;
+    a.Tbias = a.TR;
+    a.bias_scale = 1;
+    p->a = a;
+    return 0;
+}
+
 }  // namespace fv
 
 using namespace fv;
@@ -229,6 +296,24 @@ int fv_conv_transpose1d_weight_grad_bf16(const float* g, const float* xa, float*
     gg_wgrad_plan(B, Cin, (int64_t)Cout * k, Tin, Cout, &p, kBfTK);
     return gg_wgrad_bf16(p, gg_convt_args(g, xa, Cin, Cout, Tin, (int)Tout, k, stride, pad), dw, db, workspace,
                          workspace_bytes, "conv_transpose1d_weight_grad_bf16", (hipStream_t)stream, false);
+}
+
+int64_t fv_period_conv_weight_grad_bf16_workspace_bytes(int B, int Cin, int Cout, int H, int period, int k, int stride) {
+    PbPlan p;
+    if (int rc = period_wgrad_bf16_plan(B, Cin, Cout, H, period, k, stride, &p)) return rc;
+    return (int64_t)p.bytes();
+}
+
+int fv_period_conv_weight_grad_bf16(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout,
+                                    int H, int period, int k, int stride, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    const char* who = "period_conv_weight_grad_bf16";
+    PbPlan p;
+    if (int rc = period_wgrad_bf16_plan(B, Cin, Cout, H, period, k, stride, &p)) return rc;
+    p.a.a = p.a.bias_src = g_pre;
+    p.a.b = x;
+    if (p.strided) return gg_wgrad_bf16_period(p, p.a, dw, db, workspace, workspace_bytes, who, (hipStream_t)stream, period);
+    return gg_wgrad_bf16(p, p.a, dw, db, workspace, workspace_bytes, who, (hipStream_t)stream, false);
 }
 
 }  // extern "C"

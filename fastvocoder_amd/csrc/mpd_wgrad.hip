@@ -192,7 +192,8 @@ struct PwPlan : WgSplit {
     dim3 grid;
 };
 
-static int period_wgrad_plan(int B, int Cin, int Cout, int H, int period, int k, int stride, PwPlan* p) {
+// what fv_period_conv_weight_grad and its bf16 twin (gen_grad_bf16.hip) refuse alike (fv_internal.h)
+int period_wgrad_check(int B, int Cin, int Cout, int H, int period, int k, int stride) {
     if (!mpd_period_ok(period))
         return fail(FV_ERR_UNSUPPORTED, "period_conv_weight_grad: period %d (2, 3, 5, 7 or 11)", period);
     if (Cin < 1 || Cout < 1 || k < 1 || k > kPwMaxK || k % 2 == 0 || stride < 1 || stride > 3 ||
@@ -205,11 +206,16 @@ static int period_wgrad_plan(int B, int Cin, int Cout, int H, int period, int k,
     if (big * ((int64_t)H + kPwMaxK) * period >= (int64_t)1 << 31)
         return fail(FV_ERR_INVALID_ARG, "period_conv_weight_grad: a map of %lld x %d x %d words is too long",
                     (long long)big, H, period);
+    return 0;
+}
+
+static int period_wgrad_plan(int B, int Cin, int Cout, int H, int period, int k, int stride, PwPlan* p) {
+    if (int rc = period_wgrad_check(B, Cin, Cout, H, period, k, stride)) return rc;
     const int Hout = (H - 1) / stride + 1;                // padding (k - 1) / 2
     const int64_t N = (int64_t)Cin * k, Nout = (int64_t)Hout * period;
     p->Hout = Hout;
     p->R = (int64_t)Cout * N + Cout;
-    p->mfma = Cout >= 64 && N >= 64 && (Cout + kPwTile - 1) / kPwTile <= 65535;
+    p->mfma = period_wgrad_gemm_shape(Cin, Cout, k);
     if (p->mfma) {
         p->nch = (int)((Nout + kPwTK - 1) / kPwTK);
         p->U = (int64_t)B * p->nch;

@@ -1,5 +1,6 @@
 """The reference's Discriminator (model/discriminator/discriminator.py): MSD + MFD, and with ``use_mpd=True`` the
 MPD the reference keeps one commented line away (discriminator.py:11, 16), registered first as there."""
+from .. import _native
 from .common import DiscriminatorModule, NotDifferentiable, checked_input
 from .mfd import MultiResolutionSTFTDiscriminator
 from .mpd import MultiPeriodDiscriminator
@@ -14,6 +15,22 @@ class Discriminator(NotDifferentiable, DiscriminatorModule):
             self.mpd = MultiPeriodDiscriminator()
         self.msd = MelGANMultiScaleDiscriminator()
         self.mfd = MultiResolutionSTFTDiscriminator()
+
+    @property
+    def grad_precision(self):
+        """The arithmetic of the MPD's weight gradients (``self.mpd.grad_precision``); "f32" without the MPD.  The MSD
+        and MFD weight gradients have fp32 kernels only."""
+        return self.mpd.grad_precision if self.use_mpd else "f32"
+
+    @grad_precision.setter
+    def grad_precision(self, value):
+        if value not in _native.GRAD_PRECISIONS:
+            raise ValueError(f"{type(self).__name__}.grad_precision: {value!r} ('f32' or 'bf16')")
+        if self.use_mpd:
+            self.mpd.grad_precision = value
+        elif value != "f32":
+            raise NotImplementedError("Discriminator(use_mpd=False).grad_precision = 'bf16': the MSD / MFD weight "
+                                      "gradients have no bf16 kernels (only the MPD's do)")
 
     def min_length(self):
         """Shortest input every discriminator accepts (1680 samples with the default resolutions)."""

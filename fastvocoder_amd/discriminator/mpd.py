@@ -5,7 +5,14 @@ Conv2d((k, 1)) layers along H.  Here the first layer reads the raw waveform (fv_
 address arithmetic), the three strided 32 -> 128 -> 512 -> 1024 layers run on the fp32 matrix cores
 (fv_period_conv, csrc/mpd.hip), and the two stride-1 layers are dilated conv1ds on the flattened axis n = h p + c
 (fv_conv1d_fused with dilation p and zero padding 2 p / p).  The convs live in the reference's containers
-(``convs.<j>``, ``conv_post``) so that ``state_dict`` keys and 4-D shapes match; their ``forward`` is never called."""
+(``convs.<j>``, ``conv_post``) so that ``state_dict`` keys and 4-D shapes match; their ``forward`` is never called.
+
+``grad_precision`` ("f32" | "bf16", on DiscriminatorP and MultiPeriodDiscriminator) is the arithmetic of the weight
+gradients on the parameters' graph (loss.discriminator_step_terms(..., period_grad=True)): "bf16" rounds both operands
+of layers 1-5 to bf16 (nearest even) and multiplies them on the bf16 matrix cores with fp32 accumulation
+(fv_period_conv_weight_grad_bf16, csrc/gen_grad_bf16.hip).  The first layer, every bias gradient, the forwards, the
+data gradients, the input gradient of loss.generator_adversarial_terms, the parameters and the optimizer state stay
+fp32.  Read at backward time: nothing cached depends on it."""
 import torch
 from torch.nn.utils import weight_norm
 
@@ -36,6 +43,18 @@ class DiscriminatorP(NotDifferentiable, DiscriminatorModule):
     """mpd.py:131-164."""
 
     _MATERIALIZE_GRADS = False    # a map without a gradient arrives as None: _input_grad skips the layers above it
+    _grad_precision = "f32"
+
+    @property
+    def grad_precision(self):
+        """"f32" (the default) or "bf16": the arithmetic of ``_param_grad``'s weight gradients of layers 1-5."""
+        return self._grad_precision
+
+    @grad_precision.setter
+    def grad_precision(self, value):
+        if value not in _native.GRAD_PRECISIONS:
+            raise ValueError(f"{type(self).__name__}.grad_precision: {value!r} ('f32' or 'bf16')")
+        self._grad_precision = value
 
     def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
         super().__init__()
@@ -147,6 +166,7 @@ class DiscriminatorP(NotDifferentiable, DiscriminatorModule):
         """The backward of _LayersParamGrad, the layer walk of _input_grad: per layer g_pre once (fv_disc_map_grad;
         conv_post has no activation), the weight and bias gradient (fv_period_conv_weight_grad from g_pre and the
         layer's stored input, fv_mpd_first_weight_grad from the waveform; csrc/mpd_wgrad.hip), the weight-norm adjoint
+        under ``grad_precision = "bf16"`` fv_period_conv_weight_grad_bf16 for layers 1-5), the weight-norm adjoint
         on the 4-D ``weight_v`` viewed as [Cout, Cin k], and the data gradient for the layer below with the kernels
         of _input_grad.  ``need``: one flag per entry of ``params``; the walk ends at the lowest layer with a flagged
         parameter.  The waveform gets no gradient on this route (``need_x`` is refused: loss.discriminator_step_terms
@@ -155,6 +175,7 @@ class DiscriminatorP(NotDifferentiable, DiscriminatorModule):
         if need_x:
             raise NotImplementedError("DiscriminatorP: the parameters' graph carries no input gradient")
         p = self.period
+        precision = self.grad_precision                     # read here, at backward time
         layers = self._native_grad_layers()
         convs = self._convs()
         first, wanted = self._param_plan(need)
@@ -177,7 +198,7 @@ class DiscriminatorP(NotDifferentiable, DiscriminatorModule):
                     dw, db = _native.mpd_first_weight_grad(g_pre, x, want_dw, want_db)
                 else:
                     dw, db = _native.period_conv_weight_grad(g_pre, outs[l - 1], conv.kernel_size[0], conv.stride[0],
-                                                             want_dw, want_db)
+                                                             want_dw, want_db, precision=precision)
                 self._param_store(conv, params, need, at, dw, db, out)
             if l == stop:
                 break
@@ -214,6 +235,21 @@ class MultiPeriodDiscriminator(NotDifferentiable, DiscriminatorModule):
     def __init__(self):
         super().__init__()
         self.discriminators = torch.nn.ModuleList([DiscriminatorP(p) for p in PERIODS])
+
+    @property
+    def grad_precision(self):
+        """The five periods' ``grad_precision``: setting it sets all of them; reading it needs them to agree."""
+        values = {d.grad_precision for d in self.discriminators}
+        if len(values) != 1:
+            raise ValueError(f"MultiPeriodDiscriminator.grad_precision: the periods disagree ({sorted(values)})")
+        return values.pop()
+
+    @grad_precision.setter
+    def grad_precision(self, value):
+        if value not in _native.GRAD_PRECISIONS:
+            raise ValueError(f"{type(self).__name__}.grad_precision: {value!r} ('f32' or 'bf16')")
+        for d in self.discriminators:
+            d.grad_precision = value
 
     def min_length(self):
         """Shortest input every period's reflect pad accepts."""

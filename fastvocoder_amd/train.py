@@ -29,6 +29,10 @@ Reduced-precision gradients: ``Trainer(..., grad_precision="bf16")`` sets the ge
 in fp32 on the bf16 matrix cores; the forward, the data and bias gradients, the parameters and the optimizer state stay
 fp32, so there is no loss scale and no skipped step, and a checkpoint resumes under either value.  The reference's
 mixed-precision flag (apex amp O1: fp16 activations with dynamic loss scaling) is not part of this loop.
+``Trainer(..., discriminator_grad_precision="bf16")`` does the same to ``Discriminator(use_mpd=True)``: the weight
+gradients of the multi-period discriminator's layers 1-5 (discriminator/mpd.py), nothing of the MSD and MFD, whose
+weight gradients have fp32 kernels only (a discriminator without the MPD refuses it).  The two keywords are
+independent: ``grad_precision`` alone leaves the discriminator in fp32.
 
 Data-parallel training: ``Trainer(..., process_group=<a torch.distributed group>)`` hands the group to both optimizer
 steps (``optim.Adam.step(process_group=...)``: the gradients of the ranks' shards are averaged with one collective over
@@ -75,7 +79,7 @@ class Trainer:
     def __init__(self, model, discriminator, optimizer, discriminator_optimizer, scheduler=None,
                  discriminator_scheduler=None, pqmf=None, *, lambda_stft, use_feature_map_loss,
                  discriminator_train_start_steps, grad_clip_thresh, lambda_adv=1.0, lambda_fm=1.0, stack_grad=False,
-                 basis_grad=False, process_group=None, grad_precision="f32"):
+                 basis_grad=False, process_group=None, discriminator_grad_precision="f32", grad_precision="f32"):
         for opt, name in ((optimizer, "optimizer"), (discriminator_optimizer, "discriminator_optimizer")):
             if not isinstance(opt, Adam):
                 raise TypeError(f"{name} must be a fastvocoder_amd.optim.Adam (its step clips and updates in three "
@@ -90,6 +94,12 @@ class Trainer:
         elif grad_precision != "f32":
             raise NotImplementedError(f"{type(model).__name__} has no grad_precision: its weight gradients are not "
                                       "the generators' kernels")
+        if hasattr(type(discriminator), "grad_precision"):
+            # ValueError for anything but "f32" / "bf16"; NotImplementedError for "bf16" without the MPD
+            discriminator.grad_precision = discriminator_grad_precision
+        elif discriminator_grad_precision != "f32":
+            raise NotImplementedError(f"{type(discriminator).__name__} has no grad_precision: its weight gradients "
+                                      "have fp32 kernels only")
         self.model, self.discriminator = model, discriminator
         self.optimizer, self.discriminator_optimizer = optimizer, discriminator_optimizer
         self.scheduler, self.discriminator_scheduler = scheduler, discriminator_scheduler

@@ -1002,6 +1002,28 @@ int fv_conv_transpose1d_weight_grad_bf16(const float* g, const float* xa, float*
                                          size_t workspace_bytes, void* stream);
 
 /*
+ * The multi-period discriminator's weight gradients with bf16 operands (DiscriminatorP.grad_precision = "bf16");
+ * additions of ABI 18, no existing entry changes.
+ *
+ * fv_period_conv_weight_grad_bf16: fv_period_conv_weight_grad on rounded operands, the same arguments,
+ *     dw[co, ci, j] = sum_{b, h', c} bf16(g_pre[b, co, h', c]) * bf16(x[b, ci, stride h' + j - (k - 1) / 2, c])
+ *     db[co]        = sum_{b, h', c} g_pre[b, co, h', c]                                         (un-rounded)
+ * fp32 accumulation of exact products, a padding row stays zero, no scaling: the arithmetic and the kernels of
+ * fv_conv1d_weight_grad_dilated_bf16.  On the flat axis q = h' period + c a period conv is a 1-D conv: stride 1 (any
+ * Cout, conv_post's 1 included) IS that entry on the views [B, C, H period] with dil = period and zero padding
+ * (k - 1) / 2 period; stride 2 and 3 read position stride (q - q mod period) + q mod period + (j - (k - 1) / 2) period
+ * and run for the shapes the fp32 entry sends to its matrix-core kernel, Cout >= 64 with Cin k >= 64 -- any other
+ * strided shape returns FV_ERR_UNSUPPORTED (DiscriminatorP has none; the fp32 entry takes them).  Units of 64 flat
+ * positions; S a function of the shape alone, identical calls return identical bits, the workspace's contents do not
+ * matter, no atomics, no waiting between workgroups.  Whatever fv_period_conv_weight_grad refuses is refused with the
+ * same code; a map of 2^30 words and more returns FV_ERR_INVALID_ARG.  Two launches.
+ */
+int64_t fv_period_conv_weight_grad_bf16_workspace_bytes(int B, int Cin, int Cout, int H, int period, int k, int stride);
+int fv_period_conv_weight_grad_bf16(const float* g_pre, const float* x, float* dw, float* db, int B, int Cin, int Cout,
+                                    int H, int period, int k, int stride, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
+/*
  * The head of Basis-MelGAN for training (model/generator/basis_melgan.py:140-162 under bin/train.py:64-95, and the
  * weight term of loss.py:39-40); additions of ABI 18, no existing entry changes.  The trunk runs ONCE over B + 1 rows,
  * the last one the response to the all-zero mel, and ends in the raw Y [B+1, C, F]; the reference's second pass and

@@ -5,10 +5,14 @@ and Discriminator(use_mpd=True), against the same step in eager torch autograd o
 (weight norm folded inside the graph, F.conv2d / F.conv1d / F.avg_pool1d / F.leaky_relu; the STFT magnitude, a constant
 of the parameters, from the library in both), at B rows of n samples (default 32 x 33 600, the training shape); and
 each new weight-gradient call alone, per period and layer, with the rate its 2 B H' p Cout Cin k operations amount to.
+``--grad-precision bf16`` prints the bf16 figures beside the fp32 figures of the same run: per layer and period
+``bf16_ms`` / ``bf16_tflops`` (fv_period_conv_weight_grad_bf16; the first layer has none), and per step row with an MPD
+``bf16_ms`` / ``bf16_peak_mb`` (``grad_precision = "bf16"`` on the module).
 Prints one JSON line.  Timing: tools/mel_bench.ms_per_call (warm-up, device events around back-to-back calls, best of
 three).
 
     python tools/mpd_wgrad_bench.py [--samples 33600] [--batch 32] [--target-s 0.5] [--skip-kernels] [--modules mpd,discriminator,discriminator_mpd]
+        [--grad-precision bf16]
 """
 import argparse
 import json
@@ -102,8 +106,9 @@ def eager_step_fn(m):
     return step
 
 
-def kernel_rows(B, n, target_s, dev):
-    """Each new weight-gradient call alone (both launches, with the bias gradient), per period and layer."""
+def kernel_rows(B, n, target_s, dev, bf16=False):
+    """Each new weight-gradient call alone (both launches, with the bias gradient), per period and layer; ``bf16``:
+    the bf16 entry on the same tensors beside it."""
     rows = []
     rs = np.random.RandomState(3)
     for p in PERIODS:
@@ -126,12 +131,21 @@ def kernel_rows(B, n, target_s, dev):
             rows.append({"period": p, "layer": li, "cin": cin, "cout": cout, "k": k, "stride": stride, "H": H,
                          "Hout": hout, "workspace_mb": round(ws.numel() * 4 / 2 ** 20, 2), "ms": round(ms, 4),
                          "gflop": round(gflop, 3), "tflops": round(gflop / ms, 2)})
+            if bf16:
+                del ws
+                ws = torch.empty(_native.period_conv_weight_grad_workspace_floats(B, cin, cout, H, p, k, stride, "bf16"),
+                                 device=dev)
+                fn16 = lambda a: _native.period_conv_weight_grad(a[0], a[1], k, stride, True, True, ws,  # noqa: E731
+                                                                 precision="bf16")
+                ms16 = ms_per_call(fn16, (g, x), target_s)
+                rows[-1].update(bf16_workspace_mb=round(ws.numel() * 4 / 2 ** 20, 2), bf16_ms=round(ms16, 4),
+                                bf16_tflops=round(gflop / ms16, 2), bf16_speedup=round(ms / ms16, 2))
             del g, x, ws
         torch.cuda.empty_cache()
     return rows
 
 
-def step_row(name, B, n, target_s, dev):
+def step_row(name, B, n, target_s, dev, bf16=False):
     kind = "mpd" if name == "mpd" else "discriminator"
     m = MultiPeriodDiscriminator() if name == "mpd" else Discriminator(use_mpd=name == "discriminator_mpd")
     sd = seeded_discriminator_state_dict(kind, 13, **({"use_mpd": True} if name == "discriminator_mpd" else {}))
@@ -155,6 +169,11 @@ def step_row(name, B, n, target_s, dev):
     row = {"module": name, "fused_ms": round(ms_per_call(fused_step, (est, real), target_s), 3),
            "fused_forward_only_ms": round(ms_per_call(forward_only, (est, real), target_s), 3),
            "fused_peak_mb": round(peak_mb(fused_step, (est, real)), 1)}
+    if bf16 and name != "discriminator":                     # (without the MPD there is nothing in bf16)
+        m.grad_precision = "bf16"
+        row.update(bf16_ms=round(ms_per_call(fused_step, (est, real), target_s), 3),
+                   bf16_peak_mb=round(peak_mb(fused_step, (est, real)), 1))
+        m.grad_precision = "f32"
     loss_f = float(fused_step((est, real)).detach())
     g_fused = {k: q.grad.clone() for k, q in m.named_parameters()}
     try:
@@ -179,17 +198,20 @@ def main():
     ap.add_argument("--target-s", type=float, default=0.5)
     ap.add_argument("--skip-kernels", action="store_true")
     ap.add_argument("--modules", default="mpd,discriminator,discriminator_mpd")
+    ap.add_argument("--grad-precision", choices=("f32", "bf16"), default="f32")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "mpd_wgrad_bench measures on the ROCm device"
     dev = torch.device("cuda", torch.cuda.current_device())
-    B, n = args.batch, args.samples
+    B, n, bf16 = args.batch, args.samples, args.grad_precision == "bf16"
     out = {"tool": "mpd_wgrad_bench", "what": "discriminator step (two forwards + backward)", "B": B, "n": n,
-           "device": torch.cuda.get_device_name(dev)}
+           "grad_precision": args.grad_precision, "device": torch.cuda.get_device_name(dev)}
     if not args.skip_kernels:
-        out["kernels"] = kernel_rows(B, n, args.target_s, dev)
+        out["kernels"] = kernel_rows(B, n, args.target_s, dev, bf16)
         out["kernels_ms_total"] = round(sum(r["ms"] for r in out["kernels"]), 3)
         out["kernels_gflop_total"] = round(sum(r["gflop"] for r in out["kernels"]), 1)
-    out["steps"] = [step_row(name, B, n, args.target_s, dev) for name in args.modules.split(",") if name]
+        if bf16:                                              # the first layer's fp32 call counts in both totals
+            out["kernels_bf16_ms_total"] = round(sum(r.get("bf16_ms", r["ms"]) for r in out["kernels"]), 3)
+    out["steps"] = [step_row(name, B, n, args.target_s, dev, bf16) for name in args.modules.split(",") if name]
     print(json.dumps(out))
 
 
