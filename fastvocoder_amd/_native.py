@@ -368,6 +368,11 @@ def lib():
     L.fv_debug_pair_widths.argtypes = [i, i, i, i, i, ctypes.POINTER(i), i, ctypes.POINTER(ctypes.c_int64)]
     L.fv_debug_mrf_class_schedule.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint)]
     L.fv_debug_mrf_stage_class_f16.argtypes = [vp, vp, vp, i, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp]
+    L.fv_debug_launch_log.argtypes = [i]
+    L.fv_debug_launch_log_read.argtypes = [ctypes.c_char_p, i64]
+    L.fv_debug_launch_log_read.restype = i64
+    L.fv_debug_kernel_name.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64]
+    L.fv_debug_kernel_name.restype = i64
     L.fv_mrf_stage_classes_f16.argtypes = [vp, vp, vp, vp, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp, vp]
     L.fv_plan_add_mrf_stage_classes_f16.argtypes = [vp, i, i, i, vp, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64]
     L.fv_plan_set_group.argtypes = [vp, i]
@@ -454,6 +459,57 @@ class GuardWord:
 def tuning_set(key, value):
     """Test / tuning hook (fv_tuning_set): one of the launchers' switches, process-wide."""
     check(lib().fv_tuning_set(key.encode(), int(value)))
+
+
+class launch_log:
+    """Test hook (fv_debug_launch_log, host only): `with launch_log() as log:` records every kernel the library launches
+    inside the block; afterwards `log.kernels` is a dict of instantiation name ("convh_kernel<2, 2, 1>") to launch count,
+    in first-launch order.  Process-wide and not nestable: entering while one is active raises.  Launches of child
+    processes are not seen, nor which block or path inside a kernel ran."""
+    _active = False
+
+    def __init__(self):
+        self.kernels = {}
+
+    def __enter__(self):
+        if launch_log._active:
+            raise NativeError("launch_log is already active (the log is process-wide and does not nest)")
+        check(lib().fv_debug_launch_log(1))
+        launch_log._active = True
+        return self
+
+    def __exit__(self, *exc):
+        L = lib()
+        launch_log._active = False
+        check(L.fv_debug_launch_log(0))
+        need = L.fv_debug_launch_log_read(None, 0)
+        buf = ctypes.create_string_buffer(max(int(need), 1))
+        L.fv_debug_launch_log_read(buf, need)
+        self.kernels = {}
+        for line in buf.raw[:need].decode().splitlines():
+            count, name = line.split("\t", 1)
+            self.kernels[name] = self.kernels.get(name, 0) + int(count)
+        return False
+
+    def operators(self):
+        """`kernels` without the weight-preparation kernels (pack_*, row_scale_kernel, fold_*): a module packs its weights
+        inside its first call, which is not the operator a test asks about."""
+        return {name: n for name, n in self.kernels.items()
+                if not name.startswith(("pack_", "fold_")) and name not in ("row_scale_kernel", "transpose_basis_kernel")}
+
+    def families(self):
+        """The operators' names without template arguments: {"convh_kernel", ...}."""
+        return {name.split("<", 1)[0] for name in self.operators()}
+
+
+def kernel_name(symbol):
+    """fv_debug_kernel_name: the launch log's name for a dynamic symbol of the library (a kernel handle or its host stub)."""
+    L = lib()
+    sym = symbol.encode() if isinstance(symbol, str) else symbol
+    need = L.fv_debug_kernel_name(sym, None, 0)
+    buf = ctypes.create_string_buffer(max(int(need), 1))
+    L.fv_debug_kernel_name(sym, buf, need)
+    return buf.raw[:need].decode()
 
 
 def debug_pair_schedule(n_items, cost, nblk, mode=0, three_members=False):

@@ -14,6 +14,9 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <cxxabi.h>
+#include <dlfcn.h>
+
 #include "api_internal.h"
 #include "launch_host.hpp"
 
@@ -29,6 +32,63 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     g_err = buf;
     return code ? code : FV_ERR_INVALID_ARG;
+}
+
+
+// ---------------------------------------------------------------------------
+// launch log (fv_debug_launch_log; FV_KERNEL_LAUNCH of fv_internal.h): which kernels ran, host side only
+// ---------------------------------------------------------------------------
+std::atomic<int> g_launch_log_on{0};
+static std::mutex g_launch_log_mutex;
+static std::vector<std::pair<const void*, long long>> g_launch_log;   // (kernel handle, launches) in first-seen order
+
+void launch_log_note(const void* handle) {
+    std::lock_guard<std::mutex> lock(g_launch_log_mutex);
+    for (auto& e : g_launch_log)
+        if (e.first == handle) {
+            ++e.second;
+            return;
+        }
+    g_launch_log.emplace_back(handle, 1);
+}
+
+// "void fv::convh_kernel<2, 2, 1>(fv::PairParams)" -> "convh_kernel<2, 2, 1>": the return type, every "fv::", the host
+// stub's "__device_stub__" and the argument list go.  Parentheses inside template arguments (enumerators print as casts)
+// are not the argument list: that one opens outside every <>.
+// Limit: where __cxa_demangle gives up (a parameter type it does not know), only a NON-TEMPLATE kernel "_ZN2fv<length><name>E..."
+// is named right; a templated kernel with such a parameter would lose its template arguments, and two of them would share a
+// name -- tools/kernel_census.py built_kernels() refuses a library in which two stubs get one name.
+static std::string kernel_display_name(const char* mangled) {
+    int status = 0;
+    char* dem = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+    std::string s = (status == 0 && dem) ? dem : mangled;
+    free(dem);
+    if (!(status == 0) && s.compare(0, 3, "_ZN") == 0) {
+        // a demangler that does not know a parameter type (_Float16 pointers: "PDF16_") gives up on the whole symbol.  Those
+        // kernels are plain functions "_ZN2fv<length><name>E<parameters>": the last <length><name> of the nested name is theirs
+        size_t at = 3, name_at = 0, name_len = 0;
+        while (at < s.size() && isdigit((unsigned char)s[at])) {
+            size_t len = 0;
+            while (at < s.size() && isdigit((unsigned char)s[at])) len = len * 10 + (size_t)(s[at++] - '0');
+            if (at + len > s.size()) break;
+            name_at = at;
+            name_len = len;
+            at += len;
+        }
+        if (name_len) s = s.substr(name_at, name_len);
+    }
+    for (const char* drop : {"__device_stub__", "fv::"})
+        for (size_t at; (at = s.find(drop)) != std::string::npos;) s.erase(at, strlen(drop));
+    size_t begin = 0, end = s.size();
+    int depth = 0;
+    for (size_t i = 0; i < s.size(); ++i) {
+        const char c = s[i];
+        if (c == '<') ++depth;
+        else if (c == '>') --depth;
+        else if (depth == 0 && c == ' ') begin = i + 1;
+        else if (depth == 0 && c == '(') { end = i; break; }
+    }
+    return s.substr(begin, end - begin);
 }
 
 // ---------------------------------------------------------------------------
@@ -1302,6 +1362,47 @@ int fv_tuning_set(const char* key, int value) {
     return fail(FV_ERR_INVALID_ARG, "tuning_set: unknown key '%s'", key);
 }
 
+int fv_debug_launch_log(int on) {
+    if (on != 0 && on != 1) return fail(FV_ERR_INVALID_ARG, "debug_launch_log: on = %d (0 or 1)", on);
+    std::lock_guard<std::mutex> lock(fv::g_launch_log_mutex);
+    if (on) fv::g_launch_log.clear();
+    fv::g_launch_log_on.store(on, std::memory_order_relaxed);
+    return 0;
+}
+
+int64_t fv_debug_launch_log_read(char* buf, int64_t cap) {
+    std::string text;
+    {
+        std::lock_guard<std::mutex> lock(fv::g_launch_log_mutex);
+        for (const auto& e : fv::g_launch_log) {
+            Dl_info info;
+            std::string name;
+            if (dladdr(e.first, &info) && info.dli_sname && info.dli_saddr == e.first) name = fv::kernel_display_name(info.dli_sname);
+            else {                                  // a handle without an exported symbol: still one line, never a merged count
+                char raw[32];
+                snprintf(raw, sizeof(raw), "?%p", e.first);
+                name = raw;
+            }
+            text += std::to_string(e.second) + "\t" + name + "\n";
+        }
+    }
+    if (buf && cap > 0) {
+        const size_t n = text.size() < (size_t)cap ? text.size() : (size_t)cap;
+        memcpy(buf, text.data(), n);
+    }
+    return (int64_t)text.size();
+}
+
+int64_t fv_debug_kernel_name(const char* symbol, char* buf, int64_t cap) {
+    if (!symbol) return fail(FV_ERR_INVALID_ARG, "debug_kernel_name: null symbol");
+    const std::string name = fv::kernel_display_name(symbol);
+    if (buf && cap > 0) {
+        const size_t n = name.size() < (size_t)cap ? name.size() : (size_t)cap;
+        memcpy(buf, name.data(), n);
+    }
+    return (int64_t)name.size();
+}
+
 int fv_debug_pair_schedule(int n_members, const int* n_items, const int* cost, int nblk, int mode, int three_members,
                            unsigned* table) {
     if (!n_items || !cost || !table) return fail(FV_ERR_INVALID_ARG, "debug_pair_schedule: null argument");
@@ -1364,14 +1465,14 @@ int fv_profile_bracket_cost(void* stream, int n, double* ms_per_bracket) {
     ScopedEvents events((size_t)n + 4);
     if (int rc = events.create()) return rc;
     const std::vector<hipEvent_t>& ev = events.ev;
-    for (int i = 0; i < 8; ++i) hipLaunchKernelGGL(profile_null_kernel, dim3(1), dim3(64), 0, s);
+    for (int i = 0; i < 8; ++i) FV_KERNEL_LAUNCH(profile_null_kernel, dim3(1), dim3(64), 0, s);
     FV_HIP(hipEventRecord(ev[n], s));
     for (int i = 0; i < n; ++i) {
-        hipLaunchKernelGGL(profile_null_kernel, dim3(1), dim3(64), 0, s);
+        FV_KERNEL_LAUNCH(profile_null_kernel, dim3(1), dim3(64), 0, s);
         FV_HIP(hipEventRecord(ev[i], s));
     }
     FV_HIP(hipEventRecord(ev[n + 1], s));
-    for (int i = 0; i < n; ++i) hipLaunchKernelGGL(profile_null_kernel, dim3(1), dim3(64), 0, s);
+    for (int i = 0; i < n; ++i) FV_KERNEL_LAUNCH(profile_null_kernel, dim3(1), dim3(64), 0, s);
     FV_HIP(hipEventRecord(ev[n + 2], s));
     FV_HIP(hipEventSynchronize(ev[n + 2]));
     float with = 0.f, without = 0.f;
@@ -1427,7 +1528,7 @@ int fv_profile_mfma_f16_rate(float* scratch, long long scratch_floats, int launc
     const int first = launches / 2;
     for (int i = 0; i < launches; ++i) {
         if (i == first) FV_HIP(hipEventRecord(e0, s));
-        hipLaunchKernelGGL(profile_mfma_f16_kernel, dim3(blocks), dim3(512), 0, s, scratch, iters);
+        FV_KERNEL_LAUNCH(profile_mfma_f16_kernel, dim3(blocks), dim3(512), 0, s, scratch, iters);
     }
     FV_HIP(hipEventRecord(e1, s));
     FV_HIP(hipEventSynchronize(e1));

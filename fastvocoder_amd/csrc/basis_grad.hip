@@ -202,7 +202,7 @@ int fv_basis_head_forward(const float* Y, float* D, int B, int C, int F, void* s
     if (int rc = bg_check("basis_head_forward", B, C, F)) return rc;
     if (!Y || !D || Y == D) return fail(FV_ERR_INVALID_ARG, "basis_head_forward: null tensor, or D aliases Y");
     const int64_t n = (int64_t)C * F;
-    hipLaunchKernelGGL(basis_head_forward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Y,
+    FV_KERNEL_LAUNCH(basis_head_forward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Y,
                        D, B, n);
     FV_HIP(hipGetLastError());
     return 0;
@@ -220,7 +220,7 @@ int fv_basis_head_grad(const float* g_est, const float* g_w, const float* Y, con
         return fail(FV_ERR_INVALID_ARG, "basis_head_grad: g_Y aliases an input");
     const BasisHeadGeom g = basis_head_geom(C, F, L);
     BhArgs a = {g_est, g_w, Y, basis, g_Y, B, C, F, L, g.hop, g.span, g.n};
-    hipLaunchKernelGGL(basis_head_grad_kernel, dim3(g.gx, g.gy), dim3(kBhThreads), g.lds_bytes, (hipStream_t)stream, a);
+    FV_KERNEL_LAUNCH(basis_head_grad_kernel, dim3(g.gx, g.gy), dim3(kBhThreads), g.lds_bytes, (hipStream_t)stream, a);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -240,10 +240,10 @@ int fv_basis_weight_l1(const float* D, const float* target, float* out, int B, i
         return fail(FV_ERR_INVALID_ARG, "basis_weight_l1: workspace of %zu bytes, needs %zu (8-byte aligned)",
                     workspace_bytes, need);
     double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(basis_l1_kernel, dim3(g.gx, g.gy, g.gz), dim3(kBhThreads), 0, (hipStream_t)stream, D, target, part,
+    FV_KERNEL_LAUNCH(basis_l1_kernel, dim3(g.gx, g.gy, g.gz), dim3(kBhThreads), 0, (hipStream_t)stream, D, target, part,
                        C, F);
     FV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(basis_l1_finish_kernel, dim3(1), dim3(kBhThreads), 0, (hipStream_t)stream, part, g.blocks, g.count,
+    FV_KERNEL_LAUNCH(basis_l1_finish_kernel, dim3(1), dim3(kBhThreads), 0, (hipStream_t)stream, part, g.blocks, g.count,
                        out);
     FV_HIP(hipGetLastError());
     return 0;
@@ -255,7 +255,7 @@ int fv_basis_weight_l1_grad(const float* D, const float* target, const float* co
     if (!D || !target || !g || g == D || g == target)
         return fail(FV_ERR_INVALID_ARG, "basis_weight_l1_grad: null tensor, or g aliases an input");
     const BasisL1Geom geo = basis_l1_geom(B, C, F);
-    hipLaunchKernelGGL(basis_l1_grad_kernel, dim3(geo.gx, geo.gy, geo.gz), dim3(kBhThreads), 0, (hipStream_t)stream, D,
+    FV_KERNEL_LAUNCH(basis_l1_grad_kernel, dim3(geo.gx, geo.gy, geo.gz), dim3(kBhThreads), 0, (hipStream_t)stream, D,
                        target, coef, g, C, F, (float)geo.count);
     FV_HIP(hipGetLastError());
     return 0;

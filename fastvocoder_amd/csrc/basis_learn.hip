@@ -234,9 +234,9 @@ int fv_basis_encode(const float* wav, const float* enc, float* W, int B, int64_t
     const size_t lds = sizeof(float) * (size_t)(kLeTF + 1) * (L / 2);
     const unsigned gx = (unsigned)(((int64_t)F + kLeTF - 1) / kLeTF);
     if (C <= 16)
-        hipLaunchKernelGGL(basis_encode_kernel<16>, dim3(gx, 1, (unsigned)B), dim3(kLeThreads), lds, (hipStream_t)stream, a);
+        FV_KERNEL_LAUNCH(basis_encode_kernel<16>, dim3(gx, 1, (unsigned)B), dim3(kLeThreads), lds, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(basis_encode_kernel<32>, dim3(gx, (unsigned)((C + 127) / 128), (unsigned)B), dim3(kLeThreads),
+        FV_KERNEL_LAUNCH(basis_encode_kernel<32>, dim3(gx, (unsigned)((C + 127) / 128), (unsigned)B), dim3(kLeThreads),
                            lds, (hipStream_t)stream, a);
     FV_HIP(hipGetLastError());
     return 0;
@@ -268,7 +268,7 @@ int fv_basis_learn_grad(const float* wav, const float* g_est, const float* W, co
         return rc;
     LgArgs a = {wav, g_est, W, basis, static_cast<float*>(workspace), n, (int64_t)F * p.hop, p.U, p.R,
                 C, F, L, p.hop, p.S, p.nft, d_enc != nullptr, d_basis != nullptr};
-    hipLaunchKernelGGL(basis_learn_grad_kernel, dim3(p.gx, p.gy, (unsigned)p.S), dim3(kLeThreads), p.lds_bytes,
+    FV_KERNEL_LAUNCH(basis_learn_grad_kernel, dim3(p.gx, p.gy, (unsigned)p.S), dim3(kLeThreads), p.lds_bytes,
                        (hipStream_t)stream, a);
     FV_HIP(hipGetLastError());
     return launch_wgrad_combine(a.ws, d_enc, d_basis, (int64_t)C * L, C * L, p.R, p.S, (hipStream_t)stream);

@@ -1022,7 +1022,7 @@ int launch_sum3_geom(const Sum3Params& sp, size_t lds, int grid_x, hipStream_t s
     if (lds > 64 * 1024)
         FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid_x, sp.p[0].B), dim3(64 * WN), lds, s, sp);
+    FV_KERNEL_LAUNCH(kern, dim3(grid_x, sp.p[0].B), dim3(64 * WN), lds, s, sp);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -1217,7 +1217,7 @@ int launch_geom(const ConvParams& p, size_t lds, int grid_x, hipStream_t s) {
         if (lds > 64 * 1024)                                                                  \
             FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                   \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, p);                                     \
+        FV_KERNEL_LAUNCH(kern, grid, block, lds, s, p);                                       \
     } while (0)
 #define FV_LAUNCH_DIL(KT)                                  \
     switch (p.dil) {                                       \
@@ -1278,7 +1278,7 @@ int launch_group_geom(const GroupParams& gp, size_t lds, int grid_x, int B, int 
         if (lds > 64 * 1024)                                                                   \
             FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                    \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, gp);                                     \
+        FV_KERNEL_LAUNCH(kern, grid, block, lds, s, gp);                                       \
     } while (0)
     switch (dil) {
         case 1: FV_GROUP(1); break;

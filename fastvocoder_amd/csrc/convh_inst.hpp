@@ -10,7 +10,7 @@ int launch_convh_geom(const PairParams& p, int dil, size_t lds, hipStream_t s) {
     do {                                                                                       \
         auto kern = convh_kernel<CG, NFW, DIL>;                                                \
         if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc; \
-        hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(512), lds, s, p);                          \
+        FV_KERNEL_LAUNCH(kern, dim3(p.nblk), dim3(512), lds, s, p);                            \
     } while (0)
     switch (dil) {
         case 1: FV_CONVH(1); break;

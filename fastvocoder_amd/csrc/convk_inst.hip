@@ -61,12 +61,12 @@ int launch_pack_convk(const float* w1, const float* w2, const float* ws, float* 
     const int image = 5 * (C / 32) * C * 32;             // floats
     const int total = image * 2;
     if (C == 256) {
-        hipLaunchKernelGGL(pack_convk2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w1, w2, ws,
+        FV_KERNEL_LAUNCH(pack_convk2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w1, w2, ws,
                            reinterpret_cast<_Float16*>(packed), packed + image, packed + image + C, range_flag);
         FV_HIP(hipGetLastError());
         return 0;
     }
-    hipLaunchKernelGGL(pack_convk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w1, w2, ws,
+    FV_KERNEL_LAUNCH(pack_convk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w1, w2, ws,
                        reinterpret_cast<_Float16*>(packed), packed + image, packed + image + C, C, range_flag);
     FV_HIP(hipGetLastError());
     return 0;
@@ -76,7 +76,7 @@ template <int C, int DIL, int NM>
 static int launch_k2(const ConvKParams& p, hipStream_t s) {
     typedef ConvK2Geom<C, DIL, NM> G;
     if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(convk2_kernel<C, DIL, NM>), (size_t)G::LDS_BYTES)) return rc;
-    hipLaunchKernelGGL((convk2_kernel<C, DIL, NM>), dim3(p.nblk), dim3(512), (size_t)G::LDS_BYTES, s, p);
+    FV_KERNEL_LAUNCH((convk2_kernel<C, DIL, NM>), dim3(p.nblk), dim3(512), (size_t)G::LDS_BYTES, s, p);
     FV_HIP(hipGetLastError());
     return 0;
 }

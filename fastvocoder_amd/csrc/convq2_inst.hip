@@ -4,7 +4,7 @@ namespace fv {
 template <int DIL, int C>
 int launch_convq2_dil(const PairParams& p, size_t lds, hipStream_t s) {
     if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(convq2_kernel<DIL, C>), lds)) return rc;
-    hipLaunchKernelGGL((convq2_kernel<DIL, C>), dim3(p.nblk), dim3(512), lds, s, p);
+    FV_KERNEL_LAUNCH((convq2_kernel<DIL, C>), dim3(p.nblk), dim3(512), lds, s, p);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -5,7 +5,7 @@ template <int DIL, int NH>
 static int launch_convs2_dil(const PairParams& p, size_t lds, hipStream_t s) {
     auto kern = convs2_kernel<DIL, NH>;
     if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(512), lds, s, p);
+    FV_KERNEL_LAUNCH(kern, dim3(p.nblk), dim3(512), lds, s, p);
     FV_HIP(hipGetLastError());
     return 0;
 }

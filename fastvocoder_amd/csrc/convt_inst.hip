@@ -5,10 +5,10 @@ namespace fv {
 int launch_convt_geom(const PairParams& p, int cg, size_t lds, hipStream_t s) {
     if (cg == 2) {
         if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(convt_kernel<2>), lds)) return rc;
-        hipLaunchKernelGGL(convt_kernel<2>, dim3(p.nblk), dim3(512), lds, s, p);
+        FV_KERNEL_LAUNCH(convt_kernel<2>, dim3(p.nblk), dim3(512), lds, s, p);
     } else {
         if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(convt_kernel<4>), lds)) return rc;
-        hipLaunchKernelGGL(convt_kernel<4>, dim3(p.nblk), dim3(512), lds, s, p);
+        FV_KERNEL_LAUNCH(convt_kernel<4>, dim3(p.nblk), dim3(512), lds, s, p);
     }
     FV_HIP(hipGetLastError());
     return 0;

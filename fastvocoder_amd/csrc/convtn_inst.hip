@@ -18,7 +18,7 @@ __global__ void pack_convtn_kernel(const float* __restrict__ w, _Float16* __rest
 }
 
 int launch_pack_convtn(const float* w, float* packed, const float* inv, int* range_flag, hipStream_t s) {
-    hipLaunchKernelGGL(pack_convtn_kernel, dim3(16), dim3(256), 0, s, w, reinterpret_cast<_Float16*>(packed), inv, range_flag);
+    FV_KERNEL_LAUNCH(pack_convtn_kernel, dim3(16), dim3(256), 0, s, w, reinterpret_cast<_Float16*>(packed), inv, range_flag);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -48,7 +48,7 @@ int launch_convtn(const PairParams& pp, int Tout, hipStream_t s) {
     p.guard = pp.guard;
     {
         ProfileScope prof(s, FV_KERNEL_CONVT, convt_work(pp.B, pp.T, Tout, kTnCin, kTnCout, 4, mb.add1 ? (mb.add2 ? 3 : 2) : 1, mb.y_act != nullptr));
-        hipLaunchKernelGGL(convtn_kernel, dim3((unsigned)(p.n_tiles * p.B)), dim3(256), 0, s, p);
+        FV_KERNEL_LAUNCH(convtn_kernel, dim3((unsigned)(p.n_tiles * p.B)), dim3(256), 0, s, p);
     }
     FV_HIP(hipGetLastError());
     return 0;

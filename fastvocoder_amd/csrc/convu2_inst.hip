@@ -6,7 +6,7 @@ static int launch_convu2_nch(const PairParams& p, hipStream_t s) {
     typedef ConvU2Geom<NCH> G;
     auto kern = convu2_kernel<NCH>;
     if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kern), G::LDS)) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(512), G::LDS, s, p);
+    FV_KERNEL_LAUNCH(kern, dim3(p.nblk), dim3(512), G::LDS, s, p);
     FV_HIP(hipGetLastError());
     return 0;
 }

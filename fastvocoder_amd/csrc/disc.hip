@@ -110,10 +110,10 @@ int launch_grouped_conv1d(const float* x, const float* w, const float* bias, flo
     const dim3 grid((unsigned)((Tout + kDiscTT - 1) / kDiscTT), (unsigned)(G * chunks), (unsigned)B);
     const size_t lds = grouped_conv_lds_bytes(k, s, ocb);
     if (ocb == 16)
-        hipLaunchKernelGGL(grouped_conv_kernel<16>, grid, dim3(kDiscThreads), lds, st, x, w, bias, y, Cin, Cout, Tin,
+        FV_KERNEL_LAUNCH(grouped_conv_kernel<16>, grid, dim3(kDiscThreads), lds, st, x, w, bias, y, Cin, Cout, Tin,
                            Tout, k, s, pad, slope);
     else
-        hipLaunchKernelGGL(grouped_conv_kernel<4>, grid, dim3(kDiscThreads), lds, st, x, w, bias, y, Cin, Cout, Tin,
+        FV_KERNEL_LAUNCH(grouped_conv_kernel<4>, grid, dim3(kDiscThreads), lds, st, x, w, bias, y, Cin, Cout, Tin,
                            Tout, k, s, pad, slope);
     FV_HIP(hipGetLastError());
     return 0;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void avg_pool_kernel(const float* __restrict__
 
 int launch_avg_pool1d(const float* x, float* y, int rows, int64_t Tin, int64_t Tout, int k, int s, int p,
                       hipStream_t st) {
-    hipLaunchKernelGGL(avg_pool_kernel, dim3((unsigned)((Tout + 255) / 256), (unsigned)rows), dim3(256), 0, st, x, y,
+    FV_KERNEL_LAUNCH(avg_pool_kernel, dim3((unsigned)((Tout + 255) / 256), (unsigned)rows), dim3(256), 0, st, x, y,
                        Tin, Tout, k, s, p);
     FV_HIP(hipGetLastError());
     return 0;
@@ -235,9 +235,9 @@ int launch_disc_score_sums(const float* const* e, const float* const* r, const i
         c += (n[m] + kScoreChunk - 1) / kScoreChunk;
     }
     a.chunks = c;
-    hipLaunchKernelGGL(score_sums_kernel, dim3((unsigned)c, (unsigned)B), dim3(kScoreThreads), 0, st, a, ws);
+    FV_KERNEL_LAUNCH(score_sums_kernel, dim3((unsigned)c, (unsigned)B), dim3(kScoreThreads), 0, st, a, ws);
     FV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(score_combine_kernel, dim3((unsigned)M, (unsigned)B), dim3(64), 0, st, ws, a, B, out);
+    FV_KERNEL_LAUNCH(score_combine_kernel, dim3((unsigned)M, (unsigned)B), dim3(64), 0, st, ws, a, B, out);
     FV_HIP(hipGetLastError());
     return 0;
 }

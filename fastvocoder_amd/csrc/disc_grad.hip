@@ -112,7 +112,7 @@ int launch_grouped_conv1d_input_grad(const float* g_up, const float* g_map, cons
     if (lds > 65536) return fail(FV_ERR_UNSUPPORTED, "grouped_conv1d_input_grad: k=%d exceeds a block's shared memory", k);
     const dim3 grid((unsigned)((nq + QT - 1) / QT), (unsigned)G, (unsigned)B);
     if (G > 65535) return fail(FV_ERR_UNSUPPORTED, "grouped_conv1d_input_grad: %d groups (65535 at most)", G);
-    hipLaunchKernelGGL(grouped_input_grad_kernel, grid, dim3(threads), lds, st, g_up, g_map, y, w, dx, Cin, Cout, Tin,
+    FV_KERNEL_LAUNCH(grouped_input_grad_kernel, grid, dim3(threads), lds, st, g_up, g_map, y, w, dx, Cin, Cout, Tin,
                        Tout, k, s, pad, slope, occ);
     FV_HIP(hipGetLastError());
     return 0;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void map_grad_kernel(const float* __restrict__
 
 int launch_disc_map_grad(const float* g_up, const float* g_map, const float* y, float* g_pre, int64_t n, float slope,
                          hipStream_t st) {
-    hipLaunchKernelGGL(map_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g_up, g_map, y, g_pre, n,
+    FV_KERNEL_LAUNCH(map_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g_up, g_map, y, g_pre, n,
                        slope);
     FV_HIP(hipGetLastError());
     return 0;
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restri
 }
 
 int launch_reflect_pad_fold(const float* gp, float* dx, int rows, int64_t T, int P, hipStream_t st) {
-    hipLaunchKernelGGL(reflect_fold_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)rows), dim3(256), 0, st, gp, dx,
+    FV_KERNEL_LAUNCH(reflect_fold_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)rows), dim3(256), 0, st, gp, dx,
                        T, P);
     FV_HIP(hipGetLastError());
     return 0;
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void avg_pool_grad_kernel(const float* __restr
 
 int launch_avg_pool1d_input_grad(const float* g, float* dx, int rows, int64_t Tin, int64_t Tout, int k, int s, int p,
                                  hipStream_t st) {
-    hipLaunchKernelGGL(avg_pool_grad_kernel, dim3((unsigned)((Tin + 255) / 256), (unsigned)rows), dim3(256), 0, st, g,
+    FV_KERNEL_LAUNCH(avg_pool_grad_kernel, dim3((unsigned)((Tin + 255) / 256), (unsigned)rows), dim3(256), 0, st, g,
                        dx, Tin, Tout, k, s, p);
     FV_HIP(hipGetLastError());
     return 0;
@@ -237,7 +237,7 @@ int launch_disc_score_grad(const float* const* e, const float* const* r, float* 
         a.map[m] = ScoreGradMap{e[m], r[m], g[m], n[m], c, coef[3 * m], 2.f * coef[3 * m + 1], 2.f * coef[3 * m + 2]};
         c += (n[m] + kScoreGradChunk - 1) / kScoreGradChunk;
     }
-    hipLaunchKernelGGL(score_grad_kernel, dim3((unsigned)c, (unsigned)B), dim3(kScoreGradThreads), 0, st, a);
+    FV_KERNEL_LAUNCH(score_grad_kernel, dim3((unsigned)c, (unsigned)B), dim3(kScoreGradThreads), 0, st, a);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -321,7 +321,7 @@ static int grouped_wgrad_plan(int B, int Cin, int Cout, int Tin, int k, int stri
 }
 
 int launch_wgrad_combine(const float* ws, float* dw, float* db, int64_t MN, int Cout, int64_t R, int S, hipStream_t st) {
-    hipLaunchKernelGGL(wgrad_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, ws, dw, db, MN, Cout, R,
+    FV_KERNEL_LAUNCH(wgrad_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, ws, dw, db, MN, Cout, R,
                        S);
     FV_HIP(hipGetLastError());
     return 0;
@@ -337,16 +337,16 @@ static int wgrad_run(const WgPlan& p, WgArgs a, float* dw, float* db, void* work
     a.with_bias = db != nullptr;
     switch (p.path) {
     case kWgMfma:
-        hipLaunchKernelGGL(dense_wgrad_mfma_kernel, p.grid, dim3(kWgThreads), p.lds, st, a);
+        FV_KERNEL_LAUNCH(dense_wgrad_mfma_kernel, p.grid, dim3(kWgThreads), p.lds, st, a);
         break;
     case kWgPlain:
-        hipLaunchKernelGGL(dense_wgrad_plain_kernel, p.grid, dim3(kWgThreads), 0, st, a);
+        FV_KERNEL_LAUNCH(dense_wgrad_plain_kernel, p.grid, dim3(kWgThreads), 0, st, a);
         break;
     case kWgGrouped16:
-        hipLaunchKernelGGL(grouped_wgrad_kernel<16>, p.grid, dim3(p.threads), p.lds, st, a, p.TT);
+        FV_KERNEL_LAUNCH(grouped_wgrad_kernel<16>, p.grid, dim3(p.threads), p.lds, st, a, p.TT);
         break;
     default:
-        hipLaunchKernelGGL(grouped_wgrad_kernel<4>, p.grid, dim3(p.threads), p.lds, st, a, p.TT);
+        FV_KERNEL_LAUNCH(grouped_wgrad_kernel<4>, p.grid, dim3(p.threads), p.lds, st, a, p.TT);
         break;
     }
     FV_HIP(hipGetLastError());
@@ -410,7 +410,7 @@ int fv_weight_norm_grad(const float* dw, const float* v, const float* g, float* 
     if (!dw || !v || !g || (!dv && !dg) || dv == dw || dv == v || dim0 <= 0 || inner <= 0)
         return fail(FV_ERR_INVALID_ARG, "weight_norm_grad: null tensor, aliasing, dim0=%d or inner=%lld", dim0,
                     (long long)inner);
-    hipLaunchKernelGGL(weight_norm_grad_kernel, dim3(dim0), dim3(256), 0, (hipStream_t)stream, dw, v, g, dv, dg, inner);
+    FV_KERNEL_LAUNCH(weight_norm_grad_kernel, dim3(dim0), dim3(256), 0, (hipStream_t)stream, dw, v, g, dv, dg, inner);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <vector>
 #include <stdint.h>
 
@@ -19,6 +20,19 @@ int fail(int code, const char* fmt, ...);
     } while (0)
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// Every kernel launch of the library goes through FV_KERNEL_LAUNCH (same arguments as hipLaunchKernelGGL, which appears
+// nowhere else).  Test hook fv_debug_launch_log (api.hip): while it is on, the kernel's host handle is counted in a
+// process-wide table, so that a test can prove WHICH kernel produced its numbers.  Off (the default) the launch path pays
+// one relaxed atomic load: no lock, no allocation, no device work; no launch parameter changes either way.
+extern std::atomic<int> g_launch_log_on;
+void launch_log_note(const void* handle);
+#define FV_KERNEL_LAUNCH(kernel, ...)                                                  \
+    do {                                                                              \
+        if (::fv::g_launch_log_on.load(std::memory_order_relaxed))                    \
+            ::fv::launch_log_note((const void*)(kernel));                             \
+        hipLaunchKernelGGL(kernel, __VA_ARGS__);                                      \
+    } while (0)
 
 // argument checks shared by the operator entries (api.hip) and the pack entries (pack.hip)
 int check_conv_args(int Cin, int Cout, int k, int dil);

@@ -255,8 +255,8 @@ static int gg_wgrad_f32(const GgWPlan& p, const GgWArgs& a, float* dw, float* db
                         const char* who, hipStream_t st, bool reflect = false) {
     return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, who, st, 1, [&](int rows, dim3 grid, const GgWArgs& ka) {
 #define GG_WGRAD(MT)                                                                                          \
-    if (reflect) hipLaunchKernelGGL((gen_wgrad_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, ka);         \
-    else hipLaunchKernelGGL((gen_wgrad_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, ka)
+    if (reflect) FV_KERNEL_LAUNCH((gen_wgrad_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, ka);           \
+    else FV_KERNEL_LAUNCH((gen_wgrad_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, ka)
         GG_BY_ROWS(rows, GG_WGRAD)
 #undef GG_WGRAD
     });
@@ -339,7 +339,7 @@ int fv_conv1d_input_grad_reflect(const float* g, const float* wt, float* dxa, in
     if (gx > 0x7fffffff) return fail(FV_ERR_INVALID_ARG, "%s: B Tin = %lld", who, (long long)a.Q);
     const dim3 grid((unsigned)gx, (unsigned)((Cin + MT - 1) / MT));
     const hipStream_t st = (hipStream_t)stream;
-#define GG_DGRAD(MT) hipLaunchKernelGGL(gen_dgrad_reflect_kernel<MT>, grid, dim3(kWgThreads), 0, st, a)
+#define GG_DGRAD(MT) FV_KERNEL_LAUNCH(gen_dgrad_reflect_kernel<MT>, grid, dim3(kWgThreads), 0, st, a)
     GG_BY_ROWS(MT, GG_DGRAD)
 #undef GG_DGRAD
     FV_HIP(hipGetLastError());
@@ -369,7 +369,7 @@ int fv_conv_transpose1d_input_grad(const float* g, const float* w, float* dxa, i
     if (gx > 0x7fffffff) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_input_grad: B Tin = %lld", (long long)a.Q);
     const dim3 grid((unsigned)gx, (unsigned)((Cin + MT - 1) / MT));
     const hipStream_t st = (hipStream_t)stream;
-#define GG_DGRAD(MT) hipLaunchKernelGGL(gen_dgrad_kernel<MT>, grid, dim3(kWgThreads), 0, st, a)
+#define GG_DGRAD(MT) FV_KERNEL_LAUNCH(gen_dgrad_kernel<MT>, grid, dim3(kWgThreads), 0, st, a)
     GG_BY_ROWS(MT, GG_DGRAD)
 #undef GG_DGRAD
     FV_HIP(hipGetLastError());
@@ -398,7 +398,7 @@ int fv_conv_transpose1d_weight_grad(const float* g, const float* xa, float* dw, 
 
 int fv_tanh_grad(const float* g, const float* y, float* out, int64_t n, void* stream) {
     if (int rc = gg_elementwise_check("tanh_grad", g, y, out, n)) return rc;
-    hipLaunchKernelGGL(tanh_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, y, out,
+    FV_KERNEL_LAUNCH(tanh_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, y, out,
                        n);
     FV_HIP(hipGetLastError());
     return 0;
@@ -408,7 +408,7 @@ int fv_residual_merge_grad(const float* g_y, const float* d, const float* x, con
                            float slope, void* stream) {
     if (int rc = gg_elementwise_check("residual_merge_grad", g_y, d, out, n)) return rc;
     if (!x) return fail(FV_ERR_INVALID_ARG, "residual_merge_grad: null tensor");
-    hipLaunchKernelGGL(residual_merge_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    FV_KERNEL_LAUNCH(residual_merge_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        g_y, d, x, acc, out, n, slope);
     FV_HIP(hipGetLastError());
     return 0;
@@ -417,7 +417,7 @@ int fv_residual_merge_grad(const float* g_y, const float* d, const float* x, con
 int fv_grad_div(const float* g, float* out, int64_t n, float div, void* stream) {
     if (int rc = gg_elementwise_check("grad_div", g, g, out, n)) return rc;
     if (!(div != 0.f)) return fail(FV_ERR_INVALID_ARG, "grad_div: div = %g", (double)div);
-    hipLaunchKernelGGL(grad_div_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, out, n,
+    FV_KERNEL_LAUNCH(grad_div_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, out, n,
                        div);
     FV_HIP(hipGetLastError());
     return 0;

@@ -190,8 +190,8 @@ static int gg_wgrad_bf16(const GgWPlan& p, const GgWArgs& a, float* dw, float* d
     return gg_wgrad_run(p, a, dw, db, workspace, workspace_bytes, who, st, kBfBiasBlocks,
                         [&](int rows, dim3 grid, const GgWArgs& ka) {
 #define GG_WGRAD(MT)                                                                                               \
-    if (reflect) hipLaunchKernelGGL((gen_wgrad_bf16_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, ka);         \
-    else hipLaunchKernelGGL((gen_wgrad_bf16_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, ka)
+    if (reflect) FV_KERNEL_LAUNCH((gen_wgrad_bf16_kernel<MT, true>), grid, dim3(kWgThreads), 0, st, ka);           \
+    else FV_KERNEL_LAUNCH((gen_wgrad_bf16_kernel<MT, false>), grid, dim3(kWgThreads), 0, st, ka)
         GG_BY_ROWS(rows, GG_WGRAD)
 #undef GG_WGRAD
     });
@@ -204,8 +204,8 @@ static int gg_wgrad_bf16_period(const GgWPlan& p, const GgWArgs& a, float* dw, f
                         [&](int rows, dim3 grid, const GgWArgs& ka) {
 #define GG_PERIOD(P)                                                                                               \
     case P:                                                                                                        \
-        if (rows == 128) hipLaunchKernelGGL((gen_wgrad_bf16_kernel<128, false, P>), grid, dim3(kWgThreads), 0, st, ka); \
-        else hipLaunchKernelGGL((gen_wgrad_bf16_kernel<64, false, P>), grid, dim3(kWgThreads), 0, st, ka);         \
+        if (rows == 128) FV_KERNEL_LAUNCH((gen_wgrad_bf16_kernel<128, false, P>), grid, dim3(kWgThreads), 0, st, ka);   \
+        else FV_KERNEL_LAUNCH((gen_wgrad_bf16_kernel<64, false, P>), grid, dim3(kWgThreads), 0, st, ka);           \
         break;
         switch (period) {
             GG_PERIOD(2) GG_PERIOD(3) GG_PERIOD(5) GG_PERIOD(7) GG_PERIOD(11)

@@ -252,21 +252,21 @@ static dim3 gl_frame_grid(int B, int T) { return dim3((unsigned)((T + kGlFrames 
 
 static int gl_ola(const float* frames, float* y, const float* tab, int B, int T, hipStream_t s) {
     const int64_t quads = (int64_t)kGlHop * (T - 1) / 4;
-    hipLaunchKernelGGL(gl_ola_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, s, frames, y, tab, T);
+    FV_KERNEL_LAUNCH(gl_ola_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, s, frames, y, tab, T);
     FV_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_stft_complex(const float* y, float* spec, const float* tab, int B, int64_t n, hipStream_t s) {
     const int T = (int)(1 + n / kGlHop);
-    hipLaunchKernelGGL(gl_frame_kernel<GL_STFT>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, y, (const float2*)nullptr,
+    FV_KERNEL_LAUNCH(gl_frame_kernel<GL_STFT>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, y, (const float2*)nullptr,
                        (const float*)nullptr, (float*)nullptr, reinterpret_cast<float2*>(spec), tab, n, T);
     FV_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_istft(const float* spec, float* y, const float* tab, int B, int T, float* frames, hipStream_t s) {
-    hipLaunchKernelGGL(gl_frame_kernel<GL_ISTFT>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, (const float*)nullptr,
+    FV_KERNEL_LAUNCH(gl_frame_kernel<GL_ISTFT>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, (const float*)nullptr,
                        reinterpret_cast<const float2*>(spec), (const float*)nullptr, frames, (float2*)nullptr, tab,
                        (int64_t)0, T);
     FV_HIP(hipGetLastError());
@@ -277,13 +277,13 @@ int launch_griffin_lim(const float* S, const float* phase0, float* y, const floa
                        float* frames, hipStream_t s) {
     const int64_t n = (int64_t)kGlHop * (T - 1);
     if (phase0) {
-        hipLaunchKernelGGL(gl_frame_kernel<GL_INIT>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, (const float*)nullptr,
+        FV_KERNEL_LAUNCH(gl_frame_kernel<GL_INIT>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, (const float*)nullptr,
                            reinterpret_cast<const float2*>(phase0), S, frames, (float2*)nullptr, tab, n, T);
         FV_HIP(hipGetLastError());
         if (int rc = gl_ola(frames, y, tab, B, T, s)) return rc;
     }
     for (int i = 0; i < iters; ++i) {
-        hipLaunchKernelGGL(gl_frame_kernel<GL_ITER>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, (const float*)y,
+        FV_KERNEL_LAUNCH(gl_frame_kernel<GL_ITER>, gl_frame_grid(B, T), dim3(kGlThreads), 0, s, (const float*)y,
                            (const float2*)nullptr, S, frames, (float2*)nullptr, tab, n, T);
         FV_HIP(hipGetLastError());
         if (int rc = gl_ola(frames, y, tab, B, T, s)) return rc;
@@ -292,7 +292,7 @@ int launch_griffin_lim(const float* S, const float* phase0, float* y, const floa
 }
 
 int launch_mel_to_linear(const float* mel, const float* invb, float* S, int B, int T, float power, hipStream_t s) {
-    hipLaunchKernelGGL(mel_to_linear_kernel, dim3((unsigned)((T + kMlFrames - 1) / kMlFrames), (unsigned)B), dim3(256), 0, s,
+    FV_KERNEL_LAUNCH(mel_to_linear_kernel, dim3((unsigned)((T + kMlFrames - 1) / kMlFrames), (unsigned)B), dim3(256), 0, s,
                        mel, invb, S, T, power);
     FV_HIP(hipGetLastError());
     return 0;
@@ -301,7 +301,7 @@ int launch_mel_to_linear(const float* mel, const float* invb, float* S, int B, i
 int launch_inv_preemphasis(const float* y, float* out, int B, int64_t n, float coef, hipStream_t s) {
     double p = 1.0;
     for (int k = 0; k < kIpSeg; ++k) p *= (double)coef;
-    hipLaunchKernelGGL(inv_preemph_kernel, dim3((unsigned)B), dim3(kIpThreads), 0, s, y, out, n, coef, (float)p);
+    FV_KERNEL_LAUNCH(inv_preemph_kernel, dim3((unsigned)B), dim3(kIpThreads), 0, s, y, out, n, coef, (float)p);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kMelThreads) void mel_kernel(const float* __restric
 int launch_melspectrogram(const float* x, float* mel, const float* tab, int B, int64_t n, hipStream_t s) {
     const int64_t T = 1 + n / kMelHop;
     const int64_t blocks = (T + kMelFrames - 1) / kMelFrames;
-    hipLaunchKernelGGL(mel_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(kMelThreads), 0, s, x, mel, tab, n, T);
+    FV_KERNEL_LAUNCH(mel_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(kMelThreads), 0, s, x, mel, tab, n, T);
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -201,7 +201,7 @@ int fv_mpd_conv_first(const float* x, const float* w, const float* bias, float* 
     if (T + v.n_pad >= (int64_t)1 << 31)
         return fail(FV_ERR_INVALID_ARG, "mpd_conv_first: T=%lld too long", (long long)T);
     const int64_t blocks = (v.H1 * period + 255) / 256;
-    hipLaunchKernelGGL(mpd_first_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w,
+    FV_KERNEL_LAUNCH(mpd_first_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w,
                        bias, y, T, (int)v.H, (int)v.H1, period, slope);
     FV_HIP(hipGetLastError());
     return 0;
@@ -224,7 +224,7 @@ int fv_pack_period_conv(const float* w, float* packed, int Cout, int Cin, void* 
     if (!w || !packed || w == packed) return fail(FV_ERR_INVALID_ARG, "pack_period_conv: null tensor or aliasing");
     const int64_t total = (int64_t)Cout * Cin * kPT;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_period_conv_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin);
+    FV_KERNEL_LAUNCH(pack_period_conv_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -242,7 +242,7 @@ int fv_period_conv(const float* x, const float* packed, const float* bias, float
     const hipStream_t st = (hipStream_t)stream;
 #define FV_PERIOD(P)                                                                                              \
     case P:                                                                                                       \
-        hipLaunchKernelGGL(period_conv_kernel<P>, grid, dim3(kPThreads), 0, st, x, packed, bias, y, Cin, Cout, H, \
+        FV_KERNEL_LAUNCH(period_conv_kernel<P>, grid, dim3(kPThreads), 0, st, x, packed, bias, y, Cin, Cout, H,   \
                            Hout, slope);                                                                          \
         break;
     switch (period) {

@@ -241,7 +241,7 @@ int fv_pack_period_conv_grad(const float* w, float* packed, int Cout, int Cin, v
     if (!w || !packed || w == packed) return fail(FV_ERR_INVALID_ARG, "pack_period_conv_grad: null tensor or aliasing");
     const int64_t total = (int64_t)Cout * Cin * kGT;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_period_conv_grad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout,
+    FV_KERNEL_LAUNCH(pack_period_conv_grad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout,
                        Cin, Cin < 128 ? Cin : 128);
     FV_HIP(hipGetLastError());
     return 0;
@@ -269,10 +269,10 @@ int fv_period_conv_input_grad(const float* g_up, const float* g_map, const float
 #define FV_PERIOD(P)                                                                                                \
     case P:                                                                                                         \
         if (narrow)                                                                                                 \
-            hipLaunchKernelGGL((period_grad_kernel<P, 1, 1>), grid, dim3(kGThreads), 0, st, g_up, g_map, y, packed, \
+            FV_KERNEL_LAUNCH((period_grad_kernel<P, 1, 1>), grid, dim3(kGThreads), 0, st, g_up, g_map, y, packed,   \
                                dx, Cin, Cout, H, Hout, slope);                                                      \
         else                                                                                                        \
-            hipLaunchKernelGGL((period_grad_kernel<P, 2, 2>), grid, dim3(kGThreads), 0, st, g_up, g_map, y, packed, \
+            FV_KERNEL_LAUNCH((period_grad_kernel<P, 2, 2>), grid, dim3(kGThreads), 0, st, g_up, g_map, y, packed,   \
                                dx, Cin, Cout, H, Hout, slope);                                                      \
         break;
     switch (period) {
@@ -299,7 +299,7 @@ int fv_mpd_first_input_grad(const float* g_up, const float* g_map, const float* 
                     "samples", (long long)T, (long long)v.n_pad);
     if (T + v.n_pad >= (int64_t)1 << 31)
         return fail(FV_ERR_INVALID_ARG, "mpd_first_input_grad: T=%lld too long", (long long)T);
-    hipLaunchKernelGGL(mpd_first_grad_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0,
+    FV_KERNEL_LAUNCH(mpd_first_grad_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0,
                        (hipStream_t)stream, g_up, g_map, y0, w, dx, T, (int)v.n_pad, (int)v.H1, period, slope);
     FV_HIP(hipGetLastError());
     return 0;

@@ -287,11 +287,11 @@ int fv_period_conv_weight_grad(const float* g_pre, const float* x, float* dw, fl
     a.p = period;
     a.with_bias = db != nullptr;
     if (!p.mfma) {
-        hipLaunchKernelGGL(period_wgrad_plain_kernel, p.grid, dim3(kPwThreads), 0, st, a);
+        FV_KERNEL_LAUNCH(period_wgrad_plain_kernel, p.grid, dim3(kPwThreads), 0, st, a);
     } else {
 #define FV_PERIOD(P)                                                                                  \
     case P:                                                                                           \
-        hipLaunchKernelGGL((period_wgrad_mfma_kernel<P>), p.grid, dim3(kPwThreads), 0, st, a);        \
+        FV_KERNEL_LAUNCH((period_wgrad_mfma_kernel<P>), p.grid, dim3(kPwThreads), 0, st, a);          \
         break;
         switch (period) {
             FV_PERIOD(2) FV_PERIOD(3) FV_PERIOD(5) FV_PERIOD(7) FV_PERIOD(11)
@@ -316,7 +316,7 @@ int fv_mpd_first_weight_grad(const float* g_pre, const float* x, float* dw, floa
     if (int rc = wg_workspace_check("mpd_first_weight_grad", workspace, workspace_bytes, p.bytes())) return rc;
     const hipStream_t st = (hipStream_t)stream;
     float* ws = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(mpd_first_wgrad_kernel, dim3(kPwFirstC, 1, (unsigned)p.S), dim3(kPwThreads), 0, st, g_pre, x, ws,
+    FV_KERNEL_LAUNCH(mpd_first_wgrad_kernel, dim3(kPwFirstC, 1, (unsigned)p.S), dim3(kPwThreads), 0, st, g_pre, x, ws,
                        T, (int)p.v.H, (int)p.v.H1, period, p.U, p.S, p.nch, db != nullptr ? 1 : 0);
     FV_HIP(hipGetLastError());
     return launch_wgrad_combine(ws, dw, db, kPwFirstC * kPwMaxK, kPwFirstC, p.R, p.S, st);

@@ -208,10 +208,10 @@ int fv_grad_sq_norm(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, 
         return fail(FV_ERR_WORKSPACE, "grad_sq_norm: workspace of %zu bytes, %zu needed", workspace_bytes,
                     sizeof(double) * (size_t)n_chunks);
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(grad_sq_partial_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, st, tensors, chunks,
+    FV_KERNEL_LAUNCH(grad_sq_partial_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, st, tensors, chunks,
                        n_tensors, (double*)workspace);
     FV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kOaThreads), 0, st, (const double*)workspace,
+    FV_KERNEL_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(kOaThreads), 0, st, (const double*)workspace,
                        (int)n_chunks, max_norm, out);
     FV_HIP(hipGetLastError());
     return 0;
@@ -223,7 +223,7 @@ int fv_adam_step(const fv_adam_tensor* tensors, const fv_adam_chunk* chunks, int
     if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0))
         return fail(FV_ERR_INVALID_ARG, "adam_step: betas (%g, %g), eps %g", beta1, beta2, eps);
     if ((uintptr_t)coef & 3) return fail(FV_ERR_INVALID_ARG, "adam_step: misaligned coef");
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, (hipStream_t)stream, tensors,
+    FV_KERNEL_LAUNCH(adam_step_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, (hipStream_t)stream, tensors,
                        chunks, n_tensors, coef, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
     FV_HIP(hipGetLastError());
     return 0;
@@ -233,7 +233,7 @@ int fv_grad_bucket_pack(const fv_adam_tensor* tensors, const fv_adam_chunk* chun
                         const float* const* src, float scale, void* stream) {
     if (int rc = oa_table_check("grad_bucket_pack", tensors, chunks, n_tensors, n_chunks)) return rc;
     if (!src || ((uintptr_t)src & 7)) return fail(FV_ERR_INVALID_ARG, "grad_bucket_pack: null or misaligned src array");
-    hipLaunchKernelGGL(grad_bucket_pack_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, (hipStream_t)stream,
+    FV_KERNEL_LAUNCH(grad_bucket_pack_kernel, dim3((unsigned)n_chunks), dim3(kOaThreads), 0, (hipStream_t)stream,
                        tensors, chunks, n_tensors, src, scale);
     FV_HIP(hipGetLastError());
     return 0;

@@ -294,7 +294,7 @@ extern "C" {
 int fv_fold_weight_norm(const float* v, const float* g, float* w, int dim0, int64_t inner,
                         void* stream) {
     if (dim0 <= 0 || inner <= 0) return fail(FV_ERR_INVALID_ARG, "fold: dim0=%d inner=%lld", dim0, (long long)inner);
-    hipLaunchKernelGGL(fold_weight_norm_kernel, dim3(dim0), dim3(256), 0, (hipStream_t)stream, v, g,
+    FV_KERNEL_LAUNCH(fold_weight_norm_kernel, dim3(dim0), dim3(256), 0, (hipStream_t)stream, v, g,
                        w, inner);
     FV_HIP(hipGetLastError());
     return 0;
@@ -305,7 +305,7 @@ int fv_fold_batchnorm_conv(const float* w, const float* b, const float* gamma, c
                            int Cout, int Cin, int k, void* stream) {
     if (int rc = check_conv_args(Cin, Cout, k, 1)) return rc;
     if (!w || !mean || !var || !w_out || !b_out) return fail(FV_ERR_INVALID_ARG, "fold_batchnorm: null tensor");
-    hipLaunchKernelGGL(fold_batchnorm_conv_kernel, dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, b,
+    FV_KERNEL_LAUNCH(fold_batchnorm_conv_kernel, dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, b,
                        gamma, beta, mean, var, eps, w_out, b_out, Cin, k);
     FV_HIP(hipGetLastError());
     return 0;
@@ -326,7 +326,7 @@ int fv_pack_conv1d_weight(const float* w, float* packed, int Cout, int Cin, int 
     const int Mpad = pad_rows(Cout);
     const int64_t total = (int64_t)Cin * k * Mpad;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_conv1d_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w,
+    FV_KERNEL_LAUNCH(pack_conv1d_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w,
                        packed, Cout, Cin, k, Mpad);
     FV_HIP(hipGetLastError());
     return 0;
@@ -340,7 +340,7 @@ int fv_pack_conv_transpose1d_weight(const float* w, float* packed, int Cin, int 
         const int tp = k / stride, Mp = pad_rows(Cout * stride);
         const int64_t tot = (int64_t)Cin * tp * Mp;
         const int nb = (int)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-        hipLaunchKernelGGL(pack_convT_phase_major_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, w,
+        FV_KERNEL_LAUNCH(pack_convT_phase_major_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, w,
                            packed, Cin, Cout, k, stride, pad, tp, Mp);
         FV_HIP(hipGetLastError());
         return 0;
@@ -349,7 +349,7 @@ int fv_pack_conv_transpose1d_weight(const float* w, float* packed, int Cin, int 
     const int Mpad = pad_rows(Cout * stride);
     const int64_t total = (int64_t)Cin * ph.taps * Mpad;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_convT_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w,
+    FV_KERNEL_LAUNCH(pack_convT_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w,
                        packed, Cin, Cout, k, stride, pad, ph.dmin, ph.taps, Mpad);
     FV_HIP(hipGetLastError());
     return 0;
@@ -368,7 +368,7 @@ int fv_pack_upsample_conv1d_weight(const float* w, float* packed, int Cout, int 
     const int Mpad = pad_rows(Cout * rate);
     const int64_t total = (int64_t)Cin * ph.taps * Mpad;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_upconv_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed,
+    FV_KERNEL_LAUNCH(pack_upconv_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed,
                        Cout, Cin, k, rate, pad, ph.dmin, ph.taps, Mpad);
     FV_HIP(hipGetLastError());
     return 0;
@@ -392,7 +392,7 @@ int fv_pack_basis(const float* W, float* packed, int L, int C, void* stream) {
     if (!W || !packed) return fail(FV_ERR_INVALID_ARG, "pack_basis: null tensor");
     if (fv_packed_basis_floats(L, C) <= 0) return fail(FV_ERR_INVALID_ARG, "pack_basis: L=%d (even, >= 2) C=%d", L, C);
     float* wT = packed + fv_packed_conv_transpose1d_floats(C, 1, L, L / 2, 0);
-    hipLaunchKernelGGL(transpose_basis_kernel, dim3((unsigned)((L * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, wT, L, C);
+    FV_KERNEL_LAUNCH(transpose_basis_kernel, dim3((unsigned)((L * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, wT, L, C);
     FV_HIP(hipGetLastError());
     return fv_pack_conv_transpose1d_weight(wT, packed, C, 1, L, L / 2, 0, stream);
 }
@@ -412,16 +412,16 @@ int fv_pack_conv_transpose1d_split_f16(const float* w, float* packed, int Cin, i
                                        void* stream) {
     if (!w || !packed) return fail(FV_ERR_INVALID_ARG, "pack_conv_transpose1d_split_f16: null tensor");
     if (convtn_shape(Cin, Cout, k, stride)) {
-        hipLaunchKernelGGL(row_scale_kernel, dim3(32), dim3(64), 0, (hipStream_t)stream, w, (const float*)nullptr,
+        FV_KERNEL_LAUNCH(row_scale_kernel, dim3(32), dim3(64), 0, (hipStream_t)stream, w, (const float*)nullptr,
                            packed + (kTnPackedFloats - 32), 32, Cin, 2, Cout, stride);
         return launch_pack_convtn(w, packed, packed + (kTnPackedFloats - 32), range_flag, (hipStream_t)stream);
     }
     if (int rc = check_convt_split_args(Cin, Cout, k, stride, 0, 0)) return rc;
     const int rows = (Cout * stride + 63) / 64 * 64;
     const int64_t image = fv_packed_conv_transpose1d_split_floats(Cin, Cout, k, stride) - rows, total = image * 2;
-    hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, w, (const float*)nullptr,
+    FV_KERNEL_LAUNCH(row_scale_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, w, (const float*)nullptr,
                        packed + image, rows, Cin, 2, Cout, stride);
-    hipLaunchKernelGGL(pack_convth_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+    FV_KERNEL_LAUNCH(pack_convth_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
                        reinterpret_cast<_Float16*>(packed), packed + image, Cin, Cout, stride, range_flag);
     FV_HIP(hipGetLastError());
     return 0;
@@ -438,8 +438,8 @@ int fv_pack_conv1x1_2src_split_f16(const float* w1, const float* w2, float* pack
     if (fv_packed_conv1x1_2src_split_floats(C) <= 0)
         return fail(FV_ERR_UNSUPPORTED, "pack_conv1x1_2src_split_f16: C = %d (128, 256 or 512)", C);
     const int64_t image = fv_packed_conv1x1_2src_split_floats(C) - C, total = image * 2;
-    hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w1, w2, packed + image, C, C, 1, 0, 0);
-    hipLaunchKernelGGL(pack_convg_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w1, w2,
+    FV_KERNEL_LAUNCH(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w1, w2, packed + image, C, C, 1, 0, 0);
+    FV_KERNEL_LAUNCH(pack_convg_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w1, w2,
                        reinterpret_cast<_Float16*>(packed), packed + image, C, range_flag);
     FV_HIP(hipGetLastError());
     return 0;
@@ -458,9 +458,9 @@ int fv_pack_residual_stack_split_f16(const float* w_dilated, const float* w_poin
     if (n <= 0) return fail(FV_ERR_UNSUPPORTED, "pack_residual_stack_split_f16: C = %d, k = %d (32 / 64 / 128 / 256 channels, 3 taps)", C, k);
     float* inv = packed + (n - 2 * C);
     // the same row prescales as the two-launch form: conv1's rows over their 3 C weights, the 1x1 pair's over [W2 | Ws]
-    hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w_dilated, (const float*)nullptr,
+    FV_KERNEL_LAUNCH(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w_dilated, (const float*)nullptr,
                        inv, C, 3 * C, 0, 0, 0);
-    hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w_pointwise, w_skip, inv + C, C, C,
+    FV_KERNEL_LAUNCH(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w_pointwise, w_skip, inv + C, C, C,
                        1, 0, 0);
     return launch_pack_convk(w_dilated, w_pointwise, w_skip, packed, C, range_flag, (hipStream_t)stream);
 }
@@ -472,7 +472,7 @@ int fv_pack_pair_weight(const float* w, float* packed, int C, int k, void* strea
     if (C <= 0 || C % 16 != 0 || k <= 0) return fail(FV_ERR_INVALID_ARG, "pack_pair_weight: C=%d (multiple of 16) k=%d", C, k);
     const int64_t total = (int64_t)C * C * k;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_pair_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, C, k);
+    FV_KERNEL_LAUNCH(pack_pair_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, C, k);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -494,13 +494,13 @@ int fv_pack_pair_weight_ex(const float* w, float* packed, int C, int k, int prec
     if ((C != 16 && C != 32 && C != 64 && C != 128 && C != 256 && C != 512) || k <= 0)
         return fail(FV_ERR_INVALID_ARG, "pack_pair_weight: C=%d (16 ... 512, a power of two) k=%d", C, k);
     const int64_t image = fv_packed_pair_floats_ex(C, k, prec) - C, total = image * 2;
-    hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w, (const float*)nullptr,
+    FV_KERNEL_LAUNCH(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, w, (const float*)nullptr,
                        packed + image, C, C * k, 0, 0, 0);
     if (C >= 64)
-        hipLaunchKernelGGL(pack_convh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+        FV_KERNEL_LAUNCH(pack_convh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            w, reinterpret_cast<_Float16*>(packed), packed + image, C, k, range_flag);
     else
-        hipLaunchKernelGGL(pack_pairh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+        FV_KERNEL_LAUNCH(pack_pairh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            w, reinterpret_cast<_Float16*>(packed), packed + image, C, k, range_flag);
     FV_HIP(hipGetLastError());
     return 0;
@@ -532,10 +532,10 @@ int fv_pack_mrf_stage_split_f16(const float* const* w1, const float* const* w2, 
             const float* const ws[2] = {w1[i], w2[i]};
             for (int c = 0; c < 2; ++c) {
                 float* const inv = tail + (2 + c) * C;
-                hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, s, ws[c], (const float*)nullptr, inv, C,
+                FV_KERNEL_LAUNCH(row_scale_kernel, dim3((unsigned)C), dim3(64), 0, s, ws[c], (const float*)nullptr, inv, C,
                                    C * k[j], 0, 0, 0);
                 const int64_t total = (int64_t)wb / 2;                  // halves of the image
-                hipLaunchKernelGGL(pack_pairh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws[c],
+                FV_KERNEL_LAUNCH(pack_pairh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws[c],
                                    reinterpret_cast<_Float16*>(at + c * wb), inv, C, k[j], range_flag);
             }
             if (b1 && b1[i]) FV_HIP(hipMemcpyAsync(tail, b1[i], (size_t)C * 4, hipMemcpyDeviceToDevice, s));

@@ -20,7 +20,7 @@ __global__ void div_probe_kernel(unsigned first, long long n, float d, unsigned 
 }
 
 int launch_div_probe(unsigned first, long long n, float d, unsigned long long* mismatches, hipStream_t s) {
-    hipLaunchKernelGGL(div_probe_kernel, dim3(2048), dim3(256), 0, s, first, n, d, mismatches);
+    FV_KERNEL_LAUNCH(div_probe_kernel, dim3(2048), dim3(256), 0, s, first, n, d, mismatches);
     FV_HIP(hipGetLastError());
     return 0;
 }

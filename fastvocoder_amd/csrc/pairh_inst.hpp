@@ -10,7 +10,7 @@ int launch_pairh_geom(const PairParams& p, int dil, size_t lds, hipStream_t s) {
     do {                                                                                       \
         auto kern = p.fold_w && MH == 1 ? pairh_kernel<MH, NF, NG, DIL, MH == 1> : pairh_kernel<MH, NF, NG, DIL, false>; \
         if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc; \
-        hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(64 * NG), lds, s, p);                      \
+        FV_KERNEL_LAUNCH(kern, dim3(p.nblk), dim3(64 * NG), lds, s, p);                        \
     } while (0)
     switch (dil) {
         case 1: FV_PAIRH(1); break;

@@ -90,7 +90,7 @@ int launch_pqmf_analysis(const float* xin, const float* ha, float* x, int B, int
     if (B <= 0 || T < S) return 0;
     int64_t blocks = (Tsub + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(pqmf_analysis_kernel, dim3((unsigned)blocks, B), dim3(256),
+    FV_KERNEL_LAUNCH(pqmf_analysis_kernel, dim3((unsigned)blocks, B), dim3(256),
                        (size_t)S * ntaps * sizeof(float), s, xin, ha, x, S, ntaps, T, Tsub);
     FV_HIP(hipGetLastError());
     return 0;
@@ -102,7 +102,7 @@ int launch_pqmf(const float* x, const float* h, float* y, float* y2, const float
     const int64_t T = (int64_t)S * Tsub;
     int64_t blocks = (T + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(pqmf_synthesis_kernel, dim3((unsigned)blocks, B), dim3(256),
+    FV_KERNEL_LAUNCH(pqmf_synthesis_kernel, dim3((unsigned)blocks, B), dim3(256),
                        (size_t)S * ntaps * sizeof(float), s, x, h, y, y2, sub, sub_batched, S, ntaps, Tsub);
     FV_HIP(hipGetLastError());
     return 0;

@@ -62,10 +62,10 @@ int launch_resample(const void* x, int format, float* y, const float* tab, int B
     const dim3 grid((unsigned)((n_out + kRsBlock - 1) / kRsBlock), B);
     const size_t lds = (size_t)win * sizeof(float);
     if (format == FV_PCM_S16)
-        hipLaunchKernelGGL(resample_kernel<short>, grid, dim3(kRsBlock), lds, s, static_cast<const short*>(x), tab, y,
+        FV_KERNEL_LAUNCH(resample_kernel<short>, grid, dim3(kRsBlock), lds, s, static_cast<const short*>(x), tab, y,
                            n_in, n_out, L, M, half, win);
     else
-        hipLaunchKernelGGL(resample_kernel<float>, grid, dim3(kRsBlock), lds, s, static_cast<const float*>(x), tab, y,
+        FV_KERNEL_LAUNCH(resample_kernel<float>, grid, dim3(kRsBlock), lds, s, static_cast<const float*>(x), tab, y,
                            n_in, n_out, L, M, half, win);
     FV_HIP(hipGetLastError());
     return 0;

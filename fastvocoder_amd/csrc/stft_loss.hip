@@ -225,10 +225,10 @@ int launch_stft_distance(const float* x, const float* y, const float* const* tab
         c += stft_chunks(n, hop[r]);
     }
     a.chunks = c;
-    hipLaunchKernelGGL(stft_distance_kernel, dim3((unsigned)c, (unsigned)B), dim3(kStftThreads), 0, s, x, y, a, n,
+    FV_KERNEL_LAUNCH(stft_distance_kernel, dim3((unsigned)c, (unsigned)B), dim3(kStftThreads), 0, s, x, y, a, n,
                        ws);
     FV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(stft_sum_kernel, dim3((unsigned)R, (unsigned)B), dim3(64), 0, s, ws, a, B, out);
+    FV_KERNEL_LAUNCH(stft_sum_kernel, dim3((unsigned)R, (unsigned)B), dim3(64), 0, s, ws, a, B, out);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -238,10 +238,10 @@ int launch_stft_magnitude(const float* x, float* mag, const float* tab, int B, i
     const int64_t T = 1 + n / hop;
     const int64_t blocks = (T + 2 * kStftWaves - 1) / (2 * kStftWaves);
     if (bins_major)
-        hipLaunchKernelGGL(stft_magnitude_kernel<true>, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s,
+        FV_KERNEL_LAUNCH(stft_magnitude_kernel<true>, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s,
                            x, mag, tab, n, nfft, hop, win, T);
     else
-        hipLaunchKernelGGL(stft_magnitude_kernel<false>, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s,
+        FV_KERNEL_LAUNCH(stft_magnitude_kernel<false>, dim3((unsigned)blocks, (unsigned)B), dim3(kStftThreads), 0, s,
                            x, mag, tab, n, nfft, hop, win, T);
     FV_HIP(hipGetLastError());
     return 0;

@@ -191,10 +191,10 @@ int launch_stft_distance_grad(const float* x, const float* y, const float* const
         c += stft_grad_chunks(n, hop[r]);
         slab += (int64_t)B * T * win[r];
     }
-    hipLaunchKernelGGL(stft_grad_frame_kernel, dim3((unsigned)c, (unsigned)B), dim3(kSgThreads), 0, s, x, y, a, n, B,
+    FV_KERNEL_LAUNCH(stft_grad_frame_kernel, dim3((unsigned)c, (unsigned)B), dim3(kSgThreads), 0, s, x, y, a, n, B,
                        coef, ws);
     FV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(stft_grad_ola_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s,
+    FV_KERNEL_LAUNCH(stft_grad_ola_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s,
                        (const float*)ws, a, n, gx);
     FV_HIP(hipGetLastError());
     return 0;
@@ -206,7 +206,7 @@ int launch_stft_grad_ola(const float* ws, const float* tab, int B, int64_t n, in
     StftGradArgs a{};
     a.R = 1;
     a.res[0] = StftGradRes{tab, nfft, hop, win, 1 + n / hop, 0, 0};
-    hipLaunchKernelGGL(stft_grad_ola_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, ws, a, n,
+    FV_KERNEL_LAUNCH(stft_grad_ola_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, ws, a, n,
                        gx);
     FV_HIP(hipGetLastError());
     return 0;

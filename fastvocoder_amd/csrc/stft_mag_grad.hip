@@ -119,11 +119,11 @@ int launch_stft_magnitude_bins_grad(const float* x, const float* gmag, const flo
     const int64_t T = 1 + n / hop;
     const dim3 grid((unsigned)stft_mag_grad_chunks(n, hop), (unsigned)B), block(kMgThreads);
     switch (nfft) {
-        case 512: hipLaunchKernelGGL(stft_mag_grad_frame_kernel<256>, grid, block, 0, s, x, gmag, tab, n, hop, win, T,
+        case 512: FV_KERNEL_LAUNCH(stft_mag_grad_frame_kernel<256>, grid, block, 0, s, x, gmag, tab, n, hop, win, T,
                                      ws); break;
-        case 1024: hipLaunchKernelGGL(stft_mag_grad_frame_kernel<512>, grid, block, 0, s, x, gmag, tab, n, hop, win,
+        case 1024: FV_KERNEL_LAUNCH(stft_mag_grad_frame_kernel<512>, grid, block, 0, s, x, gmag, tab, n, hop, win,
                                       T, ws); break;
-        default: hipLaunchKernelGGL(stft_mag_grad_frame_kernel<1024>, grid, block, 0, s, x, gmag, tab, n, hop, win, T,
+        default: FV_KERNEL_LAUNCH(stft_mag_grad_frame_kernel<1024>, grid, block, 0, s, x, gmag, tab, n, hop, win, T,
                                     ws); break;
     }
     FV_HIP(hipGetLastError());

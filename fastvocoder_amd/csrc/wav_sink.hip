@@ -53,10 +53,10 @@ int launch_encode16(float* x, int B, int64_t n, float rescale, short* out, unsig
     int64_t blocks = (n + 1023) / 1024;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(peak_abs_kernel, dim3((unsigned)blocks, B), dim3(256), 0, s, x, n, peak_bits);
+    FV_KERNEL_LAUNCH(peak_abs_kernel, dim3((unsigned)blocks, B), dim3(256), 0, s, x, n, peak_bits);
     FV_HIP(hipGetLastError());
     const float low_scale = (float)(32767.0 / 0.01 * (double)rescale);
-    hipLaunchKernelGGL(encode16_kernel, dim3((unsigned)blocks, B), dim3(256), 0, s, x, n, peak_bits, rescale,
+    FV_KERNEL_LAUNCH(encode16_kernel, dim3((unsigned)blocks, B), dim3(256), 0, s, x, n, peak_bits, rescale,
                        low_scale, out, scale_in_place);
     FV_HIP(hipGetLastError());
     return 0;

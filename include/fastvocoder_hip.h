@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad (entries added since -- the latest: fv_mrf_stage_classes_f16 -- change no existing one); 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
+#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad (entries added since -- the latest: fv_debug_launch_log -- change no existing one); 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
 /* Entry points are added under one version number: 18 also covers the gradient, optimizer and training entries that
  * came after fv_stft_distance_grad, the latest being fv_conv1d_weight_grad_dilated_bf16 and
  * fv_conv_transpose1d_weight_grad_bf16 (the generators' bf16 weight gradients).  No existing entry changed its signature or its result. */
@@ -1393,6 +1393,22 @@ int fv_debug_mrf_class_schedule(int B, int T, int nblk, int force, int64_t* info
  */
 int fv_debug_mrf_stage_class_f16(const float* x, const float* packed, float* y, int cls, int B, int C, int T, const int* k,
                                  const int* dil, float slope, void* workspace, int64_t workspace_bytes, void* stream);
+/*
+ * Test hook, host only: the launch log.  Every kernel launch of the library goes through one helper (csrc/fv_internal.h
+ * FV_KERNEL_LAUNCH); while the log is on, the helper counts the kernel's host handle in a process-wide table (first-seen
+ * order, guarded by a mutex), so that a test can assert WHICH kernel instantiation produced the numbers it compared.  Off,
+ * which is the default, a launch pays one relaxed atomic load; on or off, no launch parameter changes and nothing is added
+ * on the device.
+ *   fv_debug_launch_log(1) clears the table and starts recording, (0) stops (the table stays readable).
+ *   fv_debug_launch_log_read writes one line "count<TAB>name<NL>" per kernel into buf (at most cap bytes, no terminator) and
+ *   returns the bytes the whole text needs: call with (NULL, 0) first.  Names come from dladdr on the handle and
+ *   __cxa_demangle, without return type, "fv::" and argument list: "convh_kernel<2, 2, 1>".
+ *   fv_debug_kernel_name gives the same name for a dynamic symbol of the library (a kernel handle or its host stub, whose
+ *   "__device_stub__" goes too): what tools/kernel_census.py lists the built instantiations with.  Returns the bytes needed.
+ */
+int fv_debug_launch_log(int on);
+int64_t fv_debug_launch_log_read(char* buf, int64_t cap);
+int64_t fv_debug_kernel_name(const char* symbol, char* buf, int64_t cap);
 
 /* ------------------------------------------------------------------ *
  * measurement hook (bench.py): per-launch timing of the dominant kernel

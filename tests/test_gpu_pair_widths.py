@@ -85,7 +85,11 @@ def test_80_column_tiles_give_the_bits_of_64_column_tiles(ks, dil, tuning):
             assert _native.debug_pair_widths(C, B, T, dil, ks, 256)["widths"][0] == nm
             for blocks in (0, 3):
                 tuning("convh_blocks", blocks)
-                outs[nm, blocks] = _launch(ks, T, dil, False) + _launch(ks, T, dil, True)
+                with _native.launch_log() as log:
+                    outs[nm, blocks] = _launch(ks, T, dil, False) + _launch(ks, T, dil, True)
+                # the two sides are different instantiations of convq2_kernel<dilation, form>: 128 -- every member on 64 columns,
+                # 130 -- the 11-tap member on 80 (csrc/convh_launch.hip launch_fused_pair)
+                assert log.kernels == {f"convq2_kernel<{dil}, {128 if nm == 64 else 130}>": 2}, (T, nm, blocks, log.kernels)
         tuning("convh_blocks", 0)
         base = outs[64, 0]
         for key, ys in outs.items():
@@ -93,8 +97,10 @@ def test_80_column_tiles_give_the_bits_of_64_column_tiles(ks, dil, tuning):
                 assert torch.equal(y, yb), (T, key, j)
         # ... and the bits of the two conv launches (convh_kernel) the fused pair replaces
         n = len(ks)
-        mids = _native.conv1d_split_f16(xs[:n], [ws[k][0] for k in ks], [ws[k][2] for k in ks], list(ks), dil, pre_slope=0.1)
-        two = _native.conv1d_split_f16(mids, [ws[k][1] for k in ks], [ws[k][3] for k in ks], list(ks), 1, pre_slope=0.1, res=xs[:n])
+        with _native.launch_log() as log:
+            mids = _native.conv1d_split_f16(xs[:n], [ws[k][0] for k in ks], [ws[k][2] for k in ks], list(ks), dil, pre_slope=0.1)
+            two = _native.conv1d_split_f16(mids, [ws[k][1] for k in ks], [ws[k][3] for k in ks], list(ks), 1, pre_slope=0.1, res=xs[:n])
+        assert log.families() <= {"convh_kernel", "convs_kernel"} and sum(log.kernels.values()) == 2, log.kernels
         for j in range(n):
             assert torch.equal(outs[80, 0][j], two[j]), (T, j)
             assert bool(torch.isfinite(two[j]).all()) and float(two[j].abs().max()) > 0.5

@@ -310,25 +310,47 @@ def test_conv1d_split_f16_on_128_row_tiles_gives_the_same_bits(case, tuning):
                                                 act_slope=0.2))
         return [t.clone() for ts in out for t in ts]
 
+    logs = {}
+
+    def logged(name):
+        with _native.launch_log() as log:
+            out = forms()
+        logs[name] = log
+        return out
+
     tuning("convh_rows64", 1)
-    narrow = forms()
+    narrow = logged("narrow")
     tuning("convh_rows64", 0)
-    wide = forms()
+    wide = logged("wide")
     tuning("convs_ringfree", 0)
-    ring = forms()
+    ring = logged("ring")
     tuning("convs_ringfree", 1)
-    rf64 = forms()
+    rf64 = logged("rf64")
     tuning("convs_ringfree", 2)
-    rf128 = forms()
+    rf128 = logged("rf128")
     tuning("convs_ringfree", -1)
     tuning("convh_blocks", 3)
-    few = forms()
+    few = logged("few")
     tuning("convh_blocks", 0)
     assert all(torch.equal(a, b) for a, b in zip(narrow, wide)) and all(torch.equal(a, b) for a, b in zip(wide, few))
     assert all(torch.equal(a, b) for a, b in zip(wide, ring))
     assert all(torch.equal(a, b) for a, b in zip(wide, rf64)) and all(torch.equal(a, b) for a, b in zip(wide, rf128))
     for y, x, w, b, k in zip(wide[:n], xs, ws, Bi, ks):
         assert _rel(y, oo.conv1d(x, w, b.cpu().numpy(), dil=dil, pad=(k - 1) * dil // 2, pre_slope=0.1)) <= 4e-6
+    # which kernels the compared sides ran on (csrc/convh_launch.hip launch_convh): 64-row tiles are convh_kernel, 128-row tiles
+    # convs_kernel; the ring-free convs2_kernel exists at 256 / 512 channels with zero padding and dilations up to 5 only -- at
+    # 128 channels, with dilation 9 and for the reflection form `convs_ringfree` changes nothing, and nothing is claimed there
+    assert logs["narrow"].families() == {"convh_kernel"} and logs["ring"].families() == {"convs_kernel"}
+    assert set(logs["ring"].kernels) == {f"convs_kernel<{dil}>"}
+    if C >= 256 and dil <= 5:
+        zero_pad = {"convs2_kernel"} | ({"convs_kernel"} if reflect else set())
+        for name in ("wide", "rf64", "rf128", "few"):
+            assert logs[name].families() == zero_pad, (name, logs[name].kernels)
+        assert f"convs2_kernel<{dil}, 1>" in logs["rf64"].kernels and f"convs2_kernel<{dil}, 2>" not in logs["rf64"].kernels
+        assert f"convs2_kernel<{dil}, 2>" in logs["rf128"].kernels and f"convs2_kernel<{dil}, 1>" not in logs["rf128"].kernels
+    else:
+        for name in ("wide", "rf64", "rf128", "few"):
+            assert logs[name].kernels == logs["ring"].kernels, (name, logs[name].kernels)
 
 
 @pytest.mark.parametrize("case", [(2, 64, 300, 9, (3,)), (1, 128, 130, 9, (3,)), (2, 256, 257, 3, (3,)), (1, 64, 12, 1, (3, 7)),
@@ -392,13 +414,23 @@ def test_block_schedule_gives_the_same_bits(tuning):
         xs = [_t(m[0]) for m in ms]
         h1, h2 = [_native.pack_pair(_t(m[1]), SPLIT) for m in ms], [_native.pack_pair(_t(m[3]), SPLIT) for m in ms]
         b1s, b2s = [_t(m[2]) for m in ms], [_t(m[4]) for m in ms]
-        sched = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
+        with _native.launch_log() as log_sched:
+            sched = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
         tuning("sched_switch", 0)
         sched0 = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
         tuning("sched_switch", 4)
         tuning("sched", 0)
-        plain = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
+        with _native.launch_log() as log_plain:
+            plain = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
         tuning("sched", 2)
+        # the schedule is an argument of the kernel, not another kernel: both modes launch the family's one -- the fused pair
+        # kernel at 64 / 128 channels, two conv launches per call at 256 (at 128 channels the 11-tap member's tile width follows
+        # the schedule's model, so the instantiation may differ: the family does not)
+        assert log_sched.families() == log_plain.families(), (log_sched.kernels, log_plain.kernels)
+        if C <= 128:
+            assert log_sched.families() == {"convq2_kernel"}, log_sched.kernels
+        else:
+            assert log_sched.families() and log_sched.families() <= {"convh_kernel", "convs_kernel", "convs2_kernel"}, log_sched.kernels
         for a, b, c in zip(sched, sched0, plain):
             assert torch.equal(a, c) and torch.equal(b, c)
         ref = _pair_ref(*ms[0], dil, 0.1)
@@ -429,11 +461,19 @@ def test_grouped_pairs_in_a_plan_equal_the_direct_entry(C, unfused, tuning):
     plan.set_group(0)
     plan.add_resblock_pair(2, _native.SLOT_OUT, h1[3], h2[3], b1[3], b2[3], C, ks[0], dil, 0.1, prec=SPLIT, add1=6, add2=7,
                            out_div=3.0, act_slope=0.1, mid=8)
-    got = plan.run(x)
-    first = _native.resblock1_fused([x, x, x], h1[:3], h2[:3], b1[:3], b2[:3], list(ks), dil, 0.1, prec=SPLIT)
-    r12 = _native.resblock1_fused(first[1:], h1[4:], h2[4:], b1[4:], b2[4:], list(ks[1:]), dil, 0.1, prec=SPLIT)
-    want, = _native.resblock1_fused([first[0]], [h1[3]], [h2[3]], [b1[3]], [b2[3]], [ks[0]], dil, 0.1, prec=SPLIT,
-                                    add1=[r12[0]], add2=[r12[1]], out_div=3.0, act_slope=0.1)
+    with _native.launch_log() as log_plan:
+        got = plan.run(x)
+    with _native.launch_log() as log_direct:
+        first = _native.resblock1_fused([x, x, x], h1[:3], h2[:3], b1[:3], b2[:3], list(ks), dil, 0.1, prec=SPLIT)
+        r12 = _native.resblock1_fused(first[1:], h1[4:], h2[4:], b1[4:], b2[4:], list(ks[1:]), dil, 0.1, prec=SPLIT)
+        want, = _native.resblock1_fused([first[0]], [h1[3]], [h2[3]], [b1[3]], [b2[3]], [ks[0]], dil, 0.1, prec=SPLIT,
+                                        add1=[r12[0]], add2=[r12[1]], out_div=3.0, act_slope=0.1)
+    # the family the case names, and the same launches on both sides: three fused launches, or (pair128_unfused) six conv ones
+    if unfused:
+        assert log_plan.families() <= {"convh_kernel", "convs_kernel"} and sum(log_plan.kernels.values()) == 6, log_plan.kernels
+    else:
+        assert log_plan.families() == {"convq2_kernel"} and sum(log_plan.kernels.values()) == 3, log_plan.kernels
+    assert log_plan.kernels == log_direct.kernels, (log_plan.kernels, log_direct.kernels)
     assert torch.equal(got, want)
     assert bool(torch.isfinite(got).all()) and float(got.abs().max()) > 0
 
@@ -496,10 +536,23 @@ def test_conv_transpose1d_split_f16_vs_oracle(case, tuning):
         ref = ref[:, :, :ref.shape[2] + op]
     X, Bi = _t(x), _t(b)
     P = _native.pack_conv_transpose1d_split(_t(w), s)
-    y = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
+    # the launcher's own condition for the lean kernel (csrc/convh_launch.hip launch_convt): at most convt_lean = 5.0
+    # (64 x 64 item, chunk) units per CU
+    ncols = (ref.shape[2] + pad + s - 1) // s
+    units = (ncols + 63) // 64 * B * ((cout * s + 63) // 64) * ((cin + 127) // 128)
+    lean = units * 10 <= 50 * torch.cuda.get_device_properties(0).multi_processor_count
+    with _native.launch_log() as log_default:
+        y = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
+        twin = torch.empty_like(y)
+        y2 = _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=twin, act_slope=0.2)
     assert tuple(y.shape) == ref.shape and _rel(y, ref) <= 4e-6
-    twin = torch.empty_like(y)
-    y2 = _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=twin, act_slope=0.2)
+    ring_forms = {"convt_kernel", "convu_kernel", "convu2_kernel"}
+    if cin == 32:                                  # 32 -> 16 x 2 has a kernel of its own; other 32-channel shapes run as 64
+        assert log_default.families() <= {"convtn_kernel", "convtl_kernel"} | ring_forms
+    elif lean:
+        assert log_default.families() == {"convtl_kernel"}, log_default.kernels
+    else:
+        assert log_default.families() <= ring_forms and log_default.families(), log_default.kernels
     assert _rel(y2, ref - b[None, :, None]) <= 4e-6 and _rel(twin, oo.lrelu(ref - b[None, :, None], 0.2)) <= 4e-6
     y3 = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1, act_slope=0.2)
     assert _rel(y3, oo.lrelu(ref, 0.2)) <= 4e-6
@@ -512,10 +565,16 @@ def test_conv_transpose1d_split_f16_vs_oracle(case, tuning):
     # L2 -> registers).  The ring pipeline (convt_kernel: 128-column tiles, weights through LDS) gives the same bits -- and
     # is what the rest of this test forces
     tuning("convt_lean", 0)
-    ring = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
-    tw_r = torch.empty_like(y)
-    ring2 = _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=tw_r, act_slope=0.2)
+    with _native.launch_log() as log_ring:
+        ring = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
+        tw_r = torch.empty_like(y)
+        ring2 = _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=tw_r, act_slope=0.2)
     assert torch.equal(ring, y) and torch.equal(ring2, y2) and torch.equal(tw_r, twin)
+    # where the default ran lean, the two sides of this comparison are different kernels (elsewhere both are the ring form:
+    # the comparison claims nothing there)
+    if "convtn_kernel" not in log_default.families():
+        assert log_ring.families() <= ring_forms and len(log_ring.families()) == 1, log_ring.kernels
+        assert not lean or log_ring.families().isdisjoint(log_default.families())
     tuning("convh_blocks", 3)
     assert torch.equal(_native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1), y)
     tuning("convh_blocks", 0)
@@ -527,12 +586,15 @@ def test_conv_transpose1d_split_f16_vs_oracle(case, tuning):
         # operands L2 -> registers, the window converted once per column tile); forced here: same bits
         tuning("convu_resident", 2)
         tw_u = torch.empty_like(y)
-        u1 = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
-        u2 = _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=tw_u, act_slope=0.2)
-        tuning("convh_blocks", 3)
-        u3 = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
-        tuning("convh_blocks", 0)
+        with _native.launch_log() as log_resident:
+            u1 = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
+            u2 = _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=tw_u, act_slope=0.2)
+            tuning("convh_blocks", 3)
+            u3 = _native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1)
+            tuning("convh_blocks", 0)
         tuning("convu_resident", 1)
+        assert log_resident.families() == {"convu2_kernel"} and sum(log_resident.kernels.values()) == 3, log_resident.kernels
+        assert log_resident.families() != log_default.families()
         assert torch.equal(u1, y) and torch.equal(u2, y2) and torch.equal(tw_u, twin) and torch.equal(u3, y)
     if cin >= 128:
         # 128-row tiles (csrc/convr_kernels.hpp convu_kernel: the window of a chunk converted once for two 64-row tiles,
@@ -541,12 +603,15 @@ def test_conv_transpose1d_split_f16_vs_oracle(case, tuning):
         for rows64 in (1, 0):
             tuning("convt_rows64", rows64)
             tw = torch.empty_like(y)
-            outs.append((_native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1).clone(),
-                         _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=tw,
-                                                            act_slope=0.2).clone(), tw))
-            tuning("convh_blocks", 3)
-            outs.append((_native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1).clone(),))
-            tuning("convh_blocks", 0)
+            with _native.launch_log() as log_rows:
+                outs.append((_native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1).clone(),
+                             _native.conv_transpose1d_split_f16(X, P, None, cout, k, s, pad, op, pre_slope=0.1, out_act=tw,
+                                                                act_slope=0.2).clone(), tw))
+                tuning("convh_blocks", 3)
+                outs.append((_native.conv_transpose1d_split_f16(X, P, Bi, cout, k, s, pad, op, pre_slope=0.1).clone(),))
+                tuning("convh_blocks", 0)
+            # (the lean form is off here; the resident form takes only launches with two column tiles per CU: none of these)
+            assert log_rows.families() == {"convt_kernel" if rows64 else "convu_kernel"}, (rows64, log_rows.kernels)
         tuning("convt_rows64", -1)
         tuning("convt_lean", 50)
         assert torch.equal(outs[0][0], y) and all(torch.equal(a, b) for a, b in zip(outs[0], outs[2]))
@@ -626,11 +691,21 @@ def test_pair_tile_forms_give_the_same_bits(tuning):
             tuning("convq_wide", wide)
             for blocks in (0, 3):
                 tuning("convh_blocks", blocks)
-                ys = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
-                merged = torch.empty_like(xs[0])
-                _native.resblock1_fused([xs[1]], [h1[1]], [h2[1]], [b1s[1]], [b2s[1]], [3], dil, 0.1, outs=[merged], prec=SPLIT,
-                                        add1=[ys[0]], add2=[ys[2]], out_div=3.0, act_slope=0.1)
+                with _native.launch_log() as log:
+                    ys = _native.resblock1_fused(xs, h1, h2, b1s, b2s, list(ks), dil, 0.1, prec=SPLIT)
+                    merged = torch.empty_like(xs[0])
+                    _native.resblock1_fused([xs[1]], [h1[1]], [h2[1]], [b1s[1]], [b2s[1]], [3], dil, 0.1, outs=[merged], prec=SPLIT,
+                                            add1=[ys[0]], add2=[ys[2]], out_div=3.0, act_slope=0.1)
                 outs[(wide, blocks)] = ys + [merged]
+                # the form each side ran on (csrc/convh_launch.hip launch_fused_pair; convq2_kernel<dilation, form>: 64 / 128 the
+                # narrow tiles, 130 the 128-channel launch whose 11-tap member has 80 columns, 65 / 129 the wide tiles).  The
+                # wide form exists at 64 channels and, at 128, for dilation 1 and 3: at dilation 5 both sides are narrow
+                # and the comparison claims nothing
+                narrow_forms = {f"convq2_kernel<{dil}, {C}>"} | ({f"convq2_kernel<{dil}, 130>"} if C == 128 else set())
+                if wide == 0 and (C == 64 or dil <= 3):
+                    assert log.kernels == {f"convq2_kernel<{dil}, {C + 1}>": 2}, (C, T, dil, blocks, log.kernels)
+                else:
+                    assert set(log.kernels) <= narrow_forms and sum(log.kernels.values()) == 2, (C, T, dil, wide, log.kernels)
         tuning("convh_blocks", 0)
         tuning("convp_wide", 20)
         tuning("convq_wide", 20)
@@ -640,8 +715,10 @@ def test_pair_tile_forms_give_the_same_bits(tuning):
         for key, ys in outs.items():
             for y, yb in zip(ys, base):
                 assert torch.equal(y, yb), key
-        mids = _native.conv1d_split_f16(xs, h1, b1s, list(ks), dil, pre_slope=0.1)
-        two = _native.conv1d_split_f16(mids, h2, b2s, list(ks), 1, pre_slope=0.1, res=xs)
+        with _native.launch_log() as log:
+            mids = _native.conv1d_split_f16(xs, h1, b1s, list(ks), dil, pre_slope=0.1)
+            two = _native.conv1d_split_f16(mids, h2, b2s, list(ks), 1, pre_slope=0.1, res=xs)
+        assert log.families() <= {"convh_kernel", "convs_kernel"} and sum(log.kernels.values()) == 2, log.kernels
         for yf, yt in zip(base[:3], two):
             assert torch.equal(yf, yt)
 
@@ -830,7 +907,10 @@ def test_range_guard_of_the_split_kernels():
         guard.zero_()
         # ... while the fp32 kernels (16 / 32 channels) take the same input in their stride
         if C <= 32:
-            y32 = _native.resblock1_fused([_t(x)], [_native.pack_pair(_t(w1))], [_native.pack_pair(_t(w2))], *args)[0]
+            with _native.launch_log() as log:
+                y32 = _native.resblock1_fused([_t(x)], [_native.pack_pair(_t(w1))], [_native.pack_pair(_t(w2))], *args)[0]
+            # the repeat ran the exact-fp32 pair kernel and no split-f16 one
+            assert log.families() == {"pair_kernel"}, log.kernels
             assert bool(torch.isfinite(y32).all()) and _rel_to(y32, _pair_ref(x, w1, b1, w2, b2, dil, 0.1)) <= 2e-5
     # the intermediate of a fused pair overflows although its input does not: large first conv
     C, T, k = 16, 500, 3
@@ -869,11 +949,13 @@ def test_conv1x1_2src_split_f16_vs_oracle(case, tuning):
     P = _native.pack_conv1x1_2src_split(_t(w1), _t(w2))
     guard = torch.zeros(1, dtype=torch.int32, device=_dev())
     tuning("convg_rows64", 0)                          # 128-row tiles whatever the size (the default picks by item count)
-    y = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, _t(b), pre_slope=0.2, guard=guard)
+    with _native.launch_log() as log_wide:
+        y = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, _t(b), pre_slope=0.2, guard=guard)
+        twin = torch.empty_like(y)
+        y2 = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, None, pre_slope=0.2, res=_t(res), post=_native.POST_RELU,
+                                            out_act=twin, act_slope=0.1, guard=guard)
+    assert log_wide.kernels == {"convr_kernel": 2}, log_wide.kernels
     assert tuple(y.shape) == ref.shape and _rel(y, ref) <= 4e-6
-    twin = torch.empty_like(y)
-    y2 = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, None, pre_slope=0.2, res=_t(res), post=_native.POST_RELU,
-                                        out_act=twin, act_slope=0.1, guard=guard)
     want = np.maximum(ref - b[None, :, None] + res, 0)
     assert _rel(y2, want) <= 4e-6 and _rel(twin, oo.lrelu(want, 0.1)) <= 4e-6
     assert int(guard.item()) == 0
@@ -886,10 +968,12 @@ def test_conv1x1_2src_split_f16_vs_oracle(case, tuning):
         assert torch.equal(one, y[1:2])
     # 128-row tiles (convr_kernel, the default) against 64-row tiles (convg_kernel): the same K order per output
     tuning("convg_rows64", 1)
-    narrow = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, _t(b), pre_slope=0.2)
-    twin64 = torch.empty_like(y)
-    narrow2 = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, None, pre_slope=0.2, res=_t(res), post=_native.POST_RELU,
-                                             out_act=twin64, act_slope=0.1)
+    with _native.launch_log() as log_narrow:
+        narrow = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, _t(b), pre_slope=0.2)
+        twin64 = torch.empty_like(y)
+        narrow2 = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, None, pre_slope=0.2, res=_t(res), post=_native.POST_RELU,
+                                                 out_act=twin64, act_slope=0.1)
+    assert log_narrow.kernels == {"convg_kernel<4>": 2}, log_narrow.kernels
     tuning("convg_rows64", -1)
     auto = _native.conv1x1_2src_split_f16(_t(x), _t(x2), P, _t(b), pre_slope=0.2)
     tuning("convg_rows64", 0)
@@ -1000,9 +1084,17 @@ def test_low_side_of_the_range_guard():
         xn = (x / np.abs(x).max()).astype(np.float32)
         _native.resblock1_fused([_t(xn * _pow2(-9))], *ws, *args, prec=SPLIT, guard=guard)
         assert fired() == 0                           # largest magnitude 2^-9: inside
-        _native.resblock1_fused([_t(xn * _pow2(-11))], *ws, *args, prec=SPLIT, guard=guard)
+        with _native.launch_log() as log_split:
+            _native.resblock1_fused([_t(xn * _pow2(-11))], *ws, *args, prec=SPLIT, guard=guard)
         assert fired() == _native.GUARD_LOW                           # 2^-11: the whole tensor is below the low side (although the
                                                       # intermediate, which the biases dominate, is ordinary)
+        assert log_split.families() == {"pairh_kernel" if C <= 32 else "convq2_kernel"}, log_split.kernels
+        if C <= 32:                                   # what a caller does then: the same call on the exact-fp32 pair kernel
+            quiet_x = xn * _pow2(-11)
+            with _native.launch_log() as log:
+                y32 = _native.resblock1_fused([_t(quiet_x)], [_native.pack_pair(_t(w1))], [_native.pack_pair(_t(w2))], *args)[0]
+            assert log.families() == {"pair_kernel"}, log.kernels
+            assert _rel_to(y32, _pair_ref(quiet_x, w1, b1, w2, b2, dil, 0.1)) <= 2e-5
         quiet = x.copy()
         quiet[:, :, T // 3: T // 3 + 40] *= _pow2(-20)     # silence inside an ordinary signal is not
         y = _native.resblock1_fused([_t(quiet)], *ws, *args, prec=SPLIT, guard=guard)[0]

@@ -54,6 +54,21 @@ def _model(name, cfg, seed):
     return m.to(_dev()).eval(), sd
 
 
+# kernel families by arithmetic (launch log names): what a call repeated after the range guard must / must not run
+SPLIT_F16_FAMILIES = {"pairh_kernel", "convh_kernel", "convs_kernel", "convs2_kernel", "convq2_kernel", "convt_kernel",
+                      "convtl_kernel", "convtn_kernel", "convu_kernel", "convu2_kernel", "convg_kernel", "convr_kernel",
+                      "convk2_kernel", "mrfh_kernel", "mrfw_kernel"}
+EXACT_FP32_FAMILIES = {"conv_mfma_kernel", "pair_kernel", "conv_group3_kernel"}
+
+
+def _ran_on_exact_fp32(log):
+    """The logged call launched exact-fp32 kernels and no split-f16 one."""
+    fams = log.families()
+    assert fams & EXACT_FP32_FAMILIES, log.kernels
+    assert not fams & SPLIT_F16_FAMILIES, log.kernels
+    return True
+
+
 def test_native_library_is_loaded():
     L = _native.lib()
     assert L.fv_version() == _native.ABI_VERSION
@@ -378,7 +393,9 @@ def test_mrf_sum3_kernel_forced_on_small_configs(golden_dir, tag):
         g = np.load(os.path.join(golden_dir, f"small_{tag}.npz"))
         m, sd = _model(name, cfg, seed=7)
         m.fuse_pairs = False                        # the conv-by-conv path is where sum3 lives
-        y = m.inference(seeded_mel(cases.SMALL_T, seed=5))
+        with _native.launch_log() as log:
+            y = m.inference(seeded_mel(cases.SMALL_T, seed=5))
+        assert "conv_sum3_kernel" in log.families(), log.kernels      # sum3_min = 1 did select the one-launch kernel
         assert _err(y, g["inference"]) <= TOL
         f = m(torch.from_numpy(seeded_mel(cases.SMALL_T, seed=6, batch=cases.SMALL_B)).to(_dev()))
         assert _err(f, g["forward"]) <= TOL
@@ -711,11 +728,17 @@ def test_lean_upsamplers_give_the_same_bits(name, path, T):
     xs = [torch.from_numpy(seeded_mel(T, seed=21, batch=1)).to(_dev()), torch.from_numpy(seeded_mel(37, seed=22, batch=3)).to(_dev())]
     try:
         with torch.no_grad():
-            lean = [m(x).clone() for x in xs]
+            with _native.launch_log() as log_lean:
+                lean = [m(x).clone() for x in xs]
             _native.tuning_set("convt_lean", 0)
-            ring = [m(x).clone() for x in xs]
+            with _native.launch_log() as log_ring:
+                ring = [m(x).clone() for x in xs]
     finally:
         _native.tuning_set("convt_lean", 50)
+    # the two sides ran different kernels: the lean one on the first, none of it on the second, whose upsamplers are on the
+    # ring pipeline's kernels instead
+    assert "convtl_kernel" in log_lean.families(), log_lean.kernels
+    assert "convtl_kernel" not in log_ring.families() and log_ring.families() & {"convt_kernel", "convu_kernel", "convu2_kernel"}, log_ring.kernels
     assert all(torch.equal(a, b) for a, b in zip(lean, ring))
     assert not m.check_range()
 
@@ -1337,13 +1360,16 @@ def test_generator_beyond_the_f16_range_repeats_on_fp32():
         want = exact.inference(mel)
     assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 1e-3
     m = _scaled_hifigan(1e6)
-    with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad():
+    with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad(), _native.launch_log() as log_first:
         got = m.inference(mel)
     assert torch.equal(got, want)
     assert m._fv_policy()[0] == "f32"
-    with torch.no_grad():
+    # the first call ran the split-f16 attempt AND its repeat on the fp32 pair kernels (which the split policy never launches);
+    # its log holds both together, so that the fp32 policy runs NO split-f16 kernel is asserted on the next call
+    assert log_first.families() & SPLIT_F16_FAMILIES and "pair_kernel" in log_first.families(), log_first.kernels
+    with torch.no_grad(), _native.launch_log() as log_again:
         again = m.inference(mel)                    # no second warning, no second split-f16 attempt
-    assert torch.equal(again, want)
+    assert torch.equal(again, want) and _ran_on_exact_fp32(log_again)
     # the oracle agrees with the fp32 path on this model (the reference's arithmetic has no such limit)
     sd = {k: v.detach().cpu().numpy() for k, v in exact.state_dict().items()}
     ref = torch_port.inference("hifigan", mel, sd, cases.load_conf("conf/hifigan/light.yaml")).numpy()
@@ -1416,9 +1442,17 @@ def test_melgan_outside_the_split_domain_repeats_on_fp32(gain):
         with torch.no_grad():
             for _ in range(m.low_range_patience):
                 assert torch.equal(m.inference(mel), want) and m._fv_policy()[0] == "split"
-    with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad():
+    with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad(), _native.launch_log() as log_first:
         got = m.inference(mel)
     assert torch.equal(got, want) and m._fv_policy()[0] == "f32"
+    # the first call's log holds the split-f16 attempt and its repeat together; the repeat shows as the 1-tap fp32 convs of the
+    # stacks' two-launch form, which the split policy never launches (that the fp32 policy runs NO split kernel is asserted on
+    # the next call, below)
+    assert log_first.families() & SPLIT_F16_FAMILIES, log_first.kernels
+    assert any(k.startswith("conv_mfma_kernel<") and k.endswith(", 1, 1, false, false>") for k in log_first.kernels), log_first.kernels
+    with torch.no_grad(), _native.launch_log() as log_again:      # the module stays on the exact-fp32 kernels
+        assert torch.equal(m.inference(mel), want)
+    assert _ran_on_exact_fp32(log_again)
     ok = _scaled_melgan(30.0 if gain > 1 else 1.0 / 30.0)          # inside the domain: stays on the split kernels
     with torch.no_grad():
         y = ok.inference(mel)
@@ -1523,9 +1557,13 @@ def test_generator_below_the_low_side_repeats_on_fp32():
     with torch.no_grad():
         for _ in range(m.low_range_patience):
             assert torch.equal(m.inference(mel), want) and m._fv_policy()[0] == "split" and not m._fv_overflow
-    with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad():
+    with pytest.warns(RuntimeWarning, match="split-f16 range"), torch.no_grad(), _native.launch_log() as log_first:
         got = m.inference(mel)
     assert torch.equal(got, want) and m._fv_policy()[0] == "f32"
+    assert log_first.families() & SPLIT_F16_FAMILIES and "pair_kernel" in log_first.families(), log_first.kernels
+    with torch.no_grad(), _native.launch_log() as log_again:      # for good: the next call is on the exact-fp32 kernels alone
+        assert torch.equal(m.inference(mel), want)
+    assert _ran_on_exact_fp32(log_again)
     # the repeated call's output against the float64 port of the scaled model
     cfg = cases.load_conf("conf/hifigan/light.yaml")
     sd = {k: v.detach().cpu().numpy() for k, v in exact.state_dict().items()}
@@ -1572,13 +1610,19 @@ def test_128_row_tiles_give_the_same_waveform_bits(name, path):
     m, _ = _model(name, cfg, seed=0)
     mel = seeded_mel(40, seed=9)
     x = torch.from_numpy(seeded_mel(33, seed=8, batch=2)).to(_dev())
-    outs = []
+    outs, logs = [], []
     try:
+        # MelGAN's and Basis-MelGAN's stacks run as ONE launch (convk2_kernel) at every size, where neither switch is read:
+        # their 256-channel stacks carry the two-launch form (conv + two-source 1x1 GEMM), which `stack_items = 0` selects
+        # -- the launches these switches are about.  HiFi-GAN large has its 256 / 512-channel convs on them as it is.
+        if name != "hifigan":
+            _native.tuning_set("stack_items", 0)
         for rows64 in (1, 0):
             _native.tuning_set("convg_rows64", rows64)
             _native.tuning_set("convh_rows64", rows64)
             m.invalidate_plans()
-            with torch.no_grad():
+            logs.append(_native.launch_log())
+            with torch.no_grad(), logs[-1]:
                 bias = m.inference(np.zeros_like(mel)).clone()
                 est, rem = m.inference_minus(mel, bias)
                 y = m(x)
@@ -1587,5 +1631,13 @@ def test_128_row_tiles_give_the_same_waveform_bits(name, path):
     finally:
         _native.tuning_set("convg_rows64", -1)
         _native.tuning_set("convh_rows64", -1)
+        _native.tuning_set("stack_items", 1 << 20)
+    # the switches took: 64-row kernels (convh_kernel at 128+ channels, convg_kernel) on one side, their 128-row twins
+    # (convs_kernel / the ring-free convs2_kernel, convr_kernel) on the other, and neither side ran the other's
+    rows64_kernels = {k for k in logs[0].kernels if k.startswith(("convh_kernel<4,", "convg_kernel"))}
+    rows128 = logs[1].families() & {"convs_kernel", "convs2_kernel", "convr_kernel"}
+    assert rows64_kernels and rows128, (logs[0].kernels, logs[1].kernels)
+    assert not logs[0].families() & {"convs_kernel", "convs2_kernel", "convr_kernel"}, logs[0].kernels
+    assert not {k for k in logs[1].kernels if k.startswith(("convh_kernel<4,", "convg_kernel"))}, logs[1].kernels
     assert all(torch.equal(a, b) for a, b in zip(*outs))
     assert not m.check_range()

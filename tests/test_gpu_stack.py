@@ -121,7 +121,12 @@ def test_residual_stack_vs_oracle(case, tuning):
             tuning("stack_wide", wide)
             for blocks in (0, 2):
                 tuning("convh_blocks", blocks)
-                assert torch.equal(_run(*m, dil, 0.2, nmode), y)
+                with _native.launch_log() as log:
+                    assert torch.equal(_run(*m, dil, 0.2, nmode), y)
+                # both tile widths ran: stack_wide = 0 is the 64-column instantiation, 1 << 20 the 32-column one (the weights
+                # are packed inside _run: pack_convk2_kernel and row_scale_kernel are not the operator)
+                assert f"convk2_kernel<256, {dil}, {64 if wide == 0 else 32}>" in log.kernels, (wide, log.kernels)
+                assert {k for k in log.kernels if k.startswith("convk2_kernel")} == {f"convk2_kernel<256, {dil}, {64 if wide == 0 else 32}>"}
         tuning("convh_blocks", 0)
         tuning("stack_wide", 10)
 
@@ -135,15 +140,26 @@ def test_residual_stack_is_the_two_launch_form_bit_for_bit(case, tuning):
     B, C, T, dil = case
     rng = np.random.RandomState(C + T + dil)
     x, w1, b1, w2, b2, ws, bs = _stack(rng, B, C, T)
-    fused = _run(x, w1, b1, w2, b2, ws, bs, dil, 0.2, _native.PAD_REFLECT)
+    with _native.launch_log() as log_fused:
+        fused = _run(x, w1, b1, w2, b2, ws, bs, dil, 0.2, _native.PAD_REFLECT)
     tuning("stack_wide", 0)                  # (256 channels: the 64-column tile; elsewhere no effect)
-    wide = _run(x, w1, b1, w2, b2, ws, bs, dil, 0.2, _native.PAD_REFLECT)
+    with _native.launch_log() as log_wide:
+        wide = _run(x, w1, b1, w2, b2, ws, bs, dil, 0.2, _native.PAD_REFLECT)
     tuning("stack_wide", 10)
     assert torch.equal(wide, fused)
-    hid = _native.conv1d_split_f16([_t(x)], [_native.pack_pair(_t(w1), SPLIT)], [_t(b1)], [3], dil, pre_slope=0.2,
-                                   pad_mode=_native.PAD_REFLECT)[0]
-    two = _native.conv1x1_2src_split_f16(hid, _t(x), _native.pack_conv1x1_2src_split(_t(w2), _t(ws)), _t(b2 + bs), pre_slope=0.2)
+    P1, P2 = _native.pack_pair(_t(w1), SPLIT), _native.pack_conv1x1_2src_split(_t(w2), _t(ws))
+    with _native.launch_log() as log_two:
+        hid = _native.conv1d_split_f16([_t(x)], [P1], [_t(b1)], [3], dil, pre_slope=0.2, pad_mode=_native.PAD_REFLECT)[0]
+        two = _native.conv1x1_2src_split_f16(hid, _t(x), P2, _t(b2 + bs), pre_slope=0.2)
     assert torch.equal(fused, two)
+    # the one-launch kernel on one side, the two launches the docstring names on the other
+    stack = {k for k in log_fused.kernels if k.startswith("convk2_kernel")}
+    assert len(stack) == 1 and log_fused.kernels[next(iter(stack))] == 1, log_fused.kernels
+    assert "convk2_kernel" not in log_two.families() and sum(log_two.kernels.values()) == 2, log_two.kernels
+    fams = log_two.families()
+    assert len(fams) == 2 and fams & {"convh_kernel", "convs_kernel"} and fams & {"convg_kernel", "convr_kernel"}, log_two.kernels
+    if C == 256:                             # stack_wide = 0 forced the 64-column instantiation
+        assert {k for k in log_wide.kernels if k.startswith("convk2_kernel")} == {f"convk2_kernel<256, {dil}, 64>"}, log_wide.kernels
 
 
 @pytest.mark.parametrize("C", [32, 64, 128, 256])
@@ -218,14 +234,18 @@ def test_melgan_module_runs_its_stacks_fused():
     rs = M.ResidualStack(kernel_size=3, channels=256, dilation=3).to(_dev())
     for T in (500, 40000):
         x = torch.randn(1, 256, T, device=_dev())
-        picked = rs(x)                                     # one launch (the default at every size)
+        with _native.launch_log() as log_one:
+            picked = rs(x)                                 # one launch (the default at every size)
         assert {k[0]: v[1].num_ops() for k, v in rs._fv_plans.items()}["forward"] == 1
         _native.tuning_set("stack_items", 0)               # the two launches the same op carries
         try:
-            other = rs(x)
+            with _native.launch_log() as log_two:
+                other = rs(x)
         finally:
             _native.tuning_set("stack_items", 1 << 20)
         assert torch.equal(picked, other)
+        assert log_one.families() == {"convk2_kernel"} and sum(log_one.operators().values()) == 1, log_one.kernels
+        assert sum(log_two.operators().values()) == 2 and log_two.families() <= {"convh_kernel", "convs_kernel", "convg_kernel", "convr_kernel"}, log_two.kernels
     g = MelGANGenerator().to(_dev()).eval()
     mel = torch.randn(1, 80, 50, device=_dev())
 

@@ -113,11 +113,17 @@ def test_mrf_stage_vs_oracle_and_pair_launches(case, tuning):
     tuning("mrf_shape", shape)
     X, P = _t(x), _pack(ws, ks)
     guard = torch.zeros(1, dtype=torch.int32, device=_dev())
-    y = _native.mrf_stage_split_f16(X, P, ks, guard=guard)
+    with _native.launch_log() as log:
+        y = _native.mrf_stage_split_f16(X, P, ks, guard=guard)
+    # mrf_shape picked the block shape: 0 -- 12 waves x 3 fragments, 1 -- 16 waves x 2 (csrc/mrfh_launch.hip)
+    assert log.kernels == {f"mrfh_kernel<{'3, 12' if shape == 0 else '2, 16'}, 1, 3, 5, false>": 1}, log.kernels
     assert _rel(y, ref) <= 4e-6
     assert int(guard.item()) == 0
     if T % 4 == 0:                                        # (the pair kernels want 16-byte aligned rows)
-        assert torch.equal(y, _pairs_stage(X, ws, ks)), "one launch and the four pair launches differ"
+        with _native.launch_log() as log_pairs:
+            pairs = _pairs_stage(X, ws, ks)
+        assert log_pairs.families() == {"pairh_kernel"}, log_pairs.kernels
+        assert torch.equal(y, pairs), "one launch and the four pair launches differ"
     # activated twin next to the raw output, and the in-place form
     twin = torch.empty_like(y)
     y2 = _native.mrf_stage_split_f16(X, P, ks, out_act=twin, act_slope=0.1)
@@ -243,11 +249,16 @@ def test_mrf_stage32_vs_oracle_and_pair_launches(case, tuning):
     tuning("mrf_blocks", blocks)
     X, P = _t(x), _pack(ws, ks)
     guard = torch.zeros(1, dtype=torch.int32, device=_dev())
-    y = _native.mrf_stage_split_f16(X, P, ks, guard=guard)
+    with _native.launch_log() as log:
+        y = _native.mrf_stage_split_f16(X, P, ks, guard=guard)
+    assert log.families() == {"mrfw_kernel"} and sum(log.kernels.values()) == 1, log.kernels
     assert _rel(y, ref) <= 4e-6
     assert int(guard.item()) == 0
     if T % 4 == 0:
-        assert torch.equal(y, _pairs_stage(X, ws, ks)), "one launch and the four pair launches differ"
+        with _native.launch_log() as log_pairs:
+            pairs = _pairs_stage(X, ws, ks)
+        assert log_pairs.families() == {"pairh_kernel"}, log_pairs.kernels
+        assert torch.equal(y, pairs), "one launch and the four pair launches differ"
     twin = torch.empty_like(y)
     y2 = _native.mrf_stage_split_f16(X, P, ks, out_act=twin, act_slope=0.1)
     assert torch.equal(y2, y) and _rel(twin, oo.lrelu(ref, 0.1)) <= 4e-6

@@ -62,8 +62,13 @@ def _pairs(x, ws, slope=0.1):
 
 
 def _check(X, P, ws, **kw):
-    r = _pairs(X, ws)
-    y_s, y_r2 = _native.mrf_stage_classes_f16(X, P, KS, **kw)
+    with _native.launch_log() as log_pairs:
+        r = _pairs(X, ws)
+    with _native.launch_log() as log:
+        y_s, y_r2 = _native.mrf_stage_classes_f16(X, P, KS, **kw)
+    # the two-class instantiation of mrfw_kernel on one side, the pair launches on the other
+    assert log.kernels == {"mrfw_kernel<3, 8, 1, 3, 5, false, true>": 1}, log.kernels
+    assert log_pairs.families() == {"pairh_kernel"}, log_pairs.kernels
     assert torch.equal(y_r2, r[2]), "r_2 differs from the pair launches"
     assert torch.equal(y_s, r[0] + r[1]), "r_0 + r_1 differs from the pair launches"
     return y_s, y_r2

@@ -109,8 +109,17 @@ def test_hifigan_light_with_the_two_class_stage_forced(frames, models):
 
     with torch.no_grad():
         split(x), pairs(x)
-        (a, n_split), (b, n_pairs) = launches(split, x), launches(pairs, x)
+        with _native.launch_log() as log_split:
+            a, n_split = launches(split, x)
+        with _native.launch_log() as log_pairs:
+            b, n_pairs = launches(pairs, x)
         assert torch.equal(a, b)
+        # the two sides differ by the kernel the test is about: the two-class instantiation of mrfw_kernel against the
+        # 32-channel pair launches, and no all-in-one stage kernel on either side
+        assert "mrfw_kernel<3, 8, 1, 3, 5, false, true>" in log_split.kernels and "mrfw_kernel" not in log_pairs.families()
+        assert {k for k in log_split.kernels if k.startswith("mrfw_kernel")} == {"mrfw_kernel<3, 8, 1, 3, 5, false, true>"}
+        assert any(k.startswith("pairh_kernel<2,") for k in log_pairs.kernels) and \
+            not any(k.startswith("pairh_kernel<2,") for k in log_split.kernels), (log_split.kernels, log_pairs.kernels)
         assert n_split == n_pairs - 2, (n_split, n_pairs)         # three launches of fused pairs -> one
         one = x[1:2].contiguous()
         assert torch.equal(split(one), pairs(one)) and torch.equal(split(one)[0], a[1])
