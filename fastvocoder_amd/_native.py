@@ -371,6 +371,8 @@ def lib():
     L.fv_debug_launch_log.argtypes = [i]
     L.fv_debug_launch_log_read.argtypes = [ctypes.c_char_p, i64]
     L.fv_debug_launch_log_read.restype = i64
+    L.fv_debug_launch_log_streams.argtypes = [vp, vp, i64, vp]
+    L.fv_debug_launch_log_streams.restype = i64
     L.fv_debug_kernel_name.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64]
     L.fv_debug_kernel_name.restype = i64
     L.fv_mrf_stage_classes_f16.argtypes = [vp, vp, vp, vp, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp, vp]
@@ -464,12 +466,15 @@ def tuning_set(key, value):
 class launch_log:
     """Test hook (fv_debug_launch_log, host only): `with launch_log() as log:` records every kernel the library launches
     inside the block; afterwards `log.kernels` is a dict of instantiation name ("convh_kernel<2, 2, 1>") to launch count,
-    in first-launch order.  Process-wide and not nestable: entering while one is active raises.  Launches of child
-    processes are not seen, nor which block or path inside a kernel ran."""
+    in first-launch order; `log.streams` is a dict of stream handle (`torch.cuda.Stream.cuda_stream`; 0: the null stream)
+    to the kernels launched plus the asynchronous memsets and copies enqueued on it, and `log.copies` is how many of those
+    were memsets and copies: sum(streams.values()) == sum(kernels.values()) + copies.  Process-wide and not nestable:
+    entering while one is active raises.  Launches of child processes are not seen, nor which block or path inside a
+    kernel ran, nor anything torch itself enqueues."""
     _active = False
 
     def __init__(self):
-        self.kernels = {}
+        self.kernels, self.streams, self.copies = {}, {}, 0
 
     def __enter__(self):
         if launch_log._active:
@@ -489,6 +494,11 @@ class launch_log:
         for line in buf.raw[:need].decode().splitlines():
             count, name = line.split("\t", 1)
             self.kernels[name] = self.kernels.get(name, 0) + int(count)
+        n = int(L.fv_debug_launch_log_streams(None, None, 0, None))
+        handles, counts, copies = (ctypes.c_uint64 * max(n, 1))(), (ctypes.c_int64 * max(n, 1))(), ctypes.c_int64(0)
+        L.fv_debug_launch_log_streams(handles, counts, n, ctypes.byref(copies))
+        self.streams = {int(handles[k]): int(counts[k]) for k in range(n)}
+        self.copies = int(copies.value)
         return False
 
     def operators(self):

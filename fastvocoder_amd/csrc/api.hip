@@ -41,15 +41,25 @@ int fail(int code, const char* fmt, ...) {
 std::atomic<int> g_launch_log_on{0};
 static std::mutex g_launch_log_mutex;
 static std::vector<std::pair<const void*, long long>> g_launch_log;   // (kernel handle, launches) in first-seen order
+static std::vector<std::pair<hipStream_t, long long>> g_launch_log_streams;   // (stream handle, launches + async copies)
+static long long g_launch_log_copies = 0;                              // async memsets / copies (memset_async, memcpy_async)
 
-void launch_log_note(const void* handle) {
-    std::lock_guard<std::mutex> lock(g_launch_log_mutex);
-    for (auto& e : g_launch_log)
-        if (e.first == handle) {
+template <class K>
+static void launch_log_count(std::vector<std::pair<K, long long>>& table, K key) {
+    for (auto& e : table)
+        if (e.first == key) {
             ++e.second;
             return;
         }
-    g_launch_log.emplace_back(handle, 1);
+    table.emplace_back(key, 1);
+}
+
+// handle: the kernel's, or null for an asynchronous memset / copy
+void launch_log_note(const void* handle, hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(g_launch_log_mutex);
+    if (handle) launch_log_count(g_launch_log, handle);
+    else ++g_launch_log_copies;
+    launch_log_count(g_launch_log_streams, stream);
 }
 
 // "void fv::convh_kernel<2, 2, 1>(fv::PairParams)" -> "convh_kernel<2, 2, 1>": the return type, every "fv::", the host
@@ -445,14 +455,18 @@ const Tuning& tuning() {
 }
 
 int device_cu_count() {
-    static int cus = 0;   // one device model per process (the boxes hold eight identical GPUs)
-    if (!cus) {
-        int dev = 0, v = 0;
-        cus = hipGetDevice(&dev) == hipSuccess &&
-                      hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0
-                  ? v : 256;
+    // one device model per process (the boxes hold eight identical GPUs).  Threads that come first together each ask the
+    // runtime and store the same number: an atomic, so that the first uses of two threads are no data race.
+    static std::atomic<int> cus{0};
+    int v = cus.load(std::memory_order_relaxed);
+    if (!v) {
+        int dev = 0;
+        v = hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0
+                ? v : 256;
+        cus.store(v, std::memory_order_relaxed);
     }
-    return cus;
+    return v;
 }
 }  // namespace fv
 
@@ -1365,9 +1379,24 @@ int fv_tuning_set(const char* key, int value) {
 int fv_debug_launch_log(int on) {
     if (on != 0 && on != 1) return fail(FV_ERR_INVALID_ARG, "debug_launch_log: on = %d (0 or 1)", on);
     std::lock_guard<std::mutex> lock(fv::g_launch_log_mutex);
-    if (on) fv::g_launch_log.clear();
+    if (on) {
+        fv::g_launch_log.clear();
+        fv::g_launch_log_streams.clear();
+        fv::g_launch_log_copies = 0;
+    }
     fv::g_launch_log_on.store(on, std::memory_order_relaxed);
     return 0;
+}
+
+int64_t fv_debug_launch_log_streams(uint64_t* handles, int64_t* counts, int64_t cap, int64_t* copies) {
+    std::lock_guard<std::mutex> lock(fv::g_launch_log_mutex);
+    const int64_t n = (int64_t)fv::g_launch_log_streams.size();
+    for (int64_t i = 0; i < n && i < cap; ++i) {
+        if (handles) handles[i] = (uint64_t)(uintptr_t)fv::g_launch_log_streams[i].first;
+        if (counts) counts[i] = fv::g_launch_log_streams[i].second;
+    }
+    if (copies) *copies = fv::g_launch_log_copies;
+    return n;
 }
 
 int64_t fv_debug_launch_log_read(char* buf, int64_t cap) {

@@ -25,14 +25,29 @@ static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // nowhere else).  Test hook fv_debug_launch_log (api.hip): while it is on, the kernel's host handle is counted in a
 // process-wide table, so that a test can prove WHICH kernel produced its numbers.  Off (the default) the launch path pays
 // one relaxed atomic load: no lock, no allocation, no device work; no launch parameter changes either way.
+// The log also counts launches per STREAM handle (the helper's fifth argument; fv_debug_launch_log_streams), so that a test
+// can prove which stream every launch of a call went to.  The kernel arguments may be empty (profile_null_kernel).
+// The library's asynchronous memsets and copies go through the two sibling helpers below, which note their stream in the
+// same table (handle null: no kernel).  No other enqueueing call is written anywhere in csrc/ -- hipLaunchKernelGGL, <<< >>>,
+// hipMemsetAsync and hipMemcpyAsync appear in this file alone (tests/test_kernel_census_host.py greps for them); the event
+// records of the measurement hooks (api.hip) move no data and are not counted.
 extern std::atomic<int> g_launch_log_on;
-void launch_log_note(const void* handle);
-#define FV_KERNEL_LAUNCH(kernel, ...)                                                  \
+void launch_log_note(const void* handle, hipStream_t stream);
+#define FV_KERNEL_LAUNCH(kernel, grid, block, lds, stream, ...)                        \
     do {                                                                              \
+        hipStream_t fv_launch_stream_ = (stream);                                     \
         if (::fv::g_launch_log_on.load(std::memory_order_relaxed))                    \
-            ::fv::launch_log_note((const void*)(kernel));                             \
-        hipLaunchKernelGGL(kernel, __VA_ARGS__);                                      \
+            ::fv::launch_log_note((const void*)(kernel), fv_launch_stream_);          \
+        hipLaunchKernelGGL(kernel, grid, block, lds, fv_launch_stream_, ##__VA_ARGS__); \
     } while (0)
+static inline hipError_t memset_async(void* dst, int value, size_t bytes, hipStream_t stream) {
+    if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_note(nullptr, stream);
+    return hipMemsetAsync(dst, value, bytes, stream);
+}
+static inline hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t stream) {
+    if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_note(nullptr, stream);
+    return hipMemcpyAsync(dst, src, bytes, kind, stream);
+}
 
 // argument checks shared by the operator entries (api.hip) and the pack entries (pack.hip)
 int check_conv_args(int Cin, int Cout, int k, int dil);

@@ -521,7 +521,7 @@ int fv_pack_mrf_stage_split_f16(const float* const* w1, const float* const* w2, 
     if (floats == 0) return fail(FV_ERR_UNSUPPORTED, "pack_mrf_stage: shape not built (16 channels, taps 3 / 7 / 11)");
     if (!w1 || !w2 || !packed) return fail(FV_ERR_INVALID_ARG, "pack_mrf_stage: null tensor");
     hipStream_t const s = (hipStream_t)stream;
-    FV_HIP(hipMemsetAsync(packed, 0, (size_t)floats * 4, s));          // absent biases and the blocks' padding: zeros
+    FV_HIP(memset_async(packed, 0, (size_t)floats * 4, s));          // absent biases and the blocks' padding: zeros
     char* at = reinterpret_cast<char*>(packed);
     for (int j = 0; j < 3; ++j)
         for (int q = 0; q < 3; ++q) {
@@ -538,8 +538,8 @@ int fv_pack_mrf_stage_split_f16(const float* const* w1, const float* const* w2, 
                 FV_KERNEL_LAUNCH(pack_pairh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws[c],
                                    reinterpret_cast<_Float16*>(at + c * wb), inv, C, k[j], range_flag);
             }
-            if (b1 && b1[i]) FV_HIP(hipMemcpyAsync(tail, b1[i], (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-            if (b2 && b2[i]) FV_HIP(hipMemcpyAsync(tail + C, b2[i], (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+            if (b1 && b1[i]) FV_HIP(memcpy_async(tail, b1[i], (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+            if (b2 && b2[i]) FV_HIP(memcpy_async(tail + C, b2[i], (size_t)C * 4, hipMemcpyDeviceToDevice, s));
             at += mrf_block_bytes(C, k[j]);
         }
     FV_HIP(hipGetLastError());

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void encode16_kernel(float* __restrict__ x, in
 int launch_encode16(float* x, int B, int64_t n, float rescale, short* out, unsigned* peak_bits,
                     int scale_in_place, hipStream_t s) {
     if (B <= 0) return 0;
-    FV_HIP(hipMemsetAsync(peak_bits, 0, sizeof(unsigned) * B, s));
+    FV_HIP(memset_async(peak_bits, 0, sizeof(unsigned) * B, s));
     if (n <= 0) return 0;
     int64_t blocks = (n + 1023) / 1024;
     if (blocks > 2048) blocks = 2048;

@@ -13,6 +13,8 @@ Every activation, bias, residual add, the MRF sum and its /num_kernels, and
 tanh are epilogue/prologue work of the conv kernels: the whole forward is
 ``num_convs`` launches (78 for the shipped 4-stage configs) and nothing else.
 """
+import threading
+
 import torch
 
 from .. import _native
@@ -27,6 +29,10 @@ DEFAULT_LRELU_SLOPE = 0.01  # F.leaky_relu's default, used before conv_post (hif
 
 
 _CU_COUNT = {}      # device -> compute units (asked once per device: the policy below runs on every forward)
+# One thread at a time asks torch for a device's properties: torch.cuda.device_count(), which get_device_properties checks the
+# index against, is not safe to call for the first time from several threads at once (it came back 0 -- "Invalid device id"
+# -- in two of three threads that built their first plan together: tests/test_gpu_threads.py, cold start).
+_CU_COUNT_LOCK = threading.Lock()
 
 
 def stage32_windows_fit(cols, cus, fill=0.65):
@@ -220,7 +226,10 @@ class _HiFiGANBase(GradPrecision, NativeModule):
         dev = self._device()
         cus = _CU_COUNT.get(dev)
         if cus is None:
-            cus = _CU_COUNT[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+            with _CU_COUNT_LOCK:
+                cus = _CU_COUNT.get(dev)
+                if cus is None:
+                    cus = _CU_COUNT[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
         if not classes:
             return "s" if stage32_windows_fit(int(batch) * int(t), cus) else False
         form = stage32_form(batch, int(t), cus)

@@ -132,9 +132,25 @@ def _sums(x, y, resolutions, differentiable=False):
     return _native.stft_distance(x, y, tables, *geometry)
 
 
+_counts_on_device = {}     # (device, geometry, n) -> _counts there
+
+
 def _counts(resolutions, n):
     """frames * bins per utterance for each resolution, float64 [R]."""
     return torch.tensor([(1 + n // hop) * (nf // 2 + 1) for nf, hop, _, _ in resolutions], dtype=torch.float64)
+
+
+def _counts_on(device, resolutions, n):
+    """``_counts`` on ``device``, uploaded once per geometry and length: the copy comes from pageable memory and waits for
+    the stream, which made every call of the loss a host synchronisation (tests/test_gpu_stft_loss_grad.py's stream
+    test, behind a busy stream, was inconclusive for it)."""
+    key = (torch.device(device), tuple((int(nf), int(hop)) for nf, hop, _, _ in resolutions), int(n))
+    hit = _counts_on_device.get(key)
+    if hit is None:
+        if len(_counts_on_device) >= 256:
+            _counts_on_device.clear()
+        hit = _counts_on_device[key] = _counts(resolutions, n).to(device)
+    return hit
 
 
 def _batch_terms(sums, counts):
@@ -142,14 +158,14 @@ def _batch_terms(sums, counts):
     tot = sums.sum(dim=1)                                      # [R, 3]
     B = sums.shape[1]
     sc = tot[:, 0].sqrt() / tot[:, 1].sqrt()
-    mag = tot[:, 2] / (B * counts.to(sums.device))
+    mag = tot[:, 2] / (B * counts)
     return sc.mean().float(), mag.mean().float()
 
 
 def _utterance_terms(sums, counts):
     """[B, 2] fp32: (sc, mag) of every row on its own, averaged over the resolutions."""
     sc = sums[:, :, 0].sqrt() / sums[:, :, 1].sqrt()            # [R, B]
-    mag = sums[:, :, 2] / counts.to(sums.device)[:, None]
+    mag = sums[:, :, 2] / counts[:, None]
     return torch.stack([sc.mean(dim=0), mag.mean(dim=0)], dim=1).float()
 
 
@@ -196,11 +212,13 @@ class STFTLoss(torch.nn.Module):
 
     def forward(self, x, y):
         """x predicted, y ground truth, both (B, T) -> (sc_loss, mag_loss), 0-d fp32 device tensors."""
-        return _batch_terms(self.partial_sums(x, y), _counts([self.resolution()], x.shape[-1]))
+        sums = self.partial_sums(x, y)
+        return _batch_terms(sums, _counts_on(sums.device, [self.resolution()], x.shape[-1]))
 
     def per_utterance(self, x, y):
         """[B, 2] fp32 device tensor: (sc_loss, mag_loss) of each row as if scored alone."""
-        return _utterance_terms(self.partial_sums(x, y), _counts([self.resolution()], x.shape[-1]))
+        sums = self.partial_sums(x, y)
+        return _utterance_terms(sums, _counts_on(sums.device, [self.resolution()], x.shape[-1]))
 
 
 class MultiResolutionSTFTLoss(torch.nn.Module):
@@ -235,9 +253,11 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     def forward(self, x, y):
         """x predicted, y ground truth, both (B, T) -> (sc_loss, mag_loss), 0-d fp32 device tensors with the
         reference's batch-level semantics, averaged over the resolutions."""
-        return _batch_terms(self.partial_sums(x, y), _counts(self.resolutions(), x.shape[-1]))
+        sums = self.partial_sums(x, y)
+        return _batch_terms(sums, _counts_on(sums.device, self.resolutions(), x.shape[-1]))
 
     def per_utterance(self, x, y):
         """[B, 2] fp32 device tensor: (sc_loss, mag_loss) of each row as if scored alone (B = 1), from the same
         partial sums as ``forward``."""
-        return _utterance_terms(self.partial_sums(x, y), _counts(self.resolutions(), x.shape[-1]))
+        sums = self.partial_sums(x, y)
+        return _utterance_terms(sums, _counts_on(sums.device, self.resolutions(), x.shape[-1]))

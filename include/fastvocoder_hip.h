@@ -18,7 +18,12 @@
  *     every call only enqueues work on it and returns (no device sync);
  *   - return value: 0 on success, otherwise a hipError_t or FV_ERR_* code,
  *     with a thread-local message available from fv_last_error();
- *   - re-entrant per (device, stream); no global mutable state.
+ *   - re-entrant per (device, stream): results depend on no process-wide state.  What the library keeps per process
+ *     is host-side and either a cache of pure functions of a launch's shape, protected by a mutex (block schedules, tile
+ *     width plans, the list of kernels granted a dynamic LDS size) or written once (the tuning table, the device's CU
+ *     count); the error text is thread-local.  Calls from several threads, each on a stream and on module state of its
+ *     own, need no lock (tests/test_gpu_threads.py).  fv_tuning_set, fv_profile_* and the launch log (fv_debug_launch_log)
+ *     are process-wide hooks of tests and tools: not for concurrent use with each other or with themselves.
  */
 #ifndef FASTVOCODER_HIP_H
 #define FASTVOCODER_HIP_H
@@ -30,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad (entries added since -- the latest: fv_debug_launch_log -- change no existing one); 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
+#define FV_ABI_VERSION 18   /* 18: fv_stft_distance_grad (entries added since -- the latest: fv_debug_launch_log_streams -- change no existing one); 17: Griffin-Lim (fv_stft, fv_istft, fv_griffin_lim, ...) */
 /* Entry points are added under one version number: 18 also covers the gradient, optimizer and training entries that
  * came after fv_stft_distance_grad, the latest being fv_conv1d_weight_grad_dilated_bf16 and
  * fv_conv_transpose1d_weight_grad_bf16 (the generators' bf16 weight gradients).  No existing entry changed its signature or its result. */
@@ -1405,9 +1410,15 @@ int fv_debug_mrf_stage_class_f16(const float* x, const float* packed, float* y, 
  *   __cxa_demangle, without return type, "fv::" and argument list: "convh_kernel<2, 2, 1>".
  *   fv_debug_kernel_name gives the same name for a dynamic symbol of the library (a kernel handle or its host stub, whose
  *   "__device_stub__" goes too): what tools/kernel_census.py lists the built instantiations with.  Returns the bytes needed.
+ *   fv_debug_launch_log_streams: the helper also counts every launch under its STREAM handle, and so do the helpers of the
+ *   library's asynchronous memsets and copies (memset_async / memcpy_async; no other enqueueing call exists in csrc/).
+ *   Writes the distinct handles (NULL stream: 0) and their counts, first-seen order, into handles[cap] / counts[cap] (either
+ *   may be NULL), the number of asynchronous memsets and copies among them into *copies (may be NULL), and returns the
+ *   number of distinct streams: call with cap = 0 first.  Sum of counts = kernel launches of fv_debug_launch_log_read + *copies.
  */
 int fv_debug_launch_log(int on);
 int64_t fv_debug_launch_log_read(char* buf, int64_t cap);
+int64_t fv_debug_launch_log_streams(uint64_t* handles, int64_t* counts, int64_t cap, int64_t* copies);
 int64_t fv_debug_kernel_name(const char* symbol, char* buf, int64_t cap);
 
 /* ------------------------------------------------------------------ *

@@ -14,6 +14,7 @@ from fastvocoder_amd.bin.synthesize import build_generator
 from fastvocoder_amd.synthetic import seeded_state_dict
 from tests import cases
 from tests import mel_reference
+from tests import stream_tools
 
 pytestmark = pytest.mark.gpu
 
@@ -94,12 +95,15 @@ def test_batch_rows_equal_single_calls_and_numpy_route():
 
 
 def test_non_default_stream_gives_identical_results():
-    x = torch.from_numpy(np.random.RandomState(9).uniform(-1, 1, (3, 50000)).astype(np.float32)).to(_dev())
-    want = audio.melspectrogram(x)
+    """On a side stream that is still busy (tests/stream_tools.py): the input arrives behind a delay and holds NaN until
+    then, so a launch on any other stream than the caller's reads NaN."""
+    x = np.random.RandomState(9).uniform(-1, 1, (3, 50000)).astype(np.float32)
+    want, wall = stream_tools.timed(lambda: audio.melspectrogram(torch.from_numpy(x).to(_dev())))
     torch.cuda.synchronize()
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        got = audio.melspectrogram(x)
+    s = stream_tools.side_stream()
+    with stream_tools.delayed(s, stream_tools.delay_ms(wall)) as put:
+        got = audio.melspectrogram(put(x))
+        stream_tools.assert_busy(put, "melspectrogram")
     s.synchronize()
     assert torch.equal(got, want)
 

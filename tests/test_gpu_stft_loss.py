@@ -17,6 +17,7 @@ from fastvocoder_amd.loss import Loss, MultiResolutionSTFTLoss, STFTLoss, stft
 from fastvocoder_amd.synthetic import seeded_state_dict
 from tests import cases
 from tests import stft_loss_reference as ref
+from tests import stream_tools
 
 pytestmark = pytest.mark.gpu
 
@@ -174,14 +175,18 @@ def test_two_calls_are_bit_identical():
 
 def test_non_default_stream_and_non_contiguous_input():
     rs = np.random.RandomState(5)
-    x, y = _t(rs.randn(3, 30000)), _t(rs.randn(3, 30000))
+    xh, yh = rs.randn(3, 30000).astype(np.float32), rs.randn(3, 30000).astype(np.float32)
+    x, y = _t(xh), _t(yh)
     mr = MultiResolutionSTFTLoss()
     with torch.no_grad():
-        want = mr.partial_sums(x, y)
+        want, wall = stream_tools.timed(mr.partial_sums, x, y)
         torch.cuda.synchronize()
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            got = mr.partial_sums(x, y)
+        # on a side stream that is still busy (tests/stream_tools.py): the inputs arrive behind a delay and hold NaN until
+        # then, so a launch on any other stream than the caller's reads NaN
+        s = stream_tools.side_stream()
+        with stream_tools.delayed(s, stream_tools.delay_ms(wall)) as put:
+            got = mr.partial_sums(put(xh), put(yh))
+            stream_tools.assert_busy(put, "partial_sums")
         s.synchronize()
         assert torch.equal(got, want)
         xt = torch.empty((30000, 3), device=_dev()).copy_(x.t()).t()      # a transposed view

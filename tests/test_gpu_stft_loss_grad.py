@@ -16,6 +16,7 @@ from tests import cases
 from tests import stft_loss_grad_reference as gref
 from tests import stft_loss_reference as ref
 from tests import stft_reference
+from tests import stream_tools
 from tests.test_gpu_stft_loss import _pairs
 
 pytestmark = pytest.mark.gpu
@@ -271,15 +272,23 @@ def test_a_row_alone_gives_its_batch_bits():
 
 def test_non_default_stream_and_non_contiguous_input():
     rs = np.random.RandomState(6)
-    x32, yt = rs.randn(3, 30000).astype(np.float32), _t(rs.randn(3, 30000))
+    x32, y32 = rs.randn(3, 30000).astype(np.float32), rs.randn(3, 30000).astype(np.float32)
+    yt = _t(y32)
     mr = _mr()
-    want = _grad(lambda v: sum(mr(v, yt)), x32)
+    want, wall = stream_tools.timed(_grad, lambda v: sum(mr(v, yt)), x32)
     torch.cuda.synchronize()
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        got = _grad(lambda v: sum(mr(v, yt)), x32)
+    # on a side stream that is still busy (tests/stream_tools.py): the inputs arrive behind a delay and hold NaN until then,
+    # so a forward or backward launch on any other stream than the caller's reads NaN  (_grad's own .cpu() would wait)
+    s = stream_tools.side_stream()
+    with stream_tools.delayed(s, stream_tools.delay_ms(wall)) as put:
+        x = put(x32).requires_grad_(True)
+        out = sum(mr(x, put(y32)))
+        assert out.grad_fn is not None
+        out.backward()
+        stream_tools.assert_busy(put, "the STFT loss and its gradient")
     s.synchronize()
-    assert np.array_equal(got, want)
+    assert x.grad is not None and x.grad.dtype == torch.float32 and x.grad.shape == x.shape
+    assert np.array_equal(x.grad.cpu().numpy().astype(np.float64), want)
     base = torch.empty((30000, 3), device=_dev()).copy_(_t(x32).t()).requires_grad_(True)
     xt = base.t()                                                 # a transposed view of a leaf
     assert not xt.is_contiguous()

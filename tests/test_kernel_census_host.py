@@ -118,6 +118,39 @@ def test_launch_log_is_off_by_default_and_does_not_nest():
     assert again.kernels == {}
 
 
+def test_the_stream_table_reads_as_empty_when_nothing_was_launched():
+    import ctypes
+    L = _native.lib()
+    with _native.launch_log() as log:
+        pass
+    assert log.streams == {} and log.copies == 0
+    copies = ctypes.c_int64(-1)
+    assert L.fv_debug_launch_log_streams(None, None, 0, ctypes.byref(copies)) == 0 and copies.value == 0
+    assert b"fv_debug_launch_log_streams" in set(_tool().dynamic_symbols(_native.LIB_PATH))
+
+
+def test_every_enqueueing_call_is_written_in_the_two_helpers_alone():
+    """Kernel launches and asynchronous memsets / copies appear in csrc/fv_internal.h only (FV_KERNEL_LAUNCH, memset_async,
+    memcpy_async): what the launch log's stream table counts is everything the library enqueues."""
+    csrc = os.path.join(ROOT, "fastvocoder_amd", "csrc")
+    forbidden = re.compile(r"hipLaunchKernelGGL|hipLaunchKernel\b|hipModuleLaunchKernel|hipExtLaunchKernel|hipLaunchCooperativeKernel|<<<|"
+                           r"hipMemsetAsync|hipMemcpyAsync|hipMemset\w*Async|hipMemcpy\w*Async|hipMemcpy\w*\(|hipMemset\w*\(|hipGraphLaunch")
+    sites, helper_uses = [], 0
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as f:
+            for n, line in enumerate(f, 1):
+                if forbidden.search(line) and name != "fv_internal.h":
+                    sites.append(f"{name}:{n}: {line.strip()}")
+                helper_uses += len(re.findall(r"\bFV_KERNEL_LAUNCH\(|\bmemset_async\(|\bmemcpy_async\(", line)) if name != "fv_internal.h" else 0
+    assert not sites, sites
+    assert helper_uses >= 128 + 4, helper_uses
+    with open(os.path.join(csrc, "fv_internal.h")) as f:
+        own = f.read()
+    code = "\n".join(line.split("//", 1)[0] for line in own.splitlines())
+    assert len(re.findall(r"hipLaunchKernelGGL\(", code)) == 1 and len(re.findall(r"hipMemsetAsync\(", code)) == 1
+    assert len(re.findall(r"hipMemcpyAsync\(", code)) == 1
+
+
 class _ScriptedLibrary:
     """The three log entries and two operators that 'launch', as the recorder's proxy sees a library."""
 
@@ -135,6 +168,9 @@ class _ScriptedLibrary:
         if buf is not None:
             buf[:min(len(text), cap)] = text[:cap]
         return len(text)
+
+    def fv_debug_launch_log_streams(self, handles, counts, cap, copies):
+        return 1 if self.table else 0
 
     def _launch(self, name):
         if self.on:
@@ -170,6 +206,7 @@ def test_recorder_books_launches_to_the_running_test(tool, monkeypatch):
     buf = ctypes.create_string_buffer(64)
     n = lib.fv_debug_launch_log_read(buf, 64)
     assert buf.raw[:n] == b"1\tb_kernel\n"                         # ... and reads what it launched, no more
+    assert lib.fv_debug_launch_log_streams(None, None, 0, None) == 1     # ... its stream table too: reading restarts nothing
     lib.fv_op_a()                                                   # recording resumes with the next call
     monkeypatch.setenv("PYTEST_CURRENT_TEST", "tests/test_gpu_x.py::test_one (teardown)")
     lib.fv_op_b()

@@ -89,6 +89,9 @@ def built_kernels(path=None):
     return names
 
 
+READERS = ("fv_debug_launch_log_read", "fv_debug_launch_log_streams")    # they read the table: no launch, no restart
+
+
 class Recorder:
     """Attributes the library's launches to the test that made them, without any hook into the test runner.  The launch
     log stays on for the whole run; the binding's library handle (`_native._lib`) is replaced by a proxy that, after every
@@ -140,7 +143,7 @@ class Recorder:
 
     def before(self, name):
         node = self.current()
-        if name == "fv_debug_launch_log_read":
+        if name in READERS:
             return
         if name == "fv_debug_launch_log":          # a test's own log: book what the table holds before it is cleared / stopped
             if not self.off:
@@ -156,7 +159,7 @@ class Recorder:
         if name == "fv_debug_launch_log":
             self.node = self.current()
             self.last, self.off = {}, not args[0]
-        elif name != "fv_debug_launch_log_read" and not self.off:
+        elif name not in READERS and not self.off:
             if self.node is not None:
                 self.seen.setdefault(self.node, {})
             self.book()
