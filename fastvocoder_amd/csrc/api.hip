@@ -1,6 +1,7 @@
 // C-ABI entry points of libfastvocoder_hip.so (include/fastvocoder_hip.h): the fused operators as direct calls, the op core they
-// share with the plan executor (plan.hip) -- run_op, the builders of every launch record (pair_params, pair_member, mrf_params)
-// and the one pair dispatch (launch_pair_family) --, error text, tuning switches and the measurement hook.  (Weight preparation: pack.hip.)
+// share with the plan executor (plan.hip) -- the op builders (build_*: the one description of each family), run_op, the builders
+// of every launch record (pair_params, pair_member, mrf_params) and the one pair dispatch (launch_pair_family) --, error text,
+// tuning switches and the measurement hook.  (Weight preparation: pack.hip.)
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -383,6 +384,191 @@ int check_convt_split_args(int Cin, int Cout, int k, int stride, int pad, int ou
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// op builders (api_internal.h): the one description of each operator family, for its direct entry and its plan entry
+// ---------------------------------------------------------------------------
+// the fields that every family but the PQMF has
+static void fill(Op& o, int prec, const float* wp, const float* bias, int Cin, int Cout, int k, int dil, float pre_slope,
+                 float out_div, int post, float act_slope) {
+    o.prec = prec;
+    o.wp = wp;
+    o.bias = bias;
+    o.Cin = Cin;
+    o.Cout = Cout;
+    o.k = k;
+    o.dil = dil;
+    o.pre_slope = pre_slope;
+    o.out_div = out_div;
+    o.post = post;
+    o.act_slope = act_slope;
+}
+
+int build_conv(Op& o, const float* packed, const float* bias, int Cin, int Cout, int k, int dil, int pad, int pad_mode,
+               float pre_slope, float out_div, int post, float act_slope) {
+    if (int rc = check_conv_args(Cin, Cout, k, dil)) return rc;
+    if (int rc = check_pad_mode(pad_mode, pad, k, dil)) return rc;
+    o.type = OP_CONV;
+    fill(o, FV_PAIR_F32, packed, bias, Cin, Cout, k, dil, pre_slope, out_div, post, act_slope);
+    o.pad = pad;
+    o.pad_mode = pad_mode;
+    return 0;
+}
+
+int build_conv_2src(Op& o, const float* packed, const float* bias, int Cin1, int Cin2, int Cout, int post, float act_slope) {
+    if (Cin1 <= 0 || Cin2 <= 0) return fail(FV_ERR_INVALID_ARG, "conv1d_2src: Cin1=%d Cin2=%d", Cin1, Cin2);
+    o.Cin1 = Cin1;
+    return build_conv(o, packed, bias, Cin1 + Cin2, Cout, 1, 1, 0, FV_PAD_ZERO, 1.f, 1.f, post, act_slope);
+}
+
+// (the conv taps are not dilated: Op::dil stays 0, as OP_CONVT and OP_UPCONV never read it)
+int build_convt(Op& o, const float* packed, const float* bias, int Cin, int Cout, int k, int stride, int pad, int out_pad,
+                float pre_slope, int post, float act_slope) {
+    if (int rc = check_conv_args(Cin, Cout, k, 1)) return rc;
+    // negative out_pad trims the tail (CausalConvTranspose1d, modules.py:297-317: -stride)
+    if (stride <= 0 || pad < 0 || out_pad < -stride)
+        return fail(FV_ERR_INVALID_ARG, "conv_transpose1d: stride=%d pad=%d out_pad=%d", stride, pad, out_pad);
+    o.type = OP_CONVT;
+    fill(o, FV_PAIR_F32, packed, bias, Cin, Cout, k, 0, pre_slope, 1.f, post, act_slope);
+    o.stride = stride;
+    o.pad = pad;
+    o.out_pad = out_pad;
+    return 0;
+}
+
+int build_convt_split(Op& o, const float* packed, const float* bias, int Cin, int Cout, int k, int stride, int pad, int out_pad,
+                      float pre_slope, float act_slope) {
+    if (int rc = check_convt_split_args(Cin, Cout, k, stride, pad, out_pad)) return rc;
+    if (int rc = build_convt(o, packed, bias, Cin, Cout, k, stride, pad, out_pad, pre_slope, FV_POST_NONE, act_slope)) return rc;
+    o.prec = FV_PAIR_SPLIT_F16;
+    return 0;
+}
+
+// (no check of C: the plan entry makes one, the direct entry leaves it to launch_convg)
+int build_convg(Op& o, const float* packed, const float* bias, int C, float pre_slope, int post, float act_slope) {
+    o.type = OP_CONVG;
+    fill(o, FV_PAIR_SPLIT_F16, packed, bias, 2 * C, C, 1, 1, pre_slope, 1.f, post, act_slope);
+    o.Cin1 = C;
+    return 0;
+}
+
+int build_stack(Op& o, const float* packed, const float* bias_dilated, const float* bias_out, int C, int k, int dil, float slope,
+                int pad_mode, int post, float act_slope) {
+    if (post != FV_POST_NONE && post != FV_POST_TANH && post != FV_POST_RELU)
+        return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: post op %d", post);
+    if (!convk_shape(C, k, dil))
+        return fail(FV_ERR_UNSUPPORTED, "residual_stack_split_f16: C = %d, k = %d, dilation %d (32 / 64 / 128 / 256 channels, 3 taps, "
+                    "dilation 1, 3 or 9)", C, k, dil);
+    if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
+        return fail(FV_ERR_UNSUPPORTED, "residual_stack_split_f16: pad_mode %d (zero or reflection padding of the 'same' conv)", pad_mode);
+    if (int rc = check_slopes("residual_stack_split_f16", slope, act_slope)) return rc;
+    o.type = OP_STACK;
+    fill(o, FV_PAIR_SPLIT_F16, packed, bias_dilated, C, C, k, dil, slope, 1.f, post, act_slope);
+    o.bias2 = bias_out;
+    o.pad = dil * (k - 1) / 2;
+    o.pad_mode = pad_mode;
+    o.stride = 1;
+    return 0;
+}
+
+int build_conv_post_pqmf(Op& o, const float* packed, const float* bias, const float* h, int Cin, int S, int k, int pad,
+                         float pre_slope, int post, int ntaps) {
+    if (S != 4 || ntaps != 63) return fail(FV_ERR_UNSUPPORTED, "conv_post_pqmf: S=%d ntaps=%d (4 sub-bands, 63 taps)", S, ntaps);
+    // a 'same' conv: y holds S * T samples per utterance (a larger pad would make the kernel store past it)
+    if (k % 2 != 1 || pad != (k - 1) / 2)
+        return fail(FV_ERR_INVALID_ARG, "conv_post_pqmf: k=%d pad=%d (odd kernel, pad = (k - 1) / 2)", k, pad);
+    o.pq_h = h;
+    o.pq_taps = ntaps;
+    return build_conv(o, packed, bias, Cin, S, k, 1, pad, FV_PAD_ZERO, pre_slope, 1.f, post, 1.f);
+}
+
+int build_pqmf(Op& o, const float* h, int S, int ntaps) {
+    if (S <= 0 || ntaps <= 0 || ntaps % 2 == 0) return fail(FV_ERR_INVALID_ARG, "pqmf: S=%d ntaps=%d", S, ntaps);
+    o.type = OP_PQMF;
+    o.wp = h;
+    o.Cin = S;
+    o.Cout = 1;
+    o.k = ntaps;
+    return 0;
+}
+
+static int check_pair_args(int n, int C, const int* k, int dil, int prec) {
+    if (n < 1 || n > 3) return fail(FV_ERR_INVALID_ARG, "resblock pair: %d members (1..3)", n);
+    if (C != 16 && C != 32 && !(prec == FV_PAIR_SPLIT_F16 && (C == 64 || C == 128 || C == 256 || C == 512)))
+        return fail(FV_ERR_UNSUPPORTED, "resblock pair: C = %d (16 or 32; 64 ... 512 with split-f16 operands); use the conv1d ops", C);
+    if (dil != 1 && dil != 3 && dil != 5) return fail(FV_ERR_UNSUPPORTED, "resblock pair: dilation %d (1, 3 or 5)", dil);
+    for (int j = 0; j < n; ++j)
+        if (int rc = check_taps("resblock pair", k[j])) return rc;
+    return 0;
+}
+
+template <class P>
+static P at(P const* a, int j) { return a ? a[j] : nullptr; }      // member j of an optional array argument
+
+// member j of the arrays as member `slot` of the op
+static void fill_member(Op& o, int slot, int j, const float* const* w1, const float* const* w2, const float* const* b1,
+                        const float* const* b2, const int* k) {
+    o.pw1[slot] = w1[j];
+    o.pw2[slot] = at(w2, j);
+    o.pb1[slot] = at(b1, j);
+    o.pb2[slot] = at(b2, j);
+    o.pk[slot] = k[j];
+}
+
+int build_pair(Op& o, int j, const float* const* w1, const float* const* w2, const float* const* b1, const float* const* b2,
+               const int* k, int C, int dil, float slope, float out_div, int post, float act_slope, int prec) {
+    if (int rc = check_pair_args(1, C, k + j, dil, prec)) return rc;
+    o.type = OP_PAIR;
+    fill(o, prec, nullptr, nullptr, C, C, k[j], dil, slope, out_div, post, act_slope);
+    fill_member(o, 0, j, w1, w2, b1, b2, k);
+    return 0;
+}
+
+int build_mrfsum(Op& o, const float* const* w1, const float* const* w2, const float* const* b1, const float* const* b2,
+                 const int* k, int C, int dil, float slope, float out_div, int post, float act_slope) {
+    if (int rc = check_pair_args(3, C, k, dil, FV_PAIR_F32)) return rc;
+    o.type = OP_MRFSUM;
+    fill(o, FV_PAIR_F32, nullptr, nullptr, C, C, k[0], dil, slope, out_div, post, act_slope);
+    for (int j = 0; j < 3; ++j) fill_member(o, j, j, w1, w2, b1, b2, k);
+    return 0;
+}
+
+int build_convh(Op& o, int j, const float* const* packed, const float* const* bias, const int* k, int C, int dil, int pad_mode,
+                float pre_slope, float out_div, int post, float act_slope) {
+    if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
+        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: pad_mode %d (FV_PAD_ZERO or FV_PAD_REFLECT)", pad_mode);
+    if (C != 64 && C != 128 && C != 256 && C != 512)
+        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: C = %d (64, 128, 256 or 512)", C);
+    if (dil != 1 && dil != 3 && dil != 5 && dil != 9)
+        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: dilation %d (1, 3, 5; 9 with 3 taps)", dil);
+    if ((k[j] != 3 && k[j] != 7 && k[j] != 11) || (dil == 9 && k[j] != 3))
+        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: %d taps at dilation %d (3, 7 or 11; 3 at dilation 9)", k[j], dil);
+    o.type = OP_CONVH;
+    fill(o, FV_PAIR_SPLIT_F16, nullptr, nullptr, C, C, k[j], dil, pre_slope, out_div, post, act_slope);
+    o.pad_mode = pad_mode;
+    fill_member(o, 0, j, packed, nullptr, bias, nullptr, k);
+    return 0;
+}
+
+// (the workspace is the entries' to check: the plan entry does when the op is added, the direct entries leave it to the launchers)
+int build_stage(Op& o, const float* packed, int C, const int* k, const int* dil, float slope, float out_div, int post,
+                float act_slope, void* workspace, int64_t workspace_bytes) {
+    if (!k || !dil) return fail(FV_ERR_INVALID_ARG, "mrf stage: null taps / dilations");
+    if (!mrf_stage_shape(C, k, dil))
+        return fail(FV_ERR_UNSUPPORTED, "mrf stage: C = %d, taps (%d, %d, %d), dilations (%d, %d, %d): built for 16 / 32 channels, "
+                    "taps 3 / 7 / 11, dilations (1, 3, 5)", C, k[0], k[1], k[2], dil[0], dil[1], dil[2]);
+    if (int rc = check_slopes("mrf stage", slope, act_slope)) return rc;
+    if (post != FV_POST_NONE && post != FV_POST_TANH && post != FV_POST_RELU) return fail(FV_ERR_INVALID_ARG, "mrf stage: post %d", post);
+    o.type = OP_STAGE;
+    fill(o, FV_PAIR_SPLIT_F16, packed, nullptr, C, C, k[0], dil[0], slope, out_div, post, act_slope);
+    for (int j = 0; j < 3; ++j) {
+        o.pk[j] = k[j];
+        o.sdil[j] = dil[j];
+    }
+    o.work = workspace;
+    o.work_bytes = workspace_bytes;
+    return 0;
+}
+
 }  // namespace fv
 
 using namespace fv;
@@ -486,24 +672,12 @@ const char* fv_last_error(void) { return g_err.c_str(); }
 int fv_upsample_conv1d_fused(const float* x, const float* packed, const float* bias, float* y,
                              float* y_act, int B, int Cin, int Cout, int Tin, int k, int rate, int pad,
                              float pre_slope, int post, float act_slope, void* stream) {
-    if (int rc = check_conv_args(Cin, Cout, k, 1)) return rc;
     if (!x || !packed || !y) return fail(FV_ERR_INVALID_ARG, "upsample_conv1d: null tensor");
-    if (rate <= 0 || pad < 0) return fail(FV_ERR_INVALID_ARG, "upsample_conv1d: rate=%d pad=%d", rate, pad);
     if (x == y || x == y_act || (y_act && y_act == y))
         return fail(FV_ERR_INVALID_ARG, "upsample_conv1d: y / y_act must not alias x or each other");
     Op o = {};
-    o.type = OP_UPCONV;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = Cout;
-    o.k = k;
-    o.stride = rate;
-    o.pad = pad;
-    o.pre_slope = pre_slope;
-    o.out_div = 1.f;
-    o.act_slope = act_slope;
-    o.post = post;
+    if (int rc = build_convt(o, packed, bias, Cin, Cout, k, rate, pad, 0, pre_slope, post, act_slope)) return rc;
+    o.type = OP_UPCONV;          // the transposed conv's record, as fv_plan_add_upsample_conv1d retypes it
     if (conv_out_len(o, Tin) <= 0) return fail(FV_ERR_INVALID_ARG, "upsample_conv1d: empty output");
     return run_op(o, x, y, y_act, nullptr, nullptr, nullptr, B, Tin, (hipStream_t)stream);
 }
@@ -512,25 +686,11 @@ int fv_conv1d_fused(const float* x, const float* packed, const float* bias, cons
                     const float* acc_in, const float* acc_in2, float* y, float* y_act, int B, int Cin,
                     int Cout, int Tin, int k, int dil, int pad, int pad_mode, float pre_slope,
                     float out_div, int post, float act_slope, void* stream) {
-    if (int rc = check_conv_args(Cin, Cout, k, dil)) return rc;
-    if (int rc = check_pad_mode(pad_mode, pad, k, dil)) return rc;
     if (!x || !packed || !y) return fail(FV_ERR_INVALID_ARG, "conv1d: null tensor");
     if (x == y || x == y_act || (y_act && y_act == y))
         return fail(FV_ERR_INVALID_ARG, "conv1d: y / y_act must not alias x or each other");
     Op o = {};
-    o.type = OP_CONV;
-    o.act_slope = act_slope;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = Cout;
-    o.k = k;
-    o.dil = dil;
-    o.pad = pad;
-    o.pad_mode = pad_mode;
-    o.pre_slope = pre_slope;
-    o.out_div = out_div;
-    o.post = post;
+    if (int rc = build_conv(o, packed, bias, Cin, Cout, k, dil, pad, pad_mode, pre_slope, out_div, post, act_slope)) return rc;
     if (conv_out_len(o, Tin) <= 0) return fail(FV_ERR_INVALID_ARG, "conv1d: empty output");
     return run_op(o, x, y, y_act, res, acc_in, acc_in2, B, Tin, (hipStream_t)stream);
 }
@@ -539,27 +699,13 @@ int fv_conv_transpose1d_fused(const float* x, const float* packed, const float* 
                               float* y_act, int B, int Cin, int Cout, int Tin, int k, int stride,
                               int pad, int out_pad, float pre_slope, int post, float act_slope,
                               void* stream) {
-    if (int rc = check_conv_args(Cin, Cout, k, 1)) return rc;
     if (!x || !packed || !y) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d: null tensor");
-    // out_pad in [-stride, stride): negative values trim the tail (CausalConvTranspose1d, modules.py:297-317: -stride)
-    if (stride <= 0 || pad < 0 || out_pad < -stride || out_pad >= stride + (stride == 1))
-        return fail(FV_ERR_INVALID_ARG, "conv_transpose1d: stride=%d pad=%d out_pad=%d", stride, pad, out_pad);
     if (x == y || x == y_act || (y_act && y_act == y))
         return fail(FV_ERR_INVALID_ARG, "conv_transpose1d: y / y_act must not alias x or each other");
     Op o = {};
-    o.type = OP_CONVT;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = Cout;
-    o.k = k;
-    o.stride = stride;
-    o.pad = pad;
-    o.out_pad = out_pad;
-    o.pre_slope = pre_slope;
-    o.out_div = 1.f;
-    o.act_slope = act_slope;
-    o.post = post;
+    if (int rc = build_convt(o, packed, bias, Cin, Cout, k, stride, pad, out_pad, pre_slope, post, act_slope)) return rc;
+    if (out_pad >= stride + (stride == 1))      // this entry alone: fv_plan_add_conv_transpose1d takes any out_pad >= -stride
+        return fail(FV_ERR_INVALID_ARG, "conv_transpose1d: out_pad=%d at stride=%d (below the stride)", out_pad, stride);
     if (conv_out_len(o, Tin) <= 0) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d: empty output");
     return run_op(o, x, y, y_act, nullptr, nullptr, nullptr, B, Tin, (hipStream_t)stream);
 }
@@ -579,23 +725,10 @@ int fv_conv_transpose1d_split_f16(const float* x, const float* packed, const flo
                                   int Cin, int Cout, int Tin, int k, int stride, int pad, int out_pad, float pre_slope,
                                   float act_slope, int* guard, void* stream) {
     if (!x || !packed || !y) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_split_f16: null tensor");
-    if (int rc = check_convt_split_args(Cin, Cout, k, stride, pad, out_pad)) return rc;
     if (x == y || x == y_act || (y_act && y_act == y))
         return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_split_f16: y / y_act must not alias x or each other");
     Op o = {};
-    o.type = OP_CONVT;
-    o.prec = FV_PAIR_SPLIT_F16;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = Cout;
-    o.k = k;
-    o.stride = stride;
-    o.pad = pad;
-    o.out_pad = out_pad;
-    o.pre_slope = pre_slope;
-    o.out_div = 1.f;
-    o.act_slope = act_slope;
+    if (int rc = build_convt_split(o, packed, bias, Cin, Cout, k, stride, pad, out_pad, pre_slope, act_slope)) return rc;
     if (B < 0 || Tin < 0) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_split_f16: B=%d Tin=%d", B, Tin);
     if (B == 0 || Tin == 0) return 0;
     if (conv_out_len(o, Tin) <= 0) return fail(FV_ERR_INVALID_ARG, "conv_transpose1d_split_f16: empty output");
@@ -604,9 +737,10 @@ int fv_conv_transpose1d_split_f16(const float* x, const float* packed, const flo
 
 int fv_pqmf_synthesis(const float* x, const float* h, float* y, int B, int S, int ntaps, int Tsub,
                       void* stream) {
-    if (!x || !h || !y || B < 0 || S <= 0 || ntaps <= 0 || ntaps % 2 == 0 || Tsub < 0)
-        return fail(FV_ERR_INVALID_ARG, "pqmf: B=%d S=%d ntaps=%d Tsub=%d", B, S, ntaps, Tsub);
-    return launch_pqmf(x, h, y, nullptr, nullptr, 0, B, S, ntaps, Tsub, (hipStream_t)stream);
+    if (!x || !h || !y || B < 0 || Tsub < 0) return fail(FV_ERR_INVALID_ARG, "pqmf: null tensor or B=%d Tsub=%d", B, Tsub);
+    Op o = {};
+    if (int rc = build_pqmf(o, h, S, ntaps)) return rc;
+    return run_op(o, x, y, nullptr, nullptr, nullptr, nullptr, B, Tsub, (hipStream_t)stream);
 }
 
 int fv_pqmf_analysis(const float* x, const float* h, float* y, int B, int S, int ntaps, int64_t T,
@@ -1014,25 +1148,12 @@ int fv_disc_score_grad(const float* const* e, const float* const* r, float* cons
 int fv_conv1d_2src_fused(const float* x, const float* x2, const float* packed, const float* bias,
                          const float* res, float* y, float* y_act, int B, int Cin1, int Cin2, int Cout,
                          int T, int post, float act_slope, void* stream) {
-    if (Cin1 <= 0 || Cin2 <= 0) return fail(FV_ERR_INVALID_ARG, "conv1d_2src: Cin1=%d Cin2=%d", Cin1, Cin2);
-    if (int rc = check_conv_args(Cin1 + Cin2, Cout, 1, 1)) return rc;
     if (!x || !x2 || !packed || !y) return fail(FV_ERR_INVALID_ARG, "conv1d_2src: null tensor");
     if (x == y || x2 == y || x == y_act || x2 == y_act || (y_act && y_act == y))
         return fail(FV_ERR_INVALID_ARG, "conv1d_2src: y / y_act must not alias an input or each other");
-    if (T <= 0) return fail(FV_ERR_INVALID_ARG, "conv1d_2src: empty output");
     Op o = {};
-    o.type = OP_CONV;
-    o.act_slope = act_slope;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin1 + Cin2;
-    o.Cin1 = Cin1;
-    o.Cout = Cout;
-    o.k = 1;
-    o.dil = 1;
-    o.pre_slope = 1.f;
-    o.out_div = 1.f;
-    o.post = post;
+    if (int rc = build_conv_2src(o, packed, bias, Cin1, Cin2, Cout, post, act_slope)) return rc;
+    if (T <= 0) return fail(FV_ERR_INVALID_ARG, "conv1d_2src: empty output");
     return run_op(o, x, y, y_act, res, nullptr, nullptr, B, T, (hipStream_t)stream, x2);
 }
 
@@ -1042,40 +1163,11 @@ int fv_conv1x1_2src_split_f16(const float* x, const float* x2, const float* pack
     if (!x || !x2 || !packed || !y) return fail(FV_ERR_INVALID_ARG, "conv1x1_2src_split_f16: null tensor");
     if (x == y || x2 == y || x == y_act || x2 == y_act || (y_act && y_act == y) || (res && (res == y || res == y_act)))
         return fail(FV_ERR_INVALID_ARG, "conv1x1_2src_split_f16: y / y_act must not alias an input or each other");
-    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "conv1x1_2src_split_f16: B=%d T=%d", B, T);
     Op o = {};
-    o.type = OP_CONVG;
-    o.prec = FV_PAIR_SPLIT_F16;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = 2 * C;
-    o.Cin1 = C;
-    o.Cout = C;
-    o.k = 1;
-    o.dil = 1;
-    o.pre_slope = pre_slope;
-    o.out_div = 1.f;
-    o.post = post;
-    o.act_slope = act_slope;
+    if (int rc = build_convg(o, packed, bias, C, pre_slope, post, act_slope)) return rc;   // C: launch_convg's to refuse
+    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "conv1x1_2src_split_f16: B=%d T=%d", B, T);
     return run_op(o, x, y, y_act, res, nullptr, nullptr, B, T, (hipStream_t)stream, x2, nullptr, 0, guard);
 }
-
-}  // extern "C"
-
-namespace fv {
-int check_stack_args(int C, int k, int dil, int pad_mode, float slope, float act_slope, int post) {
-    if (post != FV_POST_NONE && post != FV_POST_TANH && post != FV_POST_RELU)
-        return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: post op %d", post);
-    if (!convk_shape(C, k, dil))
-        return fail(FV_ERR_UNSUPPORTED, "residual_stack_split_f16: C = %d, k = %d, dilation %d (32 / 64 / 128 / 256 channels, 3 taps, "
-                    "dilation 1, 3 or 9)", C, k, dil);
-    if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
-        return fail(FV_ERR_UNSUPPORTED, "residual_stack_split_f16: pad_mode %d (zero or reflection padding of the 'same' conv)", pad_mode);
-    return check_slopes("residual_stack_split_f16", slope, act_slope);
-}
-}  // namespace fv
-
-extern "C" {
 
 int fv_residual_stack_split_f16(const float* x, const float* packed, const float* bias_dilated, const float* bias_out, float* y,
                                 float* y_act, int B, int C, int T, int k, int dil, float slope, int pad_mode, int post,
@@ -1083,49 +1175,18 @@ int fv_residual_stack_split_f16(const float* x, const float* packed, const float
     if (!x || !packed || !y) return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: null tensor");
     if (x == y || x == y_act || (y_act && y_act == y))
         return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: y / y_act must not alias x or each other");
-    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: B=%d T=%d", B, T);
-    if (int rc = check_stack_args(C, k, dil, pad_mode, slope, act_slope, post)) return rc;
     Op o = {};
-    o.type = OP_STACK;
-    o.prec = FV_PAIR_SPLIT_F16;
-    o.wp = packed;
-    o.bias = bias_dilated;
-    o.bias2 = bias_out;
-    o.Cin = o.Cout = C;
-    o.k = k;
-    o.dil = dil;
-    o.pad = dil * (k - 1) / 2;
-    o.pad_mode = pad_mode;
-    o.pre_slope = slope;
-    o.out_div = 1.f;
-    o.post = post;
-    o.act_slope = act_slope;
+    if (int rc = build_stack(o, packed, bias_dilated, bias_out, C, k, dil, slope, pad_mode, post, act_slope)) return rc;
+    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "residual_stack_split_f16: B=%d T=%d", B, T);
     return run_op(o, x, y, y_act, nullptr, nullptr, nullptr, B, T, (hipStream_t)stream, nullptr, nullptr, 0, guard);
 }
 
 int fv_conv_post_pqmf(const float* x, const float* packed, const float* bias, const float* h, float* y, int B, int Cin,
                       int S, int T, int k, int pad, float pre_slope, int post, int ntaps, void* stream) {
+    // (a null filter is FV_ERR_INVALID_ARG here and FV_ERR_UNSUPPORTED from fv_plan_add_conv_post_pqmf)
     if (!x || !packed || !h || !y) return fail(FV_ERR_INVALID_ARG, "conv_post_pqmf: null tensor");
-    if (S != 4 || ntaps != 63) return fail(FV_ERR_UNSUPPORTED, "conv_post_pqmf: S=%d ntaps=%d (4 sub-bands, 63 taps)", S, ntaps);
-    if (int rc = check_conv_args(Cin, S, k, 1)) return rc;
-    // a 'same' conv: y holds S * T samples per utterance (a larger pad would make the kernel store past it)
-    if (k % 2 != 1 || pad != (k - 1) / 2)
-        return fail(FV_ERR_INVALID_ARG, "conv_post_pqmf: k=%d pad=%d (odd kernel, pad = (k - 1) / 2)", k, pad);
     Op o = {};
-    o.type = OP_CONV;
-    o.act_slope = 1.f;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = S;
-    o.k = k;
-    o.dil = 1;
-    o.pad = pad;
-    o.pre_slope = pre_slope;
-    o.out_div = 1.f;
-    o.post = post;
-    o.pq_h = h;
-    o.pq_taps = ntaps;
+    if (int rc = build_conv_post_pqmf(o, packed, bias, h, Cin, S, k, pad, pre_slope, post, ntaps)) return rc;
     if (B <= 0 || T <= 0) return 0;
     if (conv_out_len(o, T) <= 0) return fail(FV_ERR_INVALID_ARG, "conv_post_pqmf: empty output");
     return run_op(o, x, y, nullptr, nullptr, nullptr, nullptr, B, T, (hipStream_t)stream);
@@ -1170,33 +1231,6 @@ int launch_pair_family(const PairParams& pp, float* const* mid, int C, int dil, 
     return launch_pairs(pp, C, dil, s);
 }
 
-// The op a direct entry with several members would have added to a plan (what its launch record is built from), and
-// member j of an optional array argument
-static Op pair_op(int type, int C, int dil, int pad_mode, float slope, float out_div, int post, float act_slope, int prec) {
-    Op o = {};
-    o.type = type;
-    o.Cin = o.Cout = C;
-    o.dil = dil;
-    o.pad_mode = pad_mode;
-    o.pre_slope = slope;
-    o.out_div = out_div;
-    o.post = post;
-    o.act_slope = act_slope;
-    o.prec = prec;
-    return o;
-}
-template <class P>
-static P at(P const* a, int j) { return a ? a[j] : nullptr; }
-
-int check_pair_args(int n, int C, const int* k, int dil, int prec) {
-    if (n < 1 || n > 3) return fail(FV_ERR_INVALID_ARG, "resblock pair: %d members (1..3)", n);
-    if (C != 16 && C != 32 && !(prec == FV_PAIR_SPLIT_F16 && (C == 64 || C == 128 || C == 256 || C == 512)))
-        return fail(FV_ERR_UNSUPPORTED, "resblock pair: C = %d (16 or 32; 64 ... 512 with split-f16 operands); use the conv1d ops", C);
-    if (dil != 1 && dil != 3 && dil != 5) return fail(FV_ERR_UNSUPPORTED, "resblock pair: dilation %d (1, 3 or 5)", dil);
-    for (int j = 0; j < n; ++j)
-        if (int rc = check_taps("resblock pair", k[j])) return rc;
-    return 0;
-}
 }  // namespace fv
 
 extern "C" {
@@ -1208,20 +1242,23 @@ int fv_resblock1_fused(int n, const float* const* x, const float* const* w1, con
                                  1.f, FV_POST_NONE, act_slope, FV_PAIR_F32, nullptr, stream);
 }
 
+// (an unknown `prec`, and add1 / add2 / out_div / post with FV_PAIR_F32, are the launchers' to refuse here;
+// fv_plan_add_resblock_pair_ex refuses them itself)
 int fv_resblock1_fused_ex(int n, const float* const* x, const float* const* w1, const float* const* w2,
                           const float* const* b1, const float* const* b2, float* const* y, float* const* y_act,
                           float* const* mid, const float* const* add1, const float* const* add2, const int* k, int B,
                           int C, int T, int dil, float slope, float out_div, int post, float act_slope, int prec,
                           int* guard, void* stream) {
     if (!x || !w1 || !w2 || !y || !k) return fail(FV_ERR_INVALID_ARG, "resblock1_fused: null argument");
-    if (int rc = check_pair_args(n, C, k, dil, prec)) return rc;
-    const Op o = pair_op(OP_PAIR, C, dil, FV_PAD_ZERO, slope, out_div, post, act_slope, prec);
-    PairParams pp = pair_params(o, n, B, T, prec == FV_PAIR_SPLIT_F16 ? guard : nullptr);
+    if (n < 1 || n > 3) return fail(FV_ERR_INVALID_ARG, "resblock pair: %d members (1..3)", n);
+    PairParams pp = {};
     for (int j = 0; j < n; ++j) {
+        Op o = {};
+        if (int rc = build_pair(o, j, w1, w2, b1, b2, k, C, dil, slope, out_div, post, act_slope, prec)) return rc;
+        if (j == 0) pp = pair_params(o, n, B, T, prec == FV_PAIR_SPLIT_F16 ? guard : nullptr);
         if (!x[j] || !y[j] || x[j] == y[j] || (y_act && y_act[j] && (y_act[j] == y[j] || y_act[j] == x[j])))
             return fail(FV_ERR_INVALID_ARG, "resblock1_fused: member %d: null tensor, or y / y_act aliases x or each other", j);
-        const PairMember mb = pair_member(x[j], w1[j], w2[j], at(b1, j), at(b2, j), k[j], y[j], at(y_act, j), nullptr,
-                                          at(add1, j), at(add2, j));
+        const PairMember mb = op_member(o, 0, x[j], y[j], at(y_act, j), nullptr, at(add1, j), at(add2, j));
         if ((mb.add1 && (mb.add1 == mb.y || mb.add1 == mb.y_act)) || (mb.add2 && (mb.add2 == mb.y || mb.add2 == mb.y_act)))
             return fail(FV_ERR_INVALID_ARG, "resblock1_fused: member %d: add1 / add2 alias an output", j);
         pp.m[j] = mb;
@@ -1229,80 +1266,58 @@ int fv_resblock1_fused_ex(int n, const float* const* x, const float* const* w1, 
     return launch_pair_family(pp, mid, C, dil, prec, (hipStream_t)stream);
 }
 
+// (32 channels pass the builder and are launch_pairs's to refuse; fv_plan_add_mrf_sum refuses them when the op is added)
 int fv_mrf_stage(const float* const* x, const float* const* w1, const float* const* w2, const float* const* b1,
                  const float* const* b2, float* y, float* y_act, const int* k, int B, int C, int T, int dil,
                  float slope, float out_div, int post, float act_slope, void* stream) {
     if (!x || !w1 || !w2 || !y || !k) return fail(FV_ERR_INVALID_ARG, "mrf_stage: null argument");
-    if (int rc = check_pair_args(3, C, k, dil)) return rc;
-    PairParams pp = pair_params(pair_op(OP_MRFSUM, C, dil, FV_PAD_ZERO, slope, out_div, post, act_slope, FV_PAIR_F32), 3, B, T, nullptr);
+    Op o = {};
+    if (int rc = build_mrfsum(o, w1, w2, b1, b2, k, C, dil, slope, out_div, post, act_slope)) return rc;
+    PairParams pp = pair_params(o, 3, B, T, nullptr);
     pp.sum = 1;
     for (int j = 0; j < 3; ++j) {
         if (!x[j] || x[j] == y || x[j] == y_act || (y_act && y_act == y))
             return fail(FV_ERR_INVALID_ARG, "mrf_stage: member %d: null input, or y / y_act aliases an input or each other", j);
-        pp.m[j] = pair_member(x[j], w1[j], w2[j], at(b1, j), at(b2, j), k[j], y, y_act);
+        pp.m[j] = op_member(o, j, x[j], y, y_act);
     }
     return launch_pairs(pp, C, dil, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
-namespace fv {
-int check_stage_args(int C, const int* k, const int* dil, float slope, float act_slope, int post) {
-    if (!k || !dil) return fail(FV_ERR_INVALID_ARG, "mrf stage: null taps / dilations");
-    if (!mrf_stage_shape(C, k, dil))
-        return fail(FV_ERR_UNSUPPORTED, "mrf stage: C = %d, taps (%d, %d, %d), dilations (%d, %d, %d): built for 16 / 32 channels, "
-                    "taps 3 / 7 / 11, dilations (1, 3, 5)", C, k[0], k[1], k[2], dil[0], dil[1], dil[2]);
-    if (int rc = check_slopes("mrf stage", slope, act_slope)) return rc;
-    if (post != FV_POST_NONE && post != FV_POST_TANH && post != FV_POST_RELU) return fail(FV_ERR_INVALID_ARG, "mrf stage: post %d", post);
-    return 0;
-}
-}  // namespace fv
-
-extern "C" {
-
 int64_t fv_mrf_stage_workspace_bytes(int C) { return mrf_workspace_bytes(C); }
 
+// (the workspace is launch_mrfh's to check here; fv_plan_add_mrf_stage_split_f16 checks it when the op is added)
 int fv_mrf_stage_split_f16(const float* x, const float* packed, float* y, float* y_act, int B, int C, int T, const int* k,
                            const int* dil, float slope, float out_div, int post, float act_slope, const float* fold_w,
                            const float* fold_b, float* fold_y, void* workspace, int64_t workspace_bytes, int* guard,
                            void* stream) {
-    if (int rc = check_stage_args(C, k, dil, slope, act_slope, post)) return rc;
+    Op o = {};
+    if (int rc = build_stage(o, packed, C, k, dil, slope, out_div, post, act_slope, workspace, workspace_bytes)) return rc;
     if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "mrf stage: B=%d T=%d", B, T);
-    Op o = pair_op(OP_STAGE, C, dil[0], FV_PAD_ZERO, slope, out_div, post, act_slope, FV_PAIR_SPLIT_F16);
-    o.wp = packed;
-    for (int j = 0; j < 3; ++j) o.pk[j] = k[j];
     o.fold_w = fold_w;
     o.fold_b = fold_b;
-    o.work = workspace;
-    o.work_bytes = workspace_bytes;
-    return launch_mrfh(mrf_params(o, x, y, y_act, fold_y, B, T, guard), C, dil, (hipStream_t)stream);
+    return launch_mrfh(mrf_params(o, x, y, y_act, fold_y, B, T, guard), C, o.sdil, (hipStream_t)stream);
+}
+
+// the stage in two block classes, or (cls 1 / 2) one class alone: y_r2 null.  (The order of the taps is launch_mrfw_split's to
+// check here; fv_plan_add_mrf_stage_classes_f16 checks it itself.)
+static int run_stage_classes(const float* x, const float* packed, float* y_s, float* y_r2, int cls, int B, int C, int T, const int* k,
+                             const int* dil, float slope, void* workspace, int64_t workspace_bytes, int* guard, void* stream) {
+    Op o = {};
+    if (int rc = build_stage(o, packed, C, k, dil, slope, 1.f, FV_POST_NONE, 1.f, workspace, workspace_bytes)) return rc;
+    if (C != 32) return fail(FV_ERR_UNSUPPORTED, "mrf stage (two classes): C = %d (32)", C);
+    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "mrf stage (two classes): B=%d T=%d", B, T);
+    return launch_mrfw_split(mrf_split_params(o, x, y_s, y_r2, B, T, guard), o.sdil, (hipStream_t)stream, cls);
 }
 
 int fv_mrf_stage_classes_f16(const float* x, const float* packed, float* y_s, float* y_r2, int B, int C, int T, const int* k,
                              const int* dil, float slope, void* workspace, int64_t workspace_bytes, int* guard, void* stream) {
-    if (int rc = check_stage_args(C, k, dil, slope, 1.f, FV_POST_NONE)) return rc;
-    if (C != 32) return fail(FV_ERR_UNSUPPORTED, "mrf stage (two classes): C = %d (32)", C);
-    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "mrf stage (two classes): B=%d T=%d", B, T);
-    Op o = pair_op(OP_STAGE, C, dil[0], FV_PAD_ZERO, slope, 1.f, FV_POST_NONE, 1.f, FV_PAIR_SPLIT_F16);
-    o.wp = packed;
-    for (int j = 0; j < 3; ++j) o.pk[j] = k[j];
-    o.work = workspace;
-    o.work_bytes = workspace_bytes;
-    return launch_mrfw_split(mrf_split_params(o, x, y_s, y_r2, B, T, guard), dil, (hipStream_t)stream);
+    return run_stage_classes(x, packed, y_s, y_r2, 0, B, C, T, k, dil, slope, workspace, workspace_bytes, guard, stream);
 }
 
 int fv_debug_mrf_stage_class_f16(const float* x, const float* packed, float* y, int cls, int B, int C, int T, const int* k,
                                  const int* dil, float slope, void* workspace, int64_t workspace_bytes, void* stream) {
     if (cls != 1 && cls != 2) return fail(FV_ERR_INVALID_ARG, "debug_mrf_stage_class: class %d (1: A, 2: B)", cls);
-    if (int rc = check_stage_args(C, k, dil, slope, 1.f, FV_POST_NONE)) return rc;
-    if (C != 32) return fail(FV_ERR_UNSUPPORTED, "debug_mrf_stage_class: C = %d (32)", C);
-    if (B < 0 || T < 0) return fail(FV_ERR_INVALID_ARG, "debug_mrf_stage_class: B=%d T=%d", B, T);
-    Op o = pair_op(OP_STAGE, C, dil[0], FV_PAD_ZERO, slope, 1.f, FV_POST_NONE, 1.f, FV_PAIR_SPLIT_F16);
-    o.wp = packed;
-    for (int j = 0; j < 3; ++j) o.pk[j] = k[j];
-    o.work = workspace;
-    o.work_bytes = workspace_bytes;
-    return launch_mrfw_split(mrf_split_params(o, x, y, nullptr, B, T, nullptr), dil, (hipStream_t)stream, cls);
+    return run_stage_classes(x, packed, y, nullptr, cls, B, C, T, k, dil, slope, workspace, workspace_bytes, nullptr, stream);
 }
 
 int fv_debug_mrf_class_schedule(int B, int T, int nblk, int force, int64_t* info, unsigned* table) {
@@ -1318,36 +1333,18 @@ int fv_debug_mrf_class_schedule(int B, int T, int nblk, int force, int64_t* info
     return 0;
 }
 
-}  // extern "C"
-
-namespace fv {
-int check_convh_args(int n, int C, const int* k, int dil, int pad_mode) {
-    if (pad_mode != FV_PAD_ZERO && pad_mode != FV_PAD_REFLECT)
-        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: pad_mode %d (FV_PAD_ZERO or FV_PAD_REFLECT)", pad_mode);
-    if (n < 1 || n > 3) return fail(FV_ERR_INVALID_ARG, "conv1d_split_f16: %d members (1..3)", n);
-    if (C != 64 && C != 128 && C != 256 && C != 512)
-        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: C = %d (64, 128, 256 or 512)", C);
-    if (dil != 1 && dil != 3 && dil != 5 && dil != 9)
-        return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: dilation %d (1, 3, 5; 9 with 3 taps)", dil);
-    for (int j = 0; j < n; ++j)
-        if ((k[j] != 3 && k[j] != 7 && k[j] != 11) || (dil == 9 && k[j] != 3))
-            return fail(FV_ERR_UNSUPPORTED, "conv1d_split_f16: %d taps at dilation %d (3, 7 or 11; 3 at dilation 9)", k[j], dil);
-    return 0;
-}
-}  // namespace fv
-
-extern "C" {
-
 int fv_conv1d_split_f16(int n, const float* const* x, const float* const* packed, const float* const* bias,
                         const float* const* res, const float* const* add1, const float* const* add2, float* const* y,
                         float* const* y_act, const int* k, int B, int C, int T, int dil, int pad_mode, float pre_slope,
                         float out_div, int post, float act_slope, int* guard, void* stream) {
     if (!x || !packed || !y || !k) return fail(FV_ERR_INVALID_ARG, "conv1d_split_f16: null argument");
-    if (int rc = check_convh_args(n, C, k, dil, pad_mode)) return rc;
-    PairParams pp = pair_params(pair_op(OP_CONVH, C, dil, pad_mode, pre_slope, out_div, post, act_slope, FV_PAIR_SPLIT_F16), n, B, T, guard);
+    if (n < 1 || n > 3) return fail(FV_ERR_INVALID_ARG, "conv1d_split_f16: %d members (1..3)", n);
+    PairParams pp = {};
     for (int j = 0; j < n; ++j) {
-        const PairMember& mb = pp.m[j] = pair_member(x[j], packed[j], nullptr, at(bias, j), nullptr, k[j], y[j], at(y_act, j),
-                                                     at(res, j), at(add1, j), at(add2, j));
+        Op o = {};
+        if (int rc = build_convh(o, j, packed, bias, k, C, dil, pad_mode, pre_slope, out_div, post, act_slope)) return rc;
+        if (j == 0) pp = pair_params(o, n, B, T, guard);
+        const PairMember& mb = pp.m[j] = op_member(o, 0, x[j], y[j], at(y_act, j), at(res, j), at(add1, j), at(add2, j));
         if (!mb.x || !mb.y || mb.x == mb.y || mb.y == mb.res || mb.y == mb.add1 || mb.y == mb.add2 ||
             (mb.y_act && (mb.y_act == mb.y || mb.y_act == mb.x || mb.y_act == mb.res)))
             return fail(FV_ERR_INVALID_ARG, "conv1d_split_f16: member %d: null tensor or an output aliases an input", j);

@@ -1,6 +1,7 @@
 // What api.hip (operators, measurement hook, tuning) and plan.hip (the plan executor) share: the op record, the plan, the
-// argument checks, and what both the direct entry points and their plan ops launch through: run_op, the builders of the
-// launch records (PairParams / PairMember / MrfParams from an Op and resolved pointers) and the pair dispatch.
+// op builders (argument checks + the record, one per family), and what both the direct entry points and their plan ops launch
+// through: run_op, the builders of the launch records (PairParams / PairMember / MrfParams from an Op and resolved pointers)
+// and the pair dispatch.
 #pragma once
 #include <stdint.h>
 
@@ -17,7 +18,7 @@ enum OpType { OP_CONV = 0, OP_CONVT = 1, OP_PQMF = 2, OP_UPCONV = 3, OP_PAIR = 4
 
 struct Op {
     int type;
-    int x, y, res, acc, y2, acc2;
+    int x = FV_SLOT_NONE, y = FV_SLOT_NONE, res = FV_SLOT_NONE, acc = FV_SLOT_NONE, y2 = FV_SLOT_NONE, acc2 = FV_SLOT_NONE;
     int group;     // ops with the same non-zero id are mutually independent: one grouped launch
     const float* wp;
     const float* bias;
@@ -92,8 +93,34 @@ ConvParams make_params(const Op& o, const float* x, float* y, float* y2, const f
 int run_op(const Op& o, const float* x, float* y, float* y2, const float* res, const float* acc,
                   const float* acc2, int B, int64_t Tin, hipStream_t s, const float* x2 = nullptr,
                   const float* sub = nullptr, int sub_batched = 0, int* guard = nullptr);
-int check_pad_mode(int pad_mode, int pad, int k, int dil);
-int check_stack_args(int C, int k, int dil, int pad_mode, float slope, float act_slope, int post = FV_POST_NONE);
+
+// ---------------------------------------------------------------------------
+// op builders: one per operator family, called by the family's direct entry (api.hip) and by its plan entry (plan.hip).
+// Each checks every argument that is neither a tensor nor a slot and fills every field of `o` (an `Op o = {}`) that is no
+// slot; 0, or fail()'s code.  What one of the two entries checks and its twin does not stands in that entry.
+// ---------------------------------------------------------------------------
+int build_conv(Op& o, const float* packed, const float* bias, int Cin, int Cout, int k, int dil, int pad, int pad_mode,
+               float pre_slope, float out_div, int post, float act_slope);
+int build_conv_2src(Op& o, const float* packed, const float* bias, int Cin1, int Cin2, int Cout, int post, float act_slope);
+int build_convt(Op& o, const float* packed, const float* bias, int Cin, int Cout, int k, int stride, int pad, int out_pad,
+                float pre_slope, int post, float act_slope);
+int build_convt_split(Op& o, const float* packed, const float* bias, int Cin, int Cout, int k, int stride, int pad, int out_pad,
+                      float pre_slope, float act_slope);
+int build_convg(Op& o, const float* packed, const float* bias, int C, float pre_slope, int post, float act_slope);
+int build_stack(Op& o, const float* packed, const float* bias_dilated, const float* bias_out, int C, int k, int dil, float slope,
+                int pad_mode, int post, float act_slope);
+int build_conv_post_pqmf(Op& o, const float* packed, const float* bias, const float* h, int Cin, int S, int k, int pad,
+                         float pre_slope, int post, int ntaps);
+int build_pqmf(Op& o, const float* h, int S, int ntaps);
+// (the grouped families: one member per op, its weights, biases and taps in pw1[0] and its siblings; member j of the arrays)
+int build_pair(Op& o, int j, const float* const* w1, const float* const* w2, const float* const* b1, const float* const* b2,
+               const int* k, int C, int dil, float slope, float out_div, int post, float act_slope, int prec);
+int build_convh(Op& o, int j, const float* const* packed, const float* const* bias, const int* k, int C, int dil, int pad_mode,
+                float pre_slope, float out_div, int post, float act_slope);
+int build_mrfsum(Op& o, const float* const* w1, const float* const* w2, const float* const* b1, const float* const* b2,
+                 const int* k, int C, int dil, float slope, float out_div, int post, float act_slope);
+int build_stage(Op& o, const float* packed, int C, const int* k, const int* dil, float slope, float out_div, int post,
+                float act_slope, void* workspace, int64_t workspace_bytes);
 
 // ---------------------------------------------------------------------------
 // launch records: every PairParams / PairMember / MrfParams of the direct entries and of the plan is built here
@@ -106,14 +133,16 @@ PairParams pair_params(const Op& o, int n_members, int B, int64_t T, int* guard,
 PairMember pair_member(const float* x, const float* w1, const float* w2, const float* b1, const float* b2, int k, float* y,
                        float* y_act, const float* res = nullptr, const float* add1 = nullptr, const float* add2 = nullptr,
                        const float* x2 = nullptr);
+// member j of a grouped family's op (OP_PAIR, OP_CONVH: j = 0; OP_MRFSUM: 0..2) on resolved pointers
+inline PairMember op_member(const Op& o, int j, const float* x, float* y, float* y_act, const float* res = nullptr,
+                            const float* add1 = nullptr, const float* add2 = nullptr) {
+    return pair_member(x, o.pw1[j], o.pw2[j], o.pb1[j], o.pb2[j], o.pk[j], y, y_act, res, add1, add2);
+}
 // an OP_STAGE's launch: blob, taps, slopes, out_div, post, fold_w / fold_b and the history slots from the op
 MrfParams mrf_params(const Op& o, const float* x, float* y, float* y_act, float* fold_y, int B, int64_t T, int* guard);
 // ... in two block classes (Op::classes): y_s = r_0 + r_1, y_r2 = r_2
 MrfSplitParams mrf_split_params(const Op& o, const float* x, float* y_s, float* y_r2, int B, int64_t T, int* guard);
 // a launch of fused ResBlock pairs, by the kernel family of its channel count (mid: the members' scratch tensors, C >= 64)
 int launch_pair_family(const PairParams& pp, float* const* mid, int C, int dil, int prec, hipStream_t s);
-int check_pair_args(int n, int C, const int* k, int dil, int prec = FV_PAIR_F32);
-int check_stage_args(int C, const int* k, const int* dil, float slope, float act_slope, int post);
-int check_convh_args(int n, int C, const int* k, int dil, int pad_mode);
 
 }  // namespace fv

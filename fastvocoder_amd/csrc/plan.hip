@@ -159,15 +159,22 @@ static int check_slot(int s, bool allow_none) {
     return 0;
 }
 
-// The slot checks the fv_plan_add_* functions share: x and y are slots, y_act and the `optional` ones slots or
-// FV_SLOT_NONE, and no op writes the plan's input
-static int check_op_slots(int x, int y, int y_act, std::initializer_list<int> optional = {}) {
+// What every fv_plan_add_* function ends with: the slot checks they share (x and y are slots, y_act and the optional ones
+// slots or FV_SLOT_NONE, and no op writes the plan's input), the op's slots, the push
+static int push(fv_plan* plan, Op& o, int x, int y, int y_act, int res = FV_SLOT_NONE, int acc = FV_SLOT_NONE,
+                int acc2 = FV_SLOT_NONE) {
     if (int rc = check_slot(x, false)) return rc;
     if (int rc = check_slot(y, false)) return rc;
-    if (int rc = check_slot(y_act, true)) return rc;
-    for (int s : optional)
+    for (int s : {y_act, res, acc, acc2})
         if (int rc = check_slot(s, true)) return rc;
     if (y == FV_SLOT_IN || y_act == FV_SLOT_IN) return fail(FV_ERR_INVALID_ARG, "plan: the input slot is read-only");
+    o.x = x;
+    o.y = y;
+    o.y2 = y_act;
+    o.res = res;
+    o.acc = acc;
+    o.acc2 = acc2;
+    plan->ops.push_back(o);
     return 0;
 }
 
@@ -176,33 +183,11 @@ int fv_plan_add_conv1d(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, 
                        int Cout, int k, int dil, int pad, int pad_mode, float pre_slope, float out_div,
                        int post, float act_slope) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d: null");
-    if (int rc = check_conv_args(Cin, Cout, k, dil)) return rc;
-    if (int rc = check_pad_mode(pad_mode, pad, k, dil)) return rc;
-    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {res_slot, acc_slot, acc2_slot})) return rc;
     Op o = {};
-    o.type = OP_CONV;
-    o.x = x_slot;
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.act_slope = act_slope;
-    o.res = res_slot;
-    o.acc = acc_slot;
-    o.acc2 = acc2_slot;
+    if (int rc = build_conv(o, packed, bias, Cin, Cout, k, dil, pad, pad_mode, pre_slope, out_div, post, act_slope)) return rc;
     o.group = plan->cur_group;
     o.own_first = plan->cur_own_first;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = Cout;
-    o.k = k;
-    o.dil = dil;
-    o.pad = pad;
-    o.pad_mode = pad_mode;
-    o.pre_slope = pre_slope;
-    o.out_div = out_div;
-    o.post = post;
-    plan->ops.push_back(o);
-    return 0;
+    return push(plan, o, x_slot, y_slot, y_act_slot, res_slot, acc_slot, acc2_slot);
 }
 
 int fv_plan_add_conv1d_sum3(fv_plan_t* plan, const int* x_slots, const int* res_slots, const int* tmp_slots,
@@ -241,63 +226,36 @@ int fv_plan_add_conv1d_sum3(fv_plan_t* plan, const int* x_slots, const int* res_
 int fv_plan_add_conv1d_2src(fv_plan_t* plan, int x_slot, int x2_slot, int y_slot, int y_act_slot,
                             int res_slot, const float* packed, const float* bias, int Cin1, int Cin2,
                             int Cout, int post, float act_slope) {
-    if (Cin1 <= 0 || Cin2 <= 0) return fail(FV_ERR_INVALID_ARG, "conv1d_2src: Cin1=%d Cin2=%d", Cin1, Cin2);
+    if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_2src: null");
+    Op o = {};
+    if (int rc = build_conv_2src(o, packed, bias, Cin1, Cin2, Cout, post, act_slope)) return rc;
     if (int rc = check_slot(x2_slot, false)) return rc;
-    if (int rc = fv_plan_add_conv1d(plan, x_slot, y_slot, y_act_slot, res_slot, FV_SLOT_NONE, FV_SLOT_NONE,
-                                    packed, bias, Cin1 + Cin2, Cout, 1, 1, 0, FV_PAD_ZERO, 1.f, 1.f, post,
-                                    act_slope))
-        return rc;
-    Op& o = plan->ops.back();
     o.x2 = x2_slot;
-    o.Cin1 = Cin1;
-    o.group = 0;
-    return 0;
+    o.own_first = plan->cur_own_first;
+    return push(plan, o, x_slot, y_slot, y_act_slot, res_slot);
 }
 
 int fv_plan_add_conv1x1_2src_split_f16(fv_plan_t* plan, int x_slot, int x2_slot, int y_slot, int y_act_slot, int res_slot,
                                        const float* packed, const float* bias, int C, float pre_slope, int post,
                                        float act_slope) {
-    if (fv_packed_conv1x1_2src_split_floats(C) <= 0)
+    if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1x1_2src_split_f16: null");
+    if (fv_packed_conv1x1_2src_split_floats(C) <= 0)     // this entry alone: fv_conv1x1_2src_split_f16 leaves C to launch_convg
         return fail(FV_ERR_UNSUPPORTED, "plan_add_conv1x1_2src_split_f16: C = %d (128, 256 or 512)", C);
-    if (int rc = fv_plan_add_conv1d_2src(plan, x_slot, x2_slot, y_slot, y_act_slot, res_slot, packed, bias, C, C, C, post,
-                                         act_slope))
-        return rc;
-    Op& o = plan->ops.back();
-    o.type = OP_CONVG;
-    o.pre_slope = pre_slope;
-    o.prec = FV_PAIR_SPLIT_F16;
-    return 0;
+    Op o = {};
+    if (int rc = build_convg(o, packed, bias, C, pre_slope, post, act_slope)) return rc;
+    if (int rc = check_slot(x2_slot, false)) return rc;
+    o.x2 = x2_slot;
+    o.own_first = plan->cur_own_first;
+    return push(plan, o, x_slot, y_slot, y_act_slot, res_slot);
 }
 
 int fv_plan_add_residual_stack_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, const float* packed,
                                          const float* bias_dilated, const float* bias_out, int C, int k, int dil, float slope,
                                          int pad_mode, int post, float act_slope) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_residual_stack_split_f16: null");
-    if (int rc = check_stack_args(C, k, dil, pad_mode, slope, act_slope, post)) return rc;
-    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot)) return rc;
     Op o = {};
-    o.type = OP_STACK;
-    o.prec = FV_PAIR_SPLIT_F16;
-    o.x = x_slot;
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.res = o.acc = o.acc2 = FV_SLOT_NONE;
-    o.group = 0;
-    o.wp = packed;
-    o.bias = bias_dilated;
-    o.bias2 = bias_out;
-    o.Cin = o.Cout = C;
-    o.k = k;
-    o.dil = dil;
-    o.pad = dil * (k - 1) / 2;
-    o.pad_mode = pad_mode;
-    o.stride = 1;
-    o.pre_slope = slope;
-    o.out_div = 1.f;
-    o.post = post;
-    o.act_slope = act_slope;
-    plan->ops.push_back(o);
-    return 0;
+    if (int rc = build_stack(o, packed, bias_dilated, bias_out, C, k, dil, slope, pad_mode, post, act_slope)) return rc;
+    return push(plan, o, x_slot, y_slot, y_act_slot);
 }
 
 int fv_plan_set_stack_two_launch(fv_plan_t* plan, int hidden_slot, const float* packed_dilated, const float* packed_pair) {
@@ -315,48 +273,24 @@ int fv_plan_set_stack_two_launch(fv_plan_t* plan, int hidden_slot, const float* 
     return 0;
 }
 
+// (any out_pad >= -stride here; fv_conv_transpose1d_fused refuses one of the stride or more)
 int fv_plan_add_conv_transpose1d(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot,
                                  const float* packed, const float* bias, int Cin, int Cout, int k,
                                  int stride, int pad, int out_pad, float pre_slope, int post,
                                  float act_slope) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv_transpose1d: null");
-    if (int rc = check_conv_args(Cin, Cout, k, 1)) return rc;
-    if (stride <= 0 || pad < 0 || out_pad < -stride)
-        return fail(FV_ERR_INVALID_ARG, "convT stride=%d pad=%d out_pad=%d", stride, pad, out_pad);
-    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot)) return rc;
     Op o = {};
-    o.type = OP_CONVT;
-    o.x = x_slot;
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.act_slope = act_slope;
-    o.res = FV_SLOT_NONE;
-    o.acc = FV_SLOT_NONE;
-    o.acc2 = FV_SLOT_NONE;
-    o.wp = packed;
-    o.bias = bias;
-    o.Cin = Cin;
-    o.Cout = Cout;
-    o.k = k;
-    o.stride = stride;
-    o.pad = pad;
-    o.out_pad = out_pad;
-    o.pre_slope = pre_slope;
-    o.out_div = 1.f;
-    o.post = post;
-    plan->ops.push_back(o);
-    return 0;
+    if (int rc = build_convt(o, packed, bias, Cin, Cout, k, stride, pad, out_pad, pre_slope, post, act_slope)) return rc;
+    return push(plan, o, x_slot, y_slot, y_act_slot);
 }
 
 int fv_plan_add_conv_transpose1d_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, const float* packed,
                                            const float* bias, int Cin, int Cout, int k, int stride, int pad,
                                            int out_pad, float pre_slope, float act_slope) {
-    if (int rc = check_convt_split_args(Cin, Cout, k, stride, pad, out_pad)) return rc;
-    if (int rc = fv_plan_add_conv_transpose1d(plan, x_slot, y_slot, y_act_slot, packed, bias, Cin, Cout, k, stride, pad,
-                                              out_pad, pre_slope, FV_POST_NONE, act_slope))
-        return rc;
-    plan->ops.back().prec = FV_PAIR_SPLIT_F16;
-    return 0;
+    if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv_transpose1d_split_f16: null");
+    Op o = {};
+    if (int rc = build_convt_split(o, packed, bias, Cin, Cout, k, stride, pad, out_pad, pre_slope, act_slope)) return rc;
+    return push(plan, o, x_slot, y_slot, y_act_slot);
 }
 
 int fv_plan_set_input_merge(fv_plan_t* plan, int add1_slot, int add2_slot, float div) {
@@ -377,39 +311,25 @@ int fv_plan_set_input_merge(fv_plan_t* plan, int add1_slot, int add2_slot, float
 
 int fv_plan_add_conv_post_pqmf(fv_plan_t* plan, int x_slot, int y_slot, const float* packed, const float* bias, int Cin,
                                int S, int k, int pad, float pre_slope, int post, const float* h, int ntaps) {
-    if (!h || S != 4 || ntaps != 63)
-        return fail(FV_ERR_UNSUPPORTED, "plan_add_conv_post_pqmf: S=%d ntaps=%d (4 sub-bands, 63 taps)", S, ntaps);
-    // a 'same' conv: the kernel writes S * T samples per utterance, the output's size (a larger pad would run past it)
-    if (k % 2 != 1 || pad != (k - 1) / 2)
-        return fail(FV_ERR_INVALID_ARG, "plan_add_conv_post_pqmf: k=%d pad=%d (odd kernel, pad = (k - 1) / 2)", k, pad);
-    if (int rc = fv_plan_add_conv1d(plan, x_slot, y_slot, FV_SLOT_NONE, FV_SLOT_NONE, FV_SLOT_NONE, FV_SLOT_NONE, packed, bias,
-                                    Cin, S, k, 1, pad, FV_PAD_ZERO, pre_slope, 1.f, post, 1.f))
-        return rc;
-    Op& o = plan->ops.back();
-    o.group = 0;
-    o.pq_h = h;
-    o.pq_taps = ntaps;
-    return 0;
+    if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv_post_pqmf: null");
+    // this entry alone: a null filter is FV_ERR_INVALID_ARG from fv_conv_post_pqmf
+    if (!h) return fail(FV_ERR_UNSUPPORTED, "plan_add_conv_post_pqmf: null filter");
+    Op o = {};
+    if (int rc = build_conv_post_pqmf(o, packed, bias, h, Cin, S, k, pad, pre_slope, post, ntaps)) return rc;
+    o.own_first = plan->cur_own_first;
+    return push(plan, o, x_slot, y_slot, FV_SLOT_NONE);
 }
 
+// (its two slots may be any, the plan's input included: no push())
 int fv_plan_add_pqmf_synthesis(fv_plan_t* plan, int x_slot, int y_slot, const float* h, int S,
                                int ntaps) {
-    if (!plan || !h || S <= 0 || ntaps <= 0 || ntaps % 2 == 0)
-        return fail(FV_ERR_INVALID_ARG, "plan_add_pqmf: S=%d ntaps=%d", S, ntaps);
+    if (!plan || !h) return fail(FV_ERR_INVALID_ARG, "plan_add_pqmf: null");
+    Op o = {};
+    if (int rc = build_pqmf(o, h, S, ntaps)) return rc;
     if (int rc = check_slot(x_slot, false)) return rc;
     if (int rc = check_slot(y_slot, false)) return rc;
-    Op o = {};
-    o.type = OP_PQMF;
     o.x = x_slot;
     o.y = y_slot;
-    o.y2 = FV_SLOT_NONE;
-    o.res = FV_SLOT_NONE;
-    o.acc = FV_SLOT_NONE;
-    o.acc2 = FV_SLOT_NONE;
-    o.wp = h;
-    o.Cin = S;
-    o.Cout = 1;
-    o.k = ntaps;
     plan->ops.push_back(o);
     return 0;
 }
@@ -418,35 +338,13 @@ int fv_plan_add_mrf_stage_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int
                                     const int* k, const int* dil, float slope, float out_div, int post, float act_slope,
                                     void* workspace, int64_t workspace_bytes) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_mrf_stage: null");
-    if (int rc = check_stage_args(C, k, dil, slope, act_slope, post)) return rc;
+    Op o = {};
+    if (int rc = build_stage(o, packed, C, k, dil, slope, out_div, post, act_slope, workspace, workspace_bytes)) return rc;
+    // this entry alone: fv_mrf_stage_split_f16 leaves the workspace to launch_mrfh
     if (workspace_bytes < mrf_workspace_bytes(C) || (mrf_workspace_bytes(C) > 0 && !workspace))
         return fail(FV_ERR_WORKSPACE, "plan_add_mrf_stage: C = %d needs a workspace of %lld bytes (fv_mrf_stage_workspace_bytes)", C,
                     (long long)mrf_workspace_bytes(C));
-    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot)) return rc;
-    Op o = {};
-    o.type = OP_STAGE;
-    o.x = x_slot;
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.res = o.acc = o.acc2 = FV_SLOT_NONE;
-    o.group = 0;
-    o.Cin = o.Cout = C;
-    o.k = k[0];
-    o.dil = dil[0];
-    for (int j = 0; j < 3; ++j) {
-        o.pk[j] = k[j];
-        o.sdil[j] = dil[j];
-    }
-    o.wp = packed;
-    o.work = workspace;
-    o.work_bytes = workspace_bytes;
-    o.pre_slope = slope;
-    o.act_slope = act_slope;
-    o.out_div = out_div;
-    o.post = post;
-    o.prec = FV_PAIR_SPLIT_F16;
-    plan->ops.push_back(o);
-    return 0;
+    return push(plan, o, x_slot, y_slot, y_act_slot);
 }
 
 int fv_plan_add_mrf_stage_classes_f16(fv_plan_t* plan, int x_slot, int ys_slot, int yr2_slot, const float* packed, int C,
@@ -479,75 +377,33 @@ int fv_plan_add_resblock_pair_ex(fv_plan_t* plan, int x_slot, int y_slot, int y_
                                  const float* bias2, int C, int k, int dil, float slope, float out_div, int post,
                                  float act_slope, int prec) {
     if (!plan || !packed1 || !packed2) return fail(FV_ERR_INVALID_ARG, "plan_add_resblock_pair: null");
-    if (int rc = check_pair_args(1, C, &k, dil, prec)) return rc;
+    Op o = {};
+    if (int rc = build_pair(o, 0, &packed1, &packed2, &bias1, &bias2, &k, C, dil, slope, out_div, post, act_slope, prec)) return rc;
     if ((C >= 64) != (mid_slot != FV_SLOT_NONE))
         return fail(FV_ERR_INVALID_ARG, "plan_add_resblock_pair: a scratch slot is needed at C >= 64 and only there");
     if (int rc = check_slot(mid_slot, true)) return rc;
+    // the next two are this entry's alone: fv_resblock1_fused_ex leaves them to the launchers
     if (prec != FV_PAIR_F32 && prec != FV_PAIR_SPLIT_F16)
         return fail(FV_ERR_INVALID_ARG, "plan_add_resblock_pair: unknown arithmetic %d", prec);
     if (prec == FV_PAIR_F32 && (add1_slot != FV_SLOT_NONE || add2_slot != FV_SLOT_NONE || out_div != 1.f || post != FV_POST_NONE))
         return fail(FV_ERR_UNSUPPORTED, "plan_add_resblock_pair: add1 / add2 / out_div / post exist with FV_PAIR_SPLIT_F16 only");
     if (int rc = check_adds("plan_add_resblock_pair", add1_slot != FV_SLOT_NONE, add2_slot != FV_SLOT_NONE)) return rc;
-    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {add1_slot, add2_slot})) return rc;
-    Op o = {};
-    o.type = OP_PAIR;
-    o.x = x_slot;
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.res = FV_SLOT_NONE;
-    o.acc = add1_slot;      // the MRF addends travel in the running-sum fields (dependencies, shape checks)
-    o.acc2 = add2_slot;
     o.tmpb = mid_slot;
     o.group = plan->cur_group;
-    o.Cin = o.Cout = C;
-    o.k = k;
-    o.dil = dil;
-    o.pre_slope = slope;
-    o.act_slope = act_slope;
-    o.out_div = out_div;
-    o.post = post;
-    o.prec = prec;
-    o.pw1[0] = packed1;
-    o.pw2[0] = packed2;
-    o.pb1[0] = bias1;
-    o.pb2[0] = bias2;
-    o.pk[0] = k;
-    plan->ops.push_back(o);
-    return 0;
+    return push(plan, o, x_slot, y_slot, y_act_slot, FV_SLOT_NONE, add1_slot, add2_slot);   // (the MRF addends travel as running sums)
 }
 
 int fv_plan_add_conv1d_split_f16(fv_plan_t* plan, int x_slot, int y_slot, int y_act_slot, int res_slot, int add1_slot,
                                  int add2_slot, const float* packed, const float* bias, int C, int k, int dil,
                                  int pad_mode, float pre_slope, float out_div, int post, float act_slope) {
     if (!plan || !packed) return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: null");
-    if (int rc = check_convh_args(1, C, &k, dil, pad_mode)) return rc;
+    Op o = {};
+    if (int rc = build_convh(o, 0, &packed, &bias, &k, C, dil, pad_mode, pre_slope, out_div, post, act_slope)) return rc;
     if (int rc = check_adds("plan_add_conv1d_split_f16", add1_slot != FV_SLOT_NONE, add2_slot != FV_SLOT_NONE)) return rc;
-    if (int rc = check_op_slots(x_slot, y_slot, y_act_slot, {res_slot, add1_slot, add2_slot})) return rc;
     if (y_slot == res_slot || y_slot == add1_slot || y_slot == add2_slot)
         return fail(FV_ERR_INVALID_ARG, "plan_add_conv1d_split_f16: the output aliases an addend");
-    Op o = {};
-    o.type = OP_CONVH;
-    o.x = x_slot;
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.res = res_slot;
-    o.acc = add1_slot;
-    o.acc2 = add2_slot;
     o.group = plan->cur_group;
-    o.Cin = o.Cout = C;
-    o.k = k;
-    o.dil = dil;
-    o.pad_mode = pad_mode;
-    o.pre_slope = pre_slope;
-    o.act_slope = act_slope;
-    o.out_div = out_div;
-    o.post = post;
-    o.prec = FV_PAIR_SPLIT_F16;
-    o.pw1[0] = packed;
-    o.pb1[0] = bias;
-    o.pk[0] = k;
-    plan->ops.push_back(o);
-    return 0;
+    return push(plan, o, x_slot, y_slot, y_act_slot, res_slot, add1_slot, add2_slot);
 }
 
 int fv_plan_add_mrf_sum(fv_plan_t* plan, const int* x_slots, int y_slot, int y_act_slot,
@@ -555,37 +411,16 @@ int fv_plan_add_mrf_sum(fv_plan_t* plan, const int* x_slots, int y_slot, int y_a
                         const float* const* bias2, int C, const int* k, int dil, float slope, float out_div,
                         int post, float act_slope) {
     if (!plan || !x_slots || !packed1 || !packed2 || !k) return fail(FV_ERR_INVALID_ARG, "plan_add_mrf_sum: null");
-    if (int rc = check_pair_args(3, C, k, dil)) return rc;
-    if (C != 16) return fail(FV_ERR_UNSUPPORTED, "plan_add_mrf_sum: C = %d (16)", C);
+    Op o = {};
+    if (int rc = build_mrfsum(o, packed1, packed2, bias1, bias2, k, C, dil, slope, out_div, post, act_slope)) return rc;
+    if (C != 16) return fail(FV_ERR_UNSUPPORTED, "plan_add_mrf_sum: C = %d (16)", C);     // here when the op is added: fv_mrf_stage leaves 32 channels to launch_pairs
     for (int j = 0; j < 3; ++j) {
         if (!packed1[j] || !packed2[j]) return fail(FV_ERR_INVALID_ARG, "plan_add_mrf_sum: member %d has no weights", j);
         if (int rc = check_slot(x_slots[j], false)) return rc;
     }
-    if (int rc = check_op_slots(x_slots[0], y_slot, y_act_slot)) return rc;
-    Op o = {};
-    o.type = OP_MRFSUM;
-    o.x = x_slots[0];
     o.xb = x_slots[1];
     o.xc = x_slots[2];
-    o.y = y_slot;
-    o.y2 = y_act_slot;
-    o.res = o.acc = o.acc2 = FV_SLOT_NONE;
-    o.Cin = o.Cout = C;
-    o.k = k[0];
-    o.dil = dil;
-    o.pre_slope = slope;
-    o.act_slope = act_slope;
-    o.out_div = out_div;
-    o.post = post;
-    for (int j = 0; j < 3; ++j) {
-        o.pw1[j] = packed1[j];
-        o.pw2[j] = packed2[j];
-        o.pb1[j] = bias1 ? bias1[j] : nullptr;
-        o.pb2[j] = bias2 ? bias2[j] : nullptr;
-        o.pk[j] = k[j];
-    }
-    plan->ops.push_back(o);
-    return 0;
+    return push(plan, o, x_slots[0], y_slot, y_act_slot);
 }
 
 int fv_plan_set_output_offset(fv_plan_t* plan, int aux_slot, int y2_slot) {
@@ -711,8 +546,7 @@ static int run_convh_group(const Run& r, size_t n, size_t m) {
     PairParams pp = pair_params(o, (int)(m - n), r.B, r.T(o), r.guard());
     for (size_t q = n; q < m; ++q) {
         const Op& qo = r.op(q);
-        pp.m[q - n] = pair_member(r.base[qo.x], qo.pw1[0], nullptr, qo.pb1[0], nullptr, qo.pk[0], r.base[qo.y], r.at(qo.y2),
-                                  r.at(qo.res), r.at(qo.acc), r.at(qo.acc2));
+        pp.m[q - n] = op_member(qo, 0, r.base[qo.x], r.base[qo.y], r.at(qo.y2), r.at(qo.res), r.at(qo.acc), r.at(qo.acc2));
     }
     return launch_convh(pp, o.Cin, o.dil, r.s);
 }
@@ -737,13 +571,12 @@ static int run_pair_group(const Run& r, size_t n, size_t m) {
     if (sum) {
         const int xs3[3] = {o.x, o.xb, o.xc};
         pp.sum = 1;
-        for (int j = 0; j < 3; ++j)
-            pp.m[j] = pair_member(r.base[xs3[j]], o.pw1[j], o.pw2[j], o.pb1[j], o.pb2[j], o.pk[j], r.base[o.y], r.at(o.y2));
+        for (int j = 0; j < 3; ++j) pp.m[j] = op_member(o, j, r.base[xs3[j]], r.base[o.y], r.at(o.y2));
     } else {
         for (size_t q = n; q < m; ++q) {
             const Op& qo = r.op(q);
-            pp.m[q - n] = pair_member(r.base[qo.x], qo.pw1[0], qo.pw2[0], qo.pb1[0], qo.pb2[0], qo.pk[0],
-                                      qo.fold_w ? nullptr : r.base[qo.y], r.at(qo.y2), nullptr, r.at(qo.acc), r.at(qo.acc2));
+            pp.m[q - n] = op_member(qo, 0, r.base[qo.x], qo.fold_w ? nullptr : r.base[qo.y], r.at(qo.y2), nullptr, r.at(qo.acc),
+                                    r.at(qo.acc2));
             mids[q - n] = r.at(qo.tmpb);
             if (qo.fold_w) {            // (never grouped: one member)
                 pp.fold_w = qo.fold_w;
