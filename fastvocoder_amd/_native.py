@@ -1,4 +1,5 @@
-"""ctypes binding of libfastvocoder_hip.so (include/fastvocoder_hip.h).
+"""ctypes binding of libfastvocoder_hip.so (include/fastvocoder_hip.h; every entry's signature and every FV_*
+constant below are read from that header by _abi.py, none is restated here).
 
 PyTorch-ROCm is plumbing here: it owns device memory (tensors) and the stream;
 every function below passes raw device pointers and the current HIP stream to
@@ -10,6 +11,9 @@ import os
 import subprocess
 
 import torch
+
+from . import _abi
+from ._abi import NativeError  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfastvocoder_hip.so")
@@ -26,23 +30,22 @@ HEADERS = ["fv_internal.h", "launch_host.hpp", "conv_kernels.hpp", "pair_kernels
            "pairh_inst.hpp", "convh_kernels.hpp", "convh_inst.hpp", "convr_kernels.hpp",
            "convtn_kernels.hpp", "convk_kernels.hpp", "convq2_kernels.hpp", "mrfh_kernels.hpp", "mrfh_inst.hpp", "mrfw_kernels.hpp", "convtl_kernels.hpp", "convs2_kernels.hpp", "convu2_kernels.hpp", "api_internal.h", "stft_core.hpp", "basis_grad_host.hpp", "wgrad_tile.hpp", "gen_grad_host.hpp"]
 
-PAD_ZERO, PAD_REFLECT = 0, 1
-PAD_CAUSAL = 2      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)
-POST_NONE, POST_TANH, POST_RELU = 0, 1, 2
-SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0, MAX_SLOTS = -1, 0, 1, 2, 32
-SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = 28, 29, 30    # caller-provided tensors of Plan.run(aux=..., out2=...)
-ABI_VERSION = 18
-PAIR_F32, PAIR_SPLIT_F16 = 0, 1   # arithmetic of the fused ResBlock-pair kernels (fastvocoder_hip.h)
+_C = _abi.constants()        # every FV_X below is include/fastvocoder_hip.h's `#define FV_X <integer>`
+PAD_ZERO, PAD_REFLECT = _C["FV_PAD_ZERO"], _C["FV_PAD_REFLECT"]
+PAD_CAUSAL = _C["FV_PAD_CAUSAL"]      # flag: pad (k-1)*dil on both sides, keep the first Tin outputs (CausalConv1d)
+POST_NONE, POST_TANH, POST_RELU = _C["FV_POST_NONE"], _C["FV_POST_TANH"], _C["FV_POST_RELU"]
+SLOT_NONE, SLOT_IN, SLOT_OUT, SLOT_TMP0 = _C["FV_SLOT_NONE"], _C["FV_SLOT_IN"], _C["FV_SLOT_OUT"], _C["FV_SLOT_TMP0"]
+MAX_SLOTS = _C["FV_MAX_SLOTS"]
+# caller-provided tensors of Plan.run(aux=..., out2=...)
+SLOT_AUX_IN0, SLOT_AUX_IN1, SLOT_OUT2 = _C["FV_SLOT_AUX_IN0"], _C["FV_SLOT_AUX_IN1"], _C["FV_SLOT_OUT2"]
+ABI_VERSION = _C["FV_ABI_VERSION"]
+PAIR_F32, PAIR_SPLIT_F16 = _C["FV_PAIR_F32"], _C["FV_PAIR_SPLIT_F16"]   # arithmetic of the fused ResBlock-pair kernels
 
 
-ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -2, -3
-ERR_RANGE = -4                    # fv_plan_check_range: a split-f16 kernel met an operand beyond the f16 range
-GUARD_HIGH, GUARD_LOW = 0x001, 0x100   # the two sides of a guard word (separate bytes: fastvocoder_hip.h)
-ERR_RANGE_LOW = -5                # ... only the low-side guard fired (a block's share of a tensor was small as a whole)
-
-
-class NativeError(RuntimeError):
-    pass
+ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = _C["FV_ERR_INVALID_ARG"], _C["FV_ERR_UNSUPPORTED"], _C["FV_ERR_WORKSPACE"]
+ERR_RANGE = _C["FV_ERR_RANGE"]    # fv_plan_check_range: a split-f16 kernel met an operand beyond the f16 range
+GUARD_HIGH, GUARD_LOW = _C["FV_GUARD_HIGH"], _C["FV_GUARD_LOW"]   # the two sides of a guard word (separate bytes)
+ERR_RANGE_LOW = _C["FV_ERR_RANGE_LOW"]   # ... only the low-side guard fired (a block's share of a tensor was small as a whole)
 
 
 class RangeError(NativeError):
@@ -177,220 +180,9 @@ def lib():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). fastvocoder_amd has no CPU or eager fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    vp, i, f, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
-    L.fv_version.restype = i
-    L.fv_last_error.restype = ctypes.c_char_p
-    L.fv_build_id.restype = ctypes.c_char_p
-    L.fv_fold_weight_norm.argtypes = [vp, vp, vp, i, i64, vp]
-    L.fv_packed_conv1d_floats.argtypes = [i, i, i]
-    L.fv_packed_conv1d_floats.restype = i64
-    L.fv_packed_conv_transpose1d_floats.argtypes = [i, i, i, i, i]
-    L.fv_packed_conv_transpose1d_floats.restype = i64
-    L.fv_pack_conv1d_weight.argtypes = [vp, vp, i, i, i, vp]
-    L.fv_pack_conv_transpose1d_weight.argtypes = [vp, vp, i, i, i, i, i, vp]
-    L.fv_conv1d_fused.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, f, i, f, vp]
-    L.fv_conv_transpose1d_fused.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, vp]
-    L.fv_packed_basis_floats.argtypes = [i, i]
-    L.fv_packed_basis_floats.restype = i64
-    L.fv_pack_basis.argtypes = [vp, vp, i, i, vp]
-    L.fv_basis_ola.argtypes = [vp, vp, vp, i, i, i, i, vp]
-    L.fv_generator_run.argtypes = [vp, i, i, vp, vp, vp, i64, vp]
-    L.fv_packed_conv_transpose1d_split_floats.argtypes = [i, i, i, i]
-    L.fv_packed_conv_transpose1d_split_floats.restype = i64
-    L.fv_pack_conv_transpose1d_split_f16.argtypes = [vp, vp, i, i, i, i, vp, vp]
-    L.fv_conv_transpose1d_split_f16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, f, vp, vp]
-    L.fv_plan_add_conv_transpose1d_split_f16.argtypes = [vp, i, i, i, vp, vp, i, i, i, i, i, i, f, f]
-    L.fv_plan_set_input_merge.argtypes = [vp, i, i, f]
-    L.fv_div_probe.argtypes = [ctypes.c_uint, i64, f, vp, vp]
-    L.fv_pqmf_synthesis.argtypes = [vp, vp, vp, i, i, i, i, vp]
-    L.fv_conv1d_2src_fused.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp]
-    L.fv_plan_add_conv1d_2src.argtypes = [vp, i, i, i, i, i, vp, vp, i, i, i, i, f]
-    L.fv_packed_conv1x1_2src_split_floats.argtypes = [i]
-    L.fv_packed_conv1x1_2src_split_floats.restype = i64
-    L.fv_pack_conv1x1_2src_split_f16.argtypes = [vp, vp, vp, i, vp, vp]
-    L.fv_conv1x1_2src_split_f16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, f, i, f, vp, vp]
-    L.fv_plan_add_conv1x1_2src_split_f16.argtypes = [vp, i, i, i, i, i, vp, vp, i, f, i, f]
-    L.fv_packed_residual_stack_floats.argtypes = [i, i]
-    L.fv_packed_residual_stack_floats.restype = i64
-    L.fv_pack_residual_stack_split_f16.argtypes = [vp, vp, vp, vp, i, i, vp, vp]
-    L.fv_residual_stack_split_f16.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, i, i, f, vp, vp]
-    L.fv_plan_add_residual_stack_split_f16.argtypes = [vp, i, i, i, vp, vp, vp, i, i, i, f, i, i, f]
-    L.fv_plan_set_stack_two_launch.argtypes = [vp, i, vp, vp]
-    L.fv_conv_post_pqmf.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, vp]
-    L.fv_plan_add_conv_post_pqmf.argtypes = [vp, i, i, vp, vp, i, i, i, i, f, i, vp, i]
-    L.fv_plan_set_sum_order.argtypes = [vp, i]
-    L.fv_plan_add_conv1d_sum3.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i), i, i,
-                                          ctypes.POINTER(vp), vp,
-                                          i, ctypes.POINTER(i), f, i, f]
-    L.fv_encode_16bits.argtypes = [vp, vp, vp, i, i64, f, i, vp]
-    L.fv_pqmf_analysis.argtypes = [vp, vp, vp, i, i, i, i64, vp]
-    L.fv_melspectrogram.argtypes = [vp, vp, vp, i, i64, i, i, i, i, i, f, vp]
-    L.fv_resample_out_len.argtypes = [i64, i, i]
-    L.fv_resample_out_len.restype = i64
-    L.fv_resample.argtypes = [vp, i, vp, vp, i, i64, i64, i, i, i, vp]
-    L.fv_istft_workspace_bytes.argtypes = [i, i]
-    L.fv_istft_workspace_bytes.restype = i64
-    L.fv_griffin_lim_workspace_bytes.argtypes = [i, i]
-    L.fv_griffin_lim_workspace_bytes.restype = i64
-    L.fv_stft.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
-    L.fv_istft.argtypes = [vp, vp, vp, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_griffin_lim.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_mel_to_linear.argtypes = [vp, vp, vp, i, i, i, i, f, vp]
-    L.fv_inv_preemphasis.argtypes = [vp, vp, i, i64, f, vp]
-    L.fv_stft_table_floats.argtypes = [i, i]
-    L.fv_stft_magnitude.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
-    L.fv_stft_distance_workspace_bytes.argtypes = [i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i)]
-    L.fv_stft_distance_workspace_bytes.restype = i64
-    L.fv_stft_distance.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
-                                   ctypes.POINTER(i), vp, vp, ctypes.c_size_t, vp]
-    L.fv_stft_magnitude_bins.argtypes = [vp, vp, vp, i, i64, i, i, i, vp]
-    L.fv_stft_distance_grad_workspace_bytes.argtypes = [i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
-                                                        ctypes.POINTER(i)]
-    L.fv_stft_distance_grad_workspace_bytes.restype = i64
-    L.fv_stft_distance_grad.argtypes = [vp, vp, ctypes.POINTER(vp), i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
-                                        ctypes.POINTER(i), vp, vp, vp, ctypes.c_size_t, vp]
-    L.fv_stft_magnitude_bins_grad_workspace_bytes.argtypes = [i, i64, i, i, i]
-    L.fv_stft_magnitude_bins_grad_workspace_bytes.restype = i64
-    L.fv_stft_magnitude_bins_grad.argtypes = [vp, vp, vp, i, i64, i, i, i, vp, vp, ctypes.c_size_t, vp]
-    L.fv_grouped_conv1d.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
-    L.fv_avg_pool1d.argtypes = [vp, vp, i, i64, i, i, i, vp]
-    L.fv_disc_score_workspace_bytes.argtypes = [i, i, ctypes.POINTER(i64)]
-    L.fv_disc_score_workspace_bytes.restype = i64
-    L.fv_disc_score_sums.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i, i, vp, vp,
-                                     ctypes.c_size_t, vp]
-    L.fv_disc_map_grad.argtypes = [vp, vp, vp, vp, i64, f, vp]
-    L.fv_grouped_conv1d_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
-    L.fv_conv_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i, i]
-    L.fv_conv_weight_grad_workspace_bytes.restype = i64
-    L.fv_conv1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_grouped_conv1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_period_conv_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
-    L.fv_period_conv_weight_grad_workspace_bytes.restype = i64
-    L.fv_period_conv_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_period_conv_weight_grad_bf16_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
-    L.fv_period_conv_weight_grad_bf16_workspace_bytes.restype = i64
-    L.fv_period_conv_weight_grad_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_mpd_first_weight_grad_workspace_bytes.argtypes = [i, i64, i]
-    L.fv_mpd_first_weight_grad_workspace_bytes.restype = i64
-    L.fv_mpd_first_weight_grad.argtypes = [vp, vp, vp, vp, i, i64, i, vp, ctypes.c_size_t, vp]
-    L.fv_weight_norm_grad.argtypes = [vp, vp, vp, vp, vp, i, i64, vp]
-    L.fv_conv1d_weight_grad_dilated_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
-    L.fv_conv1d_weight_grad_dilated_workspace_bytes.restype = i64
-    L.fv_conv1d_weight_grad_dilated.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_conv1d_weight_grad_dilated_mode_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
-    L.fv_conv1d_weight_grad_dilated_mode_workspace_bytes.restype = i64
-    L.fv_conv1d_weight_grad_dilated_mode.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_conv1d_input_grad_reflect.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
-    L.fv_conv_transpose1d_input_grad.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, vp]
-    L.fv_conv_transpose1d_weight_grad_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
-    L.fv_conv_transpose1d_weight_grad_workspace_bytes.restype = i64
-    L.fv_conv_transpose1d_weight_grad.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_conv1d_weight_grad_dilated_bf16_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
-    L.fv_conv1d_weight_grad_dilated_bf16_workspace_bytes.restype = i64
-    L.fv_conv1d_weight_grad_dilated_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_conv_transpose1d_weight_grad_bf16_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
-    L.fv_conv_transpose1d_weight_grad_bf16_workspace_bytes.restype = i64
-    L.fv_conv_transpose1d_weight_grad_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_tanh_grad.argtypes = [vp, vp, vp, i64, vp]
-    L.fv_residual_merge_grad.argtypes = [vp, vp, vp, vp, vp, i64, f, vp]
-    L.fv_grad_div.argtypes = [vp, vp, i64, f, vp]
-    L.fv_basis_head_forward.argtypes = [vp, vp, i, i, i, vp]
-    L.fv_basis_head_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
-    L.fv_basis_weight_l1_workspace_bytes.argtypes = [i, i, i]
-    L.fv_basis_weight_l1_workspace_bytes.restype = i64
-    L.fv_basis_weight_l1.argtypes = [vp, vp, vp, i, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_basis_weight_l1_grad.argtypes = [vp, vp, vp, vp, i, i, i, vp]
-    L.fv_basis_encode.argtypes = [vp, vp, vp, i, i64, i, i, vp]
-    L.fv_basis_learn_grad_workspace_bytes.argtypes = [i, i64, i, i]
-    L.fv_basis_learn_grad_workspace_bytes.restype = i64
-    L.fv_basis_learn_grad.argtypes = [vp, vp, vp, vp, vp, vp, i, i64, i, i, vp, ctypes.c_size_t, vp]
-    L.fv_grad_sq_norm_workspace_bytes.argtypes = [i64]
-    L.fv_grad_sq_norm_workspace_bytes.restype = i64
-    L.fv_grad_sq_norm.argtypes = [vp, vp, i, i64, f, vp, ctypes.c_size_t, vp, vp]
-    L.fv_adam_step.argtypes = [vp, vp, i, i64, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
-    L.fv_grad_bucket_pack.argtypes = [vp, vp, i, i64, vp, f, vp]
-    L.fv_reflect_pad_fold.argtypes = [vp, vp, i, i64, i, vp]
-    L.fv_avg_pool1d_input_grad.argtypes = [vp, vp, i, i64, i, i, i, vp]
-    L.fv_disc_score_grad.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
-                                     ctypes.POINTER(f), i, i, vp]
-    L.fv_mpd_conv_first.argtypes = [vp, vp, vp, vp, i, i64, i, f, vp]
-    L.fv_packed_period_conv_floats.argtypes = [i, i]
-    L.fv_packed_period_conv_floats.restype = i64
-    L.fv_pack_period_conv.argtypes = [vp, vp, i, i, vp]
-    L.fv_period_conv.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, vp]
-    L.fv_packed_period_conv_grad_floats.argtypes = [i, i]
-    L.fv_packed_period_conv_grad_floats.restype = i64
-    L.fv_pack_period_conv_grad.argtypes = [vp, vp, i, i, vp]
-    L.fv_period_conv_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
-    L.fv_mpd_first_input_grad.argtypes = [vp, vp, vp, vp, vp, i, i64, i, f, vp]
-    L.fv_fold_batchnorm_conv.argtypes = [vp, vp, vp, vp, vp, vp, f, vp, vp, i, i, i, vp]
-    L.fv_packed_upsample_conv1d_floats.argtypes = [i, i, i, i, i]
-    L.fv_packed_upsample_conv1d_floats.restype = i64
-    L.fv_pack_upsample_conv1d_weight.argtypes = [vp, vp, i, i, i, i, i, vp]
-    L.fv_upsample_conv1d_fused.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, f, vp]
-    L.fv_plan_add_upsample_conv1d.argtypes = [vp, i, i, i, vp, vp, i, i, i, i, i, f, i, f]
-    pp = ctypes.POINTER(vp)
-    L.fv_packed_pair_floats.argtypes = [i, i]
-    L.fv_packed_pair_floats.restype = i64
-    L.fv_pack_pair_weight.argtypes = [vp, vp, i, i, vp]
-    L.fv_resblock1_fused.argtypes = [i, pp, pp, pp, pp, pp, pp, pp, ctypes.POINTER(i), i, i, i, i, f, f, vp]
-    L.fv_mrf_stage.argtypes = [pp, pp, pp, pp, pp, vp, vp, ctypes.POINTER(i), i, i, i, i, f, f, i, f, vp]
-    L.fv_plan_add_resblock_pair.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, i, i, f, f]
-    L.fv_packed_pair_floats_ex.argtypes = [i, i, i]
-    L.fv_packed_pair_floats_ex.restype = i64
-    L.fv_pack_pair_weight_ex.argtypes = [vp, vp, i, i, i, vp, vp]
-    L.fv_resblock1_fused_ex.argtypes = [i, pp, pp, pp, pp, pp, pp, pp, pp, pp, pp, ctypes.POINTER(i), i, i, i, i, f, f,
-                                        i, f, i, vp, vp]
-    L.fv_plan_add_resblock_pair_ex.argtypes = [vp, i, i, i, i, i, i, vp, vp, vp, vp, i, i, i, f, f, i, f, i]
-    L.fv_conv1d_split_f16.argtypes = [i, pp, pp, pp, pp, pp, pp, pp, pp, ctypes.POINTER(i), i, i, i, i, i, f, f, i, f, vp, vp]
-    L.fv_plan_set_pair_output_conv.argtypes = [vp, vp, vp, i, f, i]
-    L.fv_packed_mrf_stage_floats.argtypes = [i, ctypes.POINTER(i)]
-    L.fv_packed_mrf_stage_floats.restype = i64
-    L.fv_pack_mrf_stage_split_f16.argtypes = [pp, pp, pp, pp, vp, i, ctypes.POINTER(i), vp, vp]
-    L.fv_mrf_stage_workspace_bytes.argtypes = [i]
-    L.fv_mrf_stage_workspace_bytes.restype = i64
-    L.fv_mrf_stage_split_f16.argtypes = [vp, vp, vp, vp, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, f, i, f, vp, vp, vp,
-                                         vp, i64, vp, vp]
-    L.fv_plan_add_mrf_stage_split_f16.argtypes = [vp, i, i, i, vp, i, ctypes.POINTER(i), ctypes.POINTER(i), f, f, i, f, vp, i64]
-    L.fv_plan_add_conv1d_split_f16.argtypes = [vp, i, i, i, i, i, i, vp, vp, i, i, i, i, f, f, i, f]
-    L.fv_plan_add_mrf_sum.argtypes = [vp, ctypes.POINTER(i), i, i, pp, pp, pp, pp, i, ctypes.POINTER(i), i, f, f, i, f]
-    L.fv_plan_create.argtypes = [i]
-    L.fv_plan_create.restype = vp
-    L.fv_plan_destroy.argtypes = [vp]
-    L.fv_plan_destroy.restype = None
-    L.fv_plan_add_conv1d.argtypes = [vp, i, i, i, i, i, i, vp, vp, i, i, i, i, i, i, f, f, i, f]
-    L.fv_plan_add_conv_transpose1d.argtypes = [vp, i, i, i, vp, vp, i, i, i, i, i, i, f, i, f]
-    L.fv_plan_add_pqmf_synthesis.argtypes = [vp, i, i, vp, i, i]
-    L.fv_plan_set_guard.argtypes = [vp, vp]
-    L.fv_plan_check_range.argtypes = [vp, vp]
-    L.fv_tuning_set.argtypes = [ctypes.c_char_p, i]
-    L.fv_debug_pair_schedule.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), i, i, i, ctypes.POINTER(ctypes.c_uint)]
-    L.fv_debug_pair_widths.argtypes = [i, i, i, i, i, ctypes.POINTER(i), i, ctypes.POINTER(ctypes.c_int64)]
-    L.fv_debug_mrf_class_schedule.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint)]
-    L.fv_debug_mrf_stage_class_f16.argtypes = [vp, vp, vp, i, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp]
-    L.fv_debug_launch_log.argtypes = [i]
-    L.fv_debug_launch_log_read.argtypes = [ctypes.c_char_p, i64]
-    L.fv_debug_launch_log_read.restype = i64
-    L.fv_debug_launch_log_streams.argtypes = [vp, vp, i64, vp]
-    L.fv_debug_launch_log_streams.restype = i64
-    L.fv_debug_kernel_name.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64]
-    L.fv_debug_kernel_name.restype = i64
-    L.fv_mrf_stage_classes_f16.argtypes = [vp, vp, vp, vp, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64, vp, vp]
-    L.fv_plan_add_mrf_stage_classes_f16.argtypes = [vp, i, i, i, vp, i, ctypes.POINTER(i), ctypes.POINTER(i), f, vp, i64]
-    L.fv_plan_set_group.argtypes = [vp, i]
-    L.fv_plan_output_shape.argtypes = [vp, i, ctypes.POINTER(i), ctypes.POINTER(i64)]
-    L.fv_plan_workspace_bytes.argtypes = [vp, i, i]
-    L.fv_plan_workspace_bytes.restype = i64
-    L.fv_plan_run.argtypes = [vp, i, i, vp, vp, vp, i64, vp]
-    L.fv_plan_run_aux.argtypes = [vp, i, i, vp, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(i), vp, i64, vp]
-    L.fv_plan_set_output_offset.argtypes = [vp, i, i]
-    L.fv_plan_slot_shape.argtypes = [vp, i, i, ctypes.POINTER(i), ctypes.POINTER(i64)]
-    L.fv_plan_num_ops.argtypes = [vp]
-    L.fv_profile_enable.argtypes = [i]
-    L.fv_profile_bracket_cost.argtypes = [vp, i, ctypes.POINTER(ctypes.c_double)]
-    L.fv_profile_mfma_f16_rate.argtypes = [vp, i64, i, i, vp, ctypes.POINTER(ctypes.c_double)]
-    L.fv_profile_collect.argtypes = [i, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double),
-                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    for name, (restype, argtypes) in _abi.prototypes().items():      # (a declared entry the library lacks raises here)
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.fv_version() != ABI_VERSION:
         raise NativeError(f"ABI mismatch: library reports {L.fv_version()}, binding expects {ABI_VERSION}")
     _lib = L
@@ -1098,9 +890,10 @@ def melspectrogram(x, tables, sample_rate=24000, n_fft=2048, hop=240, win_length
     return mel
 
 
-PCM_F32, PCM_S16 = 0, 1          # fv_resample's x_format (fastvocoder_hip.h FV_PCM_*)
+PCM_F32, PCM_S16 = _C["FV_PCM_F32"], _C["FV_PCM_S16"]          # fv_resample's x_format
 # fv_resample's limits (FV_RESAMPLE_MAX_*): L and M, floats of the table, floats of a block's input window
-RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_TABLE_FLOATS, RESAMPLE_MAX_WINDOW = 1 << 20, 1 << 20, 16384
+RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_TABLE_FLOATS = 1 << 20, 1 << 20      # (expressions in the header: mirrored by hand)
+RESAMPLE_MAX_WINDOW = _C["FV_RESAMPLE_MAX_WINDOW"]
 
 
 def resample(x, table, L, M, half):
@@ -1486,7 +1279,7 @@ def mpd_first_input_grad(g_up, g_map, y0, w, T, slope=0.1):
     return dx
 
 
-DISC_MAX_MAPS = 48      # FV_DISC_MAX_MAPS: maps per fv_disc_score_sums call
+DISC_MAX_MAPS = _C["FV_DISC_MAX_MAPS"]      # maps per fv_disc_score_sums call
 
 
 def disc_score_sums(es, rs):
@@ -1975,7 +1768,7 @@ def basis_learn_grad(wav, g_est, W, basis, want_enc=True, want_basis=True, works
 # gradient clipping + Adam over a table of tensors (csrc/optim.hip)
 # ---------------------------------------------------------------------------
 
-ADAM_CHUNK = 4096               # FV_ADAM_CHUNK: elements per table chunk, one workgroup each
+ADAM_CHUNK = _C["FV_ADAM_CHUNK"]               # elements per table chunk, one workgroup each
 ADAM_ROW_BYTES, ADAM_CHUNK_BYTES = 48, 8      # sizeof(fv_adam_tensor), sizeof(fv_adam_chunk)
 
 
@@ -2447,11 +2240,13 @@ def profile_enable(on):
     check(lib().fv_profile_enable(1 if on else 0))
 
 
-KERNEL_CONV_MFMA32, KERNEL_CONV_MFMA16, KERNEL_CONV_NARROW, KERNEL_PAIR16, KERNEL_PAIR32 = 0, 1, 2, 3, 4
-KERNEL_PAIRH16, KERNEL_PAIRH32, KERNEL_CONVH64, KERNEL_CONVH128, KERNEL_CONVT, KERNEL_CONVG = 5, 6, 7, 8, 9, 10
-KERNEL_STACK = 11
-KERNEL_MRF16 = 12     # a whole 16-channel MRF stage as one launch (mrfh_kernel)
-KERNEL_MRF32 = 13     # ... 32-channel (mrfw_kernel)
+KERNEL_CONV_MFMA32, KERNEL_CONV_MFMA16 = _C["FV_KERNEL_CONV_MFMA32"], _C["FV_KERNEL_CONV_MFMA16"]
+KERNEL_CONV_NARROW, KERNEL_PAIR16, KERNEL_PAIR32 = _C["FV_KERNEL_CONV_NARROW"], _C["FV_KERNEL_PAIR16"], _C["FV_KERNEL_PAIR32"]
+KERNEL_PAIRH16, KERNEL_PAIRH32 = _C["FV_KERNEL_PAIRH16"], _C["FV_KERNEL_PAIRH32"]
+KERNEL_CONVH64, KERNEL_CONVH128 = _C["FV_KERNEL_CONVH64"], _C["FV_KERNEL_CONVH128"]
+KERNEL_CONVT, KERNEL_CONVG, KERNEL_STACK = _C["FV_KERNEL_CONVT"], _C["FV_KERNEL_CONVG"], _C["FV_KERNEL_STACK"]
+KERNEL_MRF16 = _C["FV_KERNEL_MRF16"]     # a whole 16-channel MRF stage as one launch (mrfh_kernel)
+KERNEL_MRF32 = _C["FV_KERNEL_MRF32"]     # ... 32-channel (mrfw_kernel)
 
 
 def profile_bracket_cost(n=200):

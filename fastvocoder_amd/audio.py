@@ -38,6 +38,7 @@ import scipy.signal
 import scipy.special
 import torch
 
+from . import _abi
 from . import _native
 from . import hparams
 from ._stft_tables import device_cached, periodic_hann, rfft_twiddles
@@ -166,8 +167,9 @@ def _mel_table_host():
     return tab.astype(np.float32)
 
 
-# include/fastvocoder_hip.h FV_MEL_TAB_* (offsets in floats)
-_MEL_TAB_TWIDDLE, _MEL_TAB_SPLIT, _MEL_TAB_FILTERS, _MEL_TAB_WEIGHTS, _MEL_MAX_WEIGHTS = 1200, 3248, 5296, 5536, 2050
+_C = _abi.constants()       # offsets in floats
+_MEL_TAB_TWIDDLE, _MEL_TAB_SPLIT, _MEL_TAB_FILTERS = _C["FV_MEL_TAB_TWIDDLE"], _C["FV_MEL_TAB_SPLIT"], _C["FV_MEL_TAB_FILTERS"]
+_MEL_TAB_WEIGHTS, _MEL_MAX_WEIGHTS = _C["FV_MEL_TAB_WEIGHTS"], _C["FV_MEL_MAX_WEIGHTS"]
 _mel_tables = {}
 
 
@@ -349,7 +351,7 @@ def _inv_mel_basis_host():
     return np.ascontiguousarray(np.linalg.pinv(_build_mel_basis()).T).astype(np.float32)
 
 
-_GL_TAB_WIN2 = 5296            # include/fastvocoder_hip.h FV_GL_TAB_WIN2
+_GL_TAB_WIN2 = _C["FV_GL_TAB_WIN2"]
 _gl_tables, _inv_bases = {}, {}
 
 
